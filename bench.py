@@ -10,9 +10,15 @@ branch) on one synthetic batch per GPU: NTU-60 xsub shapes (N,3,64,25), mlp4, 64
 (BASELINE configs[1]); inputs are resident in HBM before the timed region.  One process per GPU,
 gradients summed by one RCCL all-reduce of a flat bucket per optimiser step (weak scaling).
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` (dominant kernel,
-measured live with HIP events on the launch stream) and `cpu_baseline` (the oracle's WGAN-GP
-iteration timed on the host cores, bounded sample).
+Prints ONE JSON line (rank 0) with the driver's contract (metric, value, unit, higher_is_better,
+dtype, ms_per_step).  A plain run does only that: set-up, warm-up, the timed steps, the line.
+
+    --dump-outputs DIR   after the timed steps: what the last timed step computed - the two losses
+                         and the parameters / buffers of G and D it left - as DIR/<name>.npy (float32)
+    --full               also the side figures, measured after the timed region: `work` (executed
+                         flops), `extras` (D-only / n_critic=5 rates), the `roofline*` legs with
+                         measured peaks (dominant kernels, HIP events on the launch stream) and
+                         `cpu_baseline*` (the oracle's WGAN-GP iteration timed on the host cores)
 """
 import argparse
 import json
@@ -47,9 +53,14 @@ def parse():
                     help="strong scaling: total samples, split evenly over the GPUs (overrides --batch)")
     ap.add_argument("--config", default="ntu", choices=sorted(CONFIGS))
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the D-only / n_critic=5 figures of SURVEY 8(d)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side figures after the timed steps: work / extras / roofline legs / CPU baseline "
+                         "(each can be left out with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, parameters and buffers of G and D) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the D-only / n_critic=5 figures of SURVEY 8(d)")
     ap.add_argument("--no-c5a", action="store_true", help="skip the C5a stress-block leg of the roofline")
     ap.add_argument("--segmented", action="store_true",
                     help="force the data-parallel launch structure (two graphs + eager all-reduce/Adam) on one GPU")
@@ -140,8 +151,10 @@ def _capture_pair(first, second):
     return ga.replay, gb.replay
 
 
-def make_step(tr, batch, use_graph, segmented):
+def make_step(tr, batch, use_graph, segmented, outs):
     """Returns a zero-argument callable running one G+D iteration (noise drawn in-step like generator.py:179).
+    ``outs`` receives the iteration's losses (d_loss, g_loss): with hipGraph replay, the tensors of the captured call,
+    which every replay rewrites - after the last step they hold that step's values.
 
     hipGraph modes: one graph for the whole iteration (1 GPU), or - with data parallelism - one graph per compute
     half (forward + backward + gradient gather) with the RCCL all-reduce + Adam launched eagerly in between, so
@@ -149,7 +162,7 @@ def make_step(tr, batch, use_graph, segmented):
     real, labels, z, alpha = batch
 
     def eager():
-        tr.iteration(real, labels, z, alpha, None, None, with_g=True)
+        outs["d_loss"], outs["g_loss"] = tr.iteration(real, labels, z, alpha, None, None, with_g=True)
 
     if not use_graph:
         return eager, "eager"
@@ -163,10 +176,10 @@ def make_step(tr, batch, use_graph, segmented):
                 # overlap mode hides D's all-reduce + Adam under the generator step's OWN forward pass, so that pass
                 # must stay in the generator step: no paired synthesis here (round-2 ADVICE: with the pairing on, the
                 # sample was synthesised here AND again in g_forward, with a third running-statistics update)
-                tr.d_compute(real, labels, z, alpha, None)
+                outs["d_loss"] = tr.d_compute(real, labels, z, alpha, None)
                 return
             with tr.sharing_mapping():      # tr._w of the CAPTURED call (graph memory, rewritten by every replay)
-                tr.d_compute(real, labels, z, alpha, None)
+                outs["d_loss"] = tr.d_compute(real, labels, z, alpha, None)
         def drop_warmup_graph():
             # the last warm-up call's generator sample still holds its autograd graph: while it lives, G's parameters
             # keep the AccumulateGrad nodes created on the warm-up stream and the captured backward would sync with it
@@ -180,7 +193,9 @@ def make_step(tr, batch, use_graph, segmented):
         def hand_over():
             tr._w, tr._fake_g = w_cap, f_cap
         if not tr.overlap:
-            g_replay = _capture(lambda: tr.g_compute(labels, z, None), before_capture=hand_over)
+            def g_half():
+                outs["g_loss"] = tr.g_compute(labels, z, None)
+            g_replay = _capture(g_half, before_capture=hand_over)
 
             def step():
                 d_replay()
@@ -191,7 +206,9 @@ def make_step(tr, batch, use_graph, segmented):
         # overlap: the generator step is captured as TWO graphs in one Python pass (the autograd graph built while the
         # first is captured is consumed while the second is; they share a memory pool and replay in capture order):
         # G forward - which runs while D's all-reduce + Adam are still in flight on the side stream - and the rest
-        ga_replay, gb_replay = _capture_pair(lambda: tr.g_forward(labels, z, None), lambda fake: tr.g_backward(fake, labels))
+        def g_back(fake):
+            outs["g_loss"] = tr.g_backward(fake, labels)
+        ga_replay, gb_replay = _capture_pair(lambda: tr.g_forward(labels, z, None), g_back)
 
         def step():
             d_replay()
@@ -718,6 +735,33 @@ def cpu_baseline_leg(cfg, n=16, timed=15):
             "sample": "oracle G+D iteration, %s shapes, bs=%d, 2 warm-up + %d timed (median %.0f ms)" % (cfg["dataset"], n, timed, med * 1e3)}
 
 
+DUMP_MAX_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, outs, G, D):
+    """What the timed path hands its caller after the last step: the losses it returns and the parameters / float buffers
+    of G and D it updated, as float32 .npy files.  Above DUMP_MAX_BYTES in all, every array keeps a fixed, seeded sample
+    of its elements of the same share (NTU shapes at 64 samples write 29 MB: no sampling)."""
+    import numpy as np
+    arrays = {}
+    for k in ("d_loss", "g_loss"):
+        if outs.get(k) is not None:
+            arrays[k] = outs[k]
+    for tag, m in (("G", G), ("D", D)):
+        for name, t in list(m.named_parameters()) + list(m.named_buffers()):
+            if t.is_floating_point():
+                arrays["%s.%s" % (tag, name)] = t
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    share = 0.99 * DUMP_MAX_BYTES / total if total > DUMP_MAX_BYTES else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        if share < 1.0 and a.size > 1:
+            idx = np.random.default_rng(0).choice(a.size, max(1, int(a.size * share)), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     args = parse()
     cfg = CONFIGS[args.config]
@@ -782,8 +826,9 @@ def main():
         args.no_graph = True
     tr = Trainer(G, D, world_size=world, overlap=bool(args.overlap) and not args.no_overlap, comm=comm)
     batch = synth_batch(cfg, args.batch, rank, dev)
+    outs = {}
     step, mode = make_step(tr, batch, use_graph=not args.no_graph,
-                           segmented=((world > 1 and not (args.dp_graph and comm is not None)) or args.segmented))
+                           segmented=((world > 1 and not (args.dp_graph and comm is not None)) or args.segmented), outs=outs)
     if world > 1 and mode == "hipgraph":
         mode = "hipgraph (all-reduce captured)"
 
@@ -805,6 +850,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs, G, D)
+
     out = None
     if rank == 0:
         gb = args.batch * world
@@ -823,10 +871,11 @@ def main():
                                      ("torch.distributed nccl (RCCL)" if dist.get_backend() == "nccl" else
                                       "torch.distributed %s (test hook KG_BENCH_BACKEND: NOT RCCL)" % dist.get_backend())) if world > 1 else None},
         }
-        out["work"] = work_leg(tr, batch, args, cfg, out["ms_per_step"])
-        if world == 1 and not args.no_extras:
+        if args.full:
+            out["work"] = work_leg(tr, batch, args, cfg, out["ms_per_step"])
+        if args.full and world == 1 and not args.no_extras:
             out["extras"] = extras_leg(tr, batch, args, out["ms_per_step"])
-        if world == 1 and not args.no_roofline:
+        if args.full and world == 1 and not args.no_roofline:
             out["roofline"] = roofline_leg(args.batch, dev)
             # the same layer as the critic's forward / merged backward really launch it: real + fake + interpolates
             out["roofline_critic"] = roofline_leg(3 * args.batch, dev)
@@ -841,7 +890,7 @@ def main():
             for k in [k for k in out if k.startswith("roofline")]:
                 with_measured_peak(out[k], dev)
             out["peaks_measured"] = peaks_or_error(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_leg(cfg, 16, 15)
             out["cpu_baseline_bs64"] = cpu_baseline_leg(cfg, 64, 5)
         print(json.dumps(out), flush=True)

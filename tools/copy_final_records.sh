@@ -1,10 +1,11 @@
 #!/bin/bash
-# run HERE after a tools/gpu_r06_final.sh visit: copies the visit's records from gpurun_out/ into profiles/ (copies made on the
-# GPU box do not come back: only gpurun_out/ is merged)
+# run on the development machine after a tools/gpu_r06_final.sh run on the GPU machine: copies that run's records from its
+# output folder (KG_OUT, default runs/) into profiles/
 set -eu
+export KG_OUT=${KG_OUT:-runs}; OUT=$KG_OUT      # output folder, relative to the repository root
 TAG=${1:-r06_final}
 cd "$(dirname "$0")/.."
-G=gpurun_out
+G=$OUT
 cp $G/${TAG}_bench_default.json.log $G/${TAG}_eager_kernel_stats.csv $G/${TAG}_eager_kernel_stats.json $G/${TAG}_last_step.txt \
    $G/${TAG}_other_configs.log $G/${TAG}_smoke.log $G/${TAG}_roofline_c5a_kernel_stats.csv profiles/
 cp $G/roofline_bs64/roofline_pmc.json profiles/roofline_pmc.json

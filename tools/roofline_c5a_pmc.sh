@@ -1,9 +1,10 @@
 #!/bin/bash
 # rocprofv3 evidence for the two C5a legs of bench.py (roofline_c5a: kg_conv_kernel<128,4>, roofline_agg: kg_agg_mfma_kernel):
 # kernel stats and HBM byte counters of `bench.py --roofline-only`, counters in separate --pmc passes.
+export KG_OUT=${KG_OUT:-runs}; OUT=$KG_OUT      # output folder, relative to the repository root
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
-O=$R/gpurun_out/roofline_c5a
+R=$(pwd)
+O=$R/$OUT/roofline_c5a
 rm -rf $O; mkdir -p $O
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o rf -- python3 $R/bench.py --roofline-only > $O/stats.log 2>&1
@@ -11,8 +12,8 @@ rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o rf -- python3 $R/b
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o rf -- python3 $R/bench.py --roofline-only > $O/write.log 2>&1
 cd $R
 python3 - <<'PY'
-import csv, glob, json
-O = "gpurun_out/roofline_c5a"
+import csv, glob, json, os
+O = os.path.join(os.environ["KG_OUT"], "roofline_c5a")
 def per_launch(path, counter, kernel):
     vals = [float(r["Counter_Value"]) for f in glob.glob(path) for r in csv.DictReader(open(f))
             if kernel in r["Kernel_Name"] and r["Counter_Name"] == counter]

@@ -4,11 +4,12 @@
 # Counters in separate --pmc passes (FETCH_SIZE needs 3 of the 4 TCC slots), never together with tracing.
 # usage: roofline_pmc.sh [batch]   (64: the bench's `roofline` leg -> roofline_pmc.json; 192: `roofline_critic` ->
 # roofline_pmc_bs192.json)
+export KG_OUT=${KG_OUT:-runs}; OUT=$KG_OUT      # output folder, relative to the repository root
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(pwd)
 B=${1:-64}
 export KG_RF_BATCH=$B
-O=$R/gpurun_out/roofline_bs$B
+O=$R/$OUT/roofline_bs$B
 rm -rf $O; mkdir -p $O
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o rf -- python3 $R/bench.py --roofline-only --no-c5a --batch $B > $O/stats.log 2>&1
@@ -19,7 +20,7 @@ cd $R
 python3 - <<'PY'
 import csv, glob, json, os
 B = int(os.environ.get("KG_RF_BATCH", "64"))
-O = "gpurun_out/roofline_bs%d" % B
+O = os.path.join(os.environ["KG_OUT"], "roofline_bs%d" % B)
 KD = "kg_conv_kernel<32, 4"          # the direct fp32 kernel: the plan takes its 32-row tile for this (shallow) contraction
 # the leg's kernel is the direct fp32 kernel at both sizes (round 6: the bf16-split form is opt-in, KG_CONV_BS=2 brings the
 # round-5 plan rule back - then the 192-sample leg is its tile kernel); the other form is timed next to it on the same operands
