@@ -659,6 +659,38 @@ int kg_comm_destroy(void* comm);
 int kg_peak_mfma_f32(float* sink, int32_t iters, double* flops, void* stream);
 int kg_peak_copy(const float* src, float* dst, int64_t n, void* stream);
 
+/* ---- MMD evaluation (evaluation/mmd-actions.py:79-115; additive, ABI v9) -------------------------------------------
+ * For every group g of every class c: X_g, Y_g are m points of dimension `dim`, read through strides (elements):
+ *   X_g[i][d] = x + c*x_sc + f*x_sg + i*x_sp + d*x_sd      (f < groups: the group's index inside its class)
+ * and likewise Y_g.  For every bandwidth bw[b] (k(a, b') = exp(-|a - b'|^2 / bw)):
+ *   mmd2[(c*groups + f)*nbw + b] = sum_{i != j} [k(x_i, x_j) + k(y_i, y_j) - 2 k(x_i, y_j)] / (m (m - 1))
+ *   mmd[c*nbw + b]               = (1/groups) sum_f sqrt(mmd2)    (NaN from a negative MMD^2 or m = 1, as torch's pow(0.5))
+ *   result[c]                    = r, r = 0 replaced by mmd[c, b] whenever mmd[c, b] > r (b ascending; NaN never wins)
+ *   mean (optional)              = (1/classes) sum_c result[c]
+ * The reference protocol reads the feeder's (N, C, T, V) tensor directly: point = v (x_sp = 1), dimension = c
+ * (x_sd = T*V), group = frame t (x_sg = V), class = one sample (x_sc = sample stride) in `avg` mode, and point = v,
+ * dimension = (c, t) (x_sd = V, dim = C*T, groups = 1) in `joint` mode.  One launch computes the pair sums of every
+ * (group, bandwidth) (tiles of the pair space, fp32 partial sums per tile, no Gram matrix is written) and one
+ * single-workgroup launch finishes: tile partials combined in fp64 in a fixed order - two calls on the same input give
+ * the same bits.  ws: kg_mmd_workspace_bytes(a) bytes of scratch.  m != n, m < 1, dim < 1, nbw outside [1, 16], a
+ * bandwidth <= 0, a null pointer or a small workspace are rejected (< 0, kg_last_error() names the field).            */
+#define KG_MMD_MAX_BW 16
+typedef struct KgMmdArgs {
+    const float* x;  int64_t x_sp, x_sd, x_sg, x_sc;   /* point, dimension, group and class strides (elements)    */
+    const float* y;  int64_t y_sp, y_sd, y_sg, y_sc;
+    int32_t m, n, dim;              /* points of X and Y (must be equal), dimension                                  */
+    int32_t groups, classes;        /* groups per class (frames in avg mode, 1 in joint), classes                  */
+    int32_t nbw;                    /* bandwidths used, 1..KG_MMD_MAX_BW                                           */
+    double bw[KG_MMD_MAX_BW];
+    float* mmd2;                    /* (classes*groups, nbw)                                                       */
+    float* mmd;                     /* (classes, nbw)                                                              */
+    float* result;                  /* (classes)                                                                   */
+    float* mean;                    /* (1) or NULL                                                                 */
+    void* ws;  int64_t ws_bytes;
+} KgMmdArgs;
+int64_t kg_mmd_workspace_bytes(const KgMmdArgs* a);   /* < 0 for invalid shapes                                    */
+int     kg_mmd(const KgMmdArgs* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

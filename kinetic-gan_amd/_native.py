@@ -287,6 +287,19 @@ class _GenBlockBwdArgs(C.Structure):
                 ("ws", c_f32p), ("ws_bytes", C.c_int64), ("counters", C.c_void_p), ("counters_len", C.c_int32)]
 
 
+
+MMD_MAX_BW = 16
+
+
+class _MmdArgs(C.Structure):
+    _fields_ = [("x", c_f32p), ("x_sp", C.c_int64), ("x_sd", C.c_int64), ("x_sg", C.c_int64), ("x_sc", C.c_int64),
+                ("y", c_f32p), ("y_sp", C.c_int64), ("y_sd", C.c_int64), ("y_sg", C.c_int64), ("y_sc", C.c_int64),
+                ("m", C.c_int32), ("n", C.c_int32), ("dim", C.c_int32),
+                ("groups", C.c_int32), ("classes", C.c_int32), ("nbw", C.c_int32),
+                ("bw", C.c_double * MMD_MAX_BW),
+                ("mmd2", c_f32p), ("mmd", c_f32p), ("result", c_f32p), ("mean", c_f32p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
 GEN_ADJ_MAX_JOBS = 8
 
 EXPORTS = {
@@ -363,6 +376,8 @@ EXPORTS = {
     "kg_comm_destroy": (C.c_int, [C.c_void_p]),
     "kg_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p]),
+    "kg_mmd_workspace_bytes": (C.c_int64, [C.POINTER(_MmdArgs)]),
+    "kg_mmd": (C.c_int, [C.POINTER(_MmdArgs), C.c_void_p]),
     "kg_adam_step_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                      C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
 }
@@ -1973,6 +1988,63 @@ def embed_bwd(gx: torch.Tensor, labels: torch.Tensor, demb: torch.Tensor, accumu
 # ---- data-parallel gradient exchange (kg_comm_*: RCCL over xGMI behind the C ABI) -------------------------------------
 
 COMM_ID_BYTES = 128
+
+
+# ---- MMD evaluation ----------------------------------------------------------------------------------------------------
+
+class MmdView(NamedTuple):
+    """How kg_mmd walks one operand: element (class c, group f, point i, dimension d) sits at
+    t.data_ptr() + (c*sc + f*sg + i*sp + d*sd) floats."""
+    t: torch.Tensor
+    sp: int
+    sd: int
+    sg: int
+    sc: int
+
+
+def _mmd_extent_ok(v: MmdView, m: int, dim: int, groups: int, classes: int) -> bool:
+    """every element kg_mmd will read lies inside the tensor's storage"""
+    if min(v.sp, v.sd, v.sg, v.sc) < 0:
+        return False
+    last = (classes - 1) * v.sc + (groups - 1) * v.sg + (m - 1) * v.sp + (dim - 1) * v.sd
+    return v.t.storage_offset() + last < v.t.untyped_storage().nbytes() // 4
+
+
+def mmd(x: MmdView, y: MmdView, m: int, n: int, dim: int, groups: int, classes: int,
+        bandwidths: Sequence[float], want_mean: bool = False) -> dict:
+    """Enqueue kg_mmd (pair sums of every (group, bandwidth) + the finishing launch) on the current stream; no host
+    synchronisation.  Returns dict(mmd2 (classes*groups, nbw), mmd (classes, nbw), result (classes,), mean (0-d or
+    None)), all fp32 on the device."""
+    lib = load_library()
+    for v in (x, y):
+        if v.t.dtype != torch.float32:
+            raise TypeError(f"kg_mmd: fp32 only, got {v.t.dtype}")
+    _need_cuda(x.t, y.t)
+    bws = [float(b) for b in bandwidths]
+    a = _MmdArgs()
+    a.x, a.x_sp, a.x_sd, a.x_sg, a.x_sc = x.t.data_ptr(), x.sp, x.sd, x.sg, x.sc
+    a.y, a.y_sp, a.y_sd, a.y_sg, a.y_sc = y.t.data_ptr(), y.sp, y.sd, y.sg, y.sc
+    a.m, a.n, a.dim, a.groups, a.classes, a.nbw = int(m), int(n), int(dim), int(groups), int(classes), len(bws)
+    for i, b in enumerate(bws[:MMD_MAX_BW]):
+        a.bw[i] = b
+    nbytes = lib.kg_mmd_workspace_bytes(C.byref(a))
+    if nbytes < 0:
+        _check(-1, "kg_mmd_workspace_bytes")
+    for name, v, p in (("x", x, m), ("y", y, n)):
+        if not _mmd_extent_ok(v, p, dim, groups, classes):
+            raise ValueError(f"kg_mmd: the strides of {name} reach outside its tensor")
+    dev = x.t.device
+    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+    out = dict(mmd2=torch.empty((classes * groups, len(bws)), dtype=torch.float32, device=dev),
+               mmd=torch.empty((classes, len(bws)), dtype=torch.float32, device=dev),
+               result=torch.empty(classes, dtype=torch.float32, device=dev),
+               mean=torch.empty((), dtype=torch.float32, device=dev) if want_mean else None)
+    a.mmd2, a.mmd, a.result = out["mmd2"].data_ptr(), out["mmd"].data_ptr(), out["result"].data_ptr()
+    a.mean = _ptr(out["mean"])
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    _count("kg_mmd", 3.0 * 2.0 * m * (m - 1) * dim * groups * classes)
+    _check(lib.kg_mmd(C.byref(a), _stream()), "kg_mmd")
+    return out
 
 
 class Comm:

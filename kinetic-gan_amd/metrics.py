@@ -1,0 +1,211 @@
+"""MMD evaluation of generated actions (evaluation/mmd-actions.py of the reference) on the kg_mmd HIP kernels.
+
+The reference scores samples with a kernel two-sample statistic (MMD) under 14 RBF bandwidths 10^-4 .. 10^9: per class
+the first selected fake and real sample, each a set of V points (joints) per frame (``avg``: the mean over frames of
+the per-frame MMD, points of dimension C) or one set of V points of dimension C*T (``joint``); the class value is the
+largest MMD over the bandwidths (NaN never wins, never below 0), the score the mean over classes.  It runs every
+(class, bandwidth, frame) as separate torch calls, each ending in a host sync (143 k of them for H36M at T = 1024).
+
+Here one kg_mmd call computes every (class, frame, bandwidth) in one launch plus one single-workgroup finishing launch
+and leaves the result on the device (``calculate_mmd``, ``mmd_sweep``).  ``MMD`` keeps the reference class's surface
+(methods return Python floats, one sync each).  ``select_reference_samples`` is the script's sample selection.
+
+Numerics: the result is defined against a float64 evaluation of the same formula (tests/mmd_def.py); at the
+bandwidths where every kernel value is 1 - O(1e-8) the reference's own fp32 values are roundoff.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _native
+
+DEFAULT_BANDWIDTHS = tuple(10.0 ** j for j in range(-4, 10))      # mmd-actions.py:106: 10 ** j, j = -4 .. 9
+MODES = ("avg", "joint")
+
+
+def _as_f32(t) -> torch.Tensor:
+    t = torch.as_tensor(t)
+    return t if t.dtype == torch.float32 else t.float()
+
+
+def _as_cuda(t) -> torch.Tensor:
+    """fp32 tensor on the current GPU (numpy arrays and CPU tensors are copied there: the computation has no CPU path)"""
+    t = _as_f32(t)
+    if not t.is_cuda:
+        t = t.to(torch.device("cuda", torch.cuda.current_device()))
+    return t
+
+
+def _check_mode(mode: str):
+    if mode not in MODES:
+        raise ValueError("undefined mode %r (MMD modes: 'avg', 'joint')" % (mode,))
+
+
+def _check_pair(a: torch.Tensor, b: torch.Tensor, what: str):
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("%s: m=%d != n=%d (both sets need the same number of points)" % (what, a.shape[0], b.shape[0]))
+    if a.shape[1:] != b.shape[1:]:
+        raise ValueError("%s: shapes %s and %s differ beyond the point axis" % (what, tuple(a.shape), tuple(b.shape)))
+
+
+def _seq_view(seq: torch.Tensor, mode: str) -> Tuple[_native.MmdView, int, int]:
+    """(N, L, D) sequence -> (view, dim, groups): avg = L groups of N points of dimension D; joint = one group of N
+    points of dimension L*D (the reference's ``view(-1, L*D)``: a copy only where that view would not exist)"""
+    n, L, D = seq.shape
+    if mode == "avg":
+        return _native.MmdView(seq, seq.stride(0), seq.stride(2), seq.stride(1), 0), D, L
+    if L > 1 and D > 1 and seq.stride(1) != D * seq.stride(2):
+        seq = seq.contiguous()
+    sd = seq.stride(2) if D > 1 else seq.stride(1)
+    return _native.MmdView(seq, seq.stride(0), sd, 0, 0), L * D, 1
+
+
+def _bandwidths(bandwidths) -> list:
+    bws = [float(b) for b in (bandwidths if isinstance(bandwidths, (list, tuple, np.ndarray, torch.Tensor))
+                              else [bandwidths])]
+    return bws
+
+
+def mmd_sweep(seq1, seq2, bandwidths: Sequence[float] = DEFAULT_BANDWIDTHS, mode: str = "avg") -> torch.Tensor:
+    """``compute_sequence_mmd`` of (N, L, D) sequences for every bandwidth at once: Tensor (nbw,) on the device, no
+    host sync.  avg: mean over the L frames of the per-frame MMD; joint: the MMD of the flattened (N, L*D) sets."""
+    _check_mode(mode)
+    seq1, seq2 = _as_f32(seq1), _as_f32(seq2)
+    if seq1.dim() != 3:
+        raise ValueError("mmd_sweep: sequences are (N, L, D), got %s" % (tuple(seq1.shape),))
+    _check_pair(seq1, seq2, "mmd_sweep")
+    seq1, seq2 = _as_cuda(seq1), _as_cuda(seq2)
+    x, dim, groups = _seq_view(seq1, mode)
+    y, _, _ = _seq_view(seq2, mode)
+    out = _native.mmd(x, y, seq1.shape[0], seq2.shape[0], dim, groups, 1, _bandwidths(bandwidths))
+    return out["mmd"][0]
+
+
+class MMD:
+    """The reference's ``MMD`` class (evaluation/mmd-actions.py:14-76) on the HIP kernels.  ``use_torch`` is kept for
+    the signature; inputs may be CUDA tensors, CPU tensors or numpy arrays and are evaluated on the GPU."""
+
+    def __init__(self, mode: str, use_torch: int = 1):
+        self.mode = mode
+        self.use_torch = use_torch
+
+    def reset(self, new_mode: str):
+        self.mode = new_mode
+
+    def rkhs_mmd(self, samples_1, samples_2, bandwidth: float) -> float:
+        """sqrt(sum_{i != j} [k(x_i,x_j) + k(y_i,y_j) - 2 k(x_i,y_j)] / (m (m-1))) of two (m, dim) sets"""
+        s1, s2 = _as_f32(samples_1), _as_f32(samples_2)
+        if s1.dim() != 2:
+            raise ValueError("rkhs_mmd: samples are (m, dim), got %s" % (tuple(s1.shape),))
+        _check_pair(s1, s2, "rkhs_mmd")
+        s1, s2 = _as_cuda(s1), _as_cuda(s2)
+        x = _native.MmdView(s1, s1.stride(0), s1.stride(1), 0, 0)
+        y = _native.MmdView(s2, s2.stride(0), s2.stride(1), 0, 0)
+        return _native.mmd(x, y, s1.shape[0], s2.shape[0], s1.shape[1], 1, 1, [float(bandwidth)])["mmd"].item()
+
+    def compute_sequence_mmd(self, sequence_1, sequence_2, bandwidth: float) -> float:
+        _check_mode(self.mode)
+        return mmd_sweep(sequence_1, sequence_2, [float(bandwidth)], self.mode).item()
+
+
+def _class_index(labels, n: int) -> Tuple[np.ndarray, int]:
+    """labels -> (class index per sample, number of classes); one-hot rows (the reference's form) or class ids"""
+    if isinstance(labels, torch.Tensor):
+        labels = labels.cpu().numpy()           # (one sync when the labels live on the device)
+    lab = np.asarray(labels)
+    if lab.ndim == 2:
+        k = lab.shape[-1]
+        lab = lab.argmax(-1)
+    else:
+        lab = lab.astype(np.int64)
+        k = int(lab.max()) + 1 if lab.size else 0
+    if lab.shape[0] != n:
+        raise ValueError("calculate_mmd: %d labels for %d samples" % (lab.shape[0], n))
+    return lab, k
+
+
+def calculate_mmd(gen, real, labels, mode: str = "avg", bandwidths: Sequence[float] = DEFAULT_BANDWIDTHS,
+                  per_class: bool = False):
+    """The ``calcualte_mmd`` protocol (mmd-actions.py:79-115) over all classes in one kg_mmd call.
+
+    gen, real: (N, C, T, V) as the feeder produces them (fake, real: the reference's argument order); labels: one-hot
+    (N, K) or class ids (N,).  For each class k < K the first sample labelled k of each set is compared.  Returns the
+    mean over classes as a 0-d device tensor; with ``per_class=True`` also (result (K,), mmd (K, nbw)).  No host sync
+    (labels that live on the device are read once).  When the first samples of the classes are not evenly spaced in
+    the batch they are gathered first (one copy); the reference protocol's batches (``select_reference_samples``)
+    are, and are read in place."""
+    _check_mode(mode)
+    gen, real = _as_f32(gen), _as_f32(real)
+    if gen.dim() != 4:
+        raise ValueError("calculate_mmd: samples are (N, C, T, V), got %s" % (tuple(gen.shape),))
+    if gen.shape != real.shape:
+        raise ValueError("calculate_mmd: gen %s and real %s differ" % (tuple(gen.shape), tuple(real.shape)))
+    lab, k = _class_index(labels, gen.shape[0])
+    first = np.full(k, -1, dtype=np.int64)
+    seen = np.unique(lab, return_index=True)
+    first[seen[0]] = seen[1]
+    missing = np.flatnonzero(first < 0)
+    if missing.size:
+        raise ValueError("calculate_mmd: class %d has no sample" % missing[0])
+    gen, real = _as_cuda(gen), _as_cuda(real)
+    step = int(first[1] - first[0]) if k > 1 else 1
+    if k > 1 and (step <= 0 or np.any(np.diff(first) != step)):
+        gen = torch.stack([gen[int(i)] for i in first])       # (no index upload: capturable in a graph)
+        real = torch.stack([real[int(i)] for i in first])
+        base, step = 0, 1
+    else:
+        base = int(first[0])
+    _, C, T, V = gen.shape
+    views = []
+    for t in (gen, real):
+        sc = step * t.stride(0)
+        if mode == "avg":
+            views.append(_native.MmdView(t[base], t.stride(3), t.stride(1), t.stride(2), sc))
+        else:
+            if C > 1 and T > 1 and t.stride(1) != T * t.stride(2):
+                raise ValueError("calculate_mmd: joint mode needs each sample's (C, T) block contiguous in T "
+                                 "(got strides %s)" % (t.stride(),))
+            sd = t.stride(2) if T > 1 else t.stride(1)
+            views.append(_native.MmdView(t[base], t.stride(3), sd, 0, sc))
+    dim, groups = (C, T) if mode == "avg" else (C * T, 1)
+    out = _native.mmd(views[0], views[1], V, V, dim, groups, k, _bandwidths(bandwidths), want_mean=True)
+    if per_class:
+        return out["mean"], out["result"], out["mmd"]
+    return out["mean"]
+
+
+def select_reference_samples(feeder, classes: Optional[Sequence[int]] = None, t_size: int = 64, per_class: int = 100):
+    """The sample selection of mmd-actions.py:131-163, vectorised on the label vector.
+
+    For class classes[c] (default: the ``arange(10 if h36m else 60)`` of the script) the first ``per_class`` samples
+    with that label are taken in index order - scanning from index 0 for the first class and from index 1 for every
+    later one (the script resets its index to 0 and increments it at once) - each read as ``feeder[i]`` (normalised
+    when the feeder normalises, first person for NTU) and cropped to ``t_size`` frames.  Returns (data (K*per_class,
+    C, t, V) fp32 numpy, labels (K*per_class,): the position of the class in ``classes``, dataset indices).  A class
+    with fewer samples raises ValueError (the script dies with an IndexError)."""
+    if classes is None:
+        classes = np.arange(10 if feeder.dataset == "h36m" else 60)
+    classes = np.asarray(classes)
+    lab = np.asarray(feeder.label)
+    picks = []
+    for c, cv in enumerate(classes):
+        start = 0 if c == 0 else 1
+        idx = np.flatnonzero(lab[start:] == cv)[:per_class] + start
+        if idx.size < per_class:
+            raise ValueError("select_reference_samples: class %d (label %d) has %d samples from index %d, %d needed"
+                             % (c, int(cv), idx.size, start, per_class))
+        picks.append(idx)
+    index = np.concatenate(picks) if picks else np.zeros(0, dtype=np.int64)
+    order = np.argsort(index, kind="stable")            # the memory map is read forwards
+    raw = np.empty((index.size, feeder.C, min(t_size, feeder.T), feeder.V), dtype=np.float32)
+    sel = index[order]
+    block = feeder.data[sel, :, :t_size, :, 0] if feeder.dataset == "ntu" else feeder.data[sel, :, :t_size]
+    block = np.asarray(block)
+    if feeder.norm:
+        block = 2 * ((block - feeder.min) / (feeder.max - feeder.min)) - 1     # Feeder.__getitem__, elementwise
+    raw[order] = block
+    labels = np.repeat(np.arange(classes.size), per_class)
+    return raw, labels, index
