@@ -691,6 +691,46 @@ typedef struct KgMmdArgs {
 int64_t kg_mmd_workspace_bytes(const KgMmdArgs* a);   /* < 0 for invalid shapes                                    */
 int     kg_mmd(const KgMmdArgs* a, void* stream);
 
+/* ---- inputs of one training iteration (additive, ABI v9; DESIGN.md 11, csrc/kg_input.hip) ---------------------------
+ * kg_step_inputs writes, in ONE launch, every input of iteration s = *step and then stores s + 1 (last workgroup).
+ * Batch: b = s mod batches_per_epoch, e = s div batches_per_epoch, row r_j = perm[(e & 1)*perm_stride + (b*world +
+ * rank)*B + j] (clamped into [0, n_rows)); real[j][c][t][v] = (data[r_j*d_sN + c*d_sC + t*d_sT + v*d_sV] * scale) +
+ * shift as two separately rounded fp32 operations; labels[j] = label_src[r_j].  data == NULL: no gather.
+ * Random: Philox4x32-10, key = seed (low, high word), counter = (q, stream + 4*rank, s low, s high), the four output
+ * words are elements 4q .. 4q+3 of the stream; uniform u = (word >> 8) * 2^-24; normals by Box-Muller on word pairs:
+ * sqrt(-2 log(1 - u0)) * (cos, sin)(2 pi u1).  z (B, latent) and alpha (B) are flat; noise plane i of the critic
+ * step's synthesis lies at noise + 2*P_i, of the generator step's at noise + 2*P_i + plane_len[i] (P_i = sum of the
+ * plane_len before i); a noise stream's element index counts through the synthesis' planes in order.
+ * kg_loss_append: ring[2k], ring[2k+1] = *d_loss, *g_loss, k = (*step - 1) mod ring_len; g_loss == NULL repeats the
+ * previous slot's g_loss (NaN for iteration 0).                                                                       */
+#define KG_STEP_MAX_PLANES 8
+#define KG_STREAM_Z 0
+#define KG_STREAM_ALPHA 1
+#define KG_STREAM_NOISE_D 2
+#define KG_STREAM_NOISE_G 3
+typedef struct KgStepInputsArgs {
+    int64_t* step;                  /* device: iteration counter                                                     */
+    int32_t* ticket;                /* device: one zeroed int32, left at zero                                        */
+    uint64_t seed;
+    int32_t rank, world;
+    int32_t B;
+    int32_t C, T, V;                /* sample shape of `real`                                                        */
+    const float* data;  int64_t d_sN, d_sC, d_sT, d_sV;    /* element strides                                       */
+    int64_t n_rows;
+    const int64_t* label_src;       /* (n_rows)                                                                      */
+    const int64_t* perm;  int64_t perm_stride;             /* (2, perm_stride)                                       */
+    int64_t batches_per_epoch;
+    float scale, shift;
+    float* real;                    /* (B, C, T, V) contiguous                                                       */
+    int64_t* labels;                /* (B)                                                                           */
+    float* z;  int32_t latent;      /* (B, latent) or NULL                                                           */
+    float* alpha;                   /* (B) or NULL                                                                   */
+    float* noise;  int32_t n_planes;  int64_t plane_len[KG_STEP_MAX_PLANES];   /* 2 * sum(plane_len) floats or NULL  */
+} KgStepInputsArgs;
+int kg_step_inputs(const KgStepInputsArgs* a, void* stream);
+int kg_loss_append(float* ring, int64_t ring_len, const int64_t* step, const float* d_loss, const float* g_loss,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -300,6 +300,22 @@ class _MmdArgs(C.Structure):
                 ("mmd2", c_f32p), ("mmd", c_f32p), ("result", c_f32p), ("mean", c_f32p),
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
+STEP_MAX_PLANES = 8
+STREAM_Z, STREAM_ALPHA, STREAM_NOISE_D, STREAM_NOISE_G = 0, 1, 2, 3
+
+
+class _StepInputsArgs(C.Structure):
+    _fields_ = [("step", C.c_void_p), ("ticket", C.c_void_p), ("seed", C.c_uint64),
+                ("rank", C.c_int32), ("world", C.c_int32), ("B", C.c_int32),
+                ("C", C.c_int32), ("T", C.c_int32), ("V", C.c_int32),
+                ("data", c_f32p), ("d_sN", C.c_int64), ("d_sC", C.c_int64), ("d_sT", C.c_int64), ("d_sV", C.c_int64),
+                ("n_rows", C.c_int64), ("label_src", C.c_void_p),
+                ("perm", C.c_void_p), ("perm_stride", C.c_int64), ("batches_per_epoch", C.c_int64),
+                ("scale", C.c_float), ("shift", C.c_float),
+                ("real", c_f32p), ("labels", C.c_void_p),
+                ("z", c_f32p), ("latent", C.c_int32), ("alpha", c_f32p),
+                ("noise", c_f32p), ("n_planes", C.c_int32), ("plane_len", C.c_int64 * STEP_MAX_PLANES)]
+
 GEN_ADJ_MAX_JOBS = 8
 
 EXPORTS = {
@@ -378,6 +394,8 @@ EXPORTS = {
                                C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p]),
     "kg_mmd_workspace_bytes": (C.c_int64, [C.POINTER(_MmdArgs)]),
     "kg_mmd": (C.c_int, [C.POINTER(_MmdArgs), C.c_void_p]),
+    "kg_step_inputs": (C.c_int, [C.POINTER(_StepInputsArgs), C.c_void_p]),
+    "kg_loss_append": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kg_adam_step_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                      C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
 }
@@ -2045,6 +2063,101 @@ def mmd(x: MmdView, y: MmdView, m: int, n: int, dim: int, groups: int, classes: 
     _count("kg_mmd", 3.0 * 2.0 * m * (m - 1) * dim * groups * classes)
     _check(lib.kg_mmd(C.byref(a), _stream()), "kg_mmd")
     return out
+
+
+# ---- inputs of a training iteration (kg_input.hip) ------------------------------------------------------------------------
+
+class StepData(NamedTuple):
+    """The resident gather of kg_step_inputs: ``data`` (N, C, T, V) fp32 (any strides), ``labels`` (N,) int64,
+    ``perm`` (2, perm_stride) int64 (the permutations of the even / odd epochs), outputs ``real`` (B, C, T, V) and
+    ``out_labels`` (B,)."""
+    data: torch.Tensor
+    labels: torch.Tensor
+    perm: torch.Tensor
+    batches_per_epoch: int
+    scale: float
+    shift: float
+    real: torch.Tensor
+    out_labels: torch.Tensor
+
+
+def noise_views(noise: torch.Tensor, plane_shapes: Sequence[Sequence[int]]):
+    """The (critic step, generator step) plane lists inside the flat ``noise`` buffer of kg_step_inputs: plane i of the
+    two syntheses are adjacent, so ``torch.cat((d_i, g_i))`` is the memory [2 P_i, 2 P_i + 2 len_i) itself."""
+    nd, ng, off = [], [], 0
+    for shp in plane_shapes:
+        n = 1
+        for v in shp:
+            n *= int(v)
+        nd.append(noise[off:off + n].view(*shp))
+        ng.append(noise[off + n:off + 2 * n].view(*shp))
+        off += 2 * n
+    assert off == noise.numel()
+    return nd, ng
+
+
+def step_inputs(step: torch.Tensor, ticket: torch.Tensor, seed: int, batch_size: int, z: Optional[torch.Tensor] = None,
+                alpha: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                plane_len: Sequence[int] = (), gather: Optional[StepData] = None, rank: int = 0, world: int = 1) -> None:
+    """Enqueue kg_step_inputs on the current stream: every input of iteration ``step[0]`` (device int64, advanced by the
+    launch) - the gathered batch, z (B, latent), alpha (B), the flat injected-noise buffer (``noise_views``)."""
+    lib = load_library()
+    _need_cuda(step, ticket, z, alpha, noise)
+    if step.dtype != torch.int64 or ticket.dtype != torch.int32:
+        raise TypeError("kg_step_inputs: step int64 and ticket int32 expected")
+    for t in (z, alpha, noise):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError("kg_step_inputs: contiguous fp32 outputs expected")
+    a = _StepInputsArgs()
+    a.step, a.ticket, a.seed = step.data_ptr(), ticket.data_ptr(), int(seed) & 0xffffffffffffffff
+    a.rank, a.world, a.B = int(rank), int(world), int(batch_size)
+    if z is not None:
+        if z.dim() != 2 or z.shape[0] != batch_size:
+            raise ValueError("kg_step_inputs: z must be (B, latent)")
+        a.z, a.latent = z.data_ptr(), z.shape[1]
+    if alpha is not None:
+        if alpha.numel() != batch_size:
+            raise ValueError("kg_step_inputs: alpha must hold B values")
+        a.alpha = alpha.data_ptr()
+    if noise is not None:
+        lens = [int(v) for v in plane_len]
+        if not 1 <= len(lens) <= STEP_MAX_PLANES or noise.numel() != 2 * sum(lens):
+            raise ValueError("kg_step_inputs: noise must hold 2 * sum(plane_len) values of 1..%d planes" % STEP_MAX_PLANES)
+        a.noise, a.n_planes = noise.data_ptr(), len(lens)
+        for i, v in enumerate(lens):
+            a.plane_len[i] = v
+    if gather is not None:
+        g = gather
+        _need_cuda(g.data, g.labels, g.perm, g.real, g.out_labels)
+        if g.data.dtype != torch.float32 or g.data.dim() != 4 or g.real.dtype != torch.float32 or not g.real.is_contiguous():
+            raise TypeError("kg_step_inputs: data (N, C, T, V) fp32 and a contiguous fp32 batch expected")
+        for t in (g.labels, g.perm, g.out_labels):
+            if t.dtype != torch.int64 or not t.is_contiguous():
+                raise TypeError("kg_step_inputs: contiguous int64 labels / perm expected")
+        n, c, t_, v = g.data.shape
+        need = int(g.batches_per_epoch) * int(world) * int(batch_size)
+        if tuple(g.real.shape) != (batch_size, c, t_, v) or g.out_labels.numel() != batch_size or g.labels.numel() != n or \
+                g.perm.dim() != 2 or g.perm.shape[0] != 2 or g.perm.shape[1] < need or min(g.data.stride()) < 0:
+            raise ValueError("kg_step_inputs: shapes of the gather do not fit together")
+        a.data = g.data.data_ptr()
+        a.d_sN, a.d_sC, a.d_sT, a.d_sV = g.data.stride()
+        a.C, a.T, a.V, a.n_rows = c, t_, v, n
+        a.label_src, a.perm, a.perm_stride = g.labels.data_ptr(), g.perm.data_ptr(), g.perm.shape[1]
+        a.batches_per_epoch, a.scale, a.shift = int(g.batches_per_epoch), float(g.scale), float(g.shift)
+        a.real, a.labels = g.real.data_ptr(), g.out_labels.data_ptr()
+    _check(lib.kg_step_inputs(C.byref(a), _stream()), "kg_step_inputs")
+
+
+def loss_append(ring: torch.Tensor, step: torch.Tensor, d_loss: torch.Tensor, g_loss: Optional[torch.Tensor]) -> None:
+    """Enqueue kg_loss_append: (d_loss, g_loss) into slot (step - 1) mod len of ``ring`` (len, 2) fp32."""
+    _need_cuda(ring, step, d_loss, g_loss)
+    if ring.dtype != torch.float32 or ring.dim() != 2 or ring.shape[1] != 2 or not ring.is_contiguous() or step.dtype != torch.int64:
+        raise TypeError("kg_loss_append: ring (len, 2) fp32 and step int64 expected")
+    for t in (d_loss, g_loss):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != 1):
+            raise TypeError("kg_loss_append: one-element fp32 losses expected")
+    _check(load_library().kg_loss_append(ring.data_ptr(), ring.shape[0], step.data_ptr(), d_loss.data_ptr(), _ptr(g_loss),
+                                         _stream()), "kg_loss_append")
 
 
 class Comm:

@@ -66,6 +66,16 @@ class Mapping_Net(nn.Module):
         return x
 
 
+def _cat_batch(a, b):
+    """torch.cat((a, b), 0); a view when b already follows a in memory (train.TrainLoop lays the two syntheses' noise
+    planes out that way: no copy launch per plane)"""
+    if a.is_contiguous() and b.is_contiguous() and a.shape == b.shape and a.dtype == b.dtype and a.device == b.device and \
+            a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr() and \
+            b.storage_offset() == a.storage_offset() + a.numel():
+        return a.as_strided((2 * a.shape[0],) + tuple(a.shape[1:]), a.stride())
+    return torch.cat((a, b), 0)
+
+
 class Generator(_GraphModule):
     def __init__(self, in_channels, out_channels, n_classes, t_size, mlp_dim=4,
                  edge_importance_weighting=True, dataset='ntu', **kwargs):
@@ -141,7 +151,7 @@ class Generator(_GraphModule):
         n = w.shape[0]
         if (noise_a is None) != (noise_b is None):
             raise ValueError("synthesis_pair: give both noise lists or neither")
-        noise = None if noise_a is None else [torch.cat((a, b), 0) for a, b in zip(noise_a, noise_b)]
+        noise = None if noise_a is None else [_cat_batch(a, b) for a, b in zip(noise_a, noise_b)]
         wd = w.detach()
         out, out_b = self.synthesis(torch.cat((wd, wd), 0), noise, w_b=w)
         return out[:n], out_b

@@ -1,0 +1,390 @@
+"""The training loop of the reference's main program (kinetic-gan.py:117-197) on replayed hipGraphs.
+
+One iteration is ONE graph replay.  The graph starts with ``kg_step_inputs`` (csrc/kg_input.hip): a single launch that
+gathers the batch of the iteration from the device-resident dataset through the epoch's permutation, normalises it,
+gathers its labels and draws every random input - latents, the penalty's interpolation weights, the injected noise of
+both generator syntheses - from a counter-based generator (Philox4x32-10) keyed by the seed and an iteration counter
+that lives in device memory and that the launch advances.  Then ``Trainer.iteration`` on those static buffers, then one
+launch that appends the two losses to a device ring.  A replay therefore needs no host work and no host-to-device
+traffic: the host only chooses between the two captured graphs - critic only, critic + generator (``i % n_critic == 0``
+with ``i`` the batch index inside the epoch, kinetic-gan.py:160) - and uploads the next epoch's permutation, one epoch
+ahead, on a side stream.
+
+``ResidentDataset``: the cropped raw samples (first person, first ``t_size`` frames, unnormalised) and the labels on
+the device.  A dataset that does not fit is streamed instead: ``DeviceBatches`` copies every batch into the same static
+buffers in front of the replay; the random inputs still come from the kernel.
+
+Definitions the tests pin this against: tests/train_def.py (numpy).  DESIGN.md 11.
+"""
+from __future__ import annotations
+
+import collections
+import os
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _native as nv
+from .checkpoint import AsyncCheckpointWriter
+from .feeder import DeviceBatches, Feeder
+from .sample import sample_actions
+from .wgan_gp import Trainer
+
+
+def update_pattern(batches_per_epoch: int, n_critic: int, n_steps: int, start: int = 0) -> List[bool]:
+    """with_g of iterations start .. start + n_steps - 1: the generator is updated when the batch index INSIDE the epoch
+    is a multiple of n_critic (kinetic-gan.py:160), so the pattern restarts with every epoch."""
+    return [((s % batches_per_epoch) % n_critic) == 0 for s in range(start, start + n_steps)]
+
+
+def epoch_permutation(n: int, seed: int, epoch: int, shuffle: bool = True) -> np.ndarray:
+    """The sample order of one epoch, exactly ``DeviceBatches._order``'s."""
+    idx = np.arange(n)
+    if shuffle:
+        np.random.RandomState(seed + epoch).shuffle(idx)
+    return idx
+
+
+def norm_constants(feeder: Feeder) -> Tuple[float, float]:
+    """(scale, shift) with 2 (x - min) / (max - min) - 1 == x * scale + shift, as ``DeviceBatches`` computes them."""
+    if not feeder.norm:
+        return 1.0, 0.0
+    span = float(feeder.max) - float(feeder.min)
+    return 2.0 / span, -2.0 * float(feeder.min) / span - 1.0
+
+
+class ResidentDataset:
+    """The dataset on the device: ``data`` (N, C, t, V) fp32 - cropped to ``t_size`` frames, first person of an NTU
+    array, NOT normalised (the gather normalises) - and ``labels`` (N,) int64.  ``fits`` is False (and nothing is
+    uploaded) when the cropped array is larger than ``max_bytes`` (default: half of the free device memory)."""
+
+    def __init__(self, feeder: Feeder, t_size: int, device, max_bytes: Optional[int] = None, chunk: int = 2048):
+        self.feeder = feeder
+        self.device = torch.device(device)
+        self.t = min(int(t_size), feeder.T)
+        self.n = len(feeder)
+        self.shape = (self.n, feeder.C, self.t, feeder.V)
+        self.nbytes = 4 * self.n * feeder.C * self.t * feeder.V
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(self.device)[0] // 2
+        self.fits = self.nbytes <= int(max_bytes)
+        self.scale, self.shift = norm_constants(feeder)
+        self.data = self.labels = None
+        if not self.fits:
+            return
+        self.data = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        stage = [torch.empty((chunk,) + self.shape[1:], dtype=torch.float32, pin_memory=True) for _ in range(2)]
+        done = [None, None]
+        for k, lo in enumerate(range(0, self.n, chunk)):
+            hi, slot = min(self.n, lo + chunk), k & 1
+            if done[slot] is not None:
+                done[slot].synchronize()
+            src = feeder.data[lo:hi, :, :self.t, :, 0] if feeder.dataset == 'ntu' else feeder.data[lo:hi, :, :self.t]
+            stage[slot].numpy()[:hi - lo] = src
+            self.data[lo:hi].copy_(stage[slot][:hi - lo], non_blocking=True)
+            done[slot] = torch.cuda.Event()
+            done[slot].record()
+        self.labels = torch.as_tensor(np.asarray(feeder.label, dtype=np.int64)).to(self.device)
+        torch.cuda.synchronize(self.device)
+
+
+def _capture(fn, before_capture=None, warmup: int = 3):
+    """fn() as a hipGraph: allocator warm-up on a side stream, then a thread-local capture (other threads of the process
+    - a checkpoint writer, a collective's watchdog - cannot invalidate it).  ``before_capture`` runs between the two."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(warmup):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    if before_capture is not None:
+        before_capture()
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        fn()
+    torch.cuda.synchronize()
+    return graph
+
+
+class TrainLoop:
+    """``data``: a ``Feeder`` (made resident if it fits ``max_resident_bytes``, else streamed) or a ``ResidentDataset``.
+    ``step()`` runs one iteration (a graph replay; with ``use_graph=False`` the same launches eagerly); ``run()`` is the
+    reference's loop with its side effects; ``state_dict()`` / ``load_state_dict()`` resume a run bit for bit."""
+
+    def __init__(self, G, D, data, batch_size: int, t_size: int, n_critic: int = 5, seed: int = 0, lr: float = 2e-4,
+                 b1: float = 0.5, b2: float = 0.999, lambda_gp: float = 10.0, use_graph: bool = True,
+                 ring_len: int = 4096, max_resident_bytes: Optional[int] = None, rank: int = 0, world: int = 1,
+                 run_ahead: int = 16):
+        self.G, self.D = G, D
+        self.device = next(G.parameters()).device
+        if self.device.type != "cuda":
+            raise RuntimeError("TrainLoop runs on the GPU only (there is no CPU fallback)")
+        if world > 1 and use_graph:
+            raise NotImplementedError("TrainLoop: the data-parallel loop is not captured (use_graph=False runs it eagerly)")
+        self.B, self.n_critic, self.seed = int(batch_size), int(n_critic), int(seed)
+        self.rank, self.world, self.use_graph = int(rank), int(world), bool(use_graph)
+        if isinstance(data, ResidentDataset):
+            self.resident, feeder = data, data.feeder
+        else:
+            feeder = data
+            self.resident = ResidentDataset(feeder, t_size, self.device, max_resident_bytes)
+        self.feeder = feeder
+        self.streaming = not self.resident.fits
+        self.t = self.resident.t
+        self.n = len(feeder)
+        self.bpe = (self.n // self.B) // self.world          # batches of one epoch per rank, tail dropped
+        if self.bpe < 1:
+            raise ValueError("TrainLoop: the dataset holds fewer than batch_size * world samples")
+        self.trainer = Trainer(G, D, lr=lr, b1=b1, b2=b2, lambda_gp=lambda_gp, n_critic=n_critic, world_size=self.world)
+        dev, B = self.device, self.B
+        self.latent = G.mlp.mlp[0].in_features - G.label_emb.num_embeddings
+        self.n_classes = G.label_emb.num_embeddings
+        # static inputs of the captured iteration
+        self.real = torch.zeros((B, feeder.C, self.t, feeder.V), dtype=torch.float32, device=dev)
+        self.labels = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.z = torch.zeros((B, self.latent), dtype=torch.float32, device=dev)
+        self.alpha = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.plane_shapes = [(B, 1, gcn.up_t, G.graph.num_node[gcn.lvl]) for gcn in G.st_gcn_networks]
+        self.plane_len = [int(np.prod(s)) for s in self.plane_shapes]
+        self.noise = torch.zeros(2 * sum(self.plane_len), dtype=torch.float32, device=dev)
+        self.noise_d, self.noise_g = nv.noise_views(self.noise, self.plane_shapes)
+        self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.ring_len = int(ring_len)
+        self.ring = torch.full((self.ring_len, 2), float("nan"), dtype=torch.float32, device=dev)
+        self.step_count = 0                  # host mirror of step_dev
+        # the host enqueues at most ~run_ahead iterations ahead of the device (an event every run_ahead / 2 iterations,
+        # the host waits for the one before last): a queue filled to its limit replays measurably slower
+        self.run_ahead = max(2, int(run_ahead))
+        self._marks = collections.deque()
+        self._flushed = 0                    # iterations whose losses have been read from the ring
+        self._first = 0                      # iteration the loss record starts at (a resumed run: where it resumed)
+        self._d_hist: List[np.ndarray] = []
+        self._g_hist: List[np.ndarray] = []
+        self._graphs: Dict[bool, object] = {}
+        self._perm_epochs = [None, None]     # epoch held by each slot of the device permutation
+        self._gather = None
+        self._batches = self._batch_iter = None
+        if self.streaming:
+            self._batches = DeviceBatches(feeder, B, self.t, dev, seed=self.seed, rank=self.rank, world=self.world)
+        else:
+            r = self.resident
+            plen = self.bpe * self.world * B
+            self._perm = torch.zeros((2, plen), dtype=torch.int64, device=dev)
+            self._perm_host = [torch.empty(plen, dtype=torch.int64, pin_memory=True) for _ in range(2)]
+            self._perm_done = [None, None]
+            self._perm_wait = [False, False]
+            self._copy_stream = torch.cuda.Stream(device=dev)
+            self._gather = nv.StepData(r.data, r.labels, self._perm, self.bpe, r.scale, r.shift, self.real, self.labels)
+
+    # ---- schedule ------------------------------------------------------------------------------------------------
+    @property
+    def epoch(self) -> int:
+        return self.step_count // self.bpe
+
+    def with_g(self, step: Optional[int] = None) -> bool:
+        s = self.step_count if step is None else step
+        return ((s % self.bpe) % self.n_critic) == 0
+
+    # ---- the iteration ---------------------------------------------------------------------------------------------
+    def _iteration(self, with_g: bool):
+        """kg_step_inputs, the WGAN-GP iteration on the static buffers, the loss record: what a graph holds"""
+        nv.step_inputs(self.step_dev, self._ticket, self.seed, self.B, z=self.z, alpha=self.alpha, noise=self.noise,
+                       plane_len=self.plane_len, gather=self._gather, rank=self.rank, world=self.world)
+        d_loss, g_loss = self.trainer.iteration(self.real, self.labels, self.z, self.alpha.view(-1, 1, 1, 1),
+                                                self.noise_d, self.noise_g if with_g else None, with_g=with_g)
+        nv.loss_append(self.ring, self.step_dev, d_loss, g_loss)
+
+    def _state_tensors(self) -> List[torch.Tensor]:
+        tr = self.trainer
+        ts = [self.step_dev, self.ring, self.real, self.labels, self.z, self.alpha, self.noise]
+        for f in (tr.fG, tr.fD):
+            ts += [f.flat, f.grad, f.exp_avg, f.exp_avg_sq, f.step]
+        for m in (self.G, self.D):
+            ts += list(m.buffers())
+        return ts
+
+    def _graph(self, with_g: bool):
+        """The captured iteration.  The warm-up calls in front of a capture are real iterations: everything they move
+        (parameters, optimiser state, BatchNorm statistics, the counter, the ring) is put back afterwards."""
+        g = self._graphs.get(with_g)
+        if g is not None:
+            return g
+        torch.cuda.synchronize(self.device)          # (a permutation upload in flight included)
+        ts = self._state_tensors()
+        keep = [t.clone() for t in ts]
+        tr = self.trainer
+
+        def drop_warmup_graph():
+            # a sample the last warm-up call left behind would keep its autograd graph (created on the warm-up stream)
+            tr._w = tr._fake_g = None
+        g = _capture(lambda: self._iteration(with_g), before_capture=drop_warmup_graph)
+        for t, k in zip(ts, keep):
+            t.copy_(k)
+        torch.cuda.synchronize(self.device)
+        self._graphs[with_g] = g
+        return g
+
+    def _upload_perm(self, epoch: int):
+        """permutation of `epoch` into slot epoch & 1 on the copy stream, behind the work enqueued so far (replays that
+        still read the slot's previous epoch); the training stream waits for it when it first needs the slot"""
+        slot = epoch & 1
+        if self._perm_done[slot] is not None:
+            self._perm_done[slot].synchronize()              # the pinned buffer's last copy (an epoch ago)
+        idx = epoch_permutation(self.n, self.seed, epoch)
+        self._perm_host[slot].numpy()[:] = idx[:self._perm.shape[1]]
+        self._copy_stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self._copy_stream):
+            self._perm[slot].copy_(self._perm_host[slot], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self._copy_stream)
+        self._perm_done[slot] = ev
+        self._perm_epochs[slot] = epoch
+        self._perm_wait[slot] = True
+
+    def _feed(self):
+        """host work in front of an iteration: none inside an epoch on the resident path"""
+        epoch, i = divmod(self.step_count, self.bpe)
+        if self.streaming:
+            if self._batch_iter is None:
+                self._batches.epoch = epoch
+                self._batch_iter = iter(self._batches)
+                for _ in range(i):
+                    next(self._batch_iter)
+            x, y = next(self._batch_iter)
+            self.real.copy_(x)
+            self.labels.copy_(y)
+            if i == self.bpe - 1:
+                self._batch_iter = None
+            return
+        if self._perm_epochs[epoch & 1] != epoch:            # first iteration of a (resumed) run
+            self._upload_perm(epoch)
+        if self._perm_epochs[(epoch + 1) & 1] != epoch + 1:
+            # one epoch ahead (normally at i == 0): every replay of the epoch this slot held has been enqueued
+            self._upload_perm(epoch + 1)
+        if self._perm_wait[epoch & 1]:
+            torch.cuda.current_stream(self.device).wait_event(self._perm_done[epoch & 1])
+            self._perm_wait[epoch & 1] = False
+
+    def step(self) -> None:
+        """One iteration; no host synchronisation (the losses stay in the device ring until ``losses()``)."""
+        if self.step_count - self._flushed >= self.ring_len:
+            self._flush()                    # the ring is full: one bulk read per ring_len iterations at the most
+        if self.step_count % (self.run_ahead // 2) == 0:
+            if len(self._marks) >= 2:
+                self._marks.popleft().synchronize()      # long complete unless the host is run_ahead iterations ahead
+            ev = torch.cuda.Event()
+            ev.record()
+            self._marks.append(ev)
+        self._feed()
+        wg = self.with_g()
+        if self.use_graph:
+            self._graph(wg).replay()
+        else:
+            self._iteration(wg)
+        self.step_count += 1
+
+    # ---- losses ----------------------------------------------------------------------------------------------------
+    def _flush(self):
+        n = self.step_count - self._flushed
+        if n <= 0:
+            return
+        ring = self.ring.cpu().numpy()       # ONE device -> host read
+        slots = (np.arange(self._flushed, self.step_count)) % self.ring_len
+        self._d_hist.append(ring[slots, 0].copy())
+        self._g_hist.append(ring[slots, 1].copy())
+        self._flushed = self.step_count
+
+    def losses(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(d_loss, g_loss) of every iteration since the run (or its resumption) began; an iteration without generator
+        step repeats the last g_loss, as the reference's record does.  Synchronises."""
+        self._flush()
+        cat = lambda h: np.concatenate(h) if h else np.zeros(0, dtype=np.float32)      # noqa: E731
+        return cat(self._d_hist), cat(self._g_hist)
+
+    # ---- resume ----------------------------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """Everything a bit-exact continuation needs, on the host."""
+        self._flush()
+        tr = self.trainer
+        out = {"step": self.step_count, "epoch": self.epoch, "seed": self.seed, "n_critic": self.n_critic,
+               "batch_size": self.B, "batches_per_epoch": self.bpe,
+               "last_losses": self.ring[(self.step_count - 1) % self.ring_len].cpu() if self.step_count else None}
+        for name, f, m in (("G", tr.fG, self.G), ("D", tr.fD, self.D)):
+            out[name] = {"flat": f.flat.cpu(), "exp_avg": f.exp_avg.cpu(), "exp_avg_sq": f.exp_avg_sq.cpu(),
+                         "adam_step": f.step.cpu(), "buffers": {k: b.cpu() for k, b in m.named_buffers()}}
+        return out
+
+    def load_state_dict(self, sd: dict) -> None:
+        for k, mine in (("seed", self.seed), ("n_critic", self.n_critic), ("batch_size", self.B), ("batches_per_epoch", self.bpe)):
+            if sd[k] != mine:
+                raise ValueError("TrainLoop.load_state_dict: %s is %r in the checkpoint, %r here" % (k, sd[k], mine))
+        tr = self.trainer
+        for name, f, m in (("G", tr.fG, self.G), ("D", tr.fD, self.D)):
+            s = sd[name]
+            f.flat.copy_(s["flat"])
+            f.exp_avg.copy_(s["exp_avg"])
+            f.exp_avg_sq.copy_(s["exp_avg_sq"])
+            f.step.copy_(s["adam_step"])
+            f.grad.zero_()
+            bufs = dict(m.named_buffers())
+            if set(bufs) != set(s["buffers"]):
+                raise ValueError("TrainLoop.load_state_dict: buffers of %s do not match" % name)
+            for k, b in bufs.items():
+                b.copy_(s["buffers"][k])
+        self.step_count = self._flushed = self._first = int(sd["step"])
+        self._d_hist, self._g_hist = [], []
+        self.step_dev.fill_(self.step_count)
+        if sd.get("last_losses") is not None:
+            self.ring[(self.step_count - 1) % self.ring_len].copy_(sd["last_losses"])
+        self._batch_iter = None
+        torch.cuda.synchronize(self.device)
+
+    # ---- the reference's loop ------------------------------------------------------------------------------------------
+    def sample_action(self, path: str) -> None:
+        """kinetic-gan.py:84-91: 10 samples per class, labels 0 .. n_classes-1 repeated, saved as one .npy"""
+        imgs, _, _ = sample_actions(self.G, self.n_classes, self.latent, gen_qtd=10, qtd=10)
+        with open(path, "wb") as f:
+            np.save(f, imgs.cpu().numpy())
+
+    def save_losses(self, path: str) -> None:
+        from scipy.io import savemat
+        d, g = self.losses()
+        savemat(path, {"d_loss": d, "g_loss": g})
+
+    def run(self, n_epochs: int, sample_interval: int = 5000, checkpoint_interval: int = 10000, out_dir: str = "runs",
+            log_interval: int = 100, log=print, state_path: Optional[str] = None) -> None:
+        """Epochs ``self.epoch .. n_epochs - 1`` with the reference's side effects (kinetic-gan.py:176-197), none of them
+        on the timed path: the progress line - printed every ``log_interval`` iterations from ONE bulk read of the loss
+        ring -, ``actions/<batches_done>.npy`` and ``plot_loss.mat`` every ``sample_interval`` iterations, both networks'
+        checkpoints (``models/generator_<batches_done>.pth``, written in the background) every ``checkpoint_interval``.
+        ``state_path``: ``state_dict()`` is saved there with every checkpoint and at the end (``load_state_dict`` of that
+        file continues the run bit for bit)."""
+        models_out, actions_out = os.path.join(out_dir, "models"), os.path.join(out_dir, "actions")
+        os.makedirs(models_out, exist_ok=True)
+        os.makedirs(actions_out, exist_ok=True)
+        log_interval = max(1, min(int(log_interval), self.ring_len))
+        writer = AsyncCheckpointWriter()
+        try:
+            while self.step_count < n_epochs * self.bpe:
+                batches_done = self.step_count
+                epoch, i = divmod(batches_done, self.bpe)
+                self.step()
+                if (batches_done + 1) % log_interval == 0 or batches_done + 1 == n_epochs * self.bpe:
+                    d, g = self.losses()
+                    log("[Epoch %d/%d] [Batch %d/%d] [D loss: %f] [G loss: %f]" % (epoch, n_epochs, i, self.bpe, d[-1], g[-1]))
+                if batches_done % sample_interval == 0:
+                    self.sample_action(os.path.join(actions_out, "%d.npy" % batches_done))
+                    self.save_losses(os.path.join(out_dir, "plot_loss.mat"))
+                if checkpoint_interval != -1 and batches_done % checkpoint_interval == 0:
+                    writer.save(self.G, os.path.join(models_out, "generator_%d.pth" % batches_done))
+                    writer.save(self.D, os.path.join(models_out, "discriminator_%d.pth" % batches_done))
+                    if state_path is not None:
+                        torch.save(self.state_dict(), state_path)
+            self.save_losses(os.path.join(out_dir, "plot_loss.mat"))
+            if state_path is not None:
+                torch.save(self.state_dict(), state_path)
+        finally:
+            writer.close()

@@ -1,0 +1,81 @@
+#!/usr/bin/env python
+"""The reference's training program (kinetic-gan.py) on ``kinetic_gan_amd.train.TrainLoop``: same flags, same progress
+line, same outputs (``<out>/actions/<batches_done>.npy``, ``<out>/plot_loss.mat``, ``<out>/models/generator_<n>.pth`` /
+``discriminator_<n>.pth``) - every iteration one hipGraph replay whose first launch draws the iteration's batch and
+random inputs on the device.  Extra flags: ``--seed`` (shuffling and every random input), ``--resume FILE`` (a
+``loop_state.pth`` written by an earlier run: continues it bit for bit), ``--no-graph`` (the same launches, eagerly),
+``--out``, ``--log_interval``."""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import kinetic_gan_amd  # noqa: E402,F401
+from kinetic_gan_amd.discriminator import Discriminator  # noqa: E402
+from kinetic_gan_amd.feeder import Feeder  # noqa: E402
+from kinetic_gan_amd.generator import Generator  # noqa: E402
+from kinetic_gan_amd.train import TrainLoop  # noqa: E402
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--n_epochs", type=int, default=1200, help="number of epochs of training")
+    p.add_argument("--batch_size", type=int, default=32, help="size of the batches")
+    p.add_argument("--lr", type=float, default=0.0002, help="adam: learning rate")
+    p.add_argument("--b1", type=float, default=0.5, help="adam: decay of first order momentum of gradient")
+    p.add_argument("--b2", type=float, default=0.999, help="adam: decay of first order momentum of gradient")
+    p.add_argument("--n_cpu", type=int, default=8, help="accepted for compatibility (batches are gathered on the device)")
+    p.add_argument("--latent_dim", type=int, default=512, help="dimensionality of the latent space")
+    p.add_argument("--mlp_dim", type=int, default=4, help="mapping network depth")
+    p.add_argument("--n_classes", type=int, default=60, help="number of classes for dataset")
+    p.add_argument("--t_size", type=int, default=64, help="size of each temporal dimension")
+    p.add_argument("--v_size", type=int, default=25, help="size of each spatial dimension (vertices)")
+    p.add_argument("--channels", type=int, default=3, help="number of channels (coordinates)")
+    p.add_argument("--n_critic", type=int, default=5, help="number of training steps for discriminator per generator's iteration")
+    p.add_argument("--lambda_gp", type=int, default=10, help="Loss weight for gradient penalty in WGAN-GP Loss")
+    p.add_argument("--sample_interval", type=int, default=5000, help="interval between action sampling")
+    p.add_argument("--checkpoint_interval", type=int, default=10000, help="interval between model saving")
+    p.add_argument("--dataset", type=str, default="ntu", help="dataset")
+    p.add_argument("--data_path", type=str, required=True, help="path to data")
+    p.add_argument("--label_path", type=str, required=True, help="path to label")
+    p.add_argument("--seed", type=int, default=0, help="seed of the epoch permutations and of every random input")
+    p.add_argument("--resume", type=str, default=None, help="loop_state.pth of an earlier run to continue")
+    p.add_argument("--no-graph", action="store_true", help="run the iteration eagerly instead of replaying hipGraphs")
+    p.add_argument("--out", type=str, default="runs/kinetic-gan", help="run directory")
+    p.add_argument("--log_interval", type=int, default=100, help="iterations between progress lines (one loss read each)")
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    opt = parse_args(argv)
+    print(opt)
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/train.py needs a GPU (there is no CPU fallback)")
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    os.makedirs(opt.out, exist_ok=True)
+    with open(os.path.join(opt.out, "config.txt"), "w") as f:
+        f.write(os.path.basename(__file__) + "|" + str(opt))
+    torch.manual_seed(opt.seed)
+    G = Generator(opt.latent_dim, opt.channels, opt.n_classes, opt.t_size, opt.mlp_dim, dataset=opt.dataset).to(dev)
+    D = Discriminator(opt.channels, opt.n_classes, opt.t_size, opt.latent_dim, dataset=opt.dataset).to(dev)
+    feeder = Feeder(opt.data_path, opt.label_path, dataset=opt.dataset)
+    if feeder.V != opt.v_size or feeder.C != opt.channels:
+        raise SystemExit("data is (C=%d, V=%d) but --channels %d --v_size %d" % (feeder.C, feeder.V, opt.channels, opt.v_size))
+    loop = TrainLoop(G, D, feeder, opt.batch_size, opt.t_size, n_critic=opt.n_critic, seed=opt.seed, lr=opt.lr, b1=opt.b1,
+                     b2=opt.b2, lambda_gp=float(opt.lambda_gp), use_graph=not opt.no_graph,
+                     ring_len=max(4096, opt.log_interval))
+    print("dataset: %d samples, %d batches per epoch, %s (%.1f MB cropped)" % (
+        len(feeder), loop.bpe, "streamed" if loop.streaming else "resident on the device", loop.resident.nbytes / 1e6))
+    if opt.resume:
+        loop.load_state_dict(torch.load(opt.resume, weights_only=False))
+        print("resumed at iteration %d (epoch %d)" % (loop.step_count, loop.epoch))
+    loop.run(opt.n_epochs, opt.sample_interval, opt.checkpoint_interval, opt.out, log_interval=opt.log_interval,
+             state_path=os.path.join(opt.out, "loop_state.pth"))
+
+
+if __name__ == "__main__":
+    main()
