@@ -574,6 +574,14 @@ typedef struct KgLabelBiasArgs {
 int     kg_label_bias_fwd(const KgLabelBiasArgs* a, void* stream);
 int64_t kg_label_bias_workspace_bytes(const KgLabelBiasArgs* a);
 int     kg_label_bias_bwd(const KgLabelBiasArgs* a, void* stream);
+/* kg_aggconv_label: block 0's gcn with its label bias in ONE launch - the output of
+ *     kg_label_bias_fwd(lb) -> zl;  kg_aggconv(a with add = zl, a_sN = C*W, a_sC = W, a_tstride = 0)
+ * without the zl tensor, the workspace or the class-table launch (discriminator.py:57-60, tgcn.py:58-68): every
+ * workgroup forms the bias of its sample's class from lb->emb, the label columns lb->w and the column sums of a->a
+ * (lb->ak, lb->zl and lb->ws are not read).  Tiny-channel geometry only (K <= 3, Cin <= 4, M <= 64, W <= 32, K*V*W <= 4096;
+ * K*M*J <= 12288, J <= 512); a->add must be NULL; lb->{N, K, C, V, W} must equal a->{N, K, M, V, W}.  A label outside
+ * [0, L) turns that sample's output into NaN.  The aggregated planes are written when a->xa is given.               */
+int     kg_aggconv_label(const KgAggConvArgs* a, const KgLabelBiasArgs* lb, void* stream);
 
 /* kg_mix3: out (3N, C, T, V) = [real | fake | alpha[n] real + (1 - alpha[n]) fake] - the three batches the critic step
  * runs D on (kinetic-gan.py:97-99,146-148) as one tensor.                                                            */

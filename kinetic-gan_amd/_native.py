@@ -368,6 +368,7 @@ EXPORTS = {
     "kg_label_bias_fwd": (C.c_int, [C.POINTER(_LabelBiasArgs), C.c_void_p]),
     "kg_label_bias_workspace_bytes": (C.c_int64, [C.POINTER(_LabelBiasArgs)]),
     "kg_label_bias_bwd": (C.c_int, [C.POINTER(_LabelBiasArgs), C.c_void_p]),
+    "kg_aggconv_label": (C.c_int, [C.POINTER(_AggConvArgs), C.POINTER(_LabelBiasArgs), C.c_void_p]),
     "kg_mix3": (C.c_int, [C.POINTER(_MixArgs), C.c_void_p]),
     "kg_masked_adj_fwd": (C.c_int, [C.POINTER(_MaskedAdjArgs), C.c_void_p]),
     "kg_masked_adj_bwd": (C.c_int, [C.POINTER(_MaskedAdjArgs), C.c_void_p]),
@@ -862,6 +863,13 @@ def aggconv(x: torch.Tensor, A: torch.Tensor, nbr: torch.Tensor, pcount, w: torc
     """out = sum_k W_k (x A_k) (+ add) in one launch (kg_aggconv); returns (out, xa | None), xa = the aggregated
     planes (N, K*Cin, T, W) when want_xa.  nbr: (K, W, 4) int32 neighbour table of A's fixed sparsity pattern."""
     lib = load_library()
+    a, out, xa, flops, _keep = _aggconv_args(x, A, nbr, pcount, w, wv, M, add, add_tstride, want_xa)
+    _count("kg_aggconv", flops)
+    _check(lib.kg_aggconv(C.byref(a), _stream()), "kg_aggconv")
+    return out, xa
+
+
+def _aggconv_args(x, A, nbr, pcount, w, wv, M, add, add_tstride, want_xa):
     x = as_plane(x)
     k, va, wd = A.shape
     A, tr = _adjacency(A)
@@ -892,8 +900,32 @@ def aggconv(x: torch.Tensor, A: torch.Tensor, nbr: torch.Tensor, pcount, w: torc
         xa = new_plane(n, k * c, t, wd, x.device)
         a.xa = xa.data_ptr()
         a.xa_sN, a.xa_sC = _sn_sc(xa)
-    _count("kg_aggconv", 2.0 * M * k * c * n * t * wd)
-    _check(lib.kg_aggconv(C.byref(a), _stream()), "kg_aggconv")
+    # (the operands are returned with the args: x / A / w / add may be converted copies that must outlive the launch)
+    return a, out, xa, 2.0 * M * k * c * n * t * wd, (x, A, w, add)
+
+
+def aggconv_label_supported(K: int, Cin: int, M: int, V: int, W: int, J: int) -> bool:
+    """Geometries kg_aggconv_label takes (the tiny-channel form of kg_aggconv; mirrors its checks)."""
+    return K <= 3 and Cin <= 4 and M <= 64 and W <= 32 and K * V * W <= 4096 and 0 < J <= 512 and K * M * J <= 12288
+
+
+def aggconv_label(x: torch.Tensor, A: torch.Tensor, nbr: torch.Tensor, pcount, w: torch.Tensor, wv: WView, M: int,
+                  labels: torch.Tensor, emb: torch.Tensor, wg: torch.Tensor, cin: int, J: int, want_xa: bool = False):
+    """Block 0's gcn with its label bias in ONE launch (kg_aggconv_label): the result of
+    aggconv(x, A, nbr, pcount, w, wv, M, add=label_bias_fwd(labels, emb, wg, K, M, cin, J, A), add_tstride=0, want_xa)
+    without the bias tensor or the class-table launch.  wg: the whole gcn weight (K*M, cin, 1, 1) - its first J input
+    columns multiply the label channels; w / wv address its data columns.  Returns (out, xa | None)."""
+    lib = load_library()
+    _need_cuda(labels, emb, wg)
+    a, out, xa, flops, _keep = _aggconv_args(x, A, nbr, pcount, w, wv, M, None, 0, want_xa)
+    lb = _LabelBiasArgs()
+    lb.N, lb.L, lb.J, lb.K, lb.C, lb.V, lb.W = a.N, emb.shape[0], J, a.K, M, a.V, a.W
+    assert emb.is_contiguous() and emb.shape[1] == J and labels.dtype == torch.int64 and labels.is_contiguous()
+    assert labels.numel() == a.N and wg.is_contiguous() and wg.numel() == a.K * M * cin
+    lb.labels, lb.emb = labels.data_ptr(), emb.data_ptr()
+    lb.w, lb.w_sK, lb.w_sC = wg.data_ptr(), M * cin, cin
+    _count("kg_aggconv", flops)
+    _check(lib.kg_aggconv_label(C.byref(a), C.byref(lb), _stream()), "kg_aggconv_label")
     return out, xa
 
 

@@ -294,63 +294,148 @@ __global__ __launch_bounds__(64 * NW * KS) void kg_aggconv_kernel(const KgAggCon
 }
 
 // Tiny-channel form (discriminator block 0: 3 data channels x 3 partitions = 9 aggregated values per column, 32 output
-// rows): the 32 x 128 MFMA tile contracts over a 16-channel slice of which 3 are real, and the launch - 0.08 GFLOP - took
-// 43 us at 192 samples.  Here a thread owns ONE output column: it aggregates its K * Cin values from the (L1-resident)
-// source frame with the column's neighbour list, multiplies them with the weights broadcast from LDS and writes the M
-// outputs (and the aggregated planes, if asked): a streaming VALU kernel bound by its 17 MB of output stores.
+// rows): the 32 x 128 MFMA tile contracts over a 16-channel slice of which 3 are real.  Here a workgroup owns 256 / RG
+// consecutive output columns of ONE sample and RG threads own a column (1 / RG of its output rows each): a thread
+// aggregates the column's K * Cin values from the (L1-resident) source frame with the column's neighbour list,
+// multiplies them with the weights broadcast from LDS and writes its rows (and the aggregated planes, if asked).
+// Everything the columns share - weights, the adjacency, the neighbour table and, for kg_aggconv_label, the label
+// columns of the gcn weight and the sample's class embedding - is staged with ONE round of independent loads and one
+// barrier; the feature gathers are in flight while the label bias is formed.  (The form before chained neighbour
+// index -> adjacency value -> features as three dependent global loads and repeated the aggregation in every one of
+// its four 8-row groups.)  The launch is latency-bound - one or two waves per SIMD at 64 samples - so what counts is
+// the length of a thread's instruction stream: no run-time divisions (FastDiv), no per-workgroup tables beyond one
+// barrier.
+// LB (kg_aggconv_label, discriminator block 0): the label channels' bias of the workgroup's sample is formed in the
+// launch, in the arithmetic order of kg_label_bias_table_kernel (kg_disc.hip) - P[k,m] = Wc(k,m,:) . E[label,:] as four
+// chains, S[k,w] = sum_v A[k,v,w] in vertex order, bias[m,w] = sum_k S[k,w] P[k,m] - and added where `add` would be:
+// the result is bit-identical to kg_label_bias_fwd + kg_aggconv.
 constexpr int AT_MAXM = 64, AT_K = 3, AT_C = 4;      // <= 3 partitions x <= 4 input channels
+constexpr int AT_NT = 256;
+constexpr int AT_MAXA = 4096;                        // floats of the staged adjacency (K * V * W)
+constexpr int AT_MAXWC = 12288, AT_MAXJ = 512;       // label columns of the gcn weight (K * M * J), embedding width
+constexpr int AT_NB = 6;                             // neighbour slots of a column: 1 + 4 + 1 (validate: pcount <= 1 / 4 / 1)
+constexpr int AT_P0[3] = {0, 1, 5}, AT_PN[3] = {1, 4, 1};
 
-// (every private array is indexed with compile-time constants only - loops over K / Cin are unrolled to their maxima
-// and predicated: a runtime index would put the arrays in scratch memory)
-template <int MT>
-__global__ __launch_bounds__(256, 4) void kg_aggconv_tiny_kernel(const KgAggConvArgs a) {
+struct AtPlan {
+    FastDiv fc, fw, fm;                              // x / (workgroups per sample), x / W, x / M
+};
+
+__device__ __forceinline__ float at_adj(const KgAggConvArgs& a, const float* As, int k, int v, int w) {
+    return a.a_transposed ? As[(k * a.W + w) * a.V + v] : As[(k * a.V + v) * a.W + w];
+}
+
+// (every private array is indexed with compile-time constants only - loops over K / Cin / neighbours are unrolled to
+// their maxima and predicated: a run-time index would put the arrays in scratch memory)
+template <int MT, int RG, bool LB>
+__global__ __launch_bounds__(AT_NT) void kg_aggconv_tiny_kernel(const KgAggConvArgs a, const KgLabelBiasArgs lb, const AtPlan pl) {
+    constexpr int BC = AT_NT / RG;                   // columns per workgroup
+    constexpr int MR = MT / RG;                      // output rows per thread
+    static_assert(MR % 8 == 0, "row chunks of 8");
     __shared__ float Wl[AT_K * AT_C][MT];
-    __shared__ float Av[AT_K * 32 * PMAX];
     __shared__ int Nb[AT_K * 32 * PMAX];
-    const int tid = threadIdx.x;
-    for (int e = tid; e < AT_K * AT_C * MT; e += 256) {
+    __shared__ float S[LB ? AT_K * 32 : 1], P[LB ? AT_K * MT : 1];
+    extern __shared__ float kg_atsm[];
+    float* const As = kg_atsm;                       // the adjacency as stored, K * V * W
+    const int nA = a.K * a.V * a.W;
+    float* const Wcs = kg_atsm + ((nA + 3) & ~3);    // LB: Wc(k, m, j) at (k * M + m) * J + j
+    float* const El = Wcs + (LB ? a.K * a.M * lb.J : 0);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = (int)pl.fc.div(blockIdx.x), chunk = blockIdx.x - n * (int)pl.fc.d;
+
+    // ---- staging: one round of independent loads
+    for (int e = tid; e < nA; e += AT_NT) As[e] = a.a[e];
+    for (int e = tid; e < AT_K * AT_C * MT; e += AT_NT) {
         const int kc = e / MT, m = e - kc * MT;
         const int k = kc / AT_C, c = kc - k * AT_C;
         Wl[kc][m] = (m < a.M && k < a.K && c < a.Cin) ? a.w[(long)k * a.w_sT + (long)m * a.w_sO + (long)c * a.w_sI] : 0.f;
     }
-    // the column's neighbour list and adjacency values come from LDS: read per column from global memory they are two
-    // more levels of dependent loads in front of the feature loads
-    for (int e = tid; e < a.K * a.W * PMAX; e += 256) {
-        const int kw = e / PMAX, p = e - kw * PMAX;
-        const int k = kw / a.W, w = kw - k * a.W;
-        int v = p < a.pcount[k] ? a.nbr[e] : -1;
-        float av = 0.f;
-        if (v >= 0) av = a.a_transposed ? a.a[((long)k * a.W + w) * a.V + v] : a.a[((long)k * a.V + v) * a.W + w];
-        Nb[e] = v < 0 ? 0 : v;
-        Av[e] = av;                                    // (absent neighbour: weight 0 on vertex 0)
+    for (int e = tid; e < a.K * a.W * PMAX; e += AT_NT) {
+        const int k = (int)pl.fw.div((unsigned)e >> 2), p = e & (PMAX - 1);
+        Nb[e] = p < a.pcount[k] ? a.nbr[e] : -1;
+    }
+    // a label outside [0, L) poisons its sample with NaN and is never used as an index (as kg_label_bias_lookup_kernel)
+    bool lab_ok = false;
+    if constexpr (LB) {
+        const long lab = lb.labels[n];
+        lab_ok = lab >= 0 && lab < lb.L;
+        // the label columns: 16 rows (k, m) per wave and step, lane = j - every load of a step in flight at once
+        const int rows = a.K * a.M;
+        for (int r0 = wave * 16; r0 < rows; r0 += 64)
+            for (int j = lane; j < lb.J; j += 64) {
+                float v[16];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int r = r0 + q;                                  // (wave-uniform)
+                    const int k = (int)pl.fm.div((unsigned)r), m = r - k * a.M;
+                    v[q] = r < rows ? lb.w[(long)k * lb.w_sK + (long)m * lb.w_sC + j] : 0.f;
+                }
+#pragma unroll
+                for (int q = 0; q < 16; ++q)
+                    if (r0 + q < rows) Wcs[(r0 + q) * lb.J + j] = v[q];
+            }
+        for (int j = tid; j < lb.J; j += AT_NT) El[j] = lab_ok ? lb.emb[lab * lb.J + j] : 0.f;
     }
     __syncthreads();
-    const int ncols = a.N * a.T * a.W;
-    const int j = blockIdx.x * 256 + tid;
-    if (j >= ncols) return;
-    const int f = j / a.W, wv = j - f * a.W;
-    const int n = f / a.T, t = f - n * a.T;
+
+    // ---- this thread's column: the feature gathers go out first
+    const int cl = tid % BC, rg = tid / BC;
+    const int jl = chunk * BC + cl;                   // column inside the sample
+    const bool valid = jl < a.T * a.W;
+    unsigned tu, wu;
+    pl.fw.divmod((unsigned)(valid ? jl : 0), tu, wu);
+    const int t = (int)tu, wv = (int)wu;
+    const float* xp = a.x + (long)n * a.x_sN + (long)t * a.V;
+    float xv[AT_NB][AT_C], av[AT_NB];
+#pragma unroll
+    for (int k = 0; k < AT_K; ++k)
+#pragma unroll
+        for (int p = 0; p < AT_PN[k]; ++p) {
+            const int s = AT_P0[k] + p;
+            const bool on = valid && k < a.K && p < a.pcount[k];
+            const int v = on ? Nb[(k * a.W + wv) * PMAX + p] : 0;
+            av[s] = (on && v >= 0) ? at_adj(a, As, k, v, wv) : 0.f;
+#pragma unroll
+            for (int c = 0; c < AT_C; ++c) xv[s][c] = (on && v >= 0 && c < a.Cin) ? xp[(long)c * a.x_sC + v] : 0.f;
+        }
+    if constexpr (LB) {
+        // the bias' two factors, by different waves while the gathers are in flight
+        for (int i = tid; i < a.K * a.M; i += AT_NT) {
+            const float* wp = Wcs + i * lb.J;
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;       // four chains, as kg_label_bias_table_kernel
+            int j = 0;
+#pragma unroll 4
+            for (; j + 3 < lb.J; j += 4) {
+                s0 = fmaf(wp[j], El[j], s0);
+                s1 = fmaf(wp[j + 1], El[j + 1], s1);
+                s2 = fmaf(wp[j + 2], El[j + 2], s2);
+                s3 = fmaf(wp[j + 3], El[j + 3], s3);
+            }
+            for (; j < lb.J; ++j) s0 = fmaf(wp[j], El[j], s0);
+            P[i] = (s0 + s1) + (s2 + s3);
+        }
+        const int i = tid - (AT_NT - 64);                           // the last wave (K * W <= 96: up to two rounds)
+        for (int ii = i; ii >= 0 && ii < a.K * a.W; ii += 64) {
+            const int k = (int)pl.fw.div((unsigned)ii), w = ii - k * a.W;
+            float s = 0.f;
+#pragma unroll 5
+            for (int v = 0; v < a.V; ++v) s += at_adj(a, As, k, v, w);
+            S[ii] = s;
+        }
+        __syncthreads();
+    }
+    if (!valid) return;
+    // (only the listed neighbours: an absent one adds 0 * x exactly)
     float xa[AT_K][AT_C];
 #pragma unroll
     for (int k = 0; k < AT_K; ++k)
 #pragma unroll
-        for (int c = 0; c < AT_C; ++c) xa[k][c] = 0.f;
-    const float* xp = a.x + (long)n * a.x_sN + (long)t * a.V;
+        for (int c = 0; c < AT_C; ++c) {
+            float s = 0.f;
 #pragma unroll
-    for (int k = 0; k < AT_K; ++k) {
-        if (k < a.K) {
-#pragma unroll
-            for (int p = 0; p < PMAX; ++p) {
-                const int e = (k * a.W + wv) * PMAX + p;
-                const int v = Nb[e];
-                const float av = Av[e];
-#pragma unroll
-                for (int c = 0; c < AT_C; ++c)
-                    if (c < a.Cin) xa[k][c] = fmaf(av, xp[(long)c * a.x_sC + v], xa[k][c]);
-            }
+            for (int p = 0; p < AT_PN[k]; ++p) s = fmaf(av[AT_P0[k] + p], xv[AT_P0[k] + p][c], s);
+            xa[k][c] = s;
         }
-    }
-    if (a.xa && blockIdx.y == 0) {
+    if (a.xa && rg == 0) {
         float* xo = a.xa + (long)n * a.xa_sN + (long)t * a.W + wv;
 #pragma unroll
         for (int k = 0; k < AT_K; ++k)
@@ -359,16 +444,30 @@ __global__ __launch_bounds__(256, 4) void kg_aggconv_tiny_kernel(const KgAggConv
                 if (k < a.K && c < a.Cin) xo[(long)(k * a.Cin + c) * a.xa_sC] = xa[k][c];
     }
     float* op = a.out + (long)n * a.o_sN + (long)t * a.W + wv;
-    const float* ap = a.add ? a.add + (long)n * a.a_sN + (long)(t * a.a_tstride) * a.W + wv : nullptr;
-    // eight output rows per thread, the row groups side by side in grid.y (a thread that walks all M rows is a serial
-    // chain of 4-8 load / multiply / store rounds: with one workgroup per CU at 64 samples the launch took 13 us)
-    {
-        const int m0 = blockIdx.y * 8;
+    const float* ap = (!LB && a.add) ? a.add + (long)n * a.a_sN + (long)(t * a.a_tstride) * a.W + wv : nullptr;
+    float sw[AT_K];
+    if constexpr (LB) {
+#pragma unroll
+        for (int k = 0; k < AT_K; ++k) sw[k] = k < a.K ? S[k * a.W + wv] : 0.f;
+    }
+    // eight output rows at a time: the operand loads of a chunk are issued together, the stores are not waited for
+#pragma unroll
+    for (int mc = 0; mc < MR; mc += 8) {
+        const int m0 = rg * MR + mc;
+        if (m0 >= a.M) break;
         float acc[8], addv[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             acc[q] = 0.f;
-            addv[q] = (ap && m0 + q < a.M) ? ap[(long)(m0 + q) * a.a_sC] : 0.f;
+            if constexpr (LB) {
+                float s = 0.f;
+#pragma unroll
+                for (int k = 0; k < AT_K; ++k)
+                    if (k < a.K) s = fmaf(sw[k], P[k * a.M + m0 + q], s);
+                addv[q] = lab_ok ? s : __builtin_nanf("");
+            } else {
+                addv[q] = (ap && m0 + q < a.M) ? ap[(long)(m0 + q) * a.a_sC] : 0.f;
+            }
         }
 #pragma unroll
         for (int k = 0; k < AT_K; ++k)
@@ -384,8 +483,51 @@ __global__ __launch_bounds__(256, 4) void kg_aggconv_tiny_kernel(const KgAggConv
     }
 }
 
-bool tiny_form(const KgAggConvArgs* a) {
-    return a->K <= AT_K && a->Cin <= AT_C && a->M <= AT_MAXM && a->W <= 32 && kg_env().aggconv_plan == 0;
+bool tiny_geometry(const KgAggConvArgs* a) {
+    return a->K <= AT_K && a->Cin <= AT_C && a->M <= AT_MAXM && a->W <= 32 && a->K * a->V * a->W <= AT_MAXA;
+}
+
+bool tiny_form(const KgAggConvArgs* a) { return tiny_geometry(a) && kg_env().aggconv_plan == 0; }
+
+template <int MT, bool LB>
+void launch_tiny_rg(int rg, dim3 grid, size_t lds, hipStream_t s, const KgAggConvArgs* a, const KgLabelBiasArgs& l,
+                    const AtPlan& pl) {
+    if (rg == 4)      hipLaunchKernelGGL((kg_aggconv_tiny_kernel<MT, 4, LB>), grid, dim3(AT_NT), lds, s, *a, l, pl);
+    else if (rg == 2) hipLaunchKernelGGL((kg_aggconv_tiny_kernel<MT, 2, LB>), grid, dim3(AT_NT), lds, s, *a, l, pl);
+    else              hipLaunchKernelGGL((kg_aggconv_tiny_kernel<MT, 1, LB>), grid, dim3(AT_NT), lds, s, *a, l, pl);
+}
+
+// RG: threads per column.  More of them shorten every thread's row loop but repeat the per-workgroup staging: four
+// where 256-column workgroups would leave most CUs with fewer than two (64 samples: 192 of them), else one (measured
+// on MI355X at the bench shapes, profiles/d0_fused_probe.log: 64 samples 7.6 / 8.0 / 8.7 us bias-free and 15.0 / 15.1 /
+// 16.5 us with the label bias for RG = 4 / 2 / 1; 192 samples 12.8 / 14.6 / 17.1 and 22.1 / 28.6 / 34.3 us for RG = 1 / 2 / 4)
+template <bool LB>
+int launch_tiny(const KgAggConvArgs* a, const KgLabelBiasArgs* lb, hipStream_t s) {
+    const int tw = a->T * a->W;
+    int rg = (long)a->N * kg_cdiv(tw, AT_NT) < 512 ? 4 : 1;
+    if (kg_env().aggconv_tiny_rg == 1 || kg_env().aggconv_tiny_rg == 2 || kg_env().aggconv_tiny_rg == 4) rg = kg_env().aggconv_tiny_rg;
+    const int cps = kg_cdiv(tw, AT_NT / rg);
+    KG_REQUIRE((long)a->N * cps < (1L << 31), "kg_aggconv (tiny): too many workgroups");
+    AtPlan pl;
+    pl.fc = FastDiv::make((unsigned)cps);
+    pl.fw = FastDiv::make((unsigned)a->W);
+    pl.fm = FastDiv::make((unsigned)a->M);
+    const size_t lds = (size_t)(((a->K * a->V * a->W + 3) & ~3) + (LB ? a->K * a->M * lb->J + lb->J : 0)) * sizeof(float);
+    KgLabelBiasArgs none = {};
+    const KgLabelBiasArgs& l = LB ? *lb : none;
+    const dim3 grid((unsigned)(a->N * cps));
+    static unsigned long long attr_mask = 0;
+    if (LB && kg_first_on_device(attr_mask)) {
+        KG_SET_DYN_LDS((kg_aggconv_tiny_kernel<32, 1, LB>), 80 * 1024);
+        KG_SET_DYN_LDS((kg_aggconv_tiny_kernel<32, 2, LB>), 80 * 1024);
+        KG_SET_DYN_LDS((kg_aggconv_tiny_kernel<32, 4, LB>), 80 * 1024);
+        KG_SET_DYN_LDS((kg_aggconv_tiny_kernel<64, 1, LB>), 80 * 1024);
+        KG_SET_DYN_LDS((kg_aggconv_tiny_kernel<64, 2, LB>), 80 * 1024);
+        KG_SET_DYN_LDS((kg_aggconv_tiny_kernel<64, 4, LB>), 80 * 1024);
+    }
+    if (a->M <= 32) launch_tiny_rg<32, LB>(rg, grid, lds, s, a, l, pl);
+    else            launch_tiny_rg<64, LB>(rg, grid, lds, s, a, l, pl);
+    return kg_launch_status(LB ? "kg_aggconv_label" : "kg_aggconv (tiny)");
 }
 
 int validate(const KgAggConvArgs* a) {
@@ -443,13 +585,7 @@ extern "C" int kg_aggconv_supported(const KgAggConvArgs* a) {
 extern "C" int kg_aggconv(const KgAggConvArgs* a, void* stream) {
     if (int rc = validate(a)) return rc;
     KG_REQUIRE(a->xa == nullptr || (a->xa_sC > 0), "kg_aggconv: xa strides");
-    if (tiny_form(a)) {
-        const int ncols = a->N * a->T * a->W;
-        const dim3 grid(kg_cdiv(ncols, 256), kg_cdiv(a->M, 8));
-        if (a->M <= 32) hipLaunchKernelGGL(kg_aggconv_tiny_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, *a);
-        else            hipLaunchKernelGGL(kg_aggconv_tiny_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, *a);
-        return kg_launch_status("kg_aggconv (tiny)");
-    }
+    if (tiny_form(a)) return launch_tiny<false>(a, nullptr, (hipStream_t)stream);
     const int span = span_of(a);
     KG_REQUIRE(span <= 384, "kg_aggconv: source span %d floats per tile > 384 (use kg_agg_expand + kg_conv)", span);
     KG_REQUIRE(a->xa == nullptr || (a->xa_sC > 0), "kg_aggconv: xa strides");
@@ -478,4 +614,19 @@ extern "C" int kg_aggconv(const KgAggConvArgs* a, void* stream) {
     if (bm == 64)            return wide ? launch<64, 6, 1>(a, pl, s) : launch<64, 3, 1>(a, pl, s);
     if (ks == 2)             return wide ? launch<32, 6, 2>(a, pl, s) : launch<32, 3, 2>(a, pl, s);
     return wide ? launch<32, 6, 1>(a, pl, s) : launch<32, 3, 1>(a, pl, s);
+}
+
+extern "C" int kg_aggconv_label(const KgAggConvArgs* a, const KgLabelBiasArgs* lb, void* stream) {
+    if (int rc = validate(a)) return rc;
+    KG_REQUIRE(a->xa == nullptr || (a->xa_sC > 0), "kg_aggconv_label: xa strides");
+    KG_REQUIRE(a->add == nullptr, "kg_aggconv_label: the label bias takes the place of `add`");
+    KG_REQUIRE(tiny_geometry(a), "kg_aggconv_label: K=%d Cin=%d M=%d V=%d W=%d is not the tiny-channel geometry",
+               a->K, a->Cin, a->M, a->V, a->W);
+    KG_REQUIRE(lb != nullptr && lb->labels && lb->emb && lb->w, "kg_aggconv_label: null label-bias args");
+    KG_REQUIRE(lb->N == a->N && lb->K == a->K && lb->C == a->M && lb->V == a->V && lb->W == a->W,
+               "kg_aggconv_label: label bias (N=%d K=%d C=%d V=%d W=%d) does not match the launch", lb->N, lb->K, lb->C,
+               lb->V, lb->W);
+    KG_REQUIRE(lb->L > 0 && lb->J > 0 && lb->J <= AT_MAXJ && a->K * a->M * lb->J <= AT_MAXWC,
+               "kg_aggconv_label: L=%d J=%d exceed the kernel's LDS tables", lb->L, lb->J);
+    return launch_tiny<true>(a, lb, (hipStream_t)stream);
 }

@@ -46,6 +46,7 @@ struct KgEnv {
     int wgrad_budget;     // KG_WGRAD_BUDGET: workgroups of equal cost a kg_wgrad_many pass is cut into (0 = 6144)
     int wgrad_split;      // KG_WGRAD_SPLIT: 1 = the bf16-split tiles of kg_wgrad.hip (opt-in: measured no faster overall), default the fp32 tiles
     int aggconv_plan;     // KG_AGGCONV_PLAN "<BM><KS>" or 0
+    int aggconv_tiny_rg;  // KG_AGGCONV_TINY_RG: threads per output column of the tiny-channel kg_aggconv form (1, 2, 4; 0 = built-in)
     int conv_ring;        // KG_CONV_RING: -1 unset (the plan decides), 0 = never the persistent LDS-ring form, 1 = wherever it can run
     int conv_ring_stagger; // KG_CONV_RING_STAGGER: s_sleep units the second workgroup of a CU starts late (window tiles with two workgroups per CU)
     int conv_ring_tile;   // KG_CONV_RING_TILE: force the ring tile (kg_conv_ring.hip: 0..5), -1 = automatic

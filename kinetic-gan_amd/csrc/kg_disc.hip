@@ -171,67 +171,84 @@ __global__ __launch_bounds__(NT) void kg_label_bias_lookup_kernel(const KgLabelB
     a.zl[i] = (lab >= 0 && lab < a.L) ? table[lab * CW + e] : __builtin_nanf("");
 }
 
-// backward, phase 0 - one workgroup per (sample, channel): gzl[n,c,w] = sum_t gz[n,c,t,w] (the T*W run is contiguous;
-// lane = (t mod TQ, w) so that a wave reads consecutive addresses), into ws behind the per-class records
-__global__ __launch_bounds__(NT) void kg_label_bias_bwd0_kernel(const KgLabelBiasArgs a, float* gzl) {
-    __shared__ float red[NT];
-    const int n = blockIdx.x / a.C, c = blockIdx.x - n * a.C;
-    const int W = a.W, TQ = NT / W;                      // frames summed side by side
-    const int tid = threadIdx.x;
-    const int tq = tid / W, w = tid - tq * W;
-    const float* gp = a.gz + (long)n * a.gz_sN + (long)c * a.gz_sC;
-    float s = 0.f;
-    if (tq < TQ)
-        for (int t = tq; t < a.T; t += TQ) s += gp[t * W + w];
-    red[tid] = s;
-    __syncthreads();
-    if (tid < W) {
-        float t = 0.f;
-        for (int q = 0; q < TQ; ++q) t += red[q * W + tid];
-        gzl[((long)n * a.C + c) * W + tid] = t;
-    }
-}
+// backward.  Per-class record in ws (class l at l * lb_rec(a)): Q[k,c] = sum_w dT[c,w] S[k,w], P_l[k,c], dT[c,w] =
+// sum_{n: label_n = l} sum_t gz[n,c,t,w].  Every sum runs in a fixed order (samples in index order, frames as below):
+// bit-reproducible, no atomics.
+__host__ __device__ __forceinline__ long lb_rec(const KgLabelBiasArgs& a) { return 2L * a.K * a.C + (long)a.C * a.W; }
 
-// phase 1 - one workgroup per CLASS l (its samples are visited in index order: deterministic):
-//   dT[c,w] = sum_{n: label_n = l} gzl[n,c,w];  Q[l,k,c] = sum_w dT[c,w] S[k,w];  R[l,k,w] = sum_c dT[c,w] P_l[k,c]
-//   dE[l,j] (+)= sum_{k,c} Wc(k,c,j) Q[l,k,c]
-__global__ __launch_bounds__(NT) void kg_label_bias_bwd1_kernel(const KgLabelBiasArgs a, const float* gzl) {
-    __shared__ float S[LB_MAXKW], P[LB_MAXKC], Q[LB_MAXKC], dT[LB_MAXCW], El[512], Wl[LB_MAXW];
-    const int l = blockIdx.x;
-    colsums(a, S, Wl);
-    stage_wc(a, Wl);
-    for (int j = threadIdx.x; j < a.J; j += NT) El[j] = a.emb[(long)l * a.J + j];
-    const int CW = a.C * a.W;
-    // the labels go through LDS, a chunk at a time: read from global memory inside the sample loop every sample was a
-    // (uniform) load of its own in front of the branch - 128 dependent latencies, 28 us for a 45 KB problem
-    __shared__ int Lb[1024];
-    constexpr int DQ = LB_MAXCW / NT;
-    float dacc[DQ];
-#pragma unroll
-    for (int q = 0; q < DQ; ++q) dacc[q] = 0.f;
-    for (int n0 = 0; n0 < a.N; n0 += 1024) {
-        const int nn = a.N - n0 < 1024 ? a.N - n0 : 1024;
+constexpr int LB_BATCH = 4;      // samples of a class whose frame sums are in flight together
+
+// phase 1 - one workgroup per (class l, channel c): the frame sums of the class's samples (lane = (t mod TQ, w) so that
+// a wave reads consecutive addresses; LB_BATCH samples at a time), summed in sample-index order into dT[c, :]; P_l[k,c];
+// Q[l,k,c].  Labels outside [0, L) match no class.
+__global__ __launch_bounds__(NT) void kg_label_bias_bwd_class_kernel(const KgLabelBiasArgs a) {
+    __shared__ float S[LB_MAXKW], El[512], Wr[3 * 512], red[LB_BATCH][NT], dT[NT], Pk[3];
+    __shared__ int lst[NT], wcnt[NT / 64];
+    extern __shared__ float kg_lbsm[];                    // the adjacency, K * V * W
+    const int l = blockIdx.x / a.C, c = blockIdx.x - l * a.C;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int W = a.W, TQ = NT / W;                       // frames summed side by side
+    const int tq = tid / W, w = tid - tq * W;
+    // staged with independent loads: the adjacency (for S), this channel's label weight rows Wc(k, c, :), E[l, :]
+    for (int i = tid; i < a.K * a.V * W; i += NT) kg_lbsm[i] = a.ak[i];
+    for (int i = tid; i < a.K * a.J; i += NT) {
+        const int k = i / a.J, j = i - k * a.J;
+        Wr[i] = a.w[(long)k * a.w_sK + (long)c * a.w_sC + j];
+    }
+    for (int j = tid; j < a.J; j += NT) El[j] = a.emb[(long)l * a.J + j];
+    const float* gp = a.gz + (long)c * a.gz_sC;
+    float dacc = 0.f;                                     // thread w < W: dT[c, w]
+    for (int n0 = 0; n0 < a.N; n0 += NT) {
+        // this chunk's samples of class l, in index order (wave ballots + wave offsets)
+        const bool hit = n0 + tid < a.N && a.labels[n0 + tid] == l;
+        const unsigned long long m = __ballot(hit);
+        if (lane == 0) wcnt[wave] = __popcll(m);
         __syncthreads();
-        for (int i = threadIdx.x; i < nn; i += NT) Lb[i] = (int)a.labels[n0 + i];
-        __syncthreads();
-        for (int n = 0; n < nn; ++n) {
-            if (Lb[n] != l) continue;                                   // (uniform across the workgroup)
-#pragma unroll
-            for (int q = 0; q < DQ; ++q) {
-                const int i = threadIdx.x + q * NT;
-                if (i < CW) dacc[q] += gzl[(long)(n0 + n) * CW + i];      // samples in index order: deterministic
-            }
+        int off = 0, cnt = 0;
+        for (int q = 0; q < NT / 64; ++q) {
+            if (q < wave) off += wcnt[q];
+            cnt += wcnt[q];
         }
-    }
+        if (hit) lst[off + __popcll(m & ((1ull << lane) - 1ull))] = n0 + tid;
+        __syncthreads();
+        for (int b0 = 0; b0 < cnt; b0 += LB_BATCH) {
+            const int nb = cnt - b0 < LB_BATCH ? cnt - b0 : LB_BATCH;
+            float s[LB_BATCH];
 #pragma unroll
-    for (int q = 0; q < DQ; ++q) {
-        const int i = threadIdx.x + q * NT;
-        if (i < CW) dT[i] = dacc[q];
+            for (int b = 0; b < LB_BATCH; ++b) {
+                s[b] = 0.f;
+                if (b < nb && tq < TQ) {
+                    const float* p = gp + (long)lst[b0 + b] * a.gz_sN;
+                    for (int t = tq; t < a.T; t += TQ) s[b] += p[t * W + w];
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < LB_BATCH; ++b) red[b][tid] = s[b];
+            __syncthreads();
+            if (tid < W)
+                for (int b = 0; b < nb; ++b) {
+                    float t = 0.f;
+                    for (int q = 0; q < TQ; ++q) t += red[b][q * W + tid];
+                    dacc += t;
+                }
+            __syncthreads();
+        }
+        __syncthreads();                                  // (wcnt / lst are rewritten by the next chunk)
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < a.K * a.C; i += NT) {
-        const float* wp = Wl + i * a.J;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;       // four chains: the LDS reads of a step overlap
+    float* rec = a.ws + (long)l * lb_rec(a);
+    if (tid < W) {
+        dT[tid] = dacc;
+        rec[2 * a.K * a.C + c * W + tid] = dacc;
+    }
+    for (int i = tid; i < a.K * W; i += NT) {
+        const int k = i / W, ww = i - k * W;
+        float s = 0.f;
+        for (int v = 0; v < a.V; ++v) s += kg_lbsm[(k * a.V + v) * W + ww];
+        S[i] = s;
+    }
+    if (tid < a.K) {
+        const float* wp = Wr + tid * a.J;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;       // four chains, as kg_label_bias_table_kernel
         int j = 0;
         for (; j + 3 < a.J; j += 4) {
             s0 = fmaf(wp[j], El[j], s0);
@@ -240,56 +257,79 @@ __global__ __launch_bounds__(NT) void kg_label_bias_bwd1_kernel(const KgLabelBia
             s3 = fmaf(wp[j + 3], El[j + 3], s3);
         }
         for (; j < a.J; ++j) s0 = fmaf(wp[j], El[j], s0);
-        P[i] = (s0 + s1) + (s2 + s3);
-    }
-    float* Qg = a.ws + (long)l * (a.K * a.C + a.K * a.W);
-    for (int i = threadIdx.x; i < a.K * a.C; i += NT) {
-        const int k = i / a.C, c = i - k * a.C;
-        float s = 0.f;
-        for (int w = 0; w < a.W; ++w) s = fmaf(dT[c * a.W + w], S[k * a.W + w], s);
-        Q[i] = s;
-        Qg[i] = s;
+        Pk[tid] = (s0 + s1) + (s2 + s3);
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < a.K * a.W; i += NT) {
-        const int k = i / a.W, w = i - k * a.W;
+    if (tid < a.K) {
         float s = 0.f;
-        for (int c = 0; c < a.C; ++c) s = fmaf(dT[c * a.W + w], P[k * a.C + c], s);
-        Qg[a.K * a.C + i] = s;
+        for (int ww = 0; ww < W; ++ww) s = fmaf(dT[ww], S[tid * W + ww], s);
+        rec[tid * a.C + c] = s;
+        rec[a.K * a.C + tid * a.C + c] = Pk[tid];
     }
-    if (a.demb)
-        for (int j = threadIdx.x; j < a.J; j += NT) {
+}
+
+// phase 2 - blocks [0, L): dE[l,j] (+)= sum_{k,c} Wc(k,c,j) Q[l,k,c];  [L, L + K W): dak[k,v,w] (+)= sum_l R[l,k,w] for
+// every v, R[l,k,w] = sum_c dT[l,c,w] P_l[k,c];  then thread per weight: dWc(k,c,j) (+)= sum_l E[l,j] Q[l,k,c]
+__global__ __launch_bounds__(NT) void kg_label_bias_bwd_finish_kernel(const KgLabelBiasArgs a) {
+    extern __shared__ float kg_lbsm[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const long per = lb_rec(a);
+    if (b < a.L) {
+        if (!a.demb) return;
+        float* Wl = kg_lbsm;                              // K * C * J
+        __shared__ float Q[LB_MAXKC];
+        stage_wc(a, Wl);
+        for (int i = tid; i < a.K * a.C; i += NT) Q[i] = a.ws[b * per + i];
+        __syncthreads();
+        for (int j = tid; j < a.J; j += NT) {
             float s = 0.f;
 #pragma unroll 8
             for (int i = 0; i < a.K * a.C; ++i) s = fmaf(Wl[i * a.J + j], Q[i], s);
-            float* d = a.demb + (long)l * a.J + j;
+            float* d = a.demb + (long)b * a.J + j;
             *d = (a.accumulate ? *d : 0.f) + s;
         }
-}
-
-// phase 2 - thread per output: dWc(k,c,j) (+)= sum_l E[l,j] Q[l,k,c];  dak[k,v,w] (+)= sum_l R[l,k,w] for every v
-__global__ __launch_bounds__(NT) void kg_label_bias_bwd2_kernel(const KgLabelBiasArgs a) {
-    const int i = blockIdx.x * NT + threadIdx.x;
-    const int nw = a.K * a.C * a.J, na = a.K * a.V * a.W;
-    const int per = a.K * a.C + a.K * a.W;
-    if (i < nw) {
-        if (!a.dw) return;
-        const int kc = i / a.J, j = i - kc * a.J;
-        float s = 0.f;
-#pragma unroll 8
-        for (int l = 0; l < a.L; ++l) s = fmaf(a.emb[(long)l * a.J + j], a.ws[(long)l * per + kc], s);
-        const int k = kc / a.C, c = kc - k * a.C;
-        float* d = a.dw + (long)k * a.w_sK + (long)c * a.w_sC + j;
-        *d = (a.accumulate ? *d : 0.f) + s;
-    } else if (i < nw + na) {
-        if (!a.dak) return;
-        const int e = i - nw;
-        const int k = e / (a.V * a.W), w = e % a.W;
-        float s = 0.f;
-#pragma unroll 8
-        for (int l = 0; l < a.L; ++l) s += a.ws[(long)l * per + a.K * a.C + k * a.W + w];
-        a.dak[e] = (a.dak_accumulate ? a.dak[e] : 0.f) + s;
+        return;
     }
+    if (b < a.L + a.K * a.W) {
+        if (!a.dak) return;
+        __shared__ float R[NT];
+        __shared__ float tot;
+        const int kw = b - a.L;
+        const int k = kw / a.W, w = kw - k * a.W;
+        float s = 0.f;                                     // (thread 0)
+        for (int l0 = 0; l0 < a.L; l0 += NT) {
+            const int l = l0 + tid;
+            if (l < a.L) {
+                const float* rec = a.ws + l * per;
+                float r = 0.f;
+#pragma unroll 8
+                for (int c = 0; c < a.C; ++c) r = fmaf(rec[2 * a.K * a.C + c * a.W + w], rec[a.K * a.C + k * a.C + c], r);
+                R[tid] = r;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                const int nl = a.L - l0 < NT ? a.L - l0 : NT;
+                for (int i = 0; i < nl; ++i) s += R[i];
+            }
+            __syncthreads();
+        }
+        if (tid == 0) tot = s;
+        __syncthreads();
+        for (int v = tid; v < a.V; v += NT) {
+            float* d = a.dak + ((long)k * a.V + v) * a.W + w;
+            *d = (a.dak_accumulate ? *d : 0.f) + tot;
+        }
+        return;
+    }
+    const int i = (b - a.L - a.K * a.W) * NT + tid;
+    if (!a.dw || i >= a.K * a.C * a.J) return;
+    const int kc = i / a.J, j = i - kc * a.J;
+    float s = 0.f;
+#pragma unroll 8
+    for (int l = 0; l < a.L; ++l) s = fmaf(a.emb[(long)l * a.J + j], a.ws[l * per + kc], s);
+    const int k = kc / a.C, c = kc - k * a.C;
+    float* d = a.dw + (long)k * a.w_sK + (long)c * a.w_sC + j;
+    *d = (a.accumulate ? *d : 0.f) + s;
 }
 
 // ---- critic input ------------------------------------------------------------------------------------------------
@@ -383,8 +423,8 @@ extern "C" int kg_label_bias_fwd(const KgLabelBiasArgs* a, void* stream) {
 
 extern "C" int64_t kg_label_bias_workspace_bytes(const KgLabelBiasArgs* a) {
     if (validate_lb(a, "kg_label_bias_workspace_bytes")) return -1;
-    // backward: per-class records (Q, R) + the frame-summed gradient (N, C, W); forward: the class table (L, C, W)
-    const int64_t bwd = (int64_t)a->L * (a->K * a->C + a->K * a->W) + (int64_t)a->N * a->C * a->W;
+    // backward: the per-class records (Q, P, dT); forward: the class table (L, C, W)
+    const int64_t bwd = (int64_t)a->L * lb_rec(*a);
     const int64_t fwd = (int64_t)a->L * a->C * a->W;
     return (bwd > fwd ? bwd : fwd) * (int64_t)sizeof(float);
 }
@@ -393,13 +433,18 @@ extern "C" int kg_label_bias_bwd(const KgLabelBiasArgs* a, void* stream) {
     if (int rc = validate_lb(a, "kg_label_bias_bwd")) return rc;
     KG_REQUIRE(a->gz && a->T > 0, "kg_label_bias_bwd: null gz");
     KG_REQUIRE(a->ws && a->ws_bytes >= kg_label_bias_workspace_bytes(a), "kg_label_bias_bwd: workspace too small");
-    float* gzl = a->ws + (int64_t)a->L * (a->K * a->C + a->K * a->W);
-    hipLaunchKernelGGL(kg_label_bias_bwd0_kernel, dim3(a->N * a->C), dim3(NT), 0, (hipStream_t)stream, *a, gzl);
-    if (int rc = kg_launch_status("kg_label_bias_bwd (frame sums)")) return rc;
-    hipLaunchKernelGGL(kg_label_bias_bwd1_kernel, dim3(a->L), dim3(NT), 0, (hipStream_t)stream, *a, (const float*)gzl);
+    KG_REQUIRE((long)a->L * a->C < (1L << 31), "kg_label_bias_bwd: L * C too large");
+    static unsigned long long attr_mask = 0;
+    if (kg_first_on_device(attr_mask)) {
+        KG_SET_DYN_LDS(kg_label_bias_bwd_class_kernel, LB_MAXW * sizeof(float));
+        KG_SET_DYN_LDS(kg_label_bias_bwd_finish_kernel, LB_MAXW * sizeof(float));
+    }
+    hipLaunchKernelGGL(kg_label_bias_bwd_class_kernel, dim3(a->L * a->C), dim3(NT), (size_t)a->K * a->V * a->W * sizeof(float),
+                       (hipStream_t)stream, *a);
     if (int rc = kg_launch_status("kg_label_bias_bwd (classes)")) return rc;
-    const int items = a->K * a->C * a->J + a->K * a->V * a->W;
-    hipLaunchKernelGGL(kg_label_bias_bwd2_kernel, dim3(kg_cdiv(items, NT)), dim3(NT), 0, (hipStream_t)stream, *a);
+    const int blocks = a->L + a->K * a->W + kg_cdiv((long)a->K * a->C * a->J, NT);
+    hipLaunchKernelGGL(kg_label_bias_bwd_finish_kernel, dim3(blocks), dim3(NT), (size_t)a->K * a->C * a->J * sizeof(float),
+                       (hipStream_t)stream, *a);
     return kg_launch_status("kg_label_bias_bwd (finish)");
 }
 

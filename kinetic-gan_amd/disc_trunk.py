@@ -33,6 +33,10 @@ from . import ops
 from ._native import ACT_LRELU, ACT_NONE, TAP_TIME, Group, WView
 
 SLOPE = 0.2
+# Block 0's label bias inside its gcn launch (kg_aggconv_label, _d0_fused_route): one launch instead of the class table,
+# the lookup and the gcn.  KG_D0_FUSED=0 / disc_trunk.D0_FUSED = False: the composed form (A/B, tests).
+D0_FUSED = os.environ.get("KG_D0_FUSED", "1") != "0"
+_NV_LABEL_BIAS_FWD, _NV_AGGCONV = nv.label_bias_fwd, nv.aggconv
 
 
 class BlockGeom:
@@ -306,14 +310,33 @@ def _agg_gcn(g: BlockGeom, x, ak, wg, add, want_xa: bool):
     return _gcn(g, xa, wg, add=add, add_tstride=tstride), xa
 
 
-def fwd_pass(meta: TrunkMeta, x, zl, aks, params, want_xa: bool = True):
-    """Returns (h, tape); tape[i] = (x_i, xa_i | None, z_i, out_i)."""
+def _d0_fused_route(meta: TrunkMeta, x, labels, emb, want_xa: bool) -> bool:
+    """Block 0 with the label bias formed inside its gcn launch (kg_aggconv_label) instead of kg_label_bias_fwd + the
+    gcn: wherever _agg_gcn would take the fused (kg_aggconv) route for block 0, the operands are on the GPU and the
+    library's own entry points are in place (the CPU tests swap in oracle/prim_ref.py, which has no emulation of it)."""
+    g = meta.geoms[0]
+    if not (D0_FUSED and x.is_cuda and labels.is_cuda and nv.label_bias_fwd is _NV_LABEL_BIAS_FWD
+            and nv.aggconv is _NV_AGGCONV):
+        return False
+    if g.single or (want_xa and g.cout >= 256) or not g.fused_gcn(x.shape[0] * x.shape[2] * g.W):
+        return False
+    return nv.aggconv_label_supported(g.K, g.cin - g.cc, g.cout, g.V, g.W, g.cc) and emb.shape[1] == g.cc
+
+
+def fwd_pass(meta: TrunkMeta, x, zl, aks, params, want_xa: bool = True, lb0=None):
+    """Returns (h, tape); tape[i] = (x_i, xa_i | None, z_i, out_i).  ``lb0`` = (labels, emb): block 0's label bias is
+    formed inside its gcn launch (_d0_fused_route); zl is then None."""
     tape = []
     for i, g in enumerate(meta.geoms):
         wg, wt, bt = params[meta.poff[i]:meta.poff[i] + 3]
         wr, br = (params[meta.poff[i] + 3], params[meta.poff[i] + 4]) if g.res == "conv" else (None, None)
-        # block 0: per-sample label bias, broadcast over the frames
-        z, xa = _agg_gcn(g, x, aks[i], wg, zl if g.cc else None, want_xa)
+        if i == 0 and lb0 is not None:
+            sp = g.spec_g
+            z, xa = nv.aggconv_label(x, aks[0], g.nbr, g.pcount, _wg_view(g, wg), WView(sp.wv.sT, sp.wv.sO, sp.wv.sI), sp.M,
+                                     lb0[0], lb0[1], wg, g.cin, g.cc, want_xa=want_xa)
+        else:
+            # block 0: per-sample label bias, broadcast over the frames
+            z, xa = _agg_gcn(g, x, aks[i], wg, zl if g.cc else None, want_xa)
         out = _tail(g, z, x, wt, bt, wr, br, linear=False)
         # the tape lives on the autograd context as a plain attribute: it must not hold the very tensor OBJECT the
         # Function returns (output -> grad_fn -> ctx -> tape -> output would be a reference cycle that keeps the whole
@@ -598,13 +621,17 @@ class DiscTrunkFn(Function):
         # the aggregated planes are only kept (written at all, on the fused path) when a weight gradient may follow
         want_xa = any(ctx.needs_input_grad[5:])
         with torch.no_grad():
+            lb0 = None
             if meta.lb:
                 g0 = meta.geoms[0]
                 ctx.labels = zl
-                zl_v = nv.label_bias_fwd(zl, emb.detach(), blk[0].detach(), g0.K, g0.cout, g0.cin, g0.cc, aks[0].contiguous())
+                if _d0_fused_route(meta, x, zl, emb, want_xa):
+                    zl_v, lb0 = None, (zl, emb.detach())
+                else:
+                    zl_v = nv.label_bias_fwd(zl, emb.detach(), blk[0].detach(), g0.K, g0.cout, g0.cin, g0.cc, aks[0].contiguous())
             else:
                 zl_v = None if zl is None else zl.detach()
-            h, tape = fwd_pass(meta, x, zl_v, aks, [p.detach() for p in blk], want_xa)
+            h, tape = fwd_pass(meta, x, zl_v, aks, [p.detach() for p in blk], want_xa, lb0=lb0)
             v = nv.head_fwd(h, fw.detach(), None if fb is None else fb.detach()).view(-1, 1) if meta.head else None
         ctx.meta = meta
         ctx.n_a = x_a.shape[0]
