@@ -739,6 +739,69 @@ int kg_step_inputs(const KgStepInputsArgs* a, void* stream);
 int kg_loss_append(float* ring, int64_t ring_len, const int64_t* step, const float* d_loss, const float* g_loss,
                    void* stream);
 
+/* ---- inference-only generation path (additive, ABI v9; DESIGN.md 12, sample.Sampler) --------------------------------
+ * kg_bn_eval_coef: the eval-mode coefficients of up to KG_BN_EVAL_MAX_JOBS BatchNorm layers in ONE launch.  Per layer
+ *     coef (4, C) = [scale, shift, mean, rstd],  rstd = 1/sqrtf(running_var + eps), scale = gamma*rstd,
+ *     shift = beta - running_mean*scale, mean = running_mean          (gamma / beta NULL = 1 / 0)
+ * - the layout kg_bn_fwd writes and kg_affine_act / kg_genblock_infer read.  The running statistics are read through
+ * their pointers when the launch RUNS: inside a captured graph the coefficients follow every in-place update of them.  */
+#define KG_BN_EVAL_MAX_JOBS 8
+typedef struct KgBnEvalJob {
+    int32_t C;
+    const float* gamma;  const float* beta;  const float* running_mean;  const float* running_var;
+    float eps;
+    float* coef;                    /* out: (4, C)                                                                   */
+} KgBnEvalJob;
+int kg_bn_eval_coef(const KgBnEvalJob* jobs, int32_t njobs, void* stream);
+
+/* kg_genblock_infer: one generator block (generator.py:168-182) in eval mode as ONE launch, one sample per workgroup:
+ *     yc = [W_gcn[:Kp*C]; W_res] x;  z, r = sum_k yc_k (U A_k) / yc_res U + b_res (or x U);  u = W_tcn (*) z + b_tcn;
+ *     out = act(u*s_t + b_t + r*s_r + b_r + nw*noise)
+ * with (s_t, b_t) = rows 0, 1 of coef_t (4, C) and (s_r, b_r) of coef_r (kg_bn_eval_coef; NULL = 1 / 0).  The BatchNorm
+ * coefficients are inputs, so the launch takes no statistics, writes no tape and has no communication between
+ * workgroups.  Geometry rules as kg_genblock_fwd; kg_genblock_infer_lds_bytes = -1 where the block does not fit: the
+ * LDS / contraction-shape rule of kg_genblock_lds_bytes, and T > 1 with at least 16 input-grid columns Tc*Vc (the
+ * weight-bound front blocks stay on the staged launches).                                                              */
+typedef struct KgGenBlockInferArgs {
+    int32_t N;
+    int32_t Cin, C, K, Kp, Tc, Vc, T, V, rep, res_kind, act;  float slope;
+    KgPlane x;                              /* (N, Cin, Tc, Vc)                                                          */
+    const float* wg;  const float* wr;  const float* br;  const float* wt;  const float* bt;
+    const float* b;                         /* (Kp, Vc, V) = U (A * importance), kg_gen_adj_prepare                     */
+    const float* u;                         /* (Vc, V) up-sampling matrix or NULL (Vc == V)                             */
+    const float* coef_t;  const float* coef_r;      /* (4, C) or NULL                                                   */
+    const float* noise;  const float* nw;   /* (N, 1, T, V) contiguous, (C); both or neither                            */
+    KgPlane out;                            /* (N, C, T, V)                                                              */
+} KgGenBlockInferArgs;
+int64_t kg_genblock_infer_lds_bytes(const KgGenBlockInferArgs* a);
+int     kg_genblock_infer(const KgGenBlockInferArgs* a, void* stream);
+
+/* kg_sample_inputs: the random inputs of replay s = *step of a Sampler in ONE launch, then *step = s + 1 (last workgroup
+ * to finish, as kg_step_inputs).  Philox4x32-10 / Box-Muller exactly as kg_step_inputs with counter
+ * (q, KG_STREAM_SAMPLE + stream, s low, s high): streams 0 = z (B, latent; skipped when z == NULL), 1 = noise (noise_len
+ * values: the noise planes of ONE synthesis, flat, in plane order; skipped when NULL), 2 = t (t_rows, t_cols: the
+ * truncation draws; skipped when NULL).  Word 1 of the training streams is stream + 4*rank: 0x100 .. 0x102 is reached
+ * there only by rank 64 of a data-parallel run, so a sampler and a trainer of up to 64 ranks that share a seed never
+ * draw the same numbers.                                                                                              */
+#define KG_STREAM_SAMPLE 0x100
+typedef struct KgSampleInputsArgs {
+    int64_t* step;                  /* device: replay counter                                                        */
+    int32_t* ticket;                /* device: one zeroed int32, left at zero                                        */
+    uint64_t seed;
+    int32_t B, latent;
+    float* z;                       /* (B, latent) or NULL                                                           */
+    float* noise;  int64_t noise_len;
+    float* t;  int32_t t_rows, t_cols;
+} KgSampleInputsArgs;
+int kg_sample_inputs(const KgSampleInputsArgs* a, void* stream);
+
+/* kg_trunc_lerp: the truncation trick (generate.py:14-21 on Z, generator.py:97-108 on W) in ONE launch:
+ *     m[d] = (1/M) sum_i t[i*t_ld + d]  (fixed summation order: two calls give the same bits),
+ *     x[n*x_ld + d] = m[d] + truncation * (x[n*x_ld + d] - m[d])   in place, n < N, d < D.
+ * A workgroup owns a slab of columns: it reduces them, then applies them; no step across workgroups.                  */
+int kg_trunc_lerp(float* x, int64_t x_ld, int32_t N, int32_t D, const float* t, int64_t t_ld, int32_t M, float truncation,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,4 +9,7 @@ def __getattr__(name):
     if name in ("TrainLoop", "ResidentDataset"):
         from . import train
         return getattr(train, name)
+    if name == "Sampler":
+        from . import sample
+        return sample.Sampler
     raise AttributeError(name)

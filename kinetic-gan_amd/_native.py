@@ -316,6 +316,33 @@ class _StepInputsArgs(C.Structure):
                 ("z", c_f32p), ("latent", C.c_int32), ("alpha", c_f32p),
                 ("noise", c_f32p), ("n_planes", C.c_int32), ("plane_len", C.c_int64 * STEP_MAX_PLANES)]
 
+BN_EVAL_MAX_JOBS = 8
+STREAM_SAMPLE = 0x100        # word 1 of the sampler's Philox counters: STREAM_SAMPLE + (0 = z, 1 = noise, 2 = truncation draws)
+
+
+class _BnEvalJob(C.Structure):
+    _fields_ = [("C", C.c_int32), ("gamma", c_f32p), ("beta", c_f32p), ("running_mean", c_f32p), ("running_var", c_f32p),
+                ("eps", C.c_float), ("coef", c_f32p)]
+
+
+class _GenBlockInferArgs(C.Structure):
+    _fields_ = [("N", C.c_int32),
+                ("Cin", C.c_int32), ("C", C.c_int32), ("K", C.c_int32), ("Kp", C.c_int32),
+                ("Tc", C.c_int32), ("Vc", C.c_int32), ("T", C.c_int32), ("V", C.c_int32), ("rep", C.c_int32),
+                ("res_kind", C.c_int32), ("act", C.c_int32), ("slope", C.c_float),
+                ("x", _Plane),
+                ("wg", c_f32p), ("wr", c_f32p), ("br", c_f32p), ("wt", c_f32p), ("bt", c_f32p),
+                ("b", c_f32p), ("u", c_f32p),
+                ("coef_t", c_f32p), ("coef_r", c_f32p),
+                ("noise", c_f32p), ("nw", c_f32p), ("out", _Plane)]
+
+
+class _SampleInputsArgs(C.Structure):
+    _fields_ = [("step", C.c_void_p), ("ticket", C.c_void_p), ("seed", C.c_uint64),
+                ("B", C.c_int32), ("latent", C.c_int32), ("z", c_f32p),
+                ("noise", c_f32p), ("noise_len", C.c_int64),
+                ("t", c_f32p), ("t_rows", C.c_int32), ("t_cols", C.c_int32)]
+
 GEN_ADJ_MAX_JOBS = 8
 
 EXPORTS = {
@@ -399,6 +426,12 @@ EXPORTS = {
     "kg_loss_append": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kg_adam_step_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                      C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
+    "kg_bn_eval_coef": (C.c_int, [C.POINTER(_BnEvalJob), C.c_int32, C.c_void_p]),
+    "kg_genblock_infer_lds_bytes": (C.c_int64, [C.POINTER(_GenBlockInferArgs)]),
+    "kg_genblock_infer": (C.c_int, [C.POINTER(_GenBlockInferArgs), C.c_void_p]),
+    "kg_sample_inputs": (C.c_int, [C.POINTER(_SampleInputsArgs), C.c_void_p]),
+    "kg_trunc_lerp": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_float,
+                                C.c_void_p]),
 }
 
 _lib = None
@@ -2190,6 +2223,123 @@ def loss_append(ring: torch.Tensor, step: torch.Tensor, d_loss: torch.Tensor, g_
             raise TypeError("kg_loss_append: one-element fp32 losses expected")
     _check(load_library().kg_loss_append(ring.data_ptr(), ring.shape[0], step.data_ptr(), d_loss.data_ptr(), _ptr(g_loss),
                                          _stream()), "kg_loss_append")
+
+
+# ---- inference-only generation path (kg_sample.hip, kg_genblock.hip, kg_input.hip; sample.Sampler) -----------------------
+
+def bn_eval_coef(jobs: Sequence[dict]) -> None:
+    """Eval-mode BatchNorm coefficients of up to BN_EVAL_MAX_JOBS layers in ONE launch (kg_bn_eval_coef).  Each job:
+    dict(gamma | None, beta | None, running_mean, running_var, eps, coef (4, C) out); coef = [scale, shift, mean, rstd]
+    from the running statistics as they are when the launch runs."""
+    lib = load_library()
+    if not 1 <= len(jobs) <= BN_EVAL_MAX_JOBS:
+        raise ValueError("bn_eval_coef: 1..%d jobs expected" % BN_EVAL_MAX_JOBS)
+    arr = (_BnEvalJob * len(jobs))()
+    for i, j in enumerate(jobs):
+        coef = j["coef"]
+        if coef.dim() != 2 or coef.shape[0] != 4 or not coef.is_contiguous() or coef.dtype != torch.float32:
+            raise ValueError("bn_eval_coef: coef must be a contiguous fp32 (4, C) tensor")
+        c = coef.shape[1]
+        vecs = [_vec(j.get(k), c, "bn_eval_coef") for k in ("gamma", "beta", "running_mean", "running_var")]
+        if vecs[2] is None or vecs[3] is None:
+            raise ValueError("bn_eval_coef: a layer without running statistics has no eval-mode coefficients")
+        _need_cuda(coef, *vecs)
+        e = arr[i]
+        e.C, e.eps, e.coef = c, float(j["eps"]), coef.data_ptr()
+        e.gamma, e.beta, e.running_mean, e.running_var = [_ptr(q) for q in vecs]
+    _check(lib.kg_bn_eval_coef(arr, len(jobs), _stream()), "kg_bn_eval_coef")
+
+
+def _gb_infer_dims(a, d: GenBlockDims, slope):
+    a.Cin, a.C, a.K, a.Kp, a.Tc, a.Vc, a.T, a.V, a.rep = d.Cin, d.C, d.K, d.Kp, d.Tc, d.Vc, d.T, d.V, d.rep
+    a.res_kind, a.act, a.slope = d.res_kind, d.act, slope
+
+
+def genblock_infer_supported(d: GenBlockDims, n: int, wg, wr, wt) -> bool:
+    """Can kg_genblock_infer run this block (the rule of the training forward: genblock_supported)?"""
+    a = _GenBlockInferArgs()
+    a.N = n
+    _gb_infer_dims(a, d, 0.2)
+    a.wg, a.wr, a.wt = wg.data_ptr(), _ptr(wr), wt.data_ptr()
+    return load_library().kg_genblock_infer_lds_bytes(C.byref(a)) >= 0
+
+
+def genblock_infer(d: GenBlockDims, *, x, wg, wr=None, br=None, wt, bt=None, B, U=None, ct=None, cr=None, noise=None, nw=None,
+                   slope: float = 0.2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One generator block in eval mode as ONE launch (kg_genblock_infer): x (N, Cin, Tc, Vc) -> out (N, C, T, V) =
+    act(u * ct[0] + ct[1] + r * cr[0] + cr[1] + nw * noise), ct / cr the (4, C) coefficients of bn_eval_coef (None: no
+    BatchNorm on that branch)."""
+    lib = load_library()
+    a = _GenBlockInferArgs()
+    _gb_infer_dims(a, d, slope)
+    x = as_plane(x)
+    n, dev = x.shape[0], x.device
+    if tuple(x.shape[1:]) != (d.Cin, d.Tc, d.Vc):
+        raise ValueError("genblock_infer: input %s does not match (%d, %d, %d)" % (tuple(x.shape), d.Cin, d.Tc, d.Vc))
+    a.N, a.x = n, _plane(x)
+    _gb_weights(a, wg, wr, wt, B, U)
+    a.br, a.bt = _ptr(br), _ptr(bt)
+    for name, cf in (("ct", ct), ("cr", cr)):
+        if cf is not None and (tuple(cf.shape) != (4, d.C) or not cf.is_contiguous() or cf.dtype != torch.float32):
+            raise ValueError("genblock_infer: %s must be a contiguous fp32 (4, C) tensor" % name)
+    a.coef_t, a.coef_r = _ptr(ct), _ptr(cr)
+    if noise is not None and nw is not None:
+        noise, nw = noise.contiguous(), nw.reshape(-1).contiguous()
+        if noise.numel() != n * d.T * d.V or nw.numel() != d.C:
+            raise ValueError("genblock_infer: noise (N, 1, T, V) and nw (C) expected")
+        a.noise, a.nw = noise.data_ptr(), nw.data_ptr()
+    else:
+        noise = nw = None
+    if out is None:
+        out = new_plane(n, d.C, d.T, d.V, dev)
+    elif tuple(out.shape) != (n, d.C, d.T, d.V):
+        raise ValueError("genblock_infer: out must be (N, C, T, V)")
+    a.out = _plane(out)
+    _need_cuda(x, wg, wr, br, wt, bt, B, U, ct, cr, noise, nw, out)
+    Mh = d.Kp * d.C + (d.C if d.res_kind == 2 else 0)
+    _count("kg_genblock", 2.0 * n * (Mh * d.Cin * d.Tc * d.Vc + 3 * d.C * d.C * d.T * d.V) +
+           2.0 * n * (d.Kp + (1 if d.res_kind else 0)) * d.Vc * d.V * d.C * d.Tc)
+    _check(lib.kg_genblock_infer(C.byref(a), _stream()), "kg_genblock_infer")
+    return out
+
+
+def sample_inputs(step: torch.Tensor, ticket: torch.Tensor, seed: int, z: Optional[torch.Tensor] = None,
+                  noise: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None) -> None:
+    """Enqueue kg_sample_inputs: the random inputs of replay ``step[0]`` (device int64, advanced by the launch) - z
+    (B, latent), the flat noise buffer of one synthesis, the truncation draws t (mean_size, Dt); None = not drawn."""
+    _need_cuda(step, ticket, z, noise, t)
+    if step.dtype != torch.int64 or ticket.dtype != torch.int32:
+        raise TypeError("kg_sample_inputs: step int64 and ticket int32 expected")
+    for q in (z, noise, t):
+        if q is not None and (q.dtype != torch.float32 or not q.is_contiguous()):
+            raise TypeError("kg_sample_inputs: contiguous fp32 outputs expected")
+    a = _SampleInputsArgs()
+    a.step, a.ticket, a.seed = step.data_ptr(), ticket.data_ptr(), int(seed) & 0xffffffffffffffff
+    if z is not None:
+        if z.dim() != 2:
+            raise ValueError("kg_sample_inputs: z must be (B, latent)")
+        a.z, a.B, a.latent = z.data_ptr(), z.shape[0], z.shape[1]
+    if noise is not None:
+        a.noise, a.noise_len = noise.data_ptr(), noise.numel()
+    if t is not None:
+        if t.dim() != 2:
+            raise ValueError("kg_sample_inputs: t must be (mean_size, Dt)")
+        a.t, a.t_rows, a.t_cols = t.data_ptr(), t.shape[0], t.shape[1]
+    _check(load_library().kg_sample_inputs(C.byref(a), _stream()), "kg_sample_inputs")
+
+
+def trunc_lerp(x: torch.Tensor, t: torch.Tensor, truncation: float) -> torch.Tensor:
+    """x (N, D) <- m + truncation * (x - m) in place, m = column means of t (M, D) (kg_trunc_lerp); returns x."""
+    _need_cuda(x, t)
+    for q in (x, t):
+        if q.dim() != 2 or q.dtype != torch.float32 or q.stride(1) != 1:
+            raise TypeError("kg_trunc_lerp: fp32 (rows, D) matrices with unit column stride expected")
+    if x.shape[1] != t.shape[1]:
+        raise ValueError("kg_trunc_lerp: x (N, %d) and t (M, %d) differ in D" % (x.shape[1], t.shape[1]))
+    _check(load_library().kg_trunc_lerp(x.data_ptr(), x.stride(0), x.shape[0], x.shape[1], t.data_ptr(), t.stride(0), t.shape[0],
+                                        float(truncation), _stream()), "kg_trunc_lerp")
+    return x
+
 
 
 class Comm:

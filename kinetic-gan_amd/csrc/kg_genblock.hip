@@ -23,6 +23,9 @@
 // every extent a compile-time constant (divisions by constants, the matrix-core / VALU choice and the residual kind resolved
 // at compile time) - the six instantiations of GB_GEOMETRIES are the fusable blocks of the NTU and Human3.6M generators and
 // run 1.5-2.5x faster than the run-time form GbRt, which serves every other shape (KG_GB_RT=1 forces it).
+//
+// Inference (kg_genblock_infer): in eval mode the BatchNorm coefficients are inputs, so the same stages end in
+// the block's own normalise + noise + activation - no statistics, no tape, no workspace, no ticket, no pending tail.
 #include "kg_common.h"
 
 namespace {
@@ -37,6 +40,7 @@ constexpr int NT = 512;           // 8 waves: two per SIMD hide each other's LDS
 constexpr int NW = NT / 64;
 constexpr int UB = KG_GB_UB;           // elements a thread has in flight in the streaming loops (all loads before the first use)
 constexpr int GB_MAX_LDS = 150 * 1024;
+constexpr int GB_INFER_MIN_COLS = 16;      // kg_genblock_infer: fewest input-grid columns of a block that takes the fused form
 constexpr int GB_VALU_MAXM = 32, GB_VALU_MAXMK = 2048;
 typedef float gb_f4 __attribute__((ext_vector_type(4)));
 
@@ -900,6 +904,149 @@ __global__ __launch_bounds__(NT) void kg_genblock_bwd_kernel(const KgGenBlockBwd
     }
 }
 
+// ======================================================================================================================
+// inference (eval-mode BatchNorm: the coefficients are inputs)
+// ======================================================================================================================
+// Stages 0-3 as kg_genblock_fwd_kernel, then the block's own tail.  With the coefficients known before the launch there
+// are no statistics to take, nothing the backward pass would read, and so no workspace, ticket or pending tail: a
+// workgroup never looks at what another one wrote.  (A separate template on the shared gb_* helpers: the training
+// kernels' code is untouched.)  G::BNT plays no part here - coef_t / coef_r are tested at run time, once per element run.
+template <typename G>
+__global__ __launch_bounds__(NT) void kg_genblock_infer_kernel(const KgGenBlockInferArgs a, const GbLayout L) {
+    extern __shared__ float lds[];
+    constexpr int UBE = G::CT ? 8 : UB;
+    const int tid = threadIdx.x;
+    const int n = blockIdx.x;
+    const int C = G::CT ? G::C : a.C, Cin = G::CT ? G::Cin : a.Cin, V = G::CT ? G::V : a.V, Vc = G::CT ? G::Vc : a.Vc;
+    const int Tc = G::CT ? G::Tc : a.Tc, rep = G::CT ? G::rep : a.rep, Kp = G::CT ? G::Kp : a.Kp, T_ = G::CT ? G::T : a.T;
+    const int res_kind = G::CT ? G::RES : a.res_kind;
+    const int Nc = Tc * Vc, Nf = T_ * V, ZP = (T_ + 2) * V, Mg = Kp * C, Mh = Mg + (res_kind == 2 ? C : 0);
+    const bool mfma0 = G::CT ? gb_use_mfma(Mh, Cin, Nc, false) : (L.mfma0 != 0);
+    const bool mfma1 = G::CT ? gb_use_mfma(C, 3 * C, Nf, false) : (L.mfma1 != 0);
+    float* const X = lds + L.x;
+    float* const YC = lds + L.yc;
+    float* const UO = lds + L.uo;
+    float* const Z = lds + L.z;
+    float* const R = lds + L.r;
+    float* const Bs = lds + L.bs;
+    float* const Us = lds + L.us;
+    float* const Wl = lds + L.wl;
+    float* const Brs = lds + L.brs;
+
+    // ---- stage 0: input, adjacency, tables (all loads of UBE elements before the first use)
+    {
+        const unsigned tot = (unsigned)(Cin * Nc);
+        const float* xp = a.x.p + (long)n * a.x.sN;
+        for (unsigned e0 = tid; e0 < tot; e0 += NT * UBE) {
+            float v[UBE];
+#pragma unroll
+            for (int i = 0; i < UBE; ++i) {
+                const unsigned e = e0 + i * NT;
+                unsigned c, j;
+                GB_DIVMOD(G::Tc * G::Vc, L.dNc, e < tot ? e : 0u, c, j);
+                v[i] = e < tot ? xp[(long)c * a.x.sC + j] : 0.f;
+            }
+#pragma unroll
+            for (int i = 0; i < UBE; ++i)
+                if (e0 + i * NT < tot) X[e0 + i * NT] = v[i];
+        }
+    }
+    for (int i = tid; i < Kp * Vc * V; i += NT) Bs[i] = a.b[i];
+    for (int i = tid; i < Vc * V; i += NT) Us[i] = a.u ? a.u[i] : ((i / V) == (i % V) ? 1.f : 0.f);
+    if (res_kind == 2 && a.br)
+        for (int i = tid; i < C; i += NT) Brs[i] = a.br[i];
+    for (int i = tid; i < C * 2 * V; i += NT) {          // zero halo frames of z (frame 0 and frame T + 1)
+        const int c = i / (2 * V), q = i - c * 2 * V;
+        Z[c * ZP + (q < V ? q : ZP - 2 * V + q)] = 0.f;
+    }
+    __syncthreads();
+
+    // ---- stage 1: yc = [W_gcn[:Mg]; W_res] x on the input grid
+    {
+        GbA A{a.wg, a.wr, Mg, Cin, 1};
+        gb_gemm<false>(mfma0, A, KLin{1}, Mh, Cin, X, KLin{Nc}, Nc, YC, Nc, nullptr, Wl);
+    }
+    __syncthreads();
+
+    // ---- stage 2: z = sum_k yc_k (U A_k), r = yc_res U + b_res | x U, frames repeated
+    {
+        gb_mm(C * Tc, Kp * Vc, V,
+              [&](int m, int k) {
+                  unsigned c, tc, kk, vc;
+                  GB_DIVMOD(G::Tc, L.dTc, (unsigned)m, c, tc);
+                  GB_DIVMOD(G::Vc, L.dVc, (unsigned)k, kk, vc);
+                  return YC[(kk * C + c) * Nc + tc * Vc + vc];
+              },
+              [&](int k, int j) { return Bs[k * V + j]; },
+              [&](int m, int j, float v) {
+                  unsigned c, tc;
+                  GB_DIVMOD(G::Tc, L.dTc, (unsigned)m, c, tc);
+                  float* zp = Z + c * ZP + V + (tc * rep) * V + j;
+                  for (int q = 0; q < rep; ++q) zp[q * V] = v;
+              });
+        if (res_kind != 0) {
+            const float* src = res_kind == 2 ? YC + Mg * Nc : X;          // [C][Nc]
+            const bool bias = res_kind == 2 && a.br != nullptr;
+            gb_mm(C * Tc, Vc, V,
+                  [&](int m, int k) {
+                      unsigned c, tc;
+                      GB_DIVMOD(G::Tc, L.dTc, (unsigned)m, c, tc);
+                      return src[c * Nc + tc * Vc + k];
+                  },
+                  [&](int k, int j) { return Us[k * V + j]; },
+                  [&](int m, int j, float v) {
+                      unsigned c, tc;
+                      GB_DIVMOD(G::Tc, L.dTc, (unsigned)m, c, tc);
+                      if (bias) v += Brs[c];
+                      float* rp = R + c * Nf + (tc * rep) * V + j;
+                      for (int q = 0; q < rep; ++q) rp[q * V] = v;
+                  });
+        }
+    }
+    __syncthreads();
+
+    // ---- stage 3: u = W_tcn (*) z + b
+    {
+        GbA A{a.wt, a.wt, 1 << 30, 3 * C, 1};
+        gb_gemm<false>(mfma1, A, KLin{1}, C, 3 * C, Z, KTap{ZP, V, 0}, Nf, UO, Nf, a.bt, Wl);
+    }
+    __syncthreads();
+
+    // ---- stage 4: out = act(u s_t + b_t + r s_r + b_r + nw noise): the arithmetic of the training kernel's pending tail
+    {
+        float* const ob = a.out.p + (long)n * a.out.sN;
+        const float* ct = a.coef_t;
+        const float* cr = a.coef_r;
+        const float* nz = (a.noise && a.nw) ? a.noise + (long)n * Nf : nullptr;
+        const unsigned tot = (unsigned)(C * Nf);
+        for (unsigned e0 = tid; e0 < tot; e0 += NT * UBE) {
+            float s0[UBE], b0[UBE], s1[UBE], b1[UBE], nv_[UBE], wv[UBE];
+            unsigned cc[UBE], jj[UBE];
+#pragma unroll
+            for (int i = 0; i < UBE; ++i) {
+                const unsigned e = e0 + i * NT;
+                GB_DIVMOD(G::T * G::V, L.dNf, e < tot ? e : 0u, cc[i], jj[i]);
+                const unsigned c = cc[i];
+                s0[i] = ct ? ct[c] : 1.f;
+                b0[i] = ct ? ct[C + c] : 0.f;
+                s1[i] = cr ? cr[c] : 1.f;
+                b1[i] = cr ? cr[C + c] : 0.f;
+                nv_[i] = nz ? nz[jj[i]] : 0.f;
+                wv[i] = nz ? a.nw[c] : 0.f;
+            }
+#pragma unroll
+            for (int i = 0; i < UBE; ++i) {
+                const unsigned e = e0 + i * NT;
+                if (e >= tot) continue;
+                float v = ct ? fmaf(UO[e], s0[i], b0[i]) : UO[e];
+                if (res_kind != 0) v += cr ? fmaf(R[e], s1[i], b1[i]) : R[e];
+                if (nz) v = fmaf(wv[i], nv_[i], v);
+                ob[(long)cc[i] * a.out.sC + jj[i]] = kg_act(v, a.act, a.slope);
+            }
+        }
+    }
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------
 struct Dims { int N, Cin, C, K, Kp, Tc, Vc, T, V, rep, res_kind; };
 
@@ -959,6 +1106,7 @@ long make_layout(const Dims& d, bool bwd, GbLayout& L) {
 }
 
 Dims dims_of(const KgGenBlockArgs* a) { return Dims{a->N, a->Cin, a->C, a->K, a->Kp, a->Tc, a->Vc, a->T, a->V, a->rep, a->res_kind}; }
+Dims dims_of(const KgGenBlockInferArgs* a) { return Dims{a->N, a->Cin, a->C, a->K, a->Kp, a->Tc, a->Vc, a->T, a->V, a->rep, a->res_kind}; }
 Dims dims_of(const KgGenBlockBwdArgs* a) { return Dims{a->N, a->Cin, a->C, a->K, a->Kp, a->Tc, a->Vc, a->T, a->V, a->rep, a->res_kind}; }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -1088,6 +1236,54 @@ extern "C" int kg_genblock_bwd(const KgGenBlockBwdArgs* a, void* stream) {
 #undef GB_TRY
     hipLaunchKernelGGL(kg_genblock_bwd_kernel<GbRt>, dim3(a->N), dim3(NT), (size_t)lds, (hipStream_t)stream, *a, L);
     return kg_launch_status("kg_genblock_bwd");
+}
+
+extern "C" int64_t kg_genblock_infer_lds_bytes(const KgGenBlockInferArgs* a) {
+    KG_REQUIRE(a != nullptr, "kg_genblock_infer_lds_bytes: null args");
+    if (check_dims(dims_of(a), "kg_genblock_infer_lds_bytes")) return -2;
+    // One sample per workgroup: every workgroup streams the block's weights and its contractions have Tc * Vc columns.
+    // The weight-bound front blocks (1-4 columns against 0.7-1.8 MB of weights) do not fit this form - the rule the
+    // training forward applies on the host (gen_trunk._fusable), here part of the answer.
+    if (a->T <= 1 || a->Tc * a->Vc < GB_INFER_MIN_COLS) return -1;
+    GbLayout L;
+    const long b = make_layout(dims_of(a), false, L);
+    if (b < 0) return -1;
+    // 16-byte row loads of the matrix-core contractions (the rule of kg_genblock_lds_bytes)
+    if (L.mfma0 && !(aligned16(a->wg) && (a->res_kind != 2 || aligned16(a->wr)))) return -1;
+    if (L.mfma1 && !aligned16(a->wt)) return -1;
+    return b;
+}
+
+extern "C" int kg_genblock_infer(const KgGenBlockInferArgs* a, void* stream) {
+    KG_REQUIRE(a != nullptr, "kg_genblock_infer: null args");
+    if (int rc = check_dims(dims_of(a), "kg_genblock_infer")) return rc;
+    const int64_t lds = kg_genblock_infer_lds_bytes(a);
+    KG_REQUIRE(lds >= 0, "kg_genblock_infer: the block does not fit the fused form (kg_genblock_infer_lds_bytes)");
+    KG_REQUIRE(a->wg && a->wt && a->b, "kg_genblock_infer: null weight / adjacency pointer");
+    KG_REQUIRE(a->res_kind != 2 || a->wr, "kg_genblock_infer: conv residual without its weight");
+    KG_REQUIRE(a->u != nullptr || a->Vc == a->V, "kg_genblock_infer: Vc=%d != V=%d without an up-sampling matrix", a->Vc, a->V);
+    KG_REQUIRE(a->x.p != nullptr && a->out.p != nullptr, "kg_genblock_infer: null x / out");
+    KG_REQUIRE((a->noise == nullptr) == (a->nw == nullptr), "kg_genblock_infer: noise and nw go together");
+    GbLayout L;
+    make_layout(dims_of(a), false, L);
+    static unsigned long long attr_mask = 0;
+    const bool first = kg_first_on_device(attr_mask);
+    const Dims d = dims_of(a);
+#define GB_ATTR(...) do { using G_ = GbGeo<__VA_ARGS__>; KG_SET_DYN_LDS(kg_genblock_infer_kernel<G_>, GB_MAX_LDS); } while (0)
+    if (first) {                                    // (per device: every instantiation, before any of them launches)
+        GB_GEOMETRIES(GB_ATTR);
+        KG_SET_DYN_LDS(kg_genblock_infer_kernel<GbRt>, GB_MAX_LDS);
+    }
+#undef GB_ATTR
+    // (eval mode: the BatchNorm flag of a geometry is not part of the match - the coefficient pointers say it at run time)
+#define GB_TRY(...) do { using G_ = GbGeo<__VA_ARGS__>; \
+        if (geo_matches<G_>(d, G_::BNT) && !kg_env().gb_rt) { \
+            hipLaunchKernelGGL(kg_genblock_infer_kernel<G_>, dim3(a->N), dim3(NT), (size_t)lds, (hipStream_t)stream, *a, L); \
+            return kg_launch_status("kg_genblock_infer"); } } while (0)
+    GB_GEOMETRIES(GB_TRY);
+#undef GB_TRY
+    hipLaunchKernelGGL(kg_genblock_infer_kernel<GbRt>, dim3(a->N), dim3(NT), (size_t)lds, (hipStream_t)stream, *a, L);
+    return kg_launch_status("kg_genblock_infer");
 }
 
 #ifdef KG_GB_STAMP

@@ -17,6 +17,9 @@
 // The counter: every workgroup reads *step first (the value is an input of all its work), draws a ticket when it is done;
 // the workgroup that draws the last ticket stores step + 1 and puts the ticket counter back to zero.  No workgroup reads
 // anything another one writes in the launch, so no fence is needed beyond the atomics' own ordering on one address.
+//
+// kg_sample_inputs (sample.Sampler) is the same scheme for a generation round: z, the noise planes of one
+// synthesis and the truncation draws as three flat normal streams with counter word 1 = KG_STREAM_SAMPLE + stream.
 #include <math.h>
 
 #include "kg_common.h"
@@ -208,7 +211,73 @@ __global__ __launch_bounds__(64) void kg_loss_append_kernel(float* ring, long ri
     ring[2 * k + 1] = g_loss != nullptr ? *g_loss : (s == 0 ? __builtin_nanf("") : ring[2 * kp + 1]);
 }
 
+// ---- kg_sample_inputs: the random inputs of one Sampler replay (sample.py) - three flat normal streams -----------------
+struct SampleDev {
+    long long* step;
+    int* ticket;
+    unsigned k0, k1;
+    float* dst[3];              // z, noise, t (NULL: skipped, no workgroups)
+    long len[3];
+    unsigned b[3];              // workgroup ranges: stream k owns [b[k-1], b[k])
+};
+
+__global__ __launch_bounds__(SI_NT) void kg_sample_inputs_kernel(SampleDev a) {
+    const long long s = __hip_atomic_load(a.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned blk = blockIdx.x;
+    const unsigned s_lo = (unsigned)((unsigned long long)s), s_hi = (unsigned)((unsigned long long)s >> 32);
+    const int k = blk < a.b[0] ? 0 : (blk < a.b[1] ? 1 : 2);
+    const long q = (long)(blk - (k == 0 ? 0u : a.b[k - 1])) * SI_NT + threadIdx.x;
+    const long len = a.len[k];
+    if (4 * q < len) {
+        unsigned w[4];
+        philox4x32_10((unsigned)q, KG_STREAM_SAMPLE + (unsigned)k, s_lo, s_hi, a.k0, a.k1, w);
+        float v[4];
+        box_muller(w[0], w[1], v[0], v[1]);
+        box_muller(w[2], w[3], v[2], v[3]);
+        store4(a.dst[k], 4 * q, len, v);
+    }
+    // last arriver advances the counter (every workgroup has read it before it draws its ticket): nobody waits
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int t = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (t == (int)gridDim.x - 1) {
+            __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.step, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int kg_sample_inputs(const KgSampleInputsArgs* a, void* stream) {
+    KG_REQUIRE(a != nullptr, "kg_sample_inputs: null args");
+    KG_REQUIRE(a->step != nullptr && a->ticket != nullptr, "kg_sample_inputs: null step / ticket");
+    SampleDev d = {};
+    d.step = (long long*)a->step;  d.ticket = a->ticket;
+    d.k0 = (unsigned)(a->seed & 0xffffffffull);  d.k1 = (unsigned)(a->seed >> 32);
+    if (a->z != nullptr) {
+        KG_REQUIRE(a->B >= 1 && a->latent >= 1, "kg_sample_inputs: z with B=%d latent=%d", a->B, a->latent);
+        d.dst[0] = a->z;  d.len[0] = (long)a->B * a->latent;
+    }
+    if (a->noise != nullptr) {
+        KG_REQUIRE(a->noise_len >= 1, "kg_sample_inputs: noise_len=%lld < 1", (long long)a->noise_len);
+        d.dst[1] = a->noise;  d.len[1] = (long)a->noise_len;
+    }
+    if (a->t != nullptr) {
+        KG_REQUIRE(a->t_rows >= 1 && a->t_cols >= 1, "kg_sample_inputs: t with t_rows=%d t_cols=%d", a->t_rows, a->t_cols);
+        d.dst[2] = a->t;  d.len[2] = (long)a->t_rows * a->t_cols;
+    }
+    long total = 0;
+    for (int k = 0; k < 3; ++k) {
+        KG_REQUIRE(d.len[k] <= 0x7fffffffL * 4L, "kg_sample_inputs: stream %d too long", k);
+        total += kg_cdiv((d.len[k] + 3) / 4, SI_NT);
+        KG_REQUIRE(total <= 0x7fffffffL, "kg_sample_inputs: grid too large");
+        d.b[k] = (unsigned)total;
+    }
+    KG_REQUIRE(total >= 1, "kg_sample_inputs: nothing to write (no z, noise or t)");
+    hipLaunchKernelGGL(kg_sample_inputs_kernel, dim3((unsigned)total), dim3(SI_NT), 0, (hipStream_t)stream, d);
+    return kg_launch_status("kg_sample_inputs");
+}
 
 extern "C" int kg_step_inputs(const KgStepInputsArgs* a, void* stream) {
     KG_REQUIRE(a != nullptr, "kg_step_inputs: null args");
