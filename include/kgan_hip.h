@@ -526,6 +526,15 @@ int kg_adam_step(float* p, const float* g, float* m, float* v, int64_t n,
 int kg_adam_step_fused(float* p, float* g, float* m, float* v, int64_t n,
                        float lr, float b1, float b2, float eps, const int32_t* step, float grad_scale,
                        int32_t zero_grad, void* stream);
+/* The same step with an exponential moving average of the parameters riding on the launch (still ABI v9): e is a fifth flat
+ * buffer of n elements; the thread that has computed p_new also writes  e <- e + (1 - beta_s) (p_new - e)  with
+ * beta_s = ema_decay when ema_warmup == 0, else min(ema_decay, (1 + s) / (ema_warmup + s)), s = *step read from device
+ * memory (a replayed graph follows the ramp).  p, g, m, v come out bit for bit as from kg_adam_step_fused (zero_grad != 0)
+ * or kg_adam_step (zero_grad == 0).  128-bit accesses when all FIVE buffers are 16-byte aligned.  0 <= ema_decay < 1,
+ * ema_warmup >= 0.                                                                                                      */
+int kg_adam_step_ema(float* p, float* g, float* m, float* v, float* e, int64_t n,
+                     float lr, float b1, float b2, float eps, const int32_t* step, float grad_scale,
+                     int32_t zero_grad, float ema_decay, float ema_warmup, void* stream);
 
 /* ---- container-level fusions around the discriminator's blocks ---------------------------------------
  * kg_head_fwd   : v[n] = b + sum_c w[c] * mean_{t,v} h[n,c,t,v]           global average pool + Linear(latent, 1)

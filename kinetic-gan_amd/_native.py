@@ -426,6 +426,8 @@ EXPORTS = {
     "kg_loss_append": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kg_adam_step_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                      C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
+    "kg_adam_step_ema": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
+                                   C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
     "kg_bn_eval_coef": (C.c_int, [C.POINTER(_BnEvalJob), C.c_int32, C.c_void_p]),
     "kg_genblock_infer_lds_bytes": (C.c_int64, [C.POINTER(_GenBlockInferArgs)]),
     "kg_genblock_infer": (C.c_int, [C.POINTER(_GenBlockInferArgs), C.c_void_p]),
@@ -1838,6 +1840,20 @@ def adam_step(p, g, m, v, lr, b1, b2, eps, step_t: torch.Tensor, grad_scale: flo
         return
     _check(lib.kg_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
                             lr, b1, b2, eps, step_t.data_ptr(), grad_scale, _stream()), "kg_adam_step")
+
+
+def adam_step_ema(p, g, m, v, e, lr, b1, b2, eps, step_t: torch.Tensor, grad_scale: float, zero_grad: bool, decay: float,
+                  warmup: float):
+    """``adam_step`` with the parameters' moving average ``e`` updated by the same launch (kg_adam_step_ema):
+    e += (1 - beta_s) (p_new - e), beta_s = decay, or min(decay, (1 + s) / (warmup + s)) with s = step_t when warmup != 0."""
+    lib = load_library()
+    _need_cuda(p, g, m, v, e, step_t)
+    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous() and e.is_contiguous()
+    assert g.numel() == m.numel() == v.numel() == e.numel() == p.numel() and e.dtype == torch.float32
+    assert step_t.dtype == torch.int32
+    _check(lib.kg_adam_step_ema(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), e.data_ptr(), p.numel(), lr, b1, b2, eps,
+                                step_t.data_ptr(), grad_scale, 1 if zero_grad else 0, decay, warmup, _stream()),
+           "kg_adam_step_ema")
 
 
 # ---- container-level fusions around the discriminator's blocks (kg_disc.hip) ---------------------------------------------

@@ -556,6 +556,58 @@ __global__ __launch_bounds__(NT) void kg_adam_kernel(float* p, float* g, float* 
     }
 }
 
+// kg_adam_step_ema: the step above (same adam_one, same thread map) with an exponential moving average e of the parameters
+// riding on the launch - the thread that has p_new in registers also moves e:  e += (1 - beta_s) (p_new - e).
+// beta_s = decay, or min(decay, (1 + s) / (warmup + s)) with s = *step when warmup != 0: computed here, from the live step,
+// so that a replayed graph follows the ramp.  The increment form keeps an element moving until (1 - beta_s) |p - e| drops
+// under half an ulp of e (beta e + (1 - beta) p would round the large product first).
+__device__ __forceinline__ void ema_one(float& e, float p, float omb) { e = e + omb * (p - e); }
+
+template <bool VEC>
+__global__ __launch_bounds__(NT) void kg_adam_ema_kernel(float* p, float* g, float* m, float* v, float* ema, long n,
+                                                         float lr, float b1, float b2, float eps, const int32_t* step,
+                                                         float gscale, int zero, float decay, float warmup) {
+    const float t = (float)(*step);
+    const float step_size = lr / (1.f - powf(b1, t));
+    const float rs_bc2 = 1.f / sqrtf(1.f - powf(b2, t));
+    const float beta = warmup != 0.f ? fminf(decay, (1.f + t) / (warmup + t)) : decay;
+    const float omb = 1.f - beta;
+    const long i = (long)blockIdx.x * NT + threadIdx.x;
+    if constexpr (VEC) {
+        const long e = 4 * i;
+        if (e + 3 < n) {
+            float4 pp = reinterpret_cast<float4*>(p)[i], mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+            const float4 gg = reinterpret_cast<const float4*>(g)[i];
+            float4 ee = reinterpret_cast<float4*>(ema)[i];
+            adam_one(pp.x, gg.x * gscale, mm.x, vv.x, b1, b2, eps, step_size, rs_bc2);
+            adam_one(pp.y, gg.y * gscale, mm.y, vv.y, b1, b2, eps, step_size, rs_bc2);
+            adam_one(pp.z, gg.z * gscale, mm.z, vv.z, b1, b2, eps, step_size, rs_bc2);
+            adam_one(pp.w, gg.w * gscale, mm.w, vv.w, b1, b2, eps, step_size, rs_bc2);
+            ema_one(ee.x, pp.x, omb);
+            ema_one(ee.y, pp.y, omb);
+            ema_one(ee.z, pp.z, omb);
+            ema_one(ee.w, pp.w, omb);
+            reinterpret_cast<float4*>(p)[i] = pp;
+            reinterpret_cast<float4*>(m)[i] = mm;
+            reinterpret_cast<float4*>(v)[i] = vv;
+            reinterpret_cast<float4*>(ema)[i] = ee;
+            if (zero) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            for (long k = e; k < n; ++k) {
+                adam_one(p[k], g[k] * gscale, m[k], v[k], b1, b2, eps, step_size, rs_bc2);
+                ema_one(ema[k], p[k], omb);
+                if (zero) g[k] = 0.f;
+            }
+        }
+    } else {
+        if (i < n) {
+            adam_one(p[i], g[i] * gscale, m[i], v[i], b1, b2, eps, step_size, rs_bc2);
+            ema_one(ema[i], p[i], omb);
+            if (zero) g[i] = 0.f;
+        }
+    }
+}
+
 int validate_elt(const KgEltArgs* a, const char* who) {
     KG_REQUIRE(a != nullptr, "%s: null args", who);
     KG_REQUIRE(a->N > 0 && a->C > 0 && a->T > 0 && a->V > 0, "%s: bad dims", who);
@@ -890,6 +942,23 @@ extern "C" int kg_adam_step_fused(float* p, float* g, float* m, float* v, int64_
         hipLaunchKernelGGL((kg_adam_kernel<false, true>), dim3(kg_cdiv(n, NT)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v,
                            (long)n, lr, b1, b2, eps, step, grad_scale, (int)zero_grad);
     return kg_launch_status("kg_adam_step_fused");
+}
+
+extern "C" int kg_adam_step_ema(float* p, float* g, float* m, float* v, float* e, int64_t n, float lr, float b1, float b2,
+                                float eps, const int32_t* step, float grad_scale, int32_t zero_grad, float ema_decay,
+                                float ema_warmup, void* stream) {
+    KG_REQUIRE(p && g && m && v && e && step, "kg_adam_step_ema: null pointer");
+    KG_REQUIRE(n > 0, "kg_adam_step_ema: n=%ld", (long)n);
+    KG_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "kg_adam_step_ema: ema_decay=%g (need 0 <= decay < 1)", (double)ema_decay);
+    KG_REQUIRE(ema_warmup >= 0.f, "kg_adam_step_ema: ema_warmup=%g", (double)ema_warmup);
+    const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)e) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL((kg_adam_ema_kernel<true>), dim3(kg_cdiv(kg_cdiv(n, 4), NT)), dim3(NT), 0, (hipStream_t)stream, p, g, m,
+                           v, e, (long)n, lr, b1, b2, eps, step, grad_scale, (int)zero_grad, ema_decay, ema_warmup);
+    else
+        hipLaunchKernelGGL((kg_adam_ema_kernel<false>), dim3(kg_cdiv(n, NT)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, e,
+                           (long)n, lr, b1, b2, eps, step, grad_scale, (int)zero_grad, ema_decay, ema_warmup);
+    return kg_launch_status("kg_adam_step_ema");
 }
 
 

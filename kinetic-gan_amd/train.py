@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import collections
 import os
+import warnings
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -116,7 +117,7 @@ class TrainLoop:
     def __init__(self, G, D, data, batch_size: int, t_size: int, n_critic: int = 5, seed: int = 0, lr: float = 2e-4,
                  b1: float = 0.5, b2: float = 0.999, lambda_gp: float = 10.0, use_graph: bool = True,
                  ring_len: int = 4096, max_resident_bytes: Optional[int] = None, rank: int = 0, world: int = 1,
-                 run_ahead: int = 16):
+                 run_ahead: int = 16, ema_decay: Optional[float] = None, ema_warmup: float = 10.0):
         self.G, self.D = G, D
         self.device = next(G.parameters()).device
         if self.device.type != "cuda":
@@ -137,7 +138,12 @@ class TrainLoop:
         self.bpe = (self.n // self.B) // self.world          # batches of one epoch per rank, tail dropped
         if self.bpe < 1:
             raise ValueError("TrainLoop: the dataset holds fewer than batch_size * world samples")
-        self.trainer = Trainer(G, D, lr=lr, b1=b1, b2=b2, lambda_gp=lambda_gp, n_critic=n_critic, world_size=self.world)
+        # ema_decay (None or 0: off): an exponential moving average of the generator's weights, moved by the generator's
+        # Adam launch - inside the captured iteration; ema_generator() is the module over it
+        self.ema_decay = float(ema_decay) if ema_decay else None
+        self.ema_warmup = float(ema_warmup)
+        self.trainer = Trainer(G, D, lr=lr, b1=b1, b2=b2, lambda_gp=lambda_gp, n_critic=n_critic, world_size=self.world,
+                               ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
         dev, B = self.device, self.B
         self.latent = G.mlp.mlp[0].in_features - G.label_emb.num_embeddings
         self.n_classes = G.label_emb.num_embeddings
@@ -188,6 +194,11 @@ class TrainLoop:
         s = self.step_count if step is None else step
         return ((s % self.bpe) % self.n_critic) == 0
 
+    def ema_generator(self):
+        """The averaged generator (``Trainer.ema_generator``): weights from the moving average, BatchNorm statistics shared
+        with the live generator.  A ``Sampler`` captured over it follows the training replays without a rebuild."""
+        return self.trainer.ema_generator()
+
     # ---- the iteration ---------------------------------------------------------------------------------------------
     def _iteration(self, with_g: bool):
         """kg_step_inputs, the WGAN-GP iteration on the static buffers, the loss record: what a graph holds"""
@@ -202,6 +213,8 @@ class TrainLoop:
         ts = [self.step_dev, self.ring, self.real, self.labels, self.z, self.alpha, self.noise]
         for f in (tr.fG, tr.fD):
             ts += [f.flat, f.grad, f.exp_avg, f.exp_avg_sq, f.step]
+        if tr.fG.ema is not None:
+            ts.append(tr.fG.ema)
         for m in (self.G, self.D):
             ts += list(m.buffers())
         return ts
@@ -315,6 +328,9 @@ class TrainLoop:
         for name, f, m in (("G", tr.fG, self.G), ("D", tr.fD, self.D)):
             out[name] = {"flat": f.flat.cpu(), "exp_avg": f.exp_avg.cpu(), "exp_avg_sq": f.exp_avg_sq.cpu(),
                          "adam_step": f.step.cpu(), "buffers": {k: b.cpu() for k, b in m.named_buffers()}}
+        if tr.fG.ema is not None:
+            out["G"]["ema"] = tr.fG.ema.cpu()
+            out["ema"] = {"decay": self.ema_decay, "warmup": self.ema_warmup}
         return out
 
     def load_state_dict(self, sd: dict) -> None:
@@ -322,6 +338,11 @@ class TrainLoop:
             if sd[k] != mine:
                 raise ValueError("TrainLoop.load_state_dict: %s is %r in the checkpoint, %r here" % (k, sd[k], mine))
         tr = self.trainer
+        have = sd.get("ema") is not None and sd["G"].get("ema") is not None
+        if tr.fG.ema is not None and have:
+            for k, mine in (("decay", self.ema_decay), ("warmup", self.ema_warmup)):
+                if float(sd["ema"][k]) != mine:
+                    raise ValueError("TrainLoop.load_state_dict: ema %s is %r in the checkpoint, %r here" % (k, sd["ema"][k], mine))
         for name, f, m in (("G", tr.fG, self.G), ("D", tr.fD, self.D)):
             s = sd[name]
             f.flat.copy_(s["flat"])
@@ -334,6 +355,13 @@ class TrainLoop:
                 raise ValueError("TrainLoop.load_state_dict: buffers of %s do not match" % name)
             for k, b in bufs.items():
                 b.copy_(s["buffers"][k])
+        if tr.fG.ema is not None:                # (an average in the state is ignored by a loop without one)
+            if have:
+                tr.fG.ema.copy_(sd["G"]["ema"])
+            else:
+                warnings.warn("TrainLoop.load_state_dict: the checkpoint holds no weight average; it starts from the loaded "
+                              "generator weights")
+                tr.fG.ema.copy_(tr.fG.flat)
         self.step_count = self._flushed = self._first = int(sd["step"])
         self._d_hist, self._g_hist = [], []
         self.step_dev.fill_(self.step_count)
@@ -343,9 +371,10 @@ class TrainLoop:
         torch.cuda.synchronize(self.device)
 
     # ---- the reference's loop ------------------------------------------------------------------------------------------
-    def sample_action(self, path: str) -> None:
-        """kinetic-gan.py:84-91: 10 samples per class, labels 0 .. n_classes-1 repeated, saved as one .npy"""
-        imgs, _, _ = sample_actions(self.G, self.n_classes, self.latent, gen_qtd=10, qtd=10)
+    def sample_action(self, path: str, G=None) -> None:
+        """kinetic-gan.py:84-91: 10 samples per class, labels 0 .. n_classes-1 repeated, saved as one .npy (``G``: another
+        generator than the live one - the averaged module)"""
+        imgs, _, _ = sample_actions(self.G if G is None else G, self.n_classes, self.latent, gen_qtd=10, qtd=10)
         with open(path, "wb") as f:
             np.save(f, imgs.cpu().numpy())
 
@@ -361,10 +390,16 @@ class TrainLoop:
         ring -, ``actions/<batches_done>.npy`` and ``plot_loss.mat`` every ``sample_interval`` iterations, both networks'
         checkpoints (``models/generator_<batches_done>.pth``, written in the background) every ``checkpoint_interval``.
         ``state_path``: ``state_dict()`` is saved there with every checkpoint and at the end (``load_state_dict`` of that
-        file continues the run bit for bit)."""
+        file continues the run bit for bit).  With the weight average on (``ema_decay``) the averaged generator is written
+        next to the live one at the same intervals: ``models/generator_ema_<batches_done>.pth`` and
+        ``actions_ema/<batches_done>.npy``."""
         models_out, actions_out = os.path.join(out_dir, "models"), os.path.join(out_dir, "actions")
         os.makedirs(models_out, exist_ok=True)
         os.makedirs(actions_out, exist_ok=True)
+        ema_G = self.ema_generator() if self.ema_decay else None
+        if ema_G is not None:
+            ema_actions_out = os.path.join(out_dir, "actions_ema")
+            os.makedirs(ema_actions_out, exist_ok=True)
         log_interval = max(1, min(int(log_interval), self.ring_len))
         writer = AsyncCheckpointWriter()
         try:
@@ -377,10 +412,14 @@ class TrainLoop:
                     log("[Epoch %d/%d] [Batch %d/%d] [D loss: %f] [G loss: %f]" % (epoch, n_epochs, i, self.bpe, d[-1], g[-1]))
                 if batches_done % sample_interval == 0:
                     self.sample_action(os.path.join(actions_out, "%d.npy" % batches_done))
+                    if ema_G is not None:
+                        self.sample_action(os.path.join(ema_actions_out, "%d.npy" % batches_done), ema_G)
                     self.save_losses(os.path.join(out_dir, "plot_loss.mat"))
                 if checkpoint_interval != -1 and batches_done % checkpoint_interval == 0:
                     writer.save(self.G, os.path.join(models_out, "generator_%d.pth" % batches_done))
                     writer.save(self.D, os.path.join(models_out, "discriminator_%d.pth" % batches_done))
+                    if ema_G is not None:
+                        writer.save(ema_G, os.path.join(models_out, "generator_ema_%d.pth" % batches_done))
                     if state_path is not None:
                         torch.save(self.state_dict(), state_path)
             self.save_losses(os.path.join(out_dir, "plot_loss.mat"))

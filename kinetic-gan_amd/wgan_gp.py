@@ -71,6 +71,9 @@ class FlatParams:
         # `_clean`: the bucket is known to be all zero (nothing but that launch has written it since)
         self.fused_step = False
         self._clean = False
+        # exponential moving average of `flat` (enable_ema): None = off, the optimiser launch is today's
+        self.ema = None
+        self.ema_decay = self.ema_warmup = None
         self.views = []
         keys = []
         for p, off in zip(self.params, self.offsets):
@@ -117,6 +120,19 @@ class FlatParams:
     def broadcast(self, src: int = 0):
         dist.broadcast(self.flat, src)
 
+    def enable_ema(self, decay: float, warmup: float = 10.0):
+        """Keep ``self.ema``, an exponential moving average of ``self.flat``, from now on: it starts as a copy of the
+        parameters as they are at this moment (under data parallel: enable after the broadcast) and every optimiser step
+        moves it inside its own launch (kg_adam_step_ema): e += (1 - beta_s) (p_new - e) with beta_s = decay, or
+        min(decay, (1 + s) / (warmup + s)) for warmup != 0, s = the 1-based count of the step (``self.step``)."""
+        decay, warmup = float(decay), float(warmup)
+        if not 0.0 < decay < 1.0:
+            raise ValueError("FlatParams.enable_ema: decay must lie in (0, 1), got %r" % decay)
+        if warmup < 0.0:
+            raise ValueError("FlatParams.enable_ema: warmup must be >= 0, got %r" % warmup)
+        self.ema = self.flat.detach().clone()
+        self.ema_decay, self.ema_warmup = decay, warmup
+
     def allreduce_and_step(self, lr, b1, b2, eps=1e-8, world: int = 1, gather: bool = True, comm=None):
         """``comm``: a ``_native.Comm`` - the gradient bucket is summed by kg_allreduce_flat (RCCL behind the C ABI, on
         torch's current stream: capturable) instead of torch.distributed."""
@@ -128,8 +144,13 @@ class FlatParams:
         elif world > 1:
             dist.all_reduce(self.grad, op=dist.ReduceOp.SUM)
         self.step += 1
-        nv.adam_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, lr, b1, b2, eps, self.step,
-                     1.0 / world, zero_grad=self.fused_step)
+        if self.ema is None:
+            nv.adam_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, lr, b1, b2, eps, self.step,
+                         1.0 / world, zero_grad=self.fused_step)
+        else:
+            # the same step; the launch also moves the average (kg_adam_step_ema)
+            nv.adam_step_ema(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.ema, lr, b1, b2, eps, self.step,
+                             1.0 / world, self.fused_step, self.ema_decay, self.ema_warmup)
         self._clean = self.fused_step
 
 
@@ -183,14 +204,18 @@ def gradient_penalty(D, real, fake, labels, alpha, keep: Optional[dict] = None):
 class Trainer:
     def __init__(self, G, D, lr=2e-4, b1=0.5, b2=0.999, lambda_gp=10.0, n_critic=5,
                  world_size: int = 1, flatten: bool = True, overlap: Optional[bool] = None, comm=None,
-                 fused_step: bool = True):
-        """``fused_step``: the optimiser launches clear the gradient buckets they have consumed (kg_adam_step_fused): after ``d_apply`` / ``g_apply`` the bucket reads zero - pass False to inspect the
+                 fused_step: bool = True, ema_decay: Optional[float] = None, ema_warmup: float = 10.0):
+        """``ema_decay`` (None or 0: off): keep an exponential moving average of the GENERATOR's weights, advanced once per
+        generator step inside its Adam launch (``FlatParams.enable_ema``); ``ema_generator()`` is the module over it.
+        ``fused_step``: the optimiser launches clear the gradient buckets they have consumed (kg_adam_step_fused): after ``d_apply`` / ``g_apply`` the bucket reads zero - pass False to inspect the
         gradients the optimiser used (the data-parallel tests do).
         ``overlap`` (opt-in): the critic's all-reduce + Adam run on a side stream underneath the generator step's G
         forward, which does not read D (kinetic-gan.py:167 needs the updated D only at :170); the two generator
         syntheses of the iteration are then NOT paired (the generator step keeps its own forward pass to hide the
         collective under).  Off by default."""
         self.G, self.D = G, D
+        if ema_decay and not flatten:
+            raise ValueError("Trainer: ema_decay needs the flat parameter buffers (flatten=True)")
         # ``comm``: a _native.Comm (kg_comm_init): the two gradient all-reduces of an iteration go through the C ABI
         # (kg_allreduce_flat) instead of torch.distributed.all_reduce; torch.distributed is then only used for the
         # one-off parameter / buffer broadcast at construction
@@ -219,6 +244,45 @@ class Trainer:
             self.fG.broadcast(0)
             self.fD.broadcast(0)
             self.broadcast_buffers()
+        self._ema_G = None
+        if ema_decay:
+            self.fG.enable_ema(ema_decay, ema_warmup)       # (after the broadcast: e_0 = the weights every rank starts from)
+
+    def ema_generator(self):
+        """The averaged generator: a ``Generator`` of the live one's structure whose parameters are views into ``fG.ema`` at
+        ``fG.offsets`` (``requires_grad=False``, not registered with the parameter sinks) and whose buffers - the
+        BatchNorm running statistics and batch counters - ARE the live generator's tensors: statistics are shared,
+        weights averaged.  Built once; it follows every later step (and graph replay) through those storages.  In eval
+        mode; ``state_dict()`` has the reference's keys in the reference's order."""
+        if self.fG is None or self.fG.ema is None:
+            raise RuntimeError("Trainer.ema_generator: the average is off (pass ema_decay)")
+        if self._ema_G is not None:
+            return self._ema_G
+        from .graph import Graph_h36m
+        G, f = self.G, self.fG
+        n_classes = G.label_emb.num_embeddings
+        weighted = isinstance(G.edge_importance, torch.nn.ParameterList)
+        with torch.random.fork_rng(devices=[]):         # (the constructor draws initial weights: leave the host generator alone)
+            E = type(G)(G.mlp.mlp[0].in_features - n_classes, G.st_gcn_networks[-1].out_channels, n_classes, G.t_size,
+                        sum(isinstance(m, torch.nn.Linear) for m in G.mlp.mlp), edge_importance_weighting=weighted,
+                        dataset="h36m" if isinstance(G.graph, Graph_h36m) else "ntu")
+        E.to(f.flat.device)
+        live, mine = list(G.named_parameters()), list(E.named_parameters())
+        if [(k, p.shape) for k, p in live] != [(k, p.shape) for k, p in mine] or len(live) != len(f.offsets):
+            raise RuntimeError("Trainer.ema_generator: could not rebuild the generator's structure")
+        for (_, p), off in zip(mine, f.offsets):
+            p.data = f.ema[off:off + p.numel()].view(p.shape)
+            p.requires_grad_(False)
+        for me, lm in zip(E.modules(), G.modules()):
+            if list(me._buffers) != list(lm._buffers):
+                raise RuntimeError("Trainer.ema_generator: could not rebuild the generator's structure")
+            for k, b in lm._buffers.items():
+                me._buffers[k] = b
+        for k in ("use_trunk", "map_kernels"):
+            setattr(E, k, getattr(G, k))
+        E.eval()
+        self._ema_G = E
+        return E
 
     def broadcast_buffers(self, src: int = 0):
         """Rank `src`'s module buffers (the generator's BatchNorm running statistics / batch counters) to every rank

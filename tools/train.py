@@ -4,7 +4,8 @@ line, same outputs (``<out>/actions/<batches_done>.npy``, ``<out>/plot_loss.mat`
 ``discriminator_<n>.pth``) - every iteration one hipGraph replay whose first launch draws the iteration's batch and
 random inputs on the device.  Extra flags: ``--seed`` (shuffling and every random input), ``--resume FILE`` (a
 ``loop_state.pth`` written by an earlier run: continues it bit for bit), ``--no-graph`` (the same launches, eagerly),
-``--out``, ``--log_interval``."""
+``--out``, ``--log_interval``, ``--ema_decay D`` / ``--ema_warmup W`` (a moving average of the generator's weights, updated
+inside the generator's Adam launch: also writes ``models/generator_ema_<n>.pth`` and ``actions_ema/<n>.npy``)."""
 import argparse
 import os
 import sys
@@ -46,6 +47,10 @@ def parse_args(argv=None):
     p.add_argument("--no-graph", action="store_true", help="run the iteration eagerly instead of replaying hipGraphs")
     p.add_argument("--out", type=str, default="runs/kinetic-gan", help="run directory")
     p.add_argument("--log_interval", type=int, default=100, help="iterations between progress lines (one loss read each)")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="decay of an exponential moving average of the generator's weights (0 = off; e.g. 0.999)")
+    p.add_argument("--ema_warmup", type=float, default=10.0,
+                   help="ramp of the average's decay: min(ema_decay, (1 + s) / (ema_warmup + s)) at generator step s; 0 = no ramp")
     return p.parse_args(argv)
 
 
@@ -67,7 +72,7 @@ def main(argv=None):
         raise SystemExit("data is (C=%d, V=%d) but --channels %d --v_size %d" % (feeder.C, feeder.V, opt.channels, opt.v_size))
     loop = TrainLoop(G, D, feeder, opt.batch_size, opt.t_size, n_critic=opt.n_critic, seed=opt.seed, lr=opt.lr, b1=opt.b1,
                      b2=opt.b2, lambda_gp=float(opt.lambda_gp), use_graph=not opt.no_graph,
-                     ring_len=max(4096, opt.log_interval))
+                     ring_len=max(4096, opt.log_interval), ema_decay=opt.ema_decay or None, ema_warmup=opt.ema_warmup)
     print("dataset: %d samples, %d batches per epoch, %s (%.1f MB cropped)" % (
         len(feeder), loop.bpe, "streamed" if loop.streaming else "resident on the device", loop.resident.nbytes / 1e6))
     if opt.resume:
