@@ -67,8 +67,8 @@ void        kg_reload_env(void);
 typedef struct KgConvGroup {
     const float* x;  int64_t x_sN, x_sC;
     int32_t Cin, T_in, V_in;
-    int32_t x_lead;                 /* floats in front of x that belong to the same allocation (>= 0); the
-                                       128-bit load path needs >= 32 (it reads up to one frame before a row) */
+    int32_t x_lead;                 /* floats in front of x that belong to the same allocation (>= 0).  Not read by
+                                       any kernel: no load path reads in front of a row (0 is fine); kept for the ABI */
     const int32_t* vmap;            /* device ptr, V_out entries, or NULL                         */
     const float* w;  int64_t w_sT, w_sO, w_sI, w_sMB;  int32_t w_MB;
     int32_t taps, tap_mode, t_stride, transposed;

@@ -522,13 +522,16 @@ def as_plane(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-PLANE_LEAD = 32     # floats of slack in front of every plane tensor we allocate (see KgConvGroup.x_lead)
+# floats of slack in front of every plane tensor we allocate.  No kernel needs it any more: the 128-bit-load forms of kg_conv
+# that read up to one frame in front of a row are retired (kg_conv.hip, "plan tile codes"), every remaining load path is
+# bounds-selected per tap and tests/test_guarded_gpu.py runs kg_conv / kg_aggconv / kg_wgrad on operands with lead 0 between
+# poisoned red zones.  Kept (128 bytes per tensor) so that KgConvGroup.x_lead reports what it always did; DESIGN.md 14.
+PLANE_LEAD = 32
 
 
 def new_plane(n, c, t, v, device, zero=False) -> torch.Tensor:
     """(N,C,T,V) tensor stored channel-major (C,N,T,V): every channel row is one contiguous run.  The
-    storage starts PLANE_LEAD floats early so that kg_conv's 128-bit loads may touch the frame in front of
-    a row without leaving the allocation."""
+    storage starts PLANE_LEAD floats early (historical slack: see PLANE_LEAD, no kernel reads it)."""
     numel = c * n * t * v
     buf = (torch.zeros if zero else torch.empty)(numel + PLANE_LEAD, dtype=torch.float32, device=device)
     return buf[PLANE_LEAD:].view(c, n, t, v).permute(1, 0, 2, 3)

@@ -224,7 +224,10 @@ __device__ __forceinline__ void store_tile(const KgConvArgs& a, const Split& sp,
                 const int row = i * 32 + (r & 3) + 8 * (r >> 2);
                 // clamped to the tile's first row (always < M) - NOT to this lane's base row m0 + 4*kh, which lies
                 // beyond M for the upper half-wave of a tile with <= 4 valid rows (M = 2, 3: the generator's image
-                // channels) and read up to four channel rows past the end of `add`: no branch between the loads
+                // channels) and read up to four channel rows past the end of `add`: no branch between the loads.
+                // Every load of this epilogue (here, the mask below, the slabs of finish_split) stays inside
+                // [base, base + extent) of its operand: tests/test_guarded_gpu.py runs M = 2, 3, 5, 33 with `add`, `mask`
+                // and `x` between poisoned red zones and compares the result bits with the run on plain operands.
                 rv[i][r] = KG_REG_ON(r) ? ap[(long)(row < mrem ? row : -4 * kh) * a.a_sC] : 0.f;
             }
 #pragma unroll

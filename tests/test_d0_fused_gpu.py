@@ -10,6 +10,8 @@ from kinetic_gan_amd import _native as nv
 from kinetic_gan_amd import disc_trunk
 from kinetic_gan_amd._native import WView
 from oracle import prim_ref as pr
+from tests import guard
+from tests.guard import guard_all  # noqa: F401  (autouse: every test of this module runs on poisoned, red-zoned buffers)
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5          # the project's kernel tolerance (tests/test_kernels_gpu.py): |a-b| <= TOL * max|ref|
@@ -145,9 +147,9 @@ def _bwd_case(ds, L, N, T, labels, seed=0):
 
 def _run_bwd(d, gz, labels, emb, wg, J, cin, ak, accumulate=True):
     L = emb.shape[0]
-    demb = torch.full((L, J), 0.5, device=d)
-    dw = torch.full((K * M * cin,), 0.25, device=d)
-    dak = torch.full(tuple(ak.shape), 2.0, device=d)
+    demb = guard.full((L, J), 0.5, device=d)
+    dw = guard.full((K * M * cin,), 0.25, device=d)
+    dak = guard.full(tuple(ak.shape), 2.0, device=d)
     nv.label_bias_bwd(gz.to(d), labels.to(d), emb.to(d), wg.to(d), K, M, cin, J, ak.to(d), demb=demb, dw=dw, dak=dak,
                       accumulate=accumulate, dak_accumulate=accumulate)
     return demb, dw, dak

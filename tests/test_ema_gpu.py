@@ -25,6 +25,8 @@ from kinetic_gan_amd.wgan_gp import FlatParams
 
 import ema_def
 import train_def
+from tests import guard
+from tests.guard import guarded  # noqa: F401  (fixture: poisoned, red-zoned buffers for the kernel tests below)
 from util import build_pair
 
 pytestmark = pytest.mark.gpu
@@ -89,6 +91,7 @@ def kernel_inputs(n, seed):
     return [t.to(DEV) for t in (p, g, m, v, e)]
 
 
+@pytest.mark.usefixtures("guarded")
 @pytest.mark.parametrize("shift", [0, 1], ids=["aligned", "shifted"])
 @pytest.mark.parametrize("n", [1, 3, 1023, 4101, "ntu"])
 def test_kernel_against_definition(n, shift):
@@ -96,7 +99,7 @@ def test_kernel_against_definition(n, shift):
     the float64 definition - for every step count, decay, warm-up and zero_grad of the issue's list, grad_scale 0.5"""
     n = ntu_flat_len() if n == "ntu" else n
     src = kernel_inputs(n, seed=11 + n % 97)
-    step = torch.zeros(1, dtype=torch.int32, device=DEV)
+    step = guard.zeros(1, dtype=torch.int32, device=DEV)
     worst = 0.0
     for s in (1, 2, 9, 1000, 10 ** 6):
         step.fill_(s)
@@ -127,7 +130,7 @@ def test_kernel_against_definition(n, shift):
 
 def test_bad_arguments_raise():
     p, g, m, v, e = kernel_inputs(16, seed=1)
-    step = torch.ones(1, dtype=torch.int32, device=DEV)
+    step = guard.ones(1, dtype=torch.int32, device=DEV)
     with pytest.raises(RuntimeError, match="ema_decay"):
         nv.adam_step_ema(p, g, m, v, e, LR, B1, B2, EPS, step, 1.0, True, 1.0, 10.0)
     with pytest.raises(AssertionError):
@@ -139,7 +142,7 @@ def test_bad_arguments_raise():
 def test_determinism_and_replay_follow_the_live_step():
     n = 4101
     src = kernel_inputs(n, seed=5)
-    step = torch.zeros(1, dtype=torch.int32, device=DEV)
+    step = guard.zeros(1, dtype=torch.int32, device=DEV)
 
     def fresh():
         return [t.clone() for t in src]

@@ -10,6 +10,8 @@ import kinetic_gan_amd  # noqa: F401
 from kinetic_gan_amd import _native as nv
 from kinetic_gan_amd._native import TAP_CHANBLOCK, TAP_TIME, Group, WView
 from oracle import prim_ref as pr
+from tests import guard
+from tests.guard import guard_all  # noqa: F401  (autouse: every test of this module runs on poisoned, red-zoned buffers)
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
@@ -162,7 +164,7 @@ def test_agg_big(N, C, T, V, W, K):
 
 
 def plane(t, d):
-    """copy into a plane tensor allocated by the library (channel-major, with the lead-in the 128-bit path needs)"""
+    """copy into a plane tensor allocated by the library (channel-major, PLANE_LEAD floats of historical slack in front: no kernel reads them)"""
     out = nv.new_plane(*t.shape, d)
     out.copy_(t)
     return out
@@ -520,7 +522,7 @@ def test_batchnorm_coefficients(N, C, T, V, training):
     yr = bn(xr)
     yr.backward(g.double())
     for (_, xl), (_, gl) in zip(layouts(x), layouts(g)):
-        rm, rv, nbt = rm0.clone().to(d), rv0.clone().to(d), torch.zeros((), dtype=torch.int64, device=d)
+        rm, rv, nbt = rm0.clone().to(d), rv0.clone().to(d), guard.zeros((), dtype=torch.int64, device=d)
         coef = nv.bn_fwd(xl.to(d), gamma.to(d), beta.to(d), rm, rv, nbt, training, 0.1, 1e-5)
         y = nv.affine_act(xl.to(d), coef[0], coef[1])
         close(y, yr, 2e-5)
@@ -544,8 +546,8 @@ def test_adam_matches_torch():
     p0, g = rnd(10007, seed=1), rnd(10007, seed=2)
     p_ref = p0.clone().requires_grad_(True)
     opt = torch.optim.Adam([p_ref], lr=2e-4, betas=(0.5, 0.999))
-    p, m, v = p0.clone().to(d), torch.zeros(10007, device=d), torch.zeros(10007, device=d)
-    step = torch.zeros(1, dtype=torch.int32, device=d)
+    p, m, v = p0.clone().to(d), guard.zeros(10007, device=d), guard.zeros(10007, device=d)
+    step = guard.zeros(1, dtype=torch.int32, device=d)
     for it in range(3):
         p_ref.grad = g * (it + 1)
         opt.step()
@@ -553,19 +555,19 @@ def test_adam_matches_torch():
         nv.adam_step(p, (g * (it + 1) * 2).to(d), m, v, 2e-4, 0.5, 0.999, 1e-8, step, 0.5)
     close(p, p_ref, 1e-6)
     # buffers that are not 16-byte aligned take the scalar kernel
-    big = [torch.zeros(10008, device=d) for _ in range(3)]
+    big = [guard.zeros(10008, device=d) for _ in range(3)]
     p2, m2, v2 = (b[1:] for b in big)
     p2.copy_(p0)
     step.zero_()
     for it in range(3):
         step += 1
-        gg = torch.zeros(10008, device=d)
+        gg = guard.zeros(10008, device=d)
         gg[1:] = (g * (it + 1) * 2).to(d)
         nv.adam_step(p2, gg[1:], m2, v2, 2e-4, 0.5, 0.999, 1e-8, step, 0.5)
     close(p2, p_ref, 1e-6)
     # kg_adam_step_fused: the launch also clears the gradient it has consumed - aligned and unaligned buffers
     for off in (0, 1):
-        bufs = [torch.zeros(10007 + off, device=d) for _ in range(4)]
+        bufs = [guard.zeros(10007 + off, device=d) for _ in range(4)]
         p3, m3, v3, g3 = (b[off:] for b in bufs)
         p3.copy_(p0)
         step.zero_()
@@ -579,9 +581,9 @@ def test_adam_matches_torch():
 
 def test_error_paths():
     d = dev()
-    x = torch.zeros(1, 4, 3, 30, device=d)
+    x = guard.zeros(1, 4, 3, 30, device=d)
     with pytest.raises(RuntimeError, match="V="):
-        nv.agg_expand(x, torch.zeros(3, 30, 30, device=d))
+        nv.agg_expand(x, guard.zeros(3, 30, 30, device=d))
     with pytest.raises(TypeError):
         nv.rowsum(x.half())
 
@@ -786,7 +788,7 @@ def test_agg_outer_deferred_sums_one_launch():
     d = dev()
     cases = [(3, 32, 3, 25, 11, 16), (4, 64, 3, 11, 11, 8), (2, 128, 3, 11, 5, 8), (5, 256, 3, 5, 5, 4), (3, 512, 3, 5, 1, 4), (6, 512, 3, 1, 1, 2)]
     total = sum(K * V * W for _, _, K, V, W, _ in cases)
-    packed = torch.zeros(total, device=d)
+    packed = guard.zeros(total, device=d)
     jobs, refs, off = [], [], 0
     for i, (N, C, K, V, W, T) in enumerate(cases):
         x = rnd(N, C, T, V, seed=10 + i)
@@ -841,7 +843,7 @@ def test_rowsum_product_row_alone():
         out = base.clone().to(d)
         jobs.append(dict(x=xd, y=y.to(d), out=out, accumulate=True))
         refs.append((out, ref + base.double()))
-        plain = torch.zeros(C, device=d)
+        plain = guard.zeros(C, device=d)
         jobs.append(dict(x=xd, out=plain))
         refs.append((plain, x.double().sum((0, 2, 3))))
     nv.rowsum_many(jobs)
@@ -874,9 +876,9 @@ def test_bn_fwd_many_equals_per_group_launches(shapes):
             var = xq.var((0, 2, 3), unbiased=False)
             rstd = torch.rsqrt(var + 1e-5)
             per.append(torch.stack([gamma.double() * rstd, beta.double() - mean * gamma.double() * rstd, mean, rstd]))
-        rm = torch.zeros(C, device=d)
-        rv = torch.ones(C, device=d)
-        nbt = torch.zeros((), dtype=torch.int64, device=d)
+        rm = guard.zeros(C, device=d)
+        rv = guard.ones(C, device=d)
+        nbt = guard.zeros((), dtype=torch.int64, device=d)
         jobs.append(dict(x=layouts(x)[i % 2][1].to(d), gamma=gamma.to(d), beta=beta.to(d), running_mean=rm, running_var=rv,
                          num_batches_tracked=nbt, momentum=0.1, eps=1e-5, groups=2))
         refs.append((torch.stack(per), bn.running_mean.clone(), bn.running_var.clone(), rm, rv, nbt))
@@ -898,8 +900,8 @@ def test_bn_fwd_cumulative_moving_average_on_device():
     d = dev()
     N, C, T, V = 6, 5, 7, 11
     bn = torch.nn.BatchNorm2d(C, momentum=None, eps=1e-5).double().train()
-    rm, rv = torch.zeros(C, device=d), torch.ones(C, device=d)
-    nbt = torch.zeros((), dtype=torch.int64, device=d)
+    rm, rv = guard.zeros(C, device=d), guard.ones(C, device=d)
+    nbt = guard.zeros((), dtype=torch.int64, device=d)
     for i in range(3):
         x = rnd(N, C, T, V, seed=500 + i) * (1.0 + i) + 0.5 * i
         bn(x.double())
@@ -1077,7 +1079,7 @@ def test_gen_expand_fold_adjfinish(ds, lvl, up_s, N, C, Cr, Tc, rep, K):
         zz, _ = pr.gen_expand(y, A0 * imp, U, rep, C)
         (zz * gz).sum().backward()
         dbt = nv.agg_outer(zf, yl, K, 1)                      # (K, V, Vc)
-        out = torch.full((K, V, V), 0.25, device=d)
+        out = guard.full((K, V, V), 0.25, device=d)
         nv.gen_adj_finish([dict(dbt=dbt.contiguous(), u=to(U), a=to(A0), out=out, accumulate=True)])
         close(out - 0.25, imp.grad, 1e-4)
 
@@ -1132,7 +1134,7 @@ def test_conv_tiny_channel_kernel_features():
     xa = layouts(rnd(N, 9, T, V, seed=10))[1][1]
     wg = rnd(3 * 4 * 3 + 50, seed=11)
     gc = Group(xa.to(d), wg.to(d), WView(12, 3, 1, 40, 2), 3, 3, TAP_CHANBLOCK)
-    big = nv.new_plane(N, 4, 2 * T, V, d, zero=True)
+    big = nv.new_plane(N, 4, 2 * T, V, d).zero_()
     nv.conv([gc], N, 4, T, V, out=big, out_t0=1, out_tstride=2, act=nv.ACT_LRELU)
     refb = torch.zeros(N, 4, 2 * T, V)
     pr.conv([cpu_group(gc)], N, 4, T, V, out=refb, out_t0=1, out_tstride=2, act=nv.ACT_LRELU)
@@ -1149,7 +1151,7 @@ def test_head_kernels(N, C, T, V):
     close(nv.head_fwd(h.to(d), w.to(d), b.to(d)), pr.head_fwd(h, w, b))
     for masked in (True, False):
         close(nv.head_bwd(gv.to(d), w.to(d), h.to(d), masked=masked), pr.head_bwd(gv, w, h, masked=masked))
-    dw, db = torch.full((C,), 0.5, device=d), torch.full((1,), 0.25, device=d)
+    dw, db = guard.full((C,), 0.5, device=d), guard.full((1,), 0.25, device=d)
     nv.head_wgrad(h.to(d), gv.to(d), dw, db, accumulate=True)
     rw, rb = torch.full((C,), 0.5), torch.full((1,), 0.25)
     pr.head_wgrad(h, gv, rw, rb, accumulate=True)
@@ -1178,7 +1180,7 @@ def test_label_bias_kernels(ds, N, L, T):
     zl = nv.label_bias_fwd(to(labels), to(emb), to(wg), K, C, cin, J, to(ak))
     close(zl, pr.label_bias_fwd(labels, emb, wg, K, C, cin, J, ak))
     gz = layouts(rnd(N, C, T, W, seed=5))[1][1]
-    demb, dw, dak = torch.full((L, J), 0.5, device=d), torch.full((K * C * cin,), 0.25, device=d), torch.full(tuple(ak.shape), 2.0, device=d)
+    demb, dw, dak = guard.full((L, J), 0.5, device=d), guard.full((K * C * cin,), 0.25, device=d), guard.full(tuple(ak.shape), 2.0, device=d)
     nv.label_bias_bwd(to(gz), to(labels), to(emb), to(wg), K, C, cin, J, to(ak), demb=demb, dw=dw, dak=dak)
     rdemb, rdw, rdak = torch.full((L, J), 0.5), torch.full((K * C * cin,), 0.25), torch.full(tuple(ak.shape), 2.0)
     pr.label_bias_bwd(gz, labels, emb, wg, K, C, cin, J, ak, demb=rdemb, dw=rdw, dak=rdak)
@@ -1222,7 +1224,7 @@ def test_mapping_network_kernels(N, D, L, J):
     close(nv.linear_fwd(to(x), to(w), None, nv.ACT_NONE, 0.2, emb=to(emb), labels=to(labels)), pr.linear_fwd(x, w, None, 0, 0.2, emb=emb, labels=labels))
     g = torch.randn(N, Din, generator=gen)
     for cols, acc in ((None, False), (J, True), (0, True)):
-        dw, db = torch.full((Din, Din), 0.5, device=d), torch.full((Din,), 0.25, device=d)
+        dw, db = guard.full((Din, Din), 0.5, device=d), guard.full((Din,), 0.25, device=d)
         rdw, rdb = torch.full((Din, Din), 0.5), torch.full((Din,), 0.25)
         gx = nv.linear_bwd(to(g), to(yr), to(x), to(w), nv.ACT_LRELU, 0.2, emb=to(emb), labels=to(labels), gx_cols=cols, dw=dw, db=db, accumulate=acc)
         rgx = pr.linear_bwd(g, yr, x, w, 1, 0.2, emb=emb, labels=labels, gx_cols=cols, dw=rdw, db=rdb, accumulate=acc)
@@ -1238,7 +1240,7 @@ def test_mapping_network_kernels(N, D, L, J):
     close(gx, pr.linear_bwd(g2[:, :Din], yr, x, w, 1, 0.2, emb=emb, labels=labels), 1e-4)
     if J:
         gxe = torch.randn(N, Din, generator=gen)
-        demb, rdemb = torch.full((L, J), 2.0, device=d), torch.full((L, J), 2.0)
+        demb, rdemb = guard.full((L, J), 2.0, device=d), torch.full((L, J), 2.0)
         nv.embed_bwd(to(gxe), to(labels), demb, accumulate=True)
         pr.embed_bwd(gxe, labels, rdemb, accumulate=True)
         close(demb, rdemb, 1e-4)
@@ -1269,7 +1271,7 @@ def test_mix3_and_masked_adjacency_kernels():
         close(nv.masked_adj_fwd(A.to(d), imp.to(d), sd), pr.masked_adj_fwd(A, imp, s_))
         g = rnd(170 if s_ is not None else 300, seed=6)
         for acc in (True, False):
-            dimp, ref = torch.full((300,), 0.5, device=d), torch.full((300,), 0.5)
+            dimp, ref = guard.full((300,), 0.5, device=d), torch.full((300,), 0.5)
             nv.masked_adj_bwd(g.to(d), A.to(d), sd, dimp, acc)
             pr.masked_adj_bwd(g, A, s_, ref, acc)
             close(dimp, ref)
@@ -1325,7 +1327,7 @@ def test_gen_tail_backward_kernels(N, C, T, V, bn_t, res, act):
     to = lambda t: None if t is None else t.to(d)
     for rounds in range(2):
         names = ["nw"] + (["gamma_t", "beta_t"] if bn_t else []) + (["gamma_r", "beta_r"] if res == "bn" else [])
-        sinks = {k: torch.full((C,), 0.25, device=d) for k in names}
+        sinks = {k: guard.full((C,), 0.25, device=d) for k in names}
         rsinks = {k: torch.full((C,), 0.25) for k in names}
         du, dr = nv.gen_tail_bwd(to(g), to(out), a, u=to(u) if bn_t else None, bn_t=tuple(map(to, st)) if bn_t else None,
                                  r=to(r) if res != "none" else None, bn_r=tuple(map(to, sr)) if res == "bn" else None,
@@ -1499,7 +1501,7 @@ def test_genblock_fused_forward_backward(ds, lvl, up_s, N, Cin, C, Tc, rep, res,
     for with_prev in (False, True):
         for rounds in range(2):
             names = ["nw", "gamma_t", "beta_t", "gamma_r", "beta_r"]
-            sinks = {k: torch.full((Cin,), 0.25, device=d) for k in names}
+            sinks = {k: guard.full((Cin,), 0.25, device=d) for k in names}
             rsinks = {k: torch.full((Cin,), 0.25) for k in names}
             prev = prev_d = None
             if with_prev:

@@ -12,6 +12,8 @@ from kinetic_gan_amd import _native
 from kinetic_gan_amd import metrics
 
 import mmd_def
+from tests import guard
+from tests.guard import guarded  # noqa: F401  (fixture: poisoned, red-zoned buffers for the kernel tests below)
 
 pytestmark = pytest.mark.gpu
 BWS = mmd_def.BANDWIDTHS
@@ -80,6 +82,7 @@ def rand_pair(shape, seed, spread=1.0):
     return x, y
 
 
+@pytest.mark.usefixtures("guarded")
 @pytest.mark.parametrize("K,C,T,V,mode", [(10, 2, 32, 16, "avg"), (60, 3, 64, 25, "avg"), (60, 3, 64, 25, "joint"),
                                           (3, 3, 1024, 16, "avg")])
 def test_protocol_shapes_against_f64(K, C, T, V, mode):
@@ -92,6 +95,7 @@ def test_protocol_shapes_against_f64(K, C, T, V, mode):
     check_frame_mean(out["mmd"], want.reshape(K, groups, len(BWS)), tol.reshape(K, groups, len(BWS)))
 
 
+@pytest.mark.usefixtures("guarded")
 @pytest.mark.parametrize("m,dim,G", [(1000, 75, 64), (1000, 4800, 1), (777, 33, 3)])
 def test_sample_sets_against_f64(m, dim, G):
     """regime (b): few large groups, (N, L, D) sample sets: groups = frames (avg) or the flattened set (G = 1)"""
@@ -105,6 +109,7 @@ def test_sample_sets_against_f64(m, dim, G):
     check_mmd2(out["mmd2"], x.permute(1, 0, 2), y.permute(1, 0, 2))
 
 
+@pytest.mark.usefixtures("guarded")
 def test_strided_inputs():
     """non-contiguous operands: a permuted (L, N, D) storage, every other point of a larger set, a sliced frame range"""
     base_x, base_y = rand_pair((40, 2 * 90, 7), seed=3)          # (L, 2N, D)
@@ -121,6 +126,7 @@ def test_strided_inputs():
     check_mmd2(out["mmd2"], nctv_groups(cx, "avg"), nctv_groups(cy, "avg"))
 
 
+@pytest.mark.usefixtures("guarded")
 def test_finish_rules():
     """a negative MMD^2 frame makes its bandwidth NaN; a class with NaN at every bandwidth scores 0; m = 1 is NaN"""
     a, b = [0.0, 0.0], [1.0, 0.0]
@@ -146,7 +152,7 @@ def test_finish_rules():
     assert r[0] == pytest.approx(float(np.nanmax(out["mmd"][0].cpu().numpy()))) and r[0] > 0 and r[1] == 0.0
     assert out["mean"].item() == pytest.approx(r[0] / 2, rel=1e-6)
     # m = 1: 0 / 0
-    one = torch.zeros(1, 1, 3, device="cuda")
+    one = guard.zeros(1, 1, 3, device="cuda")
     assert np.isnan(metrics.mmd_sweep(one, one + 1, bws, "avg").cpu().numpy()).all()
     assert metrics.calculate_mmd(torch.zeros(2, 3, 4, 1), torch.ones(2, 3, 4, 1), [0, 1], "avg").item() == 0.0
 
@@ -160,6 +166,7 @@ def _fixture(golden_dir, name):
     return fake, real, lab, d
 
 
+@pytest.mark.usefixtures("guarded")
 @pytest.mark.parametrize("name", ["h36m", "ntu"])
 @pytest.mark.parametrize("mode", ["avg", "joint"])
 def test_reference_fixtures(golden_dir, name, mode):
@@ -200,6 +207,7 @@ def test_sorted_batch_reads_in_place_and_agrees(golden_dir):
     assert a.item() == b.item()
 
 
+@pytest.mark.usefixtures("guarded")
 def test_rkhs_mmd_matches_definition():
     x, y = rand_pair((50, 6), seed=9)
     v = metrics.MMD("avg").rkhs_mmd(x, y, 1.0)

@@ -28,7 +28,8 @@ from kinetic_gan_amd import _native as nv
 from kinetic_gan_amd import gen_trunk as gt
 from kinetic_gan_amd.sample import Sampler, sample_actions
 from oracle.fill import block_input, fill_module, gen_block_in_shapes, rand_inputs, rand_noise
-from tests import sample_def, train_def
+from tests import guard, sample_def, train_def
+from tests.guard import guarded  # noqa: F401  (fixture: poisoned, red-zoned buffers for the kernel tests below)
 from tests.util import build_pair, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -82,6 +83,7 @@ def lerp_inputs(case):
 
 # ---- kg_bn_eval_coef ---------------------------------------------------------------------------------------------------
 
+@pytest.mark.usefixtures("guarded")
 def test_bn_eval_coef_against_definition_and_live_statistics():
     """eight layers in one launch against the float64 definition (the bound of the kg_bn_fwd coefficient test: 2e-5 of the
     largest value); an in-place change of the running statistics is picked up by the next launch"""
@@ -97,7 +99,7 @@ def test_bn_eval_coef_against_definition_and_live_statistics():
         host.append((gamma, beta, rm, rv))
         jobs.append(dict(gamma=None if gamma is None else gamma.to(DEV), beta=None if beta is None else beta.to(DEV),
                          running_mean=rm.to(DEV), running_var=rv.to(DEV), eps=1e-5,
-                         coef=torch.full((4, c), float("nan"), device=DEV)))
+                         coef=guard.full((4, c), float("nan"), device=DEV)))
 
     def check(tag):
         for j, c in zip(jobs, cs):
@@ -147,6 +149,7 @@ def _run_block(g, p, B, coefs, x, noise, out=None):
                              cr=coefs[1], noise=noise, nw=p["nw"], slope=0.2, out=out)
 
 
+@pytest.mark.usefixtures("guarded")
 @pytest.mark.parametrize("form", ["ct", "rt"])
 @pytest.mark.parametrize("cfg", ["ntu", "h36m"])
 def test_genblock_infer_vs_reference_golden(cfg, form, golden_dir, monkeypatch):
@@ -181,10 +184,10 @@ def test_genblock_infer_vs_reference_golden(cfg, form, golden_dir, monkeypatch):
             n5 = 5
             xs = torch.cat([x, block_input((3,) + tuple(gs[i][1:]), 900 + i).to(DEV)], 0)
             nz5 = torch.cat([noise[i], rnd(3, 1, g.T, g.V, seed=950 + i).to(DEV)], 0)
-            wide = nv.new_plane(n5 + 2, g.cin + 3, g.Tc, g.Vc, torch.device(DEV), zero=True)
+            wide = nv.new_plane(n5 + 2, g.cin + 3, g.Tc, g.Vc, torch.device(DEV)).zero_()
             xin = wide[1:1 + n5, 2:2 + g.cin]
             xin.copy_(xs)
-            wide_o = nv.new_plane(n5 + 1, g.cout + 2, g.T, g.V, torch.device(DEV), zero=True)
+            wide_o = nv.new_plane(n5 + 1, g.cout + 2, g.T, g.V, torch.device(DEV)).zero_()
             yo = wide_o[1:, 1:1 + g.cout]
             assert not xin.is_contiguous() and not yo.is_contiguous()
             _run_block(g, p, B, coefs, xin, nz5, out=yo)
@@ -211,14 +214,15 @@ def check_normals(got, stream, step):
     assert err <= NORMAL_TOL, err
 
 
+@pytest.mark.usefixtures("guarded")
 @pytest.mark.parametrize("layout,B,dt", DRAW_CASES)
 def test_sample_inputs_against_definition(layout, B, dt):
     nl = noise_len(layout, B)
-    step = torch.zeros(1, dtype=torch.int64, device=DEV)
-    ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
-    z = torch.full((B, 512), float("nan"), device=DEV)
-    noise = torch.full((nl,), float("nan"), device=DEV)
-    t = torch.full((1000, dt), float("nan"), device=DEV)
+    step = guard.zeros(1, dtype=torch.int64, device=DEV)
+    ticket = guard.zeros(1, dtype=torch.int32, device=DEV)
+    z = guard.full((B, 512), float("nan"), device=DEV)
+    noise = guard.full((nl,), float("nan"), device=DEV)
+    t = guard.full((1000, dt), float("nan"), device=DEV)
     for s in range(3):
         nv.sample_inputs(step, ticket, SEED, z=z, noise=noise, t=t)
         assert int(step.item()) == s + 1 and int(ticket.item()) == 0
@@ -233,8 +237,8 @@ def test_sample_inputs_against_definition(layout, B, dt):
     assert int(step.item()) == 3 and float(z.min()) == 7.0 == float(z.max())
     assert torch.equal(noise, n0) and torch.equal(t, t0)
     # the sampler's z stream is not the training z stream of the same seed and step
-    zt = torch.zeros((B, 512), device=DEV)
-    st = torch.full((1,), 2, dtype=torch.int64, device=DEV)
+    zt = guard.zeros((B, 512), device=DEV)
+    st = guard.full((1,), 2, dtype=torch.int64, device=DEV)
     nv.step_inputs(st, ticket, SEED, B, z=zt)
     nv.sample_inputs(step.fill_(2), ticket, SEED, z=z)
     assert not torch.equal(z, zt) and float((z == zt).float().mean()) < 0.01
@@ -245,9 +249,9 @@ def test_sample_inputs_replay_is_deterministic():
     nl = noise_len("h36m", B)
 
     def bufs():
-        return torch.zeros((B, 512), device=DEV), torch.zeros(nl, device=DEV), torch.zeros((1000, dt), device=DEV)
-    step = torch.zeros(1, dtype=torch.int64, device=DEV)
-    ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
+        return guard.zeros((B, 512), device=DEV), guard.zeros(nl, device=DEV), guard.zeros((1000, dt), device=DEV)
+    step = guard.zeros(1, dtype=torch.int64, device=DEV)
+    ticket = guard.zeros(1, dtype=torch.int32, device=DEV)
     outs = {}
     for s in range(3):
         b = bufs()
@@ -276,6 +280,7 @@ def test_sample_inputs_replay_is_deterministic():
 
 # ---- kg_trunc_lerp -----------------------------------------------------------------------------------------------------
 
+@pytest.mark.usefixtures("guarded")
 @pytest.mark.parametrize("case", LERP_CASES)
 def test_trunc_lerp_against_definition(case):
     x, t, trunc = lerp_inputs(case)
@@ -291,7 +296,7 @@ def test_trunc_lerp_against_definition(case):
     assert np.array_equal(bits(a), bits(b))
     # rows of wider matrices (leading dimensions)
     N, D = x.shape
-    xw, tw = torch.zeros((N, D + 5), device=DEV), torch.zeros((t.shape[0], D + 3), device=DEV)
+    xw, tw = guard.zeros((N, D + 5), device=DEV), guard.zeros((t.shape[0], D + 3), device=DEV)
     xw[:, 2:2 + D], tw[:, 1:1 + D] = xd, td
     nv.trunc_lerp(xw[:, 2:2 + D], tw[:, 1:1 + D], trunc)
     assert np.array_equal(bits(xw[:, 2:2 + D]), bits(a)) and float(xw[:, :2].abs().max()) == 0.0 == float(xw[:, 2 + D:].abs().max())
@@ -389,8 +394,8 @@ def test_next_replay_equals_eager_and_resumes(mode):
 def _raw_z(s, r):
     """the z draw of replay r as the device wrote it (before the in-place Z-space truncation)"""
     z = torch.empty_like(s.z)
-    step = torch.full((1,), r, dtype=torch.int64, device=DEV)
-    nv.sample_inputs(step, torch.zeros(1, dtype=torch.int32, device=DEV), s.seed, z=z)
+    step = guard.full((1,), r, dtype=torch.int64, device=DEV)
+    nv.sample_inputs(step, guard.zeros(1, dtype=torch.int32, device=DEV), s.seed, z=z)
     return z
 
 

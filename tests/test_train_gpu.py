@@ -22,6 +22,8 @@ from kinetic_gan_amd.feeder import Feeder
 from kinetic_gan_amd.train import ResidentDataset, TrainLoop, norm_constants, update_pattern
 
 import train_def
+from tests import guard
+from tests.guard import guarded  # noqa: F401  (fixture: poisoned, red-zoned buffers for the kernel tests below)
 from util import build_pair
 
 pytestmark = pytest.mark.gpu
@@ -69,6 +71,7 @@ def shapes_of(layout, B):
     return _SHAPES[(layout, B)]
 
 
+@pytest.mark.usefixtures("guarded")
 @pytest.mark.parametrize("layout,B,world", [("ntu", 64, 1), ("h36m", 64, 1), ("ntu", 5, 1), ("ntu", 8, 2)])
 def test_kernel_against_definition(tmp_path, layout, B, world):
     """three consecutive iterations (the second epoch starts inside them): batch, labels and alpha bit for bit, normals
@@ -86,13 +89,13 @@ def test_kernel_against_definition(tmp_path, layout, B, world):
     perm = torch.stack([torch.as_tensor(train_def.permutation(n, seed, e)[:plen]) for e in (0, 1)]).to(DEV)
     shapes, lens = shapes_of(layout, B)
     for rank in range(world):
-        step = torch.zeros(1, dtype=torch.int64, device=DEV)
-        ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
-        real = torch.full((B, c, t_size, v), float("nan"), device=DEV)
-        labels = torch.full((B,), -1, dtype=torch.int64, device=DEV)
-        z = torch.full((B, latent), float("nan"), device=DEV)
-        alpha = torch.full((B,), float("nan"), device=DEV)
-        noise = torch.full((2 * sum(lens),), float("nan"), device=DEV)
+        step = guard.zeros(1, dtype=torch.int64, device=DEV)
+        ticket = guard.zeros(1, dtype=torch.int32, device=DEV)
+        real = guard.full((B, c, t_size, v), float("nan"), device=DEV)
+        labels = guard.full((B,), -1, dtype=torch.int64, device=DEV)
+        z = guard.full((B, latent), float("nan"), device=DEV)
+        alpha = guard.full((B,), float("nan"), device=DEV)
+        noise = guard.full((2 * sum(lens),), float("nan"), device=DEV)
         nd, ng = nv.noise_views(noise, shapes)
         gather = nv.StepData(res.data, res.labels, perm, bpe, res.scale, res.shift, real, labels)
         for s in range(3):
@@ -112,6 +115,7 @@ def test_kernel_against_definition(tmp_path, layout, B, world):
                 assert tuple(p.shape) == w.shape and np.abs(p.cpu().double().numpy() - w).max() <= NORMAL_TOL
 
 
+@pytest.mark.usefixtures("guarded")
 def test_kernel_strided_source_and_random_only(tmp_path):
     """a source that is not row-contiguous (the uncropped 5-D NTU array read in place) takes the element-wise form with
     the same bits; data == NULL leaves the batch alone and still advances the counter"""
@@ -123,27 +127,28 @@ def test_kernel_strided_source_and_random_only(tmp_path):
     res_labels = torch.as_tensor(np.asarray(f.label, dtype=np.int64)).to(DEV)
     scale, shift = norm_constants(f)
     perm = torch.stack([torch.as_tensor(train_def.permutation(11, seed, e)[:8]) for e in (0, 1)]).to(DEV)
-    step = torch.zeros(1, dtype=torch.int64, device=DEV)
-    ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
-    real = torch.zeros((B, 3, t_size, 25), device=DEV)
-    labels = torch.zeros(B, dtype=torch.int64, device=DEV)
+    step = guard.zeros(1, dtype=torch.int64, device=DEV)
+    ticket = guard.zeros(1, dtype=torch.int32, device=DEV)
+    real = guard.zeros((B, 3, t_size, 25), device=DEV)
+    labels = guard.zeros(B, dtype=torch.int64, device=DEV)
     g = nv.StepData(view, res_labels, perm, 2, scale, shift, real, labels)
     for s in range(3):
         nv.step_inputs(step, ticket, seed, B, gather=g)
         w_real, w_labels = train_def.batch(f, B, t_size, seed, s)
         assert np.array_equal(bits(real), bits(w_real)) and np.array_equal(labels.cpu().numpy(), w_labels)
     keep = real.clone()
-    z = torch.zeros((B, 16), device=DEV)
+    z = guard.zeros((B, 16), device=DEV)
     nv.step_inputs(step, ticket, seed, B, z=z)
     assert int(step.item()) == 4 and torch.equal(real, keep)
     check_normals(z, seed, train_def.STREAM_Z, 3)
 
 
+@pytest.mark.usefixtures("guarded")
 def test_moments():
     """2^20 normals and 2^20 uniforms of one iteration: 5-sigma bounds from the sample size"""
     n = 1 << 20
-    step = torch.full((1,), 7, dtype=torch.int64, device=DEV)
-    ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
+    step = guard.full((1,), 7, dtype=torch.int64, device=DEV)
+    ticket = guard.zeros(1, dtype=torch.int32, device=DEV)
     z = torch.empty((2048, 512), device=DEV)
     nv.step_inputs(step, ticket, 1234, 2048, z=z)
     x = z.double().reshape(-1)
@@ -169,9 +174,9 @@ def test_determinism_and_graph_replay():
     shapes, lens = shapes_of("ntu", B)
 
     def bufs():
-        return (torch.zeros((B, 512), device=DEV), torch.zeros(B, device=DEV), torch.zeros(2 * sum(lens), device=DEV))
-    step = torch.zeros(1, dtype=torch.int64, device=DEV)
-    ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
+        return (guard.zeros((B, 512), device=DEV), guard.zeros(B, device=DEV), guard.zeros(2 * sum(lens), device=DEV))
+    step = guard.zeros(1, dtype=torch.int64, device=DEV)
+    ticket = guard.zeros(1, dtype=torch.int32, device=DEV)
     outs = {}
     for s in (0, 1, 2):
         z, a, nz = bufs()
@@ -263,8 +268,8 @@ def test_loop_matches_eager_iterations(six_steps, tmp_path):
     tr = Trainer(G, D, n_critic=N_CRITIC)
     shapes = train_def.plane_shapes(G, B_LOOP)
     lens = [int(np.prod(s)) for s in shapes]
-    step = torch.zeros(1, dtype=torch.int64, device=DEV)
-    ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
+    step = guard.zeros(1, dtype=torch.int64, device=DEV)
+    ticket = guard.zeros(1, dtype=torch.int32, device=DEV)
     pattern = update_pattern(3, N_CRITIC, 6)
     assert pattern == [True, False, True, True, False, True]
     d_want, g_want, last_g = [], [], float("nan")
