@@ -811,6 +811,40 @@ int kg_sample_inputs(const KgSampleInputsArgs* a, void* stream);
 int kg_trunc_lerp(float* x, int64_t x_ld, int32_t N, int32_t D, const float* t, int64_t t_ld, int32_t M, float truncation,
                   void* stream);
 
+/* ---- scoring the generator during training (additive, ABI v9; DESIGN.md 15, evaluate.Evaluator) ----------------------
+ * kg_eval_record: the bookkeeping of ONE evaluation, one small workgroup (as kg_loss_append).  With s = *scores[select],
+ * n = *count, it = iter ? *iter : -1:
+ *     improved = (s < *best_val)            strict: a NaN never wins, an equal score keeps the earlier snapshot
+ *     ring_val[(n mod ring_len)*nscores + i] = *scores[i];   ring_iter[(n mod ring_len)*2 + {0, 1}] = it, improved
+ *     *flag = improved;   improved: *best_val = s, *best_iter = it;   *count = n + 1
+ * The host initialises *best_val = +inf, *best_iter = -1, *count = 0.  The iteration is int64 throughout (fp32 holds
+ * integers up to 2^24 only).  Everything is read through its pointer when the launch RUNS: a captured launch follows the
+ * training replays in between.  Call sites: evaluate.Evaluator._round, behind the kg_mmd launches of an evaluation.      */
+#define KG_EVAL_MAX_SCORES 8
+typedef struct KgEvalRecordArgs {
+    const float* scores[KG_EVAL_MAX_SCORES];   /* device: one fp32 each                                               */
+    int32_t nscores, select;
+    const int64_t* iter;            /* device: the loop's iteration counter, or NULL (recorded as -1)                  */
+    int64_t* count;                 /* device: evaluations so far, advanced by the launch                              */
+    float* ring_val;                /* (ring_len, nscores)                                                             */
+    int64_t* ring_iter;             /* (ring_len, 2): [iteration, improved]                                            */
+    int64_t ring_len;
+    float* best_val;                /* (1)                                                                             */
+    int64_t* best_iter;             /* (1)                                                                             */
+    int32_t* flag;                  /* (1): the decision kg_copy_if reads                                              */
+} KgEvalRecordArgs;
+int kg_eval_record(const KgEvalRecordArgs* a, void* stream);
+
+/* kg_copy_if: when *flag != 0 every job's run of `nwords` 4-byte words is copied src -> dst bit for bit; when *flag == 0
+ * the launch writes nothing at all.  A job whose src and dst are both 16-byte aligned moves 128 bits per access with a
+ * scalar tail, any other job word by word.  No ticket, no atomic, no LDS, no scratch: the grid only reads the decision a
+ * PREVIOUS launch wrote.  Up to KG_COPY_IF_MAX_JOBS jobs per launch; src / dst 4-byte aligned; a job whose src and dst
+ * overlap is rejected.  Call site: evaluate.Evaluator._round (the snapshot of the best-scoring weights: the flat
+ * parameter buffer plus every module buffer, an int64 batch counter as two words per element).                        */
+#define KG_COPY_IF_MAX_JOBS 32
+typedef struct KgCopyJob { const void* src;  void* dst;  int64_t nwords; } KgCopyJob;
+int kg_copy_if(const int32_t* flag, const KgCopyJob* jobs, int32_t njobs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

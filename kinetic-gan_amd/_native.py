@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import NamedTuple, Optional, Sequence
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -344,6 +344,19 @@ class _SampleInputsArgs(C.Structure):
                 ("t", c_f32p), ("t_rows", C.c_int32), ("t_cols", C.c_int32)]
 
 GEN_ADJ_MAX_JOBS = 8
+EVAL_MAX_SCORES = 8
+COPY_IF_MAX_JOBS = 32
+
+
+class _EvalRecordArgs(C.Structure):
+    _fields_ = [("scores", c_f32p * EVAL_MAX_SCORES), ("nscores", C.c_int32), ("select", C.c_int32),
+                ("iter", C.c_void_p), ("count", C.c_void_p), ("ring_val", c_f32p), ("ring_iter", C.c_void_p),
+                ("ring_len", C.c_int64), ("best_val", c_f32p), ("best_iter", C.c_void_p), ("flag", C.c_void_p)]
+
+
+class _CopyJob(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("nwords", C.c_int64)]
+
 
 EXPORTS = {
     "kg_abi_version": (C.c_int, []),
@@ -434,6 +447,8 @@ EXPORTS = {
     "kg_sample_inputs": (C.c_int, [C.POINTER(_SampleInputsArgs), C.c_void_p]),
     "kg_trunc_lerp": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_float,
                                 C.c_void_p]),
+    "kg_eval_record": (C.c_int, [C.POINTER(_EvalRecordArgs), C.c_void_p]),
+    "kg_copy_if": (C.c_int, [C.c_void_p, C.POINTER(_CopyJob), C.c_int32, C.c_void_p]),
 }
 
 _lib = None
@@ -2358,6 +2373,66 @@ def trunc_lerp(x: torch.Tensor, t: torch.Tensor, truncation: float) -> torch.Ten
     _check(load_library().kg_trunc_lerp(x.data_ptr(), x.stride(0), x.shape[0], x.shape[1], t.data_ptr(), t.stride(0), t.shape[0],
                                         float(truncation), _stream()), "kg_trunc_lerp")
     return x
+
+
+# ---- scoring during training (kg_eval.hip; evaluate.Evaluator) --------------------------------------------------------------
+
+def eval_record(scores: Sequence[torch.Tensor], select: int, iteration: Optional[torch.Tensor], count: torch.Tensor,
+                ring_val: torch.Tensor, ring_iter: torch.Tensor, best_val: torch.Tensor, best_iter: torch.Tensor,
+                flag: torch.Tensor) -> None:
+    """Enqueue kg_eval_record: the one-element fp32 ``scores`` of an evaluation into slot ``count mod len`` of ``ring_val``
+    (len, nscores) fp32 and ``ring_iter`` (len, 2) int64 = [iteration, improved]; ``flag`` (int32) = scores[select] <
+    best_val (strict), and then best_val / best_iter (int64) take the score and ``iteration[0]`` (int64; None: -1);
+    ``count`` (int64) is advanced."""
+    _need_cuda(iteration, count, ring_val, ring_iter, best_val, best_iter, flag, *scores)
+    for t in scores:
+        if t.dtype != torch.float32 or t.numel() != 1:
+            raise TypeError("kg_eval_record: one-element fp32 scores expected")
+    for t in (iteration, count, best_iter):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != 1):
+            raise TypeError("kg_eval_record: one-element int64 iteration / count / best_iter expected")
+    if best_val.dtype != torch.float32 or best_val.numel() != 1 or flag.dtype != torch.int32 or flag.numel() != 1:
+        raise TypeError("kg_eval_record: one-element fp32 best_val and int32 flag expected")
+    if ring_val.dtype != torch.float32 or ring_iter.dtype != torch.int64 or not ring_val.is_contiguous() or \
+            not ring_iter.is_contiguous():
+        raise TypeError("kg_eval_record: contiguous ring_val fp32 and ring_iter int64 expected")
+    n = len(scores)
+    ring_len = ring_val.shape[0] if ring_val.dim() == 2 else 0
+    if ring_val.dim() != 2 or ring_iter.dim() != 2 or (ring_len and (ring_val.shape[1] != n or tuple(ring_iter.shape) != (ring_len, 2))):
+        raise ValueError("kg_eval_record: ring_val (len, nscores) and ring_iter (len, 2) expected")
+    a = _EvalRecordArgs()
+    for i, t in enumerate(scores[:EVAL_MAX_SCORES]):
+        a.scores[i] = t.data_ptr()
+    a.nscores, a.select, a.ring_len = n, int(select), ring_len
+    a.iter, a.count = _ptr(iteration), count.data_ptr()
+    a.ring_val, a.ring_iter = ring_val.data_ptr(), ring_iter.data_ptr()
+    a.best_val, a.best_iter, a.flag = best_val.data_ptr(), best_iter.data_ptr(), flag.data_ptr()
+    _check(load_library().kg_eval_record(C.byref(a), _stream()), "kg_eval_record")
+
+
+def copy_if(flag: torch.Tensor, jobs: Sequence[Tuple[torch.Tensor, torch.Tensor]]) -> None:
+    """Enqueue kg_copy_if: when ``flag[0]`` (int32, device) is non-zero at the time the launch RUNS, every (src, dst) pair -
+    contiguous tensors of one dtype and size, element size a multiple of 4 bytes - is copied bit for bit; otherwise nothing
+    is written.  COPY_IF_MAX_JOBS pairs per launch, more pairs take more launches."""
+    if flag.dtype != torch.int32 or flag.numel() != 1:
+        raise TypeError("kg_copy_if: one-element int32 flag expected")
+    _need_cuda(flag)
+    lib = load_library()
+    jobs = list(jobs)
+    for q in range(0, len(jobs), COPY_IF_MAX_JOBS):
+        part = jobs[q:q + COPY_IF_MAX_JOBS]
+        arr = (_CopyJob * len(part))()
+        for i, (src, dst) in enumerate(part):
+            _need_cuda(src, dst)
+            if src.dtype != dst.dtype or src.element_size() % 4:
+                raise TypeError("kg_copy_if: src and dst of one dtype with 4- or 8-byte elements expected (got %s, %s)"
+                                % (src.dtype, dst.dtype))
+            if src.numel() != dst.numel() or not src.is_contiguous() or not dst.is_contiguous():
+                raise ValueError("kg_copy_if: contiguous src and dst of one size expected")
+            arr[i].src, arr[i].dst = src.data_ptr(), dst.data_ptr()
+            arr[i].nwords = src.numel() * (src.element_size() // 4)
+        _count("kg_copy_if", 0.0)
+        _check(lib.kg_copy_if(flag.data_ptr(), arr, len(part), _stream()), "kg_copy_if")
 
 
 

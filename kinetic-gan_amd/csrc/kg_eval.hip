@@ -1,0 +1,131 @@
+// Scoring the generator during training (include/kgan_hip.h; evaluate.Evaluator):
+//   kg_eval_record : ONE thread compares the deciding score of an evaluation with the best so far, appends the evaluation
+//                    to the device record and leaves the decision in `flag`
+//   kg_copy_if     : a grid that only READS that decision and, when it is set, copies a table of word runs - the snapshot
+//                    of the best-scoring weights, taken by the device with no host synchronisation
+// Two launches on purpose: one writer of the decision, then readers of it, with a launch boundary in between - there is no
+// ordering between workgroups to get wrong (no ticket, no atomic).  Both read everything through pointers when they run,
+// so a captured evaluation follows the training replays in between.
+#include "kg_common.h"
+
+namespace {
+
+struct EvalRecDev {
+    const float* scores[KG_EVAL_MAX_SCORES];
+    int nscores, select;
+    const long long* iter;
+    long long* count;
+    float* ring_val;
+    long long* ring_iter;
+    long ring_len;
+    float* best_val;
+    long long* best_iter;
+    int* flag;
+};
+
+__global__ __launch_bounds__(64) void kg_eval_record_kernel(const EvalRecDev a) {
+    if (threadIdx.x != 0) return;
+    const long long n = *a.count;
+    const long long it = a.iter != nullptr ? *a.iter : -1ll;
+    if (n < 0) return;                              // (a counter the host never initialised: no slot to write)
+    const long k = (long)(n % a.ring_len);
+    float s = 0.f;
+    for (int i = 0; i < a.nscores; ++i) {
+        const float v = *a.scores[i];
+        a.ring_val[k * a.nscores + i] = v;
+        if (i == a.select) s = v;
+    }
+    const bool improved = s < *a.best_val;          // strict: a NaN never wins, an equal score keeps the earlier snapshot
+    a.ring_iter[2 * k] = it;
+    a.ring_iter[2 * k + 1] = improved ? 1ll : 0ll;
+    *a.flag = improved ? 1 : 0;
+    if (improved) {
+        *a.best_val = s;
+        *a.best_iter = it;
+    }
+    *a.count = n + 1;
+}
+
+struct CopyJobs {
+    const int* flag;
+    KgCopyJob j[KG_COPY_IF_MAX_JOBS];
+};
+
+constexpr int CP_NT = 256;
+constexpr int CP_MAX_BLOCKS = 512;      // per job: 2 workgroups per CU; longer runs take a grid-stride loop
+
+// grid (blocks of the longest job, njobs); a workgroup beyond its job's length has nothing to do
+__global__ __launch_bounds__(CP_NT) void kg_copy_if_kernel(const CopyJobs a) {
+    if (*a.flag == 0) return;
+    const KgCopyJob& j = a.j[blockIdx.y];
+    const unsigned* src = (const unsigned*)j.src;
+    unsigned* dst = (unsigned*)j.dst;
+    const long n = (long)j.nwords;
+    const long stride = (long)gridDim.x * CP_NT;
+    const long first = (long)blockIdx.x * CP_NT + threadIdx.x;
+    if ((((unsigned long long)j.src | (unsigned long long)j.dst) & 15ull) == 0) {
+        const long n4 = n >> 2;
+        const uint4* s4 = (const uint4*)src;
+        uint4* d4 = (uint4*)dst;
+        for (long i = first; i < n4; i += stride) d4[i] = s4[i];
+        const long t = (n4 << 2) + first;           // the scalar tail: at most 3 words, threads 0..2 of workgroup 0
+        if (first < 4 && t < n) dst[t] = src[t];
+    } else {
+        for (long i = first; i < n; i += stride) dst[i] = src[i];
+    }
+}
+
+}  // namespace
+
+extern "C" int kg_eval_record(const KgEvalRecordArgs* a, void* stream) {
+    KG_REQUIRE(a != nullptr, "kg_eval_record: null arguments");
+    KG_REQUIRE(a->nscores >= 1 && a->nscores <= KG_EVAL_MAX_SCORES, "kg_eval_record: nscores=%d outside [1, %d]", a->nscores,
+               KG_EVAL_MAX_SCORES);
+    KG_REQUIRE(a->select >= 0 && a->select < a->nscores, "kg_eval_record: select=%d outside [0, nscores=%d)", a->select, a->nscores);
+    KG_REQUIRE(a->ring_len >= 1, "kg_eval_record: ring_len=%lld < 1", (long long)a->ring_len);
+    EvalRecDev d = {};
+    for (int i = 0; i < a->nscores; ++i) {
+        KG_REQUIRE(a->scores[i] != nullptr, "kg_eval_record: null score %d", i);
+        d.scores[i] = a->scores[i];
+    }
+    KG_REQUIRE(a->count != nullptr && a->ring_val != nullptr && a->ring_iter != nullptr,
+               "kg_eval_record: null count / ring_val / ring_iter");
+    KG_REQUIRE(a->best_val != nullptr && a->best_iter != nullptr && a->flag != nullptr,
+               "kg_eval_record: null best_val / best_iter / flag");
+    d.nscores = a->nscores;
+    d.select = a->select;
+    d.iter = (const long long*)a->iter;
+    d.count = (long long*)a->count;
+    d.ring_val = a->ring_val;
+    d.ring_iter = (long long*)a->ring_iter;
+    d.ring_len = (long)a->ring_len;
+    d.best_val = a->best_val;
+    d.best_iter = (long long*)a->best_iter;
+    d.flag = a->flag;
+    hipLaunchKernelGGL(kg_eval_record_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d);
+    return kg_launch_status("kg_eval_record");
+}
+
+extern "C" int kg_copy_if(const int32_t* flag, const KgCopyJob* jobs, int32_t njobs, void* stream) {
+    KG_REQUIRE(flag != nullptr && jobs != nullptr, "kg_copy_if: null flag / jobs");
+    KG_REQUIRE(njobs >= 1 && njobs <= KG_COPY_IF_MAX_JOBS, "kg_copy_if: njobs=%d outside [1, %d]", njobs, KG_COPY_IF_MAX_JOBS);
+    CopyJobs c = {};
+    c.flag = flag;
+    long most = 0;
+    for (int i = 0; i < njobs; ++i) {
+        const KgCopyJob& j = jobs[i];
+        KG_REQUIRE(j.src != nullptr && j.dst != nullptr, "kg_copy_if: job %d: null src / dst", i);
+        KG_REQUIRE(j.nwords >= 1 && j.nwords < (1ll << 40), "kg_copy_if: job %d: nwords=%lld", i, (long long)j.nwords);
+        const uintptr_t s = (uintptr_t)j.src, d = (uintptr_t)j.dst, bytes = (uintptr_t)j.nwords * 4;
+        KG_REQUIRE(((s | d) & 3) == 0, "kg_copy_if: job %d: src / dst not 4-byte aligned", i);
+        KG_REQUIRE(s + bytes <= d || d + bytes <= s, "kg_copy_if: job %d: src and dst overlap", i);
+        c.j[i] = j;
+        // blocks of the job: 128-bit form = 4 words per thread (an unaligned job only needs more trips of its loop)
+        const long units = (j.nwords + 3) / 4;
+        most = units > most ? units : most;
+    }
+    long gx = (most + CP_NT - 1) / CP_NT;
+    gx = gx < 1 ? 1 : (gx > CP_MAX_BLOCKS ? CP_MAX_BLOCKS : gx);
+    hipLaunchKernelGGL(kg_copy_if_kernel, dim3((unsigned)gx, (unsigned)njobs), dim3(CP_NT), 0, (hipStream_t)stream, c);
+    return kg_launch_status("kg_copy_if");
+}

@@ -1,0 +1,315 @@
+"""Scoring the generator during training and keeping the best weights on the device.
+
+The live weights of a WGAN-GP generator jump from step to step and the reference's released generators are iterations
+picked by hand.  ``Evaluator`` picks them: one ``evaluate()`` is ONE fixed launch sequence - a captured
+hipGraph on a single stream - that
+
+  1. draws one ``Sampler`` round of ``pairs`` samples per class from every named generator (all Samplers share one seed
+     and advance their counters in lock-step: every generator is scored on the same z, noise and truncation draws);
+  2. lays the round out NCHW where ``joint`` mode needs each sample's (C, T) block contiguous (one copy into a static
+     buffer, inside the replay);
+  3. scores it with kg_mmd per requested mode - the reference protocol (``metrics.calculate_mmd``: one fake against one
+     real sample per class, 14 bandwidths, per-class maximum) applied to ``pairs`` (fake, real) pairs per class and
+     averaged over classes and pairs;
+  4. kg_eval_record: appends (iteration, every score, improved) to a record on the device and decides whether the
+     selected score is the best so far (strictly smaller; a NaN never wins);
+  5. kg_copy_if: when it is, copies the selected generator - its flat parameters and every module buffer (BatchNorm
+     running statistics and batch counters) - into a snapshot.
+
+Nothing synchronises the host; everything is read through pointers when the launches run, so the captured evaluation
+follows the training replays in between.  ``records()``, ``best()`` and ``state_dict()`` read the device; the Evaluator
+never writes to a generator.  Definitions the tests pin this against: tests/eval_def.py.
+"""
+from __future__ import annotations
+
+import csv
+import warnings
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _native as nv
+from . import metrics
+from .sample import Sampler
+
+
+def pair_rows(labels, n_classes: int, pairs: int) -> np.ndarray:
+    """Indices into a labelled sample set in the Sampler's row order: entry ``j * n_classes + c`` is the ``j``-th sample
+    (in index order) whose label is ``c``.  ValueError when a class has fewer than ``pairs`` samples."""
+    lab = np.asarray(labels).astype(np.int64).reshape(-1)
+    rows = np.empty(pairs * n_classes, dtype=np.int64)
+    for c in range(n_classes):
+        idx = np.flatnonzero(lab == c)
+        if idx.size < pairs:
+            raise ValueError("pair_rows: class %d has %d samples, %d needed" % (c, idx.size, pairs))
+        rows[c::n_classes] = idx[:pairs]
+    return rows
+
+
+def default_select(names: Sequence[str], modes: Sequence[str]) -> str:
+    """``"ema/<mode>"`` when an averaged generator is scored, else ``"live/<mode>"``, else the first generator; the mode
+    is ``avg`` when it is requested, else the first one"""
+    mode = "avg" if "avg" in modes else modes[0]
+    gen = "ema" if "ema" in names else ("live" if "live" in names else names[0])
+    return "%s/%s" % (gen, mode)
+
+
+def write_metrics_csv(path: str, records: dict) -> None:
+    """``metrics.csv``: a header, then one row per evaluation - iteration, every score (``repr`` of the fp32 value: it
+    reads back bit for bit), improved (0 / 1)."""
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["iteration"] + list(records["names"]) + ["improved"])
+        for it, row, imp in zip(records["iteration"], records["scores"], records["improved"]):
+            w.writerow([int(it)] + [repr(float(v)) for v in row] + [int(imp)])
+
+
+def _flat_storage(params):
+    """The parameters as ONE flat fp32 tensor when they are views into one storage (``FlatParams``, the weight average):
+    (flat, offsets in elements); else (None, None)."""
+    st = params[0].untyped_storage()
+    if any(p.untyped_storage().data_ptr() != st.data_ptr() or p.dtype != torch.float32 or not p.is_contiguous() for p in params):
+        return None, None
+    lo = min(p.storage_offset() for p in params)
+    hi = max(p.storage_offset() + p.numel() for p in params)
+    flat = torch.empty(0, dtype=torch.float32, device=params[0].device).set_(st, lo, (hi - lo,))
+    return flat, [p.storage_offset() - lo for p in params]
+
+
+class Evaluator:
+    """``generators``: {name: Generator} (one or more); the real side: a ``Feeder`` (``metrics.select_reference_samples``
+    with ``per_class=pairs``, cropped to the generator's ``t_size``), or ``real`` (N, C, T, V) with class ids
+    ``real_labels`` (N,) - the first ``pairs`` samples of every class in index order.  Score names are
+    ``"<generator>/<mode>"``; ``select`` names the one that decides (default: ``default_select``).  ``iteration``: a
+    one-element int64 device tensor read when an evaluation runs (``TrainLoop.step_dev``), None records -1."""
+
+    def __init__(self, generators: Dict[str, torch.nn.Module], real, real_labels=None, pairs: int = 10,
+                 modes: Sequence[str] = ("avg", "joint"), select: Optional[str] = None, seed: int = 0,
+                 trunc: Optional[float] = None, trunc_mode: str = "-", iteration: Optional[torch.Tensor] = None,
+                 ring_len: int = 1024, use_graph: bool = True, t_size: Optional[int] = None):
+        if not generators:
+            raise ValueError("Evaluator: at least one generator")
+        self.modes = tuple(modes)
+        for m in self.modes:
+            metrics._check_mode(m)
+        if not self.modes:
+            raise ValueError("Evaluator: at least one mode")
+        self.gens = dict(generators)
+        self.names = ["%s/%s" % (g, m) for g in self.gens for m in self.modes]
+        if len(self.names) > nv.EVAL_MAX_SCORES:
+            raise ValueError("Evaluator: %d scores, at most %d fit one record" % (len(self.names), nv.EVAL_MAX_SCORES))
+        self.select = default_select(list(self.gens), self.modes) if select is None else str(select)
+        if self.select not in self.names:
+            raise ValueError("Evaluator: select %r is none of %s" % (self.select, self.names))
+        self._select = self.names.index(self.select)
+        self.pairs, self.seed, self.ring_len = int(pairs), int(seed), int(ring_len)
+        if self.pairs < 1 or self.ring_len < 1:
+            raise ValueError("Evaluator: pairs and ring_len must be >= 1")
+        first = next(iter(self.gens.values()))
+        self.device = dev = next(first.parameters()).device
+        self.use_graph = bool(use_graph) and dev.type == "cuda"
+        self.iteration = iteration
+        # every generator behind its own Sampler; this class runs their launch sequences inside its own capture
+        self.samplers = {k: Sampler(G, qtd=self.pairs, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False)
+                         for k, G in self.gens.items()}
+        s0 = next(iter(self.samplers.values()))
+        self.n_classes, self.n = s0.n_classes, s0.n
+        if any(s.n_classes != self.n_classes for s in self.samplers.values()):
+            raise ValueError("Evaluator: the generators differ in their number of classes")
+        # the real side, once: row j*K + c = the j-th selected real sample of class c (the Sampler's label order)
+        if real_labels is None and hasattr(real, "label") and hasattr(real, "data"):
+            data, lab, _ = metrics.select_reference_samples(real, np.arange(self.n_classes),
+                                                            int(t_size) if t_size is not None else int(first.t_size), per_class=self.pairs)
+        else:
+            data = real.detach().cpu().numpy() if isinstance(real, torch.Tensor) else np.asarray(real)
+            lab = real_labels.detach().cpu().numpy() if isinstance(real_labels, torch.Tensor) else np.asarray(real_labels)
+        rows = pair_rows(lab, self.n_classes, self.pairs)
+        self.real = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32)[rows])).to(dev)
+        self._pair_labels = np.arange(self.n)                  # every (fake, real) pair is a "class" of the kg_mmd call
+        self._nchw = None
+        if "joint" in self.modes and self.real.shape[1] > 1 and self.real.shape[2] > 1:
+            self._nchw = {k: torch.zeros(self.real.shape, dtype=torch.float32, device=dev) for k in self.gens}
+        # the record
+        n = len(self.names)
+        self.count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.ring_val = torch.full((self.ring_len, n), float("nan"), dtype=torch.float32, device=dev)
+        self.ring_iter = torch.full((self.ring_len, 2), -1, dtype=torch.int64, device=dev)
+        self.best_val = torch.full((1,), float("inf"), dtype=torch.float32, device=dev)
+        self.best_iter = torch.full((1,), -1, dtype=torch.int64, device=dev)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.n_evals = 0                     # host mirror of count
+        self._flushed = 0
+        self._hist = []                      # (iteration (k,), scores (k, n), improved (k,)) blocks already read
+        # the snapshot of the selected generator: its flat parameters + one tensor per module buffer
+        G = self.gens[self.select.split("/")[0]]
+        params = [p.detach() for p in G.parameters()]
+        flat, offs = _flat_storage(params)
+        if flat is not None:
+            self.snap_flat = torch.zeros_like(flat)
+            self._jobs = [(flat, self.snap_flat)]
+        else:                                # per-tensor storage: packed, one job per parameter
+            offs = list(np.cumsum([0] + [p.numel() for p in params[:-1]]))
+            self.snap_flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
+            self._jobs = [(p.contiguous().view(-1), self.snap_flat[o:o + p.numel()]) for p, o in zip(params, offs)]
+        self._snap_offsets = [int(o) for o in offs]
+        self._G_sel = G
+        self.snap_buffers = {k: torch.zeros_like(b) for k, b in G.named_buffers()}
+        self._jobs += [(b.detach(), self.snap_buffers[k]) for k, b in G.named_buffers()]
+        self._best_G = None
+        self._scores = None
+        self._graph = None
+
+    # ---- the launch sequence -------------------------------------------------------------------------------------------
+    def _round(self):
+        """what a graph holds: per generator a Sampler round, the re-layout, kg_mmd per mode; then the record, then the
+        conditional snapshot"""
+        scores = []
+        for k, s in self.samplers.items():
+            s._round()
+            out = s._out
+            if self._nchw is not None:
+                self._nchw[k].copy_(out)
+                out = self._nchw[k]
+            for mode in self.modes:
+                scores.append(metrics.calculate_mmd(out, self.real, self._pair_labels, mode).reshape(1))
+        nv.eval_record(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
+                       self.best_iter, self.flag)
+        nv.copy_if(self.flag, self._jobs)
+        self._scores = scores                # (under capture: the graph's own memory, kept alive with it)
+
+    def _state_tensors(self):
+        ts = [s.step_dev for s in self.samplers.values()]
+        ts += [self.count, self.ring_val, self.ring_iter, self.best_val, self.best_iter, self.flag, self.snap_flat]
+        return ts + list(self.snap_buffers.values())
+
+    def _capture(self):
+        """Single-stream capture, no parallel branches.  The warm-up rounds in front of it are real evaluations:
+        everything they move is put back."""
+        from .train import _capture
+        torch.cuda.synchronize(self.device)
+        ts = self._state_tensors()
+        keep = [t.clone() for t in ts]
+        g = _capture(self._round)
+        for t, k in zip(ts, keep):
+            t.copy_(k)
+        torch.cuda.synchronize(self.device)
+        return g
+
+    @torch.no_grad()
+    def evaluate(self) -> None:
+        """One evaluation, enqueued on the current stream; no host synchronisation (a full record ring is read first)."""
+        if self.n_evals - self._flushed >= self.ring_len:
+            self._flush()
+        if self.use_graph:
+            if self._graph is None:
+                self._graph = self._capture()
+            self._graph.replay()
+        else:
+            self._round()
+        for s in self.samplers.values():
+            s.step_count += 1
+        self.n_evals += 1
+
+    # ---- reading ---------------------------------------------------------------------------------------------------------
+    def _flush(self):
+        k = self.n_evals - self._flushed
+        if k <= 0:
+            return
+        raw = torch.cat([self.ring_val.view(torch.uint8).reshape(-1), self.ring_iter.view(torch.uint8).reshape(-1)]).cpu().numpy()
+        nb = self.ring_val.numel() * 4       # ONE device -> host read
+        val = raw[:nb].view(np.float32).reshape(self.ring_len, -1)
+        it = raw[nb:].view(np.int64).reshape(self.ring_len, 2)
+        slots = np.arange(self._flushed, self.n_evals) % self.ring_len
+        self._hist.append((it[slots, 0].copy(), val[slots].copy(), it[slots, 1].astype(bool)))
+        self._flushed = self.n_evals
+
+    def records(self) -> dict:
+        """Every evaluation since the record began, in evaluation order: dict(names, iteration (n,) int64, scores
+        (n, nscores) fp32, improved (n,) bool).  Synchronises (one bulk read of what has not been read yet)."""
+        self._flush()
+        n = len(self.names)
+        if not self._hist:
+            return {"names": list(self.names), "iteration": np.zeros(0, np.int64), "scores": np.zeros((0, n), np.float32),
+                    "improved": np.zeros(0, bool)}
+        return {"names": list(self.names), "iteration": np.concatenate([h[0] for h in self._hist]),
+                "scores": np.concatenate([h[1] for h in self._hist]), "improved": np.concatenate([h[2] for h in self._hist])}
+
+    def best(self) -> dict:
+        """{"value", "iteration"} of the best evaluation so far (+inf, -1 before the first finite one).  Synchronises."""
+        return {"value": float(self.best_val.item()), "iteration": int(self.best_iter.item())}
+
+    def best_generator(self):
+        """A ``Generator`` whose parameters and buffers are views into the snapshot (built once, in eval mode;
+        ``state_dict()`` has the reference's keys in the reference's order).  It follows every later snapshot."""
+        if self._best_G is not None:
+            return self._best_G
+        from .wgan_gp import rebuild_generator
+        E = rebuild_generator(self._G_sel)
+        for p, off in zip(E.parameters(), self._snap_offsets):
+            p.data = self.snap_flat[off:off + p.numel()].view(p.shape)
+            p.requires_grad_(False)
+        names = iter(self.snap_buffers)
+        for me in E.modules():
+            for k in list(me._buffers):
+                me._buffers[k] = self.snap_buffers[next(names)]
+        assert [k for k, _ in E.named_buffers()] == list(self.snap_buffers)
+        self._best_G = E
+        return E
+
+    # ---- resume ----------------------------------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        rec = self.records()
+        s0 = next(iter(self.samplers.values()))
+        return {"seed": self.seed, "step": s0.step_count, "pairs": self.pairs, "select": self.select, "modes": list(self.modes),
+                "names": list(self.names), "count": self.n_evals, "ring_val": self.ring_val.cpu(), "ring_iter": self.ring_iter.cpu(),
+                "best_val": self.best_val.cpu(), "best_iter": self.best_iter.cpu(),
+                "snapshot": {"flat": self.snap_flat.cpu(), "buffers": {k: b.cpu() for k, b in self.snap_buffers.items()}},
+                "records": {k: rec[k] for k in ("iteration", "scores", "improved")}}
+
+    def check_compatible(self, sd: dict) -> None:
+        for k, mine in (("pairs", self.pairs), ("select", self.select), ("modes", list(self.modes)), ("names", list(self.names))):
+            if (list(sd[k]) if isinstance(mine, list) else sd[k]) != mine:
+                raise ValueError("Evaluator.load_state_dict: %s is %r in the state, %r here" % (k, sd[k], mine))
+        if tuple(sd["ring_val"].shape) != tuple(self.ring_val.shape) or tuple(sd["snapshot"]["flat"].shape) != tuple(self.snap_flat.shape) \
+                or set(sd["snapshot"]["buffers"]) != set(self.snap_buffers):
+            raise ValueError("Evaluator.load_state_dict: the record ring or the snapshot of the state has another shape")
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Continues bit for bit: the same draws, the same record, the same best so far and its snapshot."""
+        self.check_compatible(sd)
+        for s in self.samplers.values():
+            s.load_state_dict({"seed": sd["seed"], "step": sd["step"]})
+        if int(sd["seed"]) != self.seed:
+            self.seed, self._graph = int(sd["seed"]), None      # (the seed is a launch argument)
+        self.n_evals = self._flushed = int(sd["count"])
+        self.count.fill_(self.n_evals)
+        self.ring_val.copy_(sd["ring_val"])
+        self.ring_iter.copy_(sd["ring_iter"])
+        self.best_val.copy_(sd["best_val"])
+        self.best_iter.copy_(sd["best_iter"])
+        self.flag.zero_()
+        self.snap_flat.copy_(sd["snapshot"]["flat"])
+        for k, b in self.snap_buffers.items():
+            b.copy_(sd["snapshot"]["buffers"][k])
+        r = sd["records"]
+        self._hist = [(np.asarray(r["iteration"], np.int64).copy(), np.asarray(r["scores"], np.float32).copy(),
+                       np.asarray(r["improved"], bool).copy())] if len(r["iteration"]) else []
+        torch.cuda.synchronize(self.device)
+
+    def reset(self) -> None:
+        """A fresh record (``TrainLoop.load_state_dict`` of a state without one); the Sampler counters start again at 0."""
+        warnings.warn("Evaluator: the loaded state holds no evaluation record; it starts a fresh one")
+        for s in self.samplers.values():
+            s.load_state_dict({"seed": self.seed, "step": 0})
+        self.n_evals = self._flushed = 0
+        self._hist = []
+        self.count.zero_()
+        self.ring_val.fill_(float("nan"))
+        self.ring_iter.fill_(-1)
+        self.best_val.fill_(float("inf"))
+        self.best_iter.fill_(-1)
+        self.flag.zero_()
+        self.snap_flat.zero_()
+        for b in self.snap_buffers.values():
+            b.zero_()

@@ -28,6 +28,7 @@ import torch
 
 from . import _native as nv
 from .checkpoint import AsyncCheckpointWriter
+from .evaluate import write_metrics_csv
 from .feeder import DeviceBatches, Feeder
 from .sample import sample_actions
 from .wgan_gp import Trainer
@@ -117,7 +118,10 @@ class TrainLoop:
     def __init__(self, G, D, data, batch_size: int, t_size: int, n_critic: int = 5, seed: int = 0, lr: float = 2e-4,
                  b1: float = 0.5, b2: float = 0.999, lambda_gp: float = 10.0, use_graph: bool = True,
                  ring_len: int = 4096, max_resident_bytes: Optional[int] = None, rank: int = 0, world: int = 1,
-                 run_ahead: int = 16, ema_decay: Optional[float] = None, ema_warmup: float = 10.0):
+                 run_ahead: int = 16, ema_decay: Optional[float] = None, ema_warmup: float = 10.0,
+                 eval_interval: Optional[int] = None, eval_pairs: int = 10, eval_select: Optional[str] = None,
+                 eval_modes=("avg", "joint"), eval_trunc: Optional[float] = None, eval_trunc_mode: str = "-",
+                 eval_data: Optional[Feeder] = None):
         self.G, self.D = G, D
         self.device = next(G.parameters()).device
         if self.device.type != "cuda":
@@ -184,6 +188,19 @@ class TrainLoop:
             self._perm_wait = [False, False]
             self._copy_stream = torch.cuda.Stream(device=dev)
             self._gather = nv.StepData(r.data, r.labels, self._perm, self.bpe, r.scale, r.shift, self.real, self.labels)
+        # eval_interval (None or 0: off): every eval_interval finished iterations one Evaluator replay is enqueued behind the
+        # iteration - it scores the live (and the averaged) generator, appends to a record on the device and snapshots the
+        # best-scoring weights there.  Off: no launch, no file, no state key is added.
+        self.eval_interval = int(eval_interval) if eval_interval else None
+        self.evaluator = None
+        if self.eval_interval:
+            from .evaluate import Evaluator
+            gens = {"live": G}
+            if self.ema_decay:
+                gens["ema"] = self.ema_generator()
+            self.evaluator = Evaluator(gens, eval_data if eval_data is not None else feeder, pairs=eval_pairs, modes=eval_modes,
+                                       select=eval_select, seed=self.seed, trunc=eval_trunc, trunc_mode=eval_trunc_mode,
+                                       iteration=self.step_dev, use_graph=self.use_graph, t_size=self.t)
 
     # ---- schedule ------------------------------------------------------------------------------------------------
     @property
@@ -298,6 +315,8 @@ class TrainLoop:
         else:
             self._iteration(wg)
         self.step_count += 1
+        if self.evaluator is not None and self.step_count % self.eval_interval == 0:
+            self.evaluator.evaluate()        # enqueued behind the iteration; reads step_dev = the finished count
 
     # ---- losses ----------------------------------------------------------------------------------------------------
     def _flush(self):
@@ -331,6 +350,8 @@ class TrainLoop:
         if tr.fG.ema is not None:
             out["G"]["ema"] = tr.fG.ema.cpu()
             out["ema"] = {"decay": self.ema_decay, "warmup": self.ema_warmup}
+        if self.evaluator is not None:
+            out["eval"] = self.evaluator.state_dict()
         return out
 
     def load_state_dict(self, sd: dict) -> None:
@@ -338,6 +359,8 @@ class TrainLoop:
             if sd[k] != mine:
                 raise ValueError("TrainLoop.load_state_dict: %s is %r in the checkpoint, %r here" % (k, sd[k], mine))
         tr = self.trainer
+        if self.evaluator is not None and sd.get("eval") is not None:
+            self.evaluator.check_compatible(sd["eval"])      # (raises before anything is loaded)
         have = sd.get("ema") is not None and sd["G"].get("ema") is not None
         if tr.fG.ema is not None and have:
             for k, mine in (("decay", self.ema_decay), ("warmup", self.ema_warmup)):
@@ -368,6 +391,11 @@ class TrainLoop:
         if sd.get("last_losses") is not None:
             self.ring[(self.step_count - 1) % self.ring_len].copy_(sd["last_losses"])
         self._batch_iter = None
+        if self.evaluator is not None:           # (a record in the state is ignored by a loop without evaluation)
+            if sd.get("eval") is not None:
+                self.evaluator.load_state_dict(sd["eval"])
+            else:
+                self.evaluator.reset()
         torch.cuda.synchronize(self.device)
 
     # ---- the reference's loop ------------------------------------------------------------------------------------------
@@ -392,7 +420,10 @@ class TrainLoop:
         ``state_path``: ``state_dict()`` is saved there with every checkpoint and at the end (``load_state_dict`` of that
         file continues the run bit for bit).  With the weight average on (``ema_decay``) the averaged generator is written
         next to the live one at the same intervals: ``models/generator_ema_<batches_done>.pth`` and
-        ``actions_ema/<batches_done>.npy``."""
+        ``actions_ema/<batches_done>.npy``.  With evaluation on (``eval_interval``): ``metrics.csv`` (one row per evaluation:
+        iteration, every score, improved) at every ``sample_interval`` and at the end, ``models/generator_best.pth`` (the
+        snapshot of the best-scoring weights) at every ``checkpoint_interval`` and at the end whenever the best iteration
+        has changed since the last write, and the best value and its iteration on the progress line."""
         models_out, actions_out = os.path.join(out_dir, "models"), os.path.join(out_dir, "actions")
         os.makedirs(models_out, exist_ok=True)
         os.makedirs(actions_out, exist_ok=True)
@@ -402,6 +433,14 @@ class TrainLoop:
             os.makedirs(ema_actions_out, exist_ok=True)
         log_interval = max(1, min(int(log_interval), self.ring_len))
         writer = AsyncCheckpointWriter()
+        ev, best_written = self.evaluator, -1
+
+        def write_best():
+            nonlocal best_written
+            b = ev.best()
+            if b["iteration"] != best_written and b["iteration"] >= 0:
+                writer.save(ev.best_generator(), os.path.join(models_out, "generator_best.pth"))
+                best_written = b["iteration"]
         try:
             while self.step_count < n_epochs * self.bpe:
                 batches_done = self.step_count
@@ -409,20 +448,31 @@ class TrainLoop:
                 self.step()
                 if (batches_done + 1) % log_interval == 0 or batches_done + 1 == n_epochs * self.bpe:
                     d, g = self.losses()
-                    log("[Epoch %d/%d] [Batch %d/%d] [D loss: %f] [G loss: %f]" % (epoch, n_epochs, i, self.bpe, d[-1], g[-1]))
+                    line = "[Epoch %d/%d] [Batch %d/%d] [D loss: %f] [G loss: %f]" % (epoch, n_epochs, i, self.bpe, d[-1], g[-1])
+                    if ev is not None:
+                        b = ev.best()
+                        line += " [best %s: %f @ %d]" % (ev.select, b["value"], b["iteration"])
+                    log(line)
                 if batches_done % sample_interval == 0:
                     self.sample_action(os.path.join(actions_out, "%d.npy" % batches_done))
                     if ema_G is not None:
                         self.sample_action(os.path.join(ema_actions_out, "%d.npy" % batches_done), ema_G)
                     self.save_losses(os.path.join(out_dir, "plot_loss.mat"))
+                    if ev is not None:
+                        write_metrics_csv(os.path.join(out_dir, "metrics.csv"), ev.records())
                 if checkpoint_interval != -1 and batches_done % checkpoint_interval == 0:
                     writer.save(self.G, os.path.join(models_out, "generator_%d.pth" % batches_done))
                     writer.save(self.D, os.path.join(models_out, "discriminator_%d.pth" % batches_done))
                     if ema_G is not None:
                         writer.save(ema_G, os.path.join(models_out, "generator_ema_%d.pth" % batches_done))
+                    if ev is not None:
+                        write_best()
                     if state_path is not None:
                         torch.save(self.state_dict(), state_path)
             self.save_losses(os.path.join(out_dir, "plot_loss.mat"))
+            if ev is not None:
+                write_metrics_csv(os.path.join(out_dir, "metrics.csv"), ev.records())
+                write_best()
             if state_path is not None:
                 torch.save(self.state_dict(), state_path)
         finally:

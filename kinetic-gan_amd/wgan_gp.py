@@ -35,6 +35,30 @@ from . import _native as nv
 from . import ops
 
 
+def rebuild_generator(G):
+    """A ``Generator`` of ``G``'s structure on ``G``'s device with parameters and buffers of its own (freshly initialised:
+    the caller points them at the storage it wants - the weight average, a snapshot), in eval mode, carrying ``G``'s
+    schedule switches.  The host random generator is left alone."""
+    from .graph import Graph_h36m
+    n_classes = G.label_emb.num_embeddings
+    weighted = isinstance(G.edge_importance, torch.nn.ParameterList)
+    with torch.random.fork_rng(devices=[]):         # (the constructor draws initial weights: leave the host generator alone)
+        E = type(G)(G.mlp.mlp[0].in_features - n_classes, G.st_gcn_networks[-1].out_channels, n_classes, G.t_size,
+                    sum(isinstance(m, torch.nn.Linear) for m in G.mlp.mlp), edge_importance_weighting=weighted,
+                    dataset="h36m" if isinstance(G.graph, Graph_h36m) else "ntu")
+    E.to(next(G.parameters()).device)
+    live, mine = list(G.named_parameters()), list(E.named_parameters())
+    if [(k, p.shape) for k, p in live] != [(k, p.shape) for k, p in mine]:
+        raise RuntimeError("rebuild_generator: could not rebuild the generator's structure")
+    for me, lm in zip(E.modules(), G.modules()):
+        if list(me._buffers) != list(lm._buffers):
+            raise RuntimeError("rebuild_generator: could not rebuild the generator's structure")
+    for k in ("use_trunk", "map_kernels"):
+        setattr(E, k, getattr(G, k))
+    E.eval()
+    return E
+
+
 class FlatParams:
     """Re-points a module's parameters (and .grad) at slices of two flat fp32 buffers."""
 
@@ -258,29 +282,17 @@ class Trainer:
             raise RuntimeError("Trainer.ema_generator: the average is off (pass ema_decay)")
         if self._ema_G is not None:
             return self._ema_G
-        from .graph import Graph_h36m
         G, f = self.G, self.fG
-        n_classes = G.label_emb.num_embeddings
-        weighted = isinstance(G.edge_importance, torch.nn.ParameterList)
-        with torch.random.fork_rng(devices=[]):         # (the constructor draws initial weights: leave the host generator alone)
-            E = type(G)(G.mlp.mlp[0].in_features - n_classes, G.st_gcn_networks[-1].out_channels, n_classes, G.t_size,
-                        sum(isinstance(m, torch.nn.Linear) for m in G.mlp.mlp), edge_importance_weighting=weighted,
-                        dataset="h36m" if isinstance(G.graph, Graph_h36m) else "ntu")
-        E.to(f.flat.device)
+        E = rebuild_generator(G)
         live, mine = list(G.named_parameters()), list(E.named_parameters())
-        if [(k, p.shape) for k, p in live] != [(k, p.shape) for k, p in mine] or len(live) != len(f.offsets):
+        if len(live) != len(f.offsets):
             raise RuntimeError("Trainer.ema_generator: could not rebuild the generator's structure")
         for (_, p), off in zip(mine, f.offsets):
             p.data = f.ema[off:off + p.numel()].view(p.shape)
             p.requires_grad_(False)
         for me, lm in zip(E.modules(), G.modules()):
-            if list(me._buffers) != list(lm._buffers):
-                raise RuntimeError("Trainer.ema_generator: could not rebuild the generator's structure")
             for k, b in lm._buffers.items():
                 me._buffers[k] = b
-        for k in ("use_trunk", "map_kernels"):
-            setattr(E, k, getattr(G, k))
-        E.eval()
         self._ema_G = E
         return E
 

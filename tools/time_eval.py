@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""Cost of scoring the generator inside the training loop (record: profiles/eval_time.log).
+
+NTU-60 shapes, 64 samples per iteration, a generator step in every iteration (n_critic = 1), a resident synthetic dataset -
+the configuration of tools/time_train_loop.py and tools/time_ema.py.  One evaluation: 60 classes x 10 pairs, the live and
+the averaged generator, both modes (four scores).
+
+  1. the evaluation replay alone: event-timed, median over ``--replays`` replays, ``--reps`` repetitions with their spread;
+     next to it its parts timed the same way - one 600-sample Sampler round and kg_mmd per mode - whose sum
+     (2 rounds + 2 x 2 kg_mmd) is the comparator for what the re-layout and the two new launches add;
+  2. the loop with eval_interval = 100 against the loop without: two captured loops (both with the weight average)
+     alternate in one process, ``--rounds`` rounds of 300 iterations (three evaluations each); the difference per iteration
+     next to the spread between rounds.  The loop without IS the off path: its figure is the one to hold against
+     tools/time_train_loop.py's.
+
+``--only-eval N``: N evaluation replays and nothing else (the run to put under a kernel trace).
+    python tools/time_eval.py [--rounds 3] [--log FILE]"""
+import argparse
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kinetic_gan_amd  # noqa: F401,E402
+from kinetic_gan_amd import metrics  # noqa: E402
+from kinetic_gan_amd.sample import Sampler  # noqa: E402
+from kinetic_gan_amd.train import ResidentDataset, TrainLoop, _capture  # noqa: E402
+from time_train_loop import BATCH, CFG, SyntheticFeeder, models, time_loop  # noqa: E402
+
+DECAY, PAIRS, INTERVAL = 0.999, 10, 100
+
+
+def time_replays(graph, n):
+    """ms of each of n replays (one event pair per replay)"""
+    graph.replay()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        graph.replay()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return ts
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--replays", type=int, default=200)
+    ap.add_argument("--only-eval", type=int, default=0, help="this many evaluation replays and nothing else (for a kernel trace)")
+    ap.add_argument("--log", default=None, help="also write the lines to this file")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a GPU"
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    feeder = SyntheticFeeder(64 * BATCH + 17, CFG["channels"], CFG["t_size"], CFG["v"], CFG["n_classes"])
+    data = ResidentDataset(feeder, CFG["t_size"], dev)
+    say("device %s; NTU-60 shapes, %d samples per iteration, a generator step in every iteration, %d resident samples; "
+        "evaluation: %d classes x %d pairs, live and ema, avg and joint" % (
+            torch.cuda.get_device_name(0), BATCH, len(feeder), CFG["n_classes"], PAIRS))
+    loops = {}
+    for name, kw in (("off", {}), ("on", dict(eval_interval=INTERVAL, eval_pairs=PAIRS))):
+        G, D = models(dev)
+        loops[name] = TrainLoop(G, D, data, BATCH, CFG["t_size"], n_critic=1, seed=0, ema_decay=DECAY, **kw)
+    ev = loops["on"].evaluator
+    for loop in loops.values():
+        for _ in range(20):
+            loop.step()
+    ev.evaluate()                            # (captures)
+    torch.cuda.synchronize()
+    if args.only_eval:
+        for _ in range(args.only_eval):
+            ev.evaluate()
+        torch.cuda.synchronize()
+        say("%d evaluation replays done; %d copy jobs, snapshot of %d parameters" % (args.only_eval, len(ev._jobs), ev.snap_flat.numel()))
+        return
+    # 1. the evaluation replay alone, and its parts
+    meds = []
+    for r in range(args.reps):
+        ts = time_replays(ev._graph, args.replays)
+        ev.n_evals += args.replays + 1       # (host mirrors of the counters the replays advanced)
+        for s in ev.samplers.values():
+            s.step_count += args.replays + 1
+        meds.append(statistics.median(ts))
+        say("evaluation replay, repetition %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (r, meds[-1], args.replays, min(ts), max(ts)))
+    say("evaluation replay: %.4f ms (median of %d repetitions), spread between repetitions %.4f ms" % (
+        statistics.median(meds), args.reps, max(meds) - min(meds)))
+    smp = Sampler(loops["on"].G, qtd=PAIRS, seed=0)
+    smp.next()
+    t_round = statistics.median(time_replays(smp._graph, args.replays))
+    out, _, _ = smp.next()
+    nchw = out.contiguous()
+    parts = {}
+    for mode in ev.modes:
+        g = _capture(lambda: metrics.calculate_mmd(nchw, ev.real, ev._pair_labels, mode))
+        parts[mode] = statistics.median(time_replays(g, args.replays))
+    g = _capture(lambda: nchw.copy_(out))
+    t_copy = statistics.median(time_replays(g, args.replays))
+    total = 2 * t_round + 2 * sum(parts.values())
+    say("parts, each a graph of its own: Sampler round of %d samples %.4f ms; kg_mmd %s; re-layout copy_ %.4f ms" % (
+        smp.n, t_round, ", ".join("%s %.4f ms" % kv for kv in parts.items()), t_copy))
+    say("comparator 2 rounds + 2 x (%s) = %.4f ms; the evaluation replay is %+.4f ms against it (2 re-layouts, kg_eval_record, "
+        "kg_copy_if over %d jobs / %.1f MB)" % (" + ".join(parts), total, statistics.median(meds) - total, len(ev._jobs),
+                                               4 * ev.snap_flat.numel() / 1e6))
+    # 2. the loop with evaluation against the loop without
+    label = {"off": "loop without evaluation (the off path)", "on": "loop with eval_interval=%d" % INTERVAL}
+    lm = {k: [] for k in loops}
+    for r in range(args.rounds):
+        for k, loop in loops.items():
+            med, lo, hi, ms = time_loop(loop, blocks=30, per_block=10, warmup=5)
+            lm[k].append(statistics.mean(ms))
+            say("round %d %-42s mean %.4f ms per iteration over 300 replays (median of blocks of 10 %.4f, min %.4f, max %.4f)" % (
+                r, label[k], lm[k][-1], med, lo, hi))
+    for loop in loops.values():
+        d, g_ = loop.losses()
+        assert np.isfinite(d).all() and np.isfinite(g_).all(), "the timed loop diverged"
+    m = {k: statistics.median(v) for k, v in lm.items()}
+    sp = {k: max(v) - min(v) for k, v in lm.items()}
+    for k in loops:
+        say("%-42s %.4f ms per iteration (median of %d rounds), spread between rounds %.4f ms" % (label[k], m[k], args.rounds, sp[k]))
+    say("on - off = %+.2f us per iteration (one evaluation per %d iterations: %.4f ms / %d = %.2f us expected); larger spread %.2f us" % (
+        (m["on"] - m["off"]) * 1e3, INTERVAL, statistics.median(meds), INTERVAL, statistics.median(meds) / INTERVAL * 1e3,
+        max(sp.values()) * 1e3))
+    same = torch.equal(loops["on"].trainer.fG.flat, loops["off"].trainer.fG.flat)
+    rec = ev.records()
+    b = ev.best()
+    say("generator weights of the two loops after %d iterations equal: %s; %d evaluations recorded, best %s %.6f at iteration %d" % (
+        loops["on"].step_count, same, len(rec["iteration"]), ev.select, b["value"], b["iteration"]))
+    if args.log:
+        os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
+        with open(args.log, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

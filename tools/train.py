@@ -5,7 +5,10 @@ line, same outputs (``<out>/actions/<batches_done>.npy``, ``<out>/plot_loss.mat`
 random inputs on the device.  Extra flags: ``--seed`` (shuffling and every random input), ``--resume FILE`` (a
 ``loop_state.pth`` written by an earlier run: continues it bit for bit), ``--no-graph`` (the same launches, eagerly),
 ``--out``, ``--log_interval``, ``--ema_decay D`` / ``--ema_warmup W`` (a moving average of the generator's weights, updated
-inside the generator's Adam launch: also writes ``models/generator_ema_<n>.pth`` and ``actions_ema/<n>.npy``)."""
+inside the generator's Adam launch: also writes ``models/generator_ema_<n>.pth`` and ``actions_ema/<n>.npy``),
+``--eval_interval N`` (every N iterations the generator - and its average - is scored with the MMD protocol on the device,
+inside the loop: writes ``metrics.csv`` and ``models/generator_best.pth``, the weights of the best-scoring evaluation;
+``--eval_pairs``, ``--eval_select``, ``--eval_trunc``, ``--eval_trunc_mode``, ``--eval_data_path`` / ``--eval_label_path``)."""
 import argparse
 import os
 import sys
@@ -51,6 +54,15 @@ def parse_args(argv=None):
                    help="decay of an exponential moving average of the generator's weights (0 = off; e.g. 0.999)")
     p.add_argument("--ema_warmup", type=float, default=10.0,
                    help="ramp of the average's decay: min(ema_decay, (1 + s) / (ema_warmup + s)) at generator step s; 0 = no ramp")
+    p.add_argument("--eval_interval", type=int, default=0,
+                   help="iterations between evaluations inside the loop (0 = off): MMD of generated against real samples")
+    p.add_argument("--eval_pairs", type=int, default=10, help="(fake, real) pairs per class of one evaluation")
+    p.add_argument("--eval_select", type=str, default=None,
+                   help="the score that picks the best weights, '<live|ema>/<avg|joint>' (default: ema/avg with --ema_decay, else live/avg)")
+    p.add_argument("--eval_trunc", type=float, default=None, help="truncation factor of the evaluation's samples")
+    p.add_argument("--eval_trunc_mode", type=str, default="-", help="'-' none, 'z' or 'w' truncation of the evaluation's samples")
+    p.add_argument("--eval_data_path", type=str, default=None, help="real samples of the evaluation (default: the training data)")
+    p.add_argument("--eval_label_path", type=str, default=None, help="labels of --eval_data_path")
     return p.parse_args(argv)
 
 
@@ -70,9 +82,16 @@ def main(argv=None):
     feeder = Feeder(opt.data_path, opt.label_path, dataset=opt.dataset)
     if feeder.V != opt.v_size or feeder.C != opt.channels:
         raise SystemExit("data is (C=%d, V=%d) but --channels %d --v_size %d" % (feeder.C, feeder.V, opt.channels, opt.v_size))
+    eval_data = None
+    if opt.eval_interval and opt.eval_data_path:
+        if not opt.eval_label_path:
+            raise SystemExit("--eval_data_path needs --eval_label_path")
+        eval_data = Feeder(opt.eval_data_path, opt.eval_label_path, dataset=opt.dataset)
     loop = TrainLoop(G, D, feeder, opt.batch_size, opt.t_size, n_critic=opt.n_critic, seed=opt.seed, lr=opt.lr, b1=opt.b1,
                      b2=opt.b2, lambda_gp=float(opt.lambda_gp), use_graph=not opt.no_graph,
-                     ring_len=max(4096, opt.log_interval), ema_decay=opt.ema_decay or None, ema_warmup=opt.ema_warmup)
+                     ring_len=max(4096, opt.log_interval), ema_decay=opt.ema_decay or None, ema_warmup=opt.ema_warmup,
+                     eval_interval=opt.eval_interval or None, eval_pairs=opt.eval_pairs, eval_select=opt.eval_select,
+                     eval_trunc=opt.eval_trunc, eval_trunc_mode=opt.eval_trunc_mode, eval_data=eval_data)
     print("dataset: %d samples, %d batches per epoch, %s (%.1f MB cropped)" % (
         len(feeder), loop.bpe, "streamed" if loop.streaming else "resident on the device", loop.resident.nbytes / 1e6))
     if opt.resume:
