@@ -708,6 +708,44 @@ typedef struct KgMmdArgs {
 int64_t kg_mmd_workspace_bytes(const KgMmdArgs* a);   /* < 0 for invalid shapes                                    */
 int     kg_mmd(const KgMmdArgs* a, void* stream);
 
+/* ---- precision / recall / density / coverage (additive, ABI v9; DESIGN.md 16, csrc/kg_prdc.hip) -----------------------
+ * For every class c: R = n real points, F = m fake points of dimension D = d_outer*d_inner, read through strides (elements):
+ *   r_i[(o, e)] = real + c*r_sc + i*r_sp + o*r_so + e      (o < d_outer, e < d_inner: the inner run is contiguous)
+ * and likewise f_j.  With d2(a, b) = sum_d (a_d - b_d)^2 (direct differences in fp32, d ascending: the same bits per call):
+ *   rho_R(i) = the k-th smallest of { d2(r_i, r_l) : l != i }     (left out by INDEX: a duplicate is a neighbour at 0)
+ *   rho_F(j) = the k-th smallest of { d2(f_j, f_l) : l != j }
+ *   P_ij = [d2(r_i, f_j) <= rho_R(i)],  Q_ij = [d2(r_i, f_j) <= rho_F(j)]        (ties are inside)
+ *   counts[c] = (cP, cR, cD, cC) = (#{j : exists i P_ij}, #{i : exists j Q_ij}, sum_ij P_ij, #{i : exists j P_ij})
+ *   values[c] = (precision, recall, density, coverage) = (cP / m, cR / n, cD / (k m), cC / n)   (in double, rounded once)
+ *   mean (optional) = the mean over classes of values (fp64 sum in class order, rounded once)
+ * A sample (C, T, V) cropped in T is d_outer = C, d_inner = t*V, r_so = the channel stride; a contiguous one d_outer = 1.
+ * Three launches: radii (which also clears the words the next launch accumulates into: ws may hold anything), cross
+ * (integer atomics: order-independent, so two calls give the same bits), finish (one workgroup).  No n x n or n x m matrix
+ * is written: ws is kg_prdc_workspace_bytes(a) = 8 classes (n + m) bytes (radii and flag / hit words; no tile partials).
+ * Every pointer is read when the launches run; nothing is synchronised; capturable on one stream.
+ * Rejected (< 0, kg_last_error() names the field): null real / fake / counts / values / ws; n, m, classes, d_outer or
+ * d_inner < 1; k < 1, k > KG_PRDC_MAX_K or k > min(n, m) - 1; n or m above KG_PRDC_MAX_POINTS; classes x tiles of 2^24
+ * workgroups or more in one launch (first met at 64 classes of 32768 x 32768 points); ws_bytes too small.                */
+#define KG_PRDC_MAX_K 32
+#define KG_PRDC_MAX_POINTS 32768    /* per class and set: n*m stays below 2^31 (cD is an int32)                           */
+typedef struct KgPrdcArgs {
+    const float* real;  int64_t r_sc, r_sp, r_so;   /* class, point, outer-dimension strides (elements)                   */
+    const float* fake;  int64_t f_sc, f_sp, f_so;
+    int32_t n, m;                   /* real / fake points per class (n != m allowed)                                   */
+    int32_t d_outer, d_inner;       /* D = d_outer*d_inner; element (o, e) at + o*so + e                                */
+    int32_t classes, k;
+    float* radii_real;              /* (classes, n) squared radii, or NULL (kept in ws only)                           */
+    float* radii_fake;              /* (classes, m) or NULL                                                            */
+    int32_t* fake_hits;             /* (classes, m): sum_i P_ij (precision flag = hits > 0), or NULL                   */
+    uint8_t* real_flags;            /* (classes, n): bit 0 = exists j Q_ij (recall), bit 1 = exists j P_ij (coverage), or NULL */
+    int32_t* counts;                /* (classes, 4): cP, cR, cD, cC                                                    */
+    float* values;                  /* (classes, 4): precision, recall, density, coverage                              */
+    float* mean;                    /* (4) or NULL                                                                     */
+    void* ws;  int64_t ws_bytes;
+} KgPrdcArgs;
+int64_t kg_prdc_workspace_bytes(const KgPrdcArgs* a);   /* < 0 for invalid shapes                                    */
+int     kg_prdc(const KgPrdcArgs* a, void* stream);
+
 /* ---- inputs of one training iteration (additive, ABI v9; DESIGN.md 11, csrc/kg_input.hip) ---------------------------
  * kg_step_inputs writes, in ONE launch, every input of iteration s = *step and then stores s + 1 (last workgroup).
  * Batch: b = s mod batches_per_epoch, e = s div batches_per_epoch, row r_j = perm[(e & 1)*perm_stride + (b*world +

@@ -300,6 +300,19 @@ class _MmdArgs(C.Structure):
                 ("mmd2", c_f32p), ("mmd", c_f32p), ("result", c_f32p), ("mean", c_f32p),
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
+PRDC_MAX_K = 32
+PRDC_MAX_POINTS = 32768
+
+
+class _PrdcArgs(C.Structure):
+    _fields_ = [("real", c_f32p), ("r_sc", C.c_int64), ("r_sp", C.c_int64), ("r_so", C.c_int64),
+                ("fake", c_f32p), ("f_sc", C.c_int64), ("f_sp", C.c_int64), ("f_so", C.c_int64),
+                ("n", C.c_int32), ("m", C.c_int32), ("d_outer", C.c_int32), ("d_inner", C.c_int32),
+                ("classes", C.c_int32), ("k", C.c_int32),
+                ("radii_real", c_f32p), ("radii_fake", c_f32p), ("fake_hits", C.c_void_p), ("real_flags", C.c_void_p),
+                ("counts", C.c_void_p), ("values", c_f32p), ("mean", c_f32p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
 STEP_MAX_PLANES = 8
 STREAM_Z, STREAM_ALPHA, STREAM_NOISE_D, STREAM_NOISE_G = 0, 1, 2, 3
 
@@ -435,6 +448,8 @@ EXPORTS = {
                                C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p]),
     "kg_mmd_workspace_bytes": (C.c_int64, [C.POINTER(_MmdArgs)]),
     "kg_mmd": (C.c_int, [C.POINTER(_MmdArgs), C.c_void_p]),
+    "kg_prdc_workspace_bytes": (C.c_int64, [C.POINTER(_PrdcArgs)]),
+    "kg_prdc": (C.c_int, [C.POINTER(_PrdcArgs), C.c_void_p]),
     "kg_step_inputs": (C.c_int, [C.POINTER(_StepInputsArgs), C.c_void_p]),
     "kg_loss_append": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kg_adam_step_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
@@ -2161,6 +2176,77 @@ def mmd(x: MmdView, y: MmdView, m: int, n: int, dim: int, groups: int, classes: 
     a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
     _count("kg_mmd", 3.0 * 2.0 * m * (m - 1) * dim * groups * classes)
     _check(lib.kg_mmd(C.byref(a), _stream()), "kg_mmd")
+    return out
+
+
+# ---- precision / recall / density / coverage (kg_prdc.hip) ----------------------------------------------------------------
+
+class PrdcView(NamedTuple):
+    """How kg_prdc walks one set: element (class c, point i, outer o, inner e) sits at
+    t.data_ptr() + (c*sc + i*sp + o*so + e) floats."""
+    t: torch.Tensor
+    sc: int
+    sp: int
+    so: int
+
+
+def _prdc_extent_ok(v: PrdcView, pts: int, d_outer: int, d_inner: int, classes: int) -> bool:
+    """every element kg_prdc will read lies inside the tensor's storage"""
+    if min(v.sc, v.sp, v.so) < 0:
+        return False
+    last = (classes - 1) * v.sc + (pts - 1) * v.sp + (d_outer - 1) * v.so + d_inner - 1
+    return v.t.storage_offset() + last < v.t.untyped_storage().nbytes() // 4
+
+
+def prdc_workspace_bytes(n: int, m: int, d_outer: int, d_inner: int, classes: int, k: int) -> int:
+    """kg_prdc_workspace_bytes of a shape (RuntimeError naming the field for a shape kg_prdc rejects); no GPU call"""
+    a = _PrdcArgs()
+    a.n, a.m, a.d_outer, a.d_inner, a.classes, a.k = int(n), int(m), int(d_outer), int(d_inner), int(classes), int(k)
+    nbytes = load_library().kg_prdc_workspace_bytes(C.byref(a))
+    if nbytes < 0:
+        _check(-1, "kg_prdc_workspace_bytes")
+    return nbytes
+
+
+def prdc(real: PrdcView, fake: PrdcView, n: int, m: int, d_outer: int, d_inner: int, classes: int, k: int,
+         want_mean: bool = True, per_point: bool = False, ws: Optional[torch.Tensor] = None) -> dict:
+    """Enqueue kg_prdc (radii, cross and finishing launch) on the current stream; no host synchronisation.  Returns
+    dict(counts (classes, 4) int32, values (classes, 4) fp32, mean (4,) fp32 or None) on the device; with ``per_point``
+    also radii_real (classes, n), radii_fake (classes, m), fake_hits (classes, m) int32 and real_flags (classes, n)
+    uint8.  ``ws``: a caller's workspace (any dtype of 4-byte elements, at least the needed bytes; its contents do not
+    matter), else one is taken with torch.empty."""
+    lib = load_library()
+    for v in (real, fake):
+        if v.t.dtype != torch.float32:
+            raise TypeError(f"kg_prdc: fp32 only, got {v.t.dtype}")
+    nbytes = prdc_workspace_bytes(n, m, d_outer, d_inner, classes, k)
+    _need_cuda(real.t, fake.t, ws)
+    for name, v, p in (("real", real, n), ("fake", fake, m)):
+        if not _prdc_extent_ok(v, p, d_outer, d_inner, classes):
+            raise ValueError(f"kg_prdc: the strides of {name} reach outside its tensor")
+    dev = real.t.device
+    if ws is None:
+        ws = torch.empty(max(1, nbytes // 4), dtype=torch.int32, device=dev)
+    elif not ws.is_contiguous() or ws.element_size() != 4:
+        raise ValueError("kg_prdc: ws must be a contiguous tensor of 4-byte elements")
+    out = dict(counts=torch.empty((classes, 4), dtype=torch.int32, device=dev),
+               values=torch.empty((classes, 4), dtype=torch.float32, device=dev),
+               mean=torch.empty(4, dtype=torch.float32, device=dev) if want_mean else None)
+    if per_point:
+        out.update(radii_real=torch.empty((classes, n), dtype=torch.float32, device=dev),
+                   radii_fake=torch.empty((classes, m), dtype=torch.float32, device=dev),
+                   fake_hits=torch.empty((classes, m), dtype=torch.int32, device=dev),
+                   real_flags=torch.empty((classes, n), dtype=torch.uint8, device=dev))
+    a = _PrdcArgs()
+    a.real, a.r_sc, a.r_sp, a.r_so = real.t.data_ptr(), real.sc, real.sp, real.so
+    a.fake, a.f_sc, a.f_sp, a.f_so = fake.t.data_ptr(), fake.sc, fake.sp, fake.so
+    a.n, a.m, a.d_outer, a.d_inner, a.classes, a.k = int(n), int(m), int(d_outer), int(d_inner), int(classes), int(k)
+    a.radii_real, a.radii_fake = _ptr(out.get("radii_real")), _ptr(out.get("radii_fake"))
+    a.fake_hits, a.real_flags = _ptr(out.get("fake_hits")), _ptr(out.get("real_flags"))
+    a.counts, a.values, a.mean = out["counts"].data_ptr(), out["values"].data_ptr(), _ptr(out["mean"])
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    _count("kg_prdc", 3.0 * (float(n) * n + float(m) * m + float(n) * m) * d_outer * d_inner * classes)
+    _check(lib.kg_prdc(C.byref(a), _stream()), "kg_prdc")
     return out
 
 

@@ -1,4 +1,5 @@
-"""MMD evaluation of generated actions (evaluation/mmd-actions.py of the reference) on the kg_mmd HIP kernels.
+"""MMD evaluation of generated actions (evaluation/mmd-actions.py of the reference) on the kg_mmd HIP kernels, and
+precision / recall / density / coverage of sample sets on the kg_prdc kernels (``prdc``, at the end).
 
 The reference scores samples with a kernel two-sample statistic (MMD) under 14 RBF bandwidths 10^-4 .. 10^9: per class
 the first selected fake and real sample, each a set of V points (joints) per frame (``avg``: the mean over frames of
@@ -175,6 +176,110 @@ def calculate_mmd(gen, real, labels, mode: str = "avg", bandwidths: Sequence[flo
     if per_class:
         return out["mean"], out["result"], out["mmd"]
     return out["mean"]
+
+
+PRDC_NAMES = ("precision", "recall", "density", "coverage")
+
+
+def _label_ids(labels, n: int, what: str) -> Tuple[np.ndarray, int]:
+    """labels -> (class id per sample, classes the labels can name); None = one class"""
+    if labels is None:
+        return np.zeros(n, dtype=np.int64), 1
+    if isinstance(labels, torch.Tensor):
+        labels = labels.cpu().numpy()           # (one sync when the labels live on the device)
+    lab = np.asarray(labels)
+    if lab.ndim == 2:
+        k = lab.shape[-1]
+        lab = lab.argmax(-1)
+    else:
+        lab = lab.astype(np.int64)
+        k = int(lab.max()) + 1 if lab.size else 0
+    if lab.shape[0] != n:
+        raise ValueError("prdc: %d %s for %d samples" % (lab.shape[0], what, n))
+    return lab, k
+
+
+def _class_rows(lab: np.ndarray, classes: int, per_class: Optional[int], what: str) -> np.ndarray:
+    """(classes, count) sample indices: the first ``per_class`` samples of every class in index order (default: all of
+    them; the classes must then hold the same number)"""
+    rows = [np.flatnonzero(lab == c) for c in range(classes)]
+    if per_class is None:
+        count = rows[0].size
+        for c, r in enumerate(rows):
+            if r.size != count:
+                raise ValueError("prdc: class %d has %d %s samples, class 0 has %d (ragged classes: pass per_class)"
+                                 % (c, r.size, what, count))
+    else:
+        count = int(per_class)
+        for c, r in enumerate(rows):
+            if r.size < count:
+                raise ValueError("prdc: class %d has %d %s samples, per_class=%d needed" % (c, r.size, what, count))
+    if count < 1:
+        raise ValueError("prdc: class 0 has no %s sample" % what)
+    return np.stack([r[:count] for r in rows])
+
+
+def _prdc_view(t: torch.Tensor, idx: np.ndarray):
+    """(view, d_outer, d_inner) of the samples idx (classes, count) of t (N, C, T, V) on the device: read in place when
+    idx is evenly spaced along both axes, else gathered once; a (C, T, V) block that is not outer x contiguous inner
+    (a crop in T is: outer = C) is made contiguous"""
+    K, cnt = idx.shape
+    ps = int(idx[0, 1] - idx[0, 0]) if cnt > 1 else 1
+    cs = int(idx[1, 0] - idx[0, 0]) if K > 1 else 0
+    even = ps > 0 and cs >= 0 and np.array_equal(idx, idx[0, 0] + cs * np.arange(K)[:, None] + ps * np.arange(cnt)[None, :])
+    if even:
+        base = int(idx[0, 0])
+    else:
+        t = t.index_select(0, torch.as_tensor(idx.reshape(-1), device=t.device))
+        base, ps, cs = 0, 1, cnt
+    _, C, T, V = t.shape
+    if not ((V == 1 or t.stride(3) == 1) and (T == 1 or t.stride(2) == V)):
+        t = t.contiguous()
+    if C == 1 or t.stride(1) == T * V:
+        d_outer, d_inner, so = 1, C * T * V, 0
+    else:
+        d_outer, d_inner, so = C, T * V, t.stride(1)
+    return _native.PrdcView(t[base], cs * t.stride(0), ps * t.stride(0), so), d_outer, d_inner
+
+
+def prdc(gen, real, labels_gen=None, labels_real=None, k: int = 5, per_class: Optional[int] = None,
+         per_point: bool = False) -> dict:
+    """Improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020) per class on the
+    sequences themselves (a sample = one point of dimension C*T*V), in one kg_prdc call (three launches).
+
+    gen (Nf, C, T, V), real (Nr, C, T, V): fake, real - calculate_mmd's argument order; CUDA tensors, CPU tensors or
+    numpy.  Labels: one-hot (N, K) or class ids (N,); without labels everything is one class.  For every class the first
+    ``per_class`` samples of each set are used (default: all; every class must then hold the same number within a set -
+    ragged classes raise ValueError naming the class).  Samples that lie class by class and evenly spaced in the batch are
+    read in place through strides, otherwise they are gathered once.  Returns device tensors: ``mean`` (4,) - the plain
+    mean over classes in the order PRDC_NAMES -, ``values`` (K, 4), ``counts`` (K, 4) int32 (cP, cR, cD, cC); with
+    ``per_point`` also ``radii_real`` (K, n), ``radii_fake`` (K, m) (squared k-th-neighbour distances), ``fake_hits``
+    (K, m) int32 and ``real_flags`` (K, n) uint8 (bit 0: recall, bit 1: coverage).  No host sync (labels that live on
+    the device are read once)."""
+    gen, real = _as_f32(gen), _as_f32(real)
+    if gen.dim() != 4 or real.dim() != 4:
+        raise ValueError("prdc: samples are (N, C, T, V), got %s and %s" % (tuple(gen.shape), tuple(real.shape)))
+    if gen.shape[1:] != real.shape[1:]:
+        raise ValueError("prdc: gen samples %s and real samples %s differ in shape" % (tuple(gen.shape[1:]),
+                                                                                      tuple(real.shape[1:])))
+    lab_g, kg = _label_ids(labels_gen, gen.shape[0], "labels_gen")
+    lab_r, kr = _label_ids(labels_real, real.shape[0], "labels_real")
+    classes = max(kg, kr)
+    if classes < 1:
+        raise ValueError("prdc: no samples")
+    idx_r = _class_rows(lab_r, classes, per_class, "real")
+    idx_g = _class_rows(lab_g, classes, per_class, "fake")
+    n, m = idx_r.shape[1], idx_g.shape[1]
+    if not 1 <= k <= min(_native.PRDC_MAX_K, min(n, m) - 1):
+        raise ValueError("prdc: k=%d outside [1, min(%d, min(n=%d, m=%d) - 1)]" % (k, _native.PRDC_MAX_K, n, m))
+    gen, real = _as_cuda(gen), _as_cuda(real)
+    rv, d_outer, d_inner = _prdc_view(real, idx_r)
+    gv, go, gi = _prdc_view(gen, idx_g)
+    if (go, gi) != (d_outer, d_inner):          # one side is a crop, the other is not: both as channel rows
+        C, T, V = real.shape[1:]
+        rv, gv = (v if v.so or C == 1 else v._replace(so=T * V) for v in (rv, gv))
+        d_outer, d_inner = C, T * V
+    return _native.prdc(rv, gv, n, m, d_outer, d_inner, classes, k, want_mean=True, per_point=per_point)
 
 
 def select_reference_samples(feeder, classes: Optional[Sequence[int]] = None, t_size: int = 64, per_class: int = 100):
