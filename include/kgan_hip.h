@@ -746,6 +746,52 @@ typedef struct KgPrdcArgs {
 int64_t kg_prdc_workspace_bytes(const KgPrdcArgs* a);   /* < 0 for invalid shapes                                    */
 int     kg_prdc(const KgPrdcArgs* a, void* stream);
 
+/* ---- several fake sets against ONE real set whose radii are given (additive, ABI v9; DESIGN.md 17, csrc/kg_prdc.hip) --------
+ * The Evaluator's case: the real set is fixed for a whole run and every named generator is scored against it.
+ * kg_prdc_radii: rho(i) of ONE point set alone, as defined above (k-th smallest d2 to the other points of its class, left
+ * out by index), read through the strides of kg_prdc (x + c*sc + i*sp + o*so + e), written to radii (classes, n).  ONE
+ * launch of the radii kernel restricted to that set; no workspace.  Rejected: null x / radii; n, classes, d_outer or
+ * d_inner < 1; k < 1, k > KG_PRDC_MAX_K or k > n - 1; n above KG_PRDC_MAX_POINTS; 2^24 workgroups or more.
+ * kg_prdc_sets: nsets (1..KG_PRDC_MAX_SETS) fake sets fake[g] with shared strides and m, one real set, and the real set's
+ * radii as an INPUT (radii_real (classes, n), read when the launches run).  For every set g every output - counts[g],
+ * values[g], mean[g], radii_fake[g], fake_hits[g], real_flags[g] - equals, bit for bit, the same output of
+ * kg_prdc(real, fake[g]) given radii_real as kg_prdc computes it: every pair is the same fmaf chain over d ascending, the
+ * counts are integers, and neither the tile plan nor the grouping into sets shows in any bit.
+ * Three launches whatever nsets is: radii of all fake sets (row-tile workgroups for fake rows only; it clears the words
+ * the next launch accumulates into, so ws may hold anything), cross counts of every (set, class, tile) (vector integer
+ * atomics), finish (a wave per (set, class), then the class means).  No n x n or n x m matrix is written.
+ * ws = kg_prdc_sets_workspace_bytes(a) = 4 nsets classes (2 m + n) bytes: the fake radii (nsets, classes, m) fp32, the hit
+ * words (nsets, classes, m) int32, the per-set flag words (nsets, classes, n) int32.
+ * Every pointer is read when the launches run; nothing is synchronised; capturable on one stream.
+ * Rejected (< 0, kg_last_error() names the field): null real / fake[g] / radii_real / counts / values / ws; nsets outside
+ * [1, KG_PRDC_MAX_SETS]; n, m, classes, d_outer or d_inner < 1; k < 1, k > KG_PRDC_MAX_K or k > min(n, m) - 1; n or m above
+ * KG_PRDC_MAX_POINTS; nsets x classes x tiles of 2^24 workgroups or more in one launch; ws_bytes too small.                */
+#define KG_PRDC_MAX_SETS 4
+typedef struct KgPrdcRadiiArgs {
+    const float* x;  int64_t sc, sp, so;            /* class, point, outer-dimension strides (elements)                  */
+    int32_t n, d_outer, d_inner, classes, k;
+    float* radii;                   /* (classes, n) squared radii                                                      */
+} KgPrdcRadiiArgs;
+typedef struct KgPrdcSetsArgs {
+    const float* real;  int64_t r_sc, r_sp, r_so;
+    const float* fake[KG_PRDC_MAX_SETS];  int64_t f_sc, f_sp, f_so;   /* fake[0 .. nsets): strides and m are shared        */
+    int32_t nsets;
+    int32_t n, m;
+    int32_t d_outer, d_inner;
+    int32_t classes, k;
+    const float* radii_real;        /* (classes, n): INPUT (kg_prdc_radii of the real set, or radii_real of kg_prdc)   */
+    float* radii_fake;              /* (nsets, classes, m) or NULL                                                     */
+    int32_t* fake_hits;             /* (nsets, classes, m) or NULL                                                     */
+    uint8_t* real_flags;            /* (nsets, classes, n) or NULL                                                     */
+    int32_t* counts;                /* (nsets, classes, 4)                                                             */
+    float* values;                  /* (nsets, classes, 4)                                                             */
+    float* mean;                    /* (nsets, 4) or NULL                                                              */
+    void* ws;  int64_t ws_bytes;
+} KgPrdcSetsArgs;
+int     kg_prdc_radii(const KgPrdcRadiiArgs* a, void* stream);
+int64_t kg_prdc_sets_workspace_bytes(const KgPrdcSetsArgs* a);   /* < 0 for invalid shapes                           */
+int     kg_prdc_sets(const KgPrdcSetsArgs* a, void* stream);
+
 /* ---- inputs of one training iteration (additive, ABI v9; DESIGN.md 11, csrc/kg_input.hip) ---------------------------
  * kg_step_inputs writes, in ONE launch, every input of iteration s = *step and then stores s + 1 (last workgroup).
  * Batch: b = s mod batches_per_epoch, e = s div batches_per_epoch, row r_j = perm[(e & 1)*perm_stride + (b*world +
@@ -872,6 +918,29 @@ typedef struct KgEvalRecordArgs {
     int32_t* flag;                  /* (1): the decision kg_copy_if reads                                              */
 } KgEvalRecordArgs;
 int kg_eval_record(const KgEvalRecordArgs* a, void* stream);
+
+/* kg_eval_record2: kg_eval_record with room for KG_EVAL2_MAX_SCORES scores and a sense:
+ *     improved = maximise ? (s > *best_val) : (s < *best_val)      strict either way: a NaN never wins, an equal score
+ *                                                                  keeps the earlier snapshot
+ * The host initialises *best_val = -inf when maximising, +inf otherwise.  Everything else is the definition above (ring
+ * rows, [iteration, improved] in int64, *flag, *count, one thread of one small workgroup); with maximise = 0 and nscores <=
+ * KG_EVAL_MAX_SCORES it leaves the same bits as kg_eval_record.  Call site: evaluate.Evaluator._round when precision /
+ * recall / density / coverage are recorded (live + ema x 6 scores = 12 > 8).                                          */
+#define KG_EVAL2_MAX_SCORES 32
+typedef struct KgEvalRecord2Args {
+    const float* scores[KG_EVAL2_MAX_SCORES];  /* device: one fp32 each                                               */
+    int32_t nscores, select;
+    const int64_t* iter;
+    int64_t* count;
+    float* ring_val;                /* (ring_len, nscores)                                                             */
+    int64_t* ring_iter;             /* (ring_len, 2): [iteration, improved]                                            */
+    int64_t ring_len;
+    float* best_val;
+    int64_t* best_iter;
+    int32_t* flag;
+    int32_t maximise;               /* 0: smaller is better, else larger is better                                     */
+} KgEvalRecord2Args;
+int kg_eval_record2(const KgEvalRecord2Args* a, void* stream);
 
 /* kg_copy_if: when *flag != 0 every job's run of `nwords` 4-byte words is copied src -> dst bit for bit; when *flag == 0
  * the launch writes nothing at all.  A job whose src and dst are both 16-byte aligned moves 128 bits per access with a

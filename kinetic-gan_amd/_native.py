@@ -313,6 +313,24 @@ class _PrdcArgs(C.Structure):
                 ("counts", C.c_void_p), ("values", c_f32p), ("mean", c_f32p),
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
+PRDC_MAX_SETS = 4
+
+
+class _PrdcRadiiArgs(C.Structure):
+    _fields_ = [("x", c_f32p), ("sc", C.c_int64), ("sp", C.c_int64), ("so", C.c_int64),
+                ("n", C.c_int32), ("d_outer", C.c_int32), ("d_inner", C.c_int32), ("classes", C.c_int32), ("k", C.c_int32),
+                ("radii", c_f32p)]
+
+
+class _PrdcSetsArgs(C.Structure):
+    _fields_ = [("real", c_f32p), ("r_sc", C.c_int64), ("r_sp", C.c_int64), ("r_so", C.c_int64),
+                ("fake", c_f32p * PRDC_MAX_SETS), ("f_sc", C.c_int64), ("f_sp", C.c_int64), ("f_so", C.c_int64),
+                ("nsets", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("d_outer", C.c_int32), ("d_inner", C.c_int32),
+                ("classes", C.c_int32), ("k", C.c_int32),
+                ("radii_real", c_f32p), ("radii_fake", c_f32p), ("fake_hits", C.c_void_p), ("real_flags", C.c_void_p),
+                ("counts", C.c_void_p), ("values", c_f32p), ("mean", c_f32p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
 STEP_MAX_PLANES = 8
 STREAM_Z, STREAM_ALPHA, STREAM_NOISE_D, STREAM_NOISE_G = 0, 1, 2, 3
 
@@ -365,6 +383,16 @@ class _EvalRecordArgs(C.Structure):
     _fields_ = [("scores", c_f32p * EVAL_MAX_SCORES), ("nscores", C.c_int32), ("select", C.c_int32),
                 ("iter", C.c_void_p), ("count", C.c_void_p), ("ring_val", c_f32p), ("ring_iter", C.c_void_p),
                 ("ring_len", C.c_int64), ("best_val", c_f32p), ("best_iter", C.c_void_p), ("flag", C.c_void_p)]
+
+
+EVAL2_MAX_SCORES = 32
+
+
+class _EvalRecord2Args(C.Structure):
+    _fields_ = [("scores", c_f32p * EVAL2_MAX_SCORES), ("nscores", C.c_int32), ("select", C.c_int32),
+                ("iter", C.c_void_p), ("count", C.c_void_p), ("ring_val", c_f32p), ("ring_iter", C.c_void_p),
+                ("ring_len", C.c_int64), ("best_val", c_f32p), ("best_iter", C.c_void_p), ("flag", C.c_void_p),
+                ("maximise", C.c_int32)]
 
 
 class _CopyJob(C.Structure):
@@ -450,6 +478,9 @@ EXPORTS = {
     "kg_mmd": (C.c_int, [C.POINTER(_MmdArgs), C.c_void_p]),
     "kg_prdc_workspace_bytes": (C.c_int64, [C.POINTER(_PrdcArgs)]),
     "kg_prdc": (C.c_int, [C.POINTER(_PrdcArgs), C.c_void_p]),
+    "kg_prdc_radii": (C.c_int, [C.POINTER(_PrdcRadiiArgs), C.c_void_p]),
+    "kg_prdc_sets_workspace_bytes": (C.c_int64, [C.POINTER(_PrdcSetsArgs)]),
+    "kg_prdc_sets": (C.c_int, [C.POINTER(_PrdcSetsArgs), C.c_void_p]),
     "kg_step_inputs": (C.c_int, [C.POINTER(_StepInputsArgs), C.c_void_p]),
     "kg_loss_append": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kg_adam_step_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
@@ -463,6 +494,7 @@ EXPORTS = {
     "kg_trunc_lerp": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_float,
                                 C.c_void_p]),
     "kg_eval_record": (C.c_int, [C.POINTER(_EvalRecordArgs), C.c_void_p]),
+    "kg_eval_record2": (C.c_int, [C.POINTER(_EvalRecord2Args), C.c_void_p]),
     "kg_copy_if": (C.c_int, [C.c_void_p, C.POINTER(_CopyJob), C.c_int32, C.c_void_p]),
 }
 
@@ -2250,6 +2282,92 @@ def prdc(real: PrdcView, fake: PrdcView, n: int, m: int, d_outer: int, d_inner: 
     return out
 
 
+def prdc_radii(x: PrdcView, n: int, d_outer: int, d_inner: int, classes: int, k: int,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Enqueue kg_prdc_radii: the (classes, n) squared k-th-neighbour radii of ONE point set (one launch, no workspace);
+    ``out``: a contiguous fp32 tensor of classes * n elements to write into, else one is taken with torch.empty."""
+    if x.t.dtype != torch.float32:
+        raise TypeError(f"kg_prdc_radii: fp32 only, got {x.t.dtype}")
+    _need_cuda(x.t, out)
+    if min(n, d_outer, d_inner, classes) >= 1 and not _prdc_extent_ok(x, n, d_outer, d_inner, classes):
+        raise ValueError("kg_prdc_radii: the strides of x reach outside its tensor")
+    if out is None:
+        out = torch.empty((max(classes, 0), max(n, 0)), dtype=torch.float32, device=x.t.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != classes * n:
+        raise ValueError("kg_prdc_radii: out must be a contiguous fp32 tensor of classes * n elements")
+    a = _PrdcRadiiArgs()
+    a.x, a.sc, a.sp, a.so = x.t.data_ptr(), x.sc, x.sp, x.so
+    a.n, a.d_outer, a.d_inner, a.classes, a.k = int(n), int(d_outer), int(d_inner), int(classes), int(k)
+    a.radii = out.data_ptr()
+    _count("kg_prdc_radii", 3.0 * float(n) * n * d_outer * d_inner * classes)
+    _check(load_library().kg_prdc_radii(C.byref(a), _stream()), "kg_prdc_radii")
+    return out
+
+
+def prdc_sets_workspace_bytes(nsets: int, n: int, m: int, d_outer: int, d_inner: int, classes: int, k: int) -> int:
+    """kg_prdc_sets_workspace_bytes of a shape = 4 nsets classes (2 m + n) (RuntimeError naming the field for a shape
+    kg_prdc_sets rejects); no GPU call"""
+    a = _PrdcSetsArgs()
+    a.nsets, a.n, a.m = int(nsets), int(n), int(m)
+    a.d_outer, a.d_inner, a.classes, a.k = int(d_outer), int(d_inner), int(classes), int(k)
+    nbytes = load_library().kg_prdc_sets_workspace_bytes(C.byref(a))
+    if nbytes < 0:
+        _check(-1, "kg_prdc_sets_workspace_bytes")
+    return nbytes
+
+
+def prdc_sets(real: PrdcView, fakes: Sequence[torch.Tensor], f_sc: int, f_sp: int, f_so: int, radii_real: torch.Tensor,
+              n: int, m: int, d_outer: int, d_inner: int, classes: int, k: int, want_mean: bool = True,
+              per_point: bool = False, ws: Optional[torch.Tensor] = None) -> dict:
+    """Enqueue kg_prdc_sets: the ``fakes`` (1..PRDC_MAX_SETS fp32 tensors walked with the shared strides f_sc / f_sp /
+    f_so) against ONE real set whose (classes, n) radii ``radii_real`` are an input (``prdc_radii``); three launches
+    whatever the number of sets, no host synchronisation.  Returns dict(counts (nsets, classes, 4) int32, values (nsets,
+    classes, 4) fp32, mean (nsets, 4) fp32 or None) on the device; with ``per_point`` also radii_fake (nsets, classes, m),
+    fake_hits (nsets, classes, m) int32 and real_flags (nsets, classes, n) uint8.  Every entry of set g equals, bit for
+    bit, that of ``prdc(real, fakes[g])``.  ``ws`` as in ``prdc``."""
+    lib = load_library()
+    fakes = list(fakes)
+    for t in [real.t, radii_real] + fakes:
+        if t.dtype != torch.float32:
+            raise TypeError(f"kg_prdc_sets: fp32 only, got {t.dtype}")
+    nsets = len(fakes)
+    nbytes = prdc_sets_workspace_bytes(nsets, n, m, d_outer, d_inner, classes, k)
+    _need_cuda(real.t, radii_real, ws, *fakes)
+    if not _prdc_extent_ok(real, n, d_outer, d_inner, classes):
+        raise ValueError("kg_prdc_sets: the strides of real reach outside its tensor")
+    for g, t in enumerate(fakes):
+        if not _prdc_extent_ok(PrdcView(t, f_sc, f_sp, f_so), m, d_outer, d_inner, classes):
+            raise ValueError(f"kg_prdc_sets: the strides of fake set {g} reach outside its tensor")
+    if not radii_real.is_contiguous() or radii_real.numel() != classes * n:
+        raise ValueError("kg_prdc_sets: radii_real must be a contiguous fp32 tensor of classes * n elements")
+    dev = real.t.device
+    if ws is None:
+        ws = torch.empty(max(1, nbytes // 4), dtype=torch.int32, device=dev)
+    elif not ws.is_contiguous() or ws.element_size() != 4:
+        raise ValueError("kg_prdc_sets: ws must be a contiguous tensor of 4-byte elements")
+    out = dict(counts=torch.empty((nsets, classes, 4), dtype=torch.int32, device=dev),
+               values=torch.empty((nsets, classes, 4), dtype=torch.float32, device=dev),
+               mean=torch.empty((nsets, 4), dtype=torch.float32, device=dev) if want_mean else None)
+    if per_point:
+        out.update(radii_fake=torch.empty((nsets, classes, m), dtype=torch.float32, device=dev),
+                   fake_hits=torch.empty((nsets, classes, m), dtype=torch.int32, device=dev),
+                   real_flags=torch.empty((nsets, classes, n), dtype=torch.uint8, device=dev))
+    a = _PrdcSetsArgs()
+    a.real, a.r_sc, a.r_sp, a.r_so = real.t.data_ptr(), real.sc, real.sp, real.so
+    for g, t in enumerate(fakes):
+        a.fake[g] = t.data_ptr()
+    a.f_sc, a.f_sp, a.f_so = int(f_sc), int(f_sp), int(f_so)
+    a.nsets, a.n, a.m = nsets, int(n), int(m)
+    a.d_outer, a.d_inner, a.classes, a.k = int(d_outer), int(d_inner), int(classes), int(k)
+    a.radii_real, a.radii_fake = radii_real.data_ptr(), _ptr(out.get("radii_fake"))
+    a.fake_hits, a.real_flags = _ptr(out.get("fake_hits")), _ptr(out.get("real_flags"))
+    a.counts, a.values, a.mean = out["counts"].data_ptr(), out["values"].data_ptr(), _ptr(out["mean"])
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    _count("kg_prdc_sets", 3.0 * nsets * (float(m) * m + float(n) * m) * d_outer * d_inner * classes)
+    _check(lib.kg_prdc_sets(C.byref(a), _stream()), "kg_prdc_sets")
+    return out
+
+
 # ---- inputs of a training iteration (kg_input.hip) ------------------------------------------------------------------------
 
 class StepData(NamedTuple):
@@ -2494,6 +2612,37 @@ def eval_record(scores: Sequence[torch.Tensor], select: int, iteration: Optional
     a.ring_val, a.ring_iter = ring_val.data_ptr(), ring_iter.data_ptr()
     a.best_val, a.best_iter, a.flag = best_val.data_ptr(), best_iter.data_ptr(), flag.data_ptr()
     _check(load_library().kg_eval_record(C.byref(a), _stream()), "kg_eval_record")
+
+
+def eval_record2(scores: Sequence[torch.Tensor], select: int, iteration: Optional[torch.Tensor], count: torch.Tensor,
+                 ring_val: torch.Tensor, ring_iter: torch.Tensor, best_val: torch.Tensor, best_iter: torch.Tensor,
+                 flag: torch.Tensor, maximise: bool = False) -> None:
+    """Enqueue kg_eval_record2: ``eval_record`` for up to EVAL2_MAX_SCORES scores and with a sense - ``maximise``: ``flag``
+    = scores[select] > best_val (strict; the host starts best_val at -inf), else scores[select] < best_val."""
+    _need_cuda(iteration, count, ring_val, ring_iter, best_val, best_iter, flag, *scores)
+    for t in scores:
+        if t.dtype != torch.float32 or t.numel() != 1:
+            raise TypeError("kg_eval_record2: one-element fp32 scores expected")
+    for t in (iteration, count, best_iter):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != 1):
+            raise TypeError("kg_eval_record2: one-element int64 iteration / count / best_iter expected")
+    if best_val.dtype != torch.float32 or best_val.numel() != 1 or flag.dtype != torch.int32 or flag.numel() != 1:
+        raise TypeError("kg_eval_record2: one-element fp32 best_val and int32 flag expected")
+    if ring_val.dtype != torch.float32 or ring_iter.dtype != torch.int64 or not ring_val.is_contiguous() or \
+            not ring_iter.is_contiguous():
+        raise TypeError("kg_eval_record2: contiguous ring_val fp32 and ring_iter int64 expected")
+    n = len(scores)
+    ring_len = ring_val.shape[0] if ring_val.dim() == 2 else 0
+    if ring_val.dim() != 2 or ring_iter.dim() != 2 or (ring_len and (ring_val.shape[1] != n or tuple(ring_iter.shape) != (ring_len, 2))):
+        raise ValueError("kg_eval_record2: ring_val (len, nscores) and ring_iter (len, 2) expected")
+    a = _EvalRecord2Args()
+    for i, t in enumerate(scores[:EVAL2_MAX_SCORES]):
+        a.scores[i] = t.data_ptr()
+    a.nscores, a.select, a.ring_len, a.maximise = n, int(select), ring_len, 1 if maximise else 0
+    a.iter, a.count = _ptr(iteration), count.data_ptr()
+    a.ring_val, a.ring_iter = ring_val.data_ptr(), ring_iter.data_ptr()
+    a.best_val, a.best_iter, a.flag = best_val.data_ptr(), best_iter.data_ptr(), flag.data_ptr()
+    _check(load_library().kg_eval_record2(C.byref(a), _stream()), "kg_eval_record2")
 
 
 def copy_if(flag: torch.Tensor, jobs: Sequence[Tuple[torch.Tensor, torch.Tensor]]) -> None:

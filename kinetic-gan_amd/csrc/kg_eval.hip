@@ -1,6 +1,7 @@
 // Scoring the generator during training (include/kgan_hip.h; evaluate.Evaluator):
 //   kg_eval_record : ONE thread compares the deciding score of an evaluation with the best so far, appends the evaluation
 //                    to the device record and leaves the decision in `flag`
+//   kg_eval_record2: the same kernel with room for KG_EVAL2_MAX_SCORES scores and a sense (larger or smaller is better)
 //   kg_copy_if     : a grid that only READS that decision and, when it is set, copies a table of word runs - the snapshot
 //                    of the best-scoring weights, taken by the device with no host synchronisation
 // Two launches on purpose: one writer of the decision, then readers of it, with a launch boundary in between - there is no
@@ -10,9 +11,10 @@
 
 namespace {
 
+template <int MAXS>
 struct EvalRecDev {
-    const float* scores[KG_EVAL_MAX_SCORES];
-    int nscores, select;
+    const float* scores[MAXS];
+    int nscores, select, maximise;
     const long long* iter;
     long long* count;
     float* ring_val;
@@ -23,7 +25,8 @@ struct EvalRecDev {
     int* flag;
 };
 
-__global__ __launch_bounds__(64) void kg_eval_record_kernel(const EvalRecDev a) {
+template <int MAXS>
+__global__ __launch_bounds__(64) void kg_eval_record_kernel(const EvalRecDev<MAXS> a) {
     if (threadIdx.x != 0) return;
     const long long n = *a.count;
     const long long it = a.iter != nullptr ? *a.iter : -1ll;
@@ -35,7 +38,8 @@ __global__ __launch_bounds__(64) void kg_eval_record_kernel(const EvalRecDev a) 
         a.ring_val[k * a.nscores + i] = v;
         if (i == a.select) s = v;
     }
-    const bool improved = s < *a.best_val;          // strict: a NaN never wins, an equal score keeps the earlier snapshot
+    const float b = *a.best_val;                    // strict: a NaN never wins, an equal score keeps the earlier snapshot
+    const bool improved = a.maximise ? s > b : s < b;
     a.ring_iter[2 * k] = it;
     a.ring_iter[2 * k + 1] = improved ? 1ll : 0ll;
     *a.flag = improved ? 1 : 0;
@@ -83,7 +87,7 @@ extern "C" int kg_eval_record(const KgEvalRecordArgs* a, void* stream) {
                KG_EVAL_MAX_SCORES);
     KG_REQUIRE(a->select >= 0 && a->select < a->nscores, "kg_eval_record: select=%d outside [0, nscores=%d)", a->select, a->nscores);
     KG_REQUIRE(a->ring_len >= 1, "kg_eval_record: ring_len=%lld < 1", (long long)a->ring_len);
-    EvalRecDev d = {};
+    EvalRecDev<KG_EVAL_MAX_SCORES> d = {};
     for (int i = 0; i < a->nscores; ++i) {
         KG_REQUIRE(a->scores[i] != nullptr, "kg_eval_record: null score %d", i);
         d.scores[i] = a->scores[i];
@@ -102,8 +106,38 @@ extern "C" int kg_eval_record(const KgEvalRecordArgs* a, void* stream) {
     d.best_val = a->best_val;
     d.best_iter = (long long*)a->best_iter;
     d.flag = a->flag;
-    hipLaunchKernelGGL(kg_eval_record_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d);
+    hipLaunchKernelGGL(kg_eval_record_kernel<KG_EVAL_MAX_SCORES>, dim3(1), dim3(64), 0, (hipStream_t)stream, d);
     return kg_launch_status("kg_eval_record");
+}
+
+extern "C" int kg_eval_record2(const KgEvalRecord2Args* a, void* stream) {
+    KG_REQUIRE(a != nullptr, "kg_eval_record2: null arguments");
+    KG_REQUIRE(a->nscores >= 1 && a->nscores <= KG_EVAL2_MAX_SCORES, "kg_eval_record2: nscores=%d outside [1, %d]", a->nscores,
+               KG_EVAL2_MAX_SCORES);
+    KG_REQUIRE(a->select >= 0 && a->select < a->nscores, "kg_eval_record2: select=%d outside [0, nscores=%d)", a->select, a->nscores);
+    KG_REQUIRE(a->ring_len >= 1, "kg_eval_record2: ring_len=%lld < 1", (long long)a->ring_len);
+    EvalRecDev<KG_EVAL2_MAX_SCORES> d = {};
+    for (int i = 0; i < a->nscores; ++i) {
+        KG_REQUIRE(a->scores[i] != nullptr, "kg_eval_record2: null score %d", i);
+        d.scores[i] = a->scores[i];
+    }
+    KG_REQUIRE(a->count != nullptr && a->ring_val != nullptr && a->ring_iter != nullptr,
+               "kg_eval_record2: null count / ring_val / ring_iter");
+    KG_REQUIRE(a->best_val != nullptr && a->best_iter != nullptr && a->flag != nullptr,
+               "kg_eval_record2: null best_val / best_iter / flag");
+    d.nscores = a->nscores;
+    d.select = a->select;
+    d.maximise = a->maximise != 0 ? 1 : 0;
+    d.iter = (const long long*)a->iter;
+    d.count = (long long*)a->count;
+    d.ring_val = a->ring_val;
+    d.ring_iter = (long long*)a->ring_iter;
+    d.ring_len = (long)a->ring_len;
+    d.best_val = a->best_val;
+    d.best_iter = (long long*)a->best_iter;
+    d.flag = a->flag;
+    hipLaunchKernelGGL(kg_eval_record_kernel<KG_EVAL2_MAX_SCORES>, dim3(1), dim3(64), 0, (hipStream_t)stream, d);
+    return kg_launch_status("kg_eval_record2");
 }
 
 extern "C" int kg_copy_if(const int32_t* flag, const KgCopyJob* jobs, int32_t njobs, void* stream) {

@@ -16,6 +16,13 @@
 // kg_prdc_finish_kernel: one workgroup; per class the four counts, the four quotients (evaluated in double, rounded once)
 // and the class means (fp64 sum in class order, rounded once); copies hits / flags to the caller's arrays.
 // No n x n or n x m matrix is written; no scratch; no dynamically indexed private array.
+//
+// Several fake sets against one real set (kg_prdc_sets) are the SAME three kernels: a fake set g is one more
+// leading index - its base pointer from a table of KG_PRDC_MAX_SETS, its radii / hit / flag words at (g * classes + c) - and
+// the real radii are an input, so the radii launch has row-tile workgroups for fake rows only (they also clear the flag
+// words of their (set, class), which the real rows clear in kg_prdc).  kg_prdc is the case of one set with the real rows in
+// the radii launch; kg_prdc_radii is the radii launch of one set alone.  The tile body is shared: no bit depends on the
+// grouping.
 #include <float.h>
 #include <math.h>
 
@@ -36,14 +43,15 @@ struct PrdcSet {
 };
 
 struct PrdcDev {
-    PrdcSet set[2];             // 0 = real, 1 = fake
+    PrdcSet set[2];             // 0 = real, 1 = fake (its p: fake set 0)
+    const float* fp[KG_PRDC_MAX_SETS];  // base pointers of the fake sets (strides and m shared: set[1])
     FastDiv inner;              // dimension d = o * d_inner + e
-    int D, classes, k;
-    float* rho[2];              // ws: (classes, n), (classes, m)
+    int D, classes, k, nsets;
+    float* rho[2];              // (classes, n), (nsets, classes, m): ws, or the caller's real radii (an input of kg_prdc_sets)
     float* rho_out[2];          // the caller's radii arrays or null
-    int* flags;                 // ws: (classes, n)  bit 0 = exists j Q_ij, bit 1 = exists j P_ij
-    int* hits;                  // ws: (classes, m)  sum_i P_ij
-    int nrt[2];                 // radii launch: row tiles of each set
+    int* flags;                 // ws: (nsets, classes, n)  bit 0 = exists j Q_ij, bit 1 = exists j P_ij; null: kg_prdc_radii
+    int* hits;                  // ws: (nsets, classes, m)  sum_i P_ij; null: kg_prdc_radii
+    int nrt[2];                 // radii launch: row tiles of the real set (0: it takes no part) and of EACH fake set
     int nti, ntj;               // cross launch: tiles along i and j
 };
 
@@ -51,7 +59,7 @@ struct PrdcFin {
     const int* flags;  const int* hits;
     int32_t* hits_out;  uint8_t* flags_out;
     int32_t* counts;  float* values;  float* mean;
-    int n, m, classes, k;
+    int n, m, classes, k, nsets;
 };
 
 // Stage PR_KC dimensions of TI points (points p0.. of base) into s[k][p]; zeros outside the set / dimension.
@@ -129,17 +137,32 @@ __global__ __launch_bounds__(PR_NT) void kg_prdc_radii_kernel(PrdcDev a) {
     __shared__ float cand[TI][CW];
     __shared__ float best[TI][KG_PRDC_MAX_K];
 
-    const unsigned per = (unsigned)(a.nrt[0] + a.nrt[1]);
+    // per class: the row tiles of the real set (if it takes part), then those of fake set 0, 1, ..
+    const unsigned per = (unsigned)a.nrt[0] + (unsigned)a.nsets * (unsigned)a.nrt[1];
     const unsigned cls = blockIdx.x / per, t = blockIdx.x % per;
     const int set = t >= (unsigned)a.nrt[0] ? 1 : 0;
-    const int i0 = (int)(t - (set ? (unsigned)a.nrt[0] : 0u)) * TI;
-    const PrdcSet X = a.set[set];
+    const unsigned u = t - (set ? (unsigned)a.nrt[0] : 0u);
+    const unsigned g = set ? u / (unsigned)a.nrt[1] : 0u;          // the fake set
+    const unsigned rt = set ? u % (unsigned)a.nrt[1] : u;          // its row tile
+    const int i0 = (int)rt * TI;
+    PrdcSet X = a.set[set];
+    if (set) X.p = a.fp[g];
     const int n = X.n, k = a.k;
     const float* xb = X.p + (long)cls * X.sc;
+    const long row0 = ((long)g * a.classes + cls) * n;             // of this (set, class) in rho / hits (real: g = 0)
     const int tid = threadIdx.x, ri = tid >> 4, rj = tid & 15;
 
-    // the words the cross launch accumulates into: real rows own the flags, fake rows the hit counts
-    if (tid < TI && i0 + tid < n) (set ? a.hits : a.flags)[(long)cls * n + i0 + tid] = 0;
+    // the words the cross launch accumulates into: real rows own the flags, fake rows the hit counts; without real rows
+    // in the launch the workgroups of a fake (set, class) share out its flag words
+    {
+        int* own = set ? a.hits : a.flags;
+        if (own != nullptr && tid < TI && i0 + tid < n) own[row0 + i0 + tid] = 0;
+        if (set && a.nrt[0] == 0 && a.flags != nullptr) {
+            const int nr = a.set[0].n;
+            int* fl = a.flags + ((long)g * a.classes + cls) * nr;
+            for (int i = (int)rt * PR_NT + tid; i < nr; i += a.nrt[1] * PR_NT) fl[i] = 0;
+        }
+    }
     for (int e = tid; e < TI * KG_PRDC_MAX_K; e += PR_NT) cand[e / KG_PRDC_MAX_K][e % KG_PRDC_MAX_K] = INFINITY;
 
     const bool live = i0 + (tid >> 6) * 4 * MI < n;
@@ -179,8 +202,8 @@ __global__ __launch_bounds__(PR_NT) void kg_prdc_radii_kernel(PrdcDev a) {
     }
     if (tid < TI && i0 + tid < n) {
         const float rho = cand[tid][k - 1];
-        a.rho[set][(long)cls * n + i0 + tid] = rho;
-        if (a.rho_out[set] != nullptr) a.rho_out[set][(long)cls * n + i0 + tid] = rho;
+        a.rho[set][row0 + i0 + tid] = rho;
+        if (a.rho_out[set] != nullptr) a.rho_out[set][row0 + i0 + tid] = rho;
     }
 }
 
@@ -193,9 +216,12 @@ __global__ __launch_bounds__(PR_NT) void kg_prdc_cross_kernel(PrdcDev a) {
     __shared__ int scol[PR_NT / 64][TI];
 
     const unsigned ntiles = (unsigned)a.nti * (unsigned)a.ntj;
-    const unsigned cls = blockIdx.x / ntiles, tile = blockIdx.x % ntiles;
+    const unsigned gc = blockIdx.x / ntiles, tile = blockIdx.x % ntiles;      // gc = set * classes + class
+    const unsigned g = gc / (unsigned)a.classes, cls = gc % (unsigned)a.classes;
     const int i0 = (int)(tile / (unsigned)a.ntj) * TI, j0 = (int)(tile % (unsigned)a.ntj) * TI;
-    const PrdcSet R = a.set[0], F = a.set[1];
+    const PrdcSet R = a.set[0];
+    PrdcSet F = a.set[1];
+    F.p = a.fp[g];
     const int n = R.n, m = F.n;
     const int tid = threadIdx.x, ri = tid >> 4, rj = tid & 15, wave = tid >> 6;
     const bool live = i0 + wave * 4 * MI < n;
@@ -208,7 +234,7 @@ __global__ __launch_bounds__(PR_NT) void kg_prdc_cross_kernel(PrdcDev a) {
     for (int r = 0; r < MI; ++r) {
         const int i = i0 + ri * MI + r, j = j0 + rj * MI + r;
         rr[r] = i < n ? a.rho[0][(long)cls * n + i] : 0.f;
-        rf[r] = j < m ? a.rho[1][(long)cls * m + j] : 0.f;
+        rf[r] = j < m ? a.rho[1][(long)gc * m + j] : 0.f;
     }
     int rowbits[MI], colcnt[MI];
 #pragma unroll
@@ -236,11 +262,11 @@ __global__ __launch_bounds__(PR_NT) void kg_prdc_cross_kernel(PrdcDev a) {
     __syncthreads();
     if (tid < TI) {
         const int i = i0 + tid, v = srow[tid];
-        if (i < n && v != 0) atomicOr(&a.flags[(long)cls * n + i], v);
+        if (i < n && v != 0) atomicOr(&a.flags[(long)gc * n + i], v);
     } else if (tid < 2 * TI) {
         const int c = tid - TI, j = j0 + c;
         const int v = (scol[0][c] + scol[1][c]) + (scol[2][c] + scol[3][c]);
-        if (j < m && v != 0) atomicAdd(&a.hits[(long)cls * m + j], v);
+        if (j < m && v != 0) atomicAdd(&a.hits[(long)gc * m + j], v);
     }
 }
 
@@ -253,7 +279,7 @@ __device__ __forceinline__ int prdc_wave_sum(int v) {
 __global__ __launch_bounds__(PR_FIN) void kg_prdc_finish_kernel(PrdcFin a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int NW = PR_FIN / 64;
-    for (int c = wave; c < a.classes; c += NW) {
+    for (int c = wave; c < a.nsets * a.classes; c += NW) {       // c = set * classes + class
         int cP = 0, cR = 0, cD = 0, cC = 0;
         for (int j = lane; j < a.m; j += 64) {
             const int h = a.hits[(long)c * a.m + j];
@@ -278,9 +304,10 @@ __global__ __launch_bounds__(PR_FIN) void kg_prdc_finish_kernel(PrdcFin a) {
     }
     if (a.mean == nullptr) return;
     __syncthreads();
-    if (tid < 4) {
+    if (tid < 4 * a.nsets) {
+        const int g = tid >> 2, q = tid & 3;
         double s = 0.0;
-        for (int c = 0; c < a.classes; ++c) s += (double)a.values[c * 4 + tid];
+        for (int c = 0; c < a.classes; ++c) s += (double)a.values[((long)g * a.classes + c) * 4 + q];
         a.mean[tid] = (float)(s / a.classes);
     }
 }
@@ -360,7 +387,8 @@ extern "C" int kg_prdc(const KgPrdcArgs* a, void* stream) {
     const PrdcPlan p = prdc_plan(a);
     const long cn = (long)a->classes * a->n, cm = (long)a->classes * a->m;
 
-    PrdcDev d;
+    PrdcDev d = {};
+    d.nsets = 1;  d.fp[0] = a->fake;
     d.set[0].p = a->real;  d.set[0].sc = a->r_sc;  d.set[0].sp = a->r_sp;  d.set[0].so = a->r_so;  d.set[0].n = a->n;
     d.set[1].p = a->fake;  d.set[1].sc = a->f_sc;  d.set[1].sp = a->f_sp;  d.set[1].so = a->f_so;  d.set[1].n = a->m;
     d.inner = FastDiv::make((unsigned)a->d_inner);
@@ -384,7 +412,133 @@ extern "C" int kg_prdc(const KgPrdcArgs* a, void* stream) {
     fin.flags = d.flags;  fin.hits = d.hits;
     fin.hits_out = a->fake_hits;  fin.flags_out = a->real_flags;
     fin.counts = a->counts;  fin.values = a->values;  fin.mean = a->mean;
-    fin.n = a->n;  fin.m = a->m;  fin.classes = a->classes;  fin.k = a->k;
+    fin.n = a->n;  fin.m = a->m;  fin.classes = a->classes;  fin.k = a->k;  fin.nsets = 1;
     hipLaunchKernelGGL(kg_prdc_finish_kernel, dim3(1), dim3(PR_FIN), 0, s, fin);
     return kg_launch_status("kg_prdc_finish");
+}
+
+// ---- one set's radii alone; several fake sets against one real set with given radii ------------------------
+
+namespace {
+
+// The rule of prdc_plan with the workgroups these launches really have: row tiles of ONE set (kg_prdc_radii), of the
+// nsets fake sets (kg_prdc_sets, radii), tiles of nsets x classes x (n x m) (kg_prdc_sets, cross).
+int prdc_edge(long groups64) { return groups64 >= 512 ? 64 : 32; }
+
+PrdcPlan prdc_sets_plan(const KgPrdcSetsArgs* a) {
+    PrdcPlan p;
+    const long gc = (long)a->nsets * a->classes;
+    p.ti_radii = prdc_edge(gc * kg_cdiv(a->m, 64));
+    p.grid_radii = gc * kg_cdiv(a->m, p.ti_radii);
+    p.ti_cross = prdc_edge(gc * kg_cdiv(a->n, 64) * kg_cdiv(a->m, 64));
+    p.grid_cross = gc * kg_cdiv(a->n, p.ti_cross) * kg_cdiv(a->m, p.ti_cross);
+    return p;
+}
+
+int prdc_sets_validate(const KgPrdcSetsArgs* a, const char* who) {
+    KG_REQUIRE(a != nullptr, "%s: null args", who);
+    KG_REQUIRE(a->nsets >= 1 && a->nsets <= KG_PRDC_MAX_SETS, "%s: nsets=%d outside [1, %d]", who, a->nsets, KG_PRDC_MAX_SETS);
+    KG_REQUIRE(a->n >= 1, "%s: n=%d < 1", who, a->n);
+    KG_REQUIRE(a->m >= 1, "%s: m=%d < 1", who, a->m);
+    KG_REQUIRE(a->classes >= 1, "%s: classes=%d < 1", who, a->classes);
+    KG_REQUIRE(a->d_outer >= 1, "%s: d_outer=%d < 1", who, a->d_outer);
+    KG_REQUIRE(a->d_inner >= 1, "%s: d_inner=%d < 1", who, a->d_inner);
+    KG_REQUIRE((long)a->d_outer * a->d_inner <= 0x7fffffffL, "%s: d_outer=%d x d_inner=%d does not fit 31 bits", who, a->d_outer,
+               a->d_inner);
+    KG_REQUIRE(a->k >= 1 && a->k <= KG_PRDC_MAX_K, "%s: k=%d outside [1, %d]", who, a->k, KG_PRDC_MAX_K);
+    KG_REQUIRE(a->n <= KG_PRDC_MAX_POINTS, "%s: n=%d above the cap of %d points per class", who, a->n, KG_PRDC_MAX_POINTS);
+    KG_REQUIRE(a->m <= KG_PRDC_MAX_POINTS, "%s: m=%d above the cap of %d points per class", who, a->m, KG_PRDC_MAX_POINTS);
+    KG_REQUIRE(a->k <= (a->n < a->m ? a->n : a->m) - 1, "%s: k=%d > min(n=%d, m=%d) - 1 neighbours", who, a->k, a->n, a->m);
+    const PrdcPlan p = prdc_sets_plan(a);
+    KG_REQUIRE(p.grid_radii < PR_MAX_GRID && p.grid_cross < PR_MAX_GRID,
+               "%s: nsets=%d x classes=%d x tiles of n=%d x m=%d make %ld workgroups, one launch takes fewer than %ld", who, a->nsets,
+               a->classes, a->n, a->m, p.grid_cross > p.grid_radii ? p.grid_cross : p.grid_radii, PR_MAX_GRID);
+    return 0;
+}
+
+int64_t prdc_sets_ws_bytes(const KgPrdcSetsArgs* a) {
+    return 4 * (int64_t)a->nsets * a->classes * (2 * (int64_t)a->m + a->n);
+}
+
+}  // namespace
+
+extern "C" int kg_prdc_radii(const KgPrdcRadiiArgs* a, void* stream) {
+    const char* who = "kg_prdc_radii";
+    KG_REQUIRE(a != nullptr, "%s: null args", who);
+    KG_REQUIRE(a->n >= 1, "%s: n=%d < 1", who, a->n);
+    KG_REQUIRE(a->classes >= 1, "%s: classes=%d < 1", who, a->classes);
+    KG_REQUIRE(a->d_outer >= 1, "%s: d_outer=%d < 1", who, a->d_outer);
+    KG_REQUIRE(a->d_inner >= 1, "%s: d_inner=%d < 1", who, a->d_inner);
+    KG_REQUIRE((long)a->d_outer * a->d_inner <= 0x7fffffffL, "%s: d_outer=%d x d_inner=%d does not fit 31 bits", who, a->d_outer,
+               a->d_inner);
+    KG_REQUIRE(a->k >= 1 && a->k <= KG_PRDC_MAX_K, "%s: k=%d outside [1, %d]", who, a->k, KG_PRDC_MAX_K);
+    KG_REQUIRE(a->n <= KG_PRDC_MAX_POINTS, "%s: n=%d above the cap of %d points per class", who, a->n, KG_PRDC_MAX_POINTS);
+    KG_REQUIRE(a->k <= a->n - 1, "%s: k=%d > n=%d - 1 neighbours", who, a->k, a->n);
+    const int ti = prdc_edge((long)a->classes * kg_cdiv(a->n, 64));
+    const long grid = (long)a->classes * kg_cdiv(a->n, ti);
+    KG_REQUIRE(grid < PR_MAX_GRID, "%s: classes=%d x row tiles of n=%d make %ld workgroups, one launch takes fewer than %ld", who,
+               a->classes, a->n, grid, PR_MAX_GRID);
+    KG_REQUIRE(a->x != nullptr, "%s: null pointer x", who);
+    KG_REQUIRE(a->radii != nullptr, "%s: null pointer radii", who);
+
+    PrdcDev d = {};             // the set takes the real side's place; no fake rows, no flag / hit words
+    d.set[0].p = a->x;  d.set[0].sc = a->sc;  d.set[0].sp = a->sp;  d.set[0].so = a->so;  d.set[0].n = a->n;
+    d.inner = FastDiv::make((unsigned)a->d_inner);
+    d.D = a->d_outer * a->d_inner;  d.classes = a->classes;  d.k = a->k;  d.nsets = 1;
+    d.rho[0] = a->radii;
+    d.nrt[0] = kg_cdiv(a->n, ti);  d.nrt[1] = 0;
+    if (ti == 32) prdc_launch_radii<32, 2>(d, grid, (hipStream_t)stream);
+    else prdc_launch_radii<64, 4>(d, grid, (hipStream_t)stream);
+    return kg_launch_status("kg_prdc_radii");
+}
+
+extern "C" int64_t kg_prdc_sets_workspace_bytes(const KgPrdcSetsArgs* a) {
+    if (int rc = prdc_sets_validate(a, "kg_prdc_sets_workspace_bytes")) return rc;
+    return prdc_sets_ws_bytes(a);
+}
+
+extern "C" int kg_prdc_sets(const KgPrdcSetsArgs* a, void* stream) {
+    if (int rc = prdc_sets_validate(a, "kg_prdc_sets")) return rc;
+    KG_REQUIRE(a->real != nullptr, "kg_prdc_sets: null pointer real");
+    for (int g = 0; g < a->nsets; ++g) KG_REQUIRE(a->fake[g] != nullptr, "kg_prdc_sets: null pointer fake[%d]", g);
+    KG_REQUIRE(a->radii_real != nullptr, "kg_prdc_sets: null pointer radii_real");
+    KG_REQUIRE(a->counts != nullptr, "kg_prdc_sets: null pointer counts");
+    KG_REQUIRE(a->values != nullptr, "kg_prdc_sets: null pointer values");
+    KG_REQUIRE(a->ws != nullptr, "kg_prdc_sets: null pointer ws");
+    const int64_t need = prdc_sets_ws_bytes(a);
+    KG_REQUIRE(a->ws_bytes >= need, "kg_prdc_sets: ws_bytes=%lld < %lld (kg_prdc_sets_workspace_bytes)", (long long)a->ws_bytes,
+               (long long)need);
+    const PrdcPlan p = prdc_sets_plan(a);
+    const long gcm = (long)a->nsets * a->classes * a->m;
+
+    PrdcDev d = {};
+    d.set[0].p = a->real;  d.set[0].sc = a->r_sc;  d.set[0].sp = a->r_sp;  d.set[0].so = a->r_so;  d.set[0].n = a->n;
+    d.set[1].p = a->fake[0];  d.set[1].sc = a->f_sc;  d.set[1].sp = a->f_sp;  d.set[1].so = a->f_so;  d.set[1].n = a->m;
+    d.nsets = a->nsets;
+    for (int g = 0; g < a->nsets; ++g) d.fp[g] = a->fake[g];
+    d.inner = FastDiv::make((unsigned)a->d_inner);
+    d.D = a->d_outer * a->d_inner;  d.classes = a->classes;  d.k = a->k;
+    float* wf = (float*)a->ws;  // fake radii (nsets, classes, m) | hit words (nsets, classes, m) | flag words (nsets, classes, n)
+    d.rho[0] = const_cast<float*>(a->radii_real);   // read only: no real row takes part in the radii launch
+    d.rho[1] = wf;
+    d.hits = (int*)(wf + gcm);  d.flags = d.hits + gcm;
+    d.rho_out[0] = nullptr;  d.rho_out[1] = a->radii_fake;
+    d.nrt[0] = 0;  d.nrt[1] = kg_cdiv(a->m, p.ti_radii);
+    d.nti = kg_cdiv(a->n, p.ti_cross);  d.ntj = kg_cdiv(a->m, p.ti_cross);
+    hipStream_t s = (hipStream_t)stream;
+
+    if (p.ti_radii == 32) prdc_launch_radii<32, 2>(d, p.grid_radii, s);
+    else prdc_launch_radii<64, 4>(d, p.grid_radii, s);
+    if (int rc = kg_launch_status("kg_prdc_sets_radii")) return rc;
+    if (p.ti_cross == 32) prdc_launch_cross<32, 2>(d, p.grid_cross, s);
+    else prdc_launch_cross<64, 4>(d, p.grid_cross, s);
+    if (int rc = kg_launch_status("kg_prdc_sets_cross")) return rc;
+
+    PrdcFin fin;
+    fin.flags = d.flags;  fin.hits = d.hits;
+    fin.hits_out = a->fake_hits;  fin.flags_out = a->real_flags;
+    fin.counts = a->counts;  fin.values = a->values;  fin.mean = a->mean;
+    fin.n = a->n;  fin.m = a->m;  fin.classes = a->classes;  fin.k = a->k;  fin.nsets = a->nsets;
+    hipLaunchKernelGGL(kg_prdc_finish_kernel, dim3(1), dim3(PR_FIN), 0, s, fin);
+    return kg_launch_status("kg_prdc_sets_finish");
 }

@@ -16,6 +16,14 @@ hipGraph on a single stream - that
   5. kg_copy_if: when it is, copies the selected generator - its flat parameters and every module buffer (BatchNorm
      running statistics and batch counters) - into a snapshot.
 
+With ``prdc_per_class > 0`` the same launch sequence also scores fidelity AND diversity: a second
+Sampler round of ``prdc_per_class`` samples per class from every generator - a round of its own, so that the MMD rounds
+and with them the MMD columns stay bit for bit what they are without it -, read in place through strides by ONE
+kg_prdc_sets call (three launches for all generators) against ``prdc_per_class`` real samples per class whose
+k-th-neighbour radii were computed once, at construction (kg_prdc_radii).  The record then holds, after the MMD scores,
+``"<g>/precision"``, ``"<g>/recall"``, ``"<g>/density"``, ``"<g>/coverage"`` per generator and goes through
+kg_eval_record2, which knows the sense of the deciding score: the four new names are better when larger.
+
 Nothing synchronises the host; everything is read through pointers when the launches run, so the captured evaluation
 follows the training replays in between.  ``records()``, ``best()`` and ``state_dict()`` read the device; the Evaluator
 never writes to a generator.  Definitions the tests pin this against: tests/eval_def.py.
@@ -55,6 +63,33 @@ def default_select(names: Sequence[str], modes: Sequence[str]) -> str:
     return "%s/%s" % (gen, mode)
 
 
+def score_sense(name: str) -> str:
+    """``"max"`` for precision / recall / density / coverage (larger is better), ``"min"`` for the MMD modes"""
+    return "max" if str(name).rsplit("/", 1)[-1] in metrics.PRDC_NAMES else "min"
+
+
+def score_names(generators: Sequence[str], modes: Sequence[str], prdc: bool = False) -> list:
+    """The record's columns: ``"<g>/<mode>"`` generator by generator, then - with precision / recall / density / coverage
+    on - ``"<g>/<name>"`` generator by generator in the order of ``metrics.PRDC_NAMES``"""
+    names = ["%s/%s" % (g, m) for g in generators for m in modes]
+    if prdc:
+        names += ["%s/%s" % (g, q) for g in generators for q in metrics.PRDC_NAMES]
+    return names
+
+
+def class_rows(labels, n_classes: int, per_class: int) -> np.ndarray:
+    """(n_classes * per_class,) indices, class by class: the first ``per_class`` samples (in index order) of class 0, then of
+    class 1, ...  ValueError when a class has fewer."""
+    lab = np.asarray(labels).astype(np.int64).reshape(-1)
+    rows = []
+    for c in range(n_classes):
+        idx = np.flatnonzero(lab == c)
+        if idx.size < per_class:
+            raise ValueError("class_rows: class %d has %d samples, %d needed" % (c, idx.size, per_class))
+        rows.append(idx[:per_class])
+    return np.concatenate(rows)
+
+
 def write_metrics_csv(path: str, records: dict) -> None:
     """``metrics.csv``: a header, then one row per evaluation - iteration, every score (``repr`` of the fp32 value: it
     reads back bit for bit), improved (0 / 1)."""
@@ -82,27 +117,42 @@ class Evaluator:
     with ``per_class=pairs``, cropped to the generator's ``t_size``), or ``real`` (N, C, T, V) with class ids
     ``real_labels`` (N,) - the first ``pairs`` samples of every class in index order.  Score names are
     ``"<generator>/<mode>"``; ``select`` names the one that decides (default: ``default_select``).  ``iteration``: a
-    one-element int64 device tensor read when an evaluation runs (``TrainLoop.step_dev``), None records -1."""
+    one-element int64 device tensor read when an evaluation runs (``TrainLoop.step_dev``), None records -1.
+    ``prdc_per_class`` (0: off): also score precision / recall / density / coverage with ``prdc_k`` neighbours on that many
+    fake and real samples per class (``"<generator>/precision"`` ...; ``select`` may name one of them: larger is better)."""
 
     def __init__(self, generators: Dict[str, torch.nn.Module], real, real_labels=None, pairs: int = 10,
                  modes: Sequence[str] = ("avg", "joint"), select: Optional[str] = None, seed: int = 0,
                  trunc: Optional[float] = None, trunc_mode: str = "-", iteration: Optional[torch.Tensor] = None,
-                 ring_len: int = 1024, use_graph: bool = True, t_size: Optional[int] = None):
+                 ring_len: int = 1024, use_graph: bool = True, t_size: Optional[int] = None, prdc_per_class: int = 0,
+                 prdc_k: int = 5):
         if not generators:
             raise ValueError("Evaluator: at least one generator")
+        self.prdc_per_class, self.prdc_k = int(prdc_per_class), int(prdc_k)
+        if self.prdc_per_class < 0:
+            raise ValueError("Evaluator: prdc_per_class=%d < 0" % self.prdc_per_class)
+        if self.prdc_per_class and not 1 <= self.prdc_k <= min(nv.PRDC_MAX_K, self.prdc_per_class - 1):
+            raise ValueError("Evaluator: prdc_k=%d outside [1, min(%d, prdc_per_class=%d - 1)]" % (
+                self.prdc_k, nv.PRDC_MAX_K, self.prdc_per_class))
+        if self.prdc_per_class > nv.PRDC_MAX_POINTS:
+            raise ValueError("Evaluator: prdc_per_class=%d above the cap of %d points per class" % (
+                self.prdc_per_class, nv.PRDC_MAX_POINTS))
         self.modes = tuple(modes)
         for m in self.modes:
             metrics._check_mode(m)
         if not self.modes:
             raise ValueError("Evaluator: at least one mode")
         self.gens = dict(generators)
-        self.names = ["%s/%s" % (g, m) for g in self.gens for m in self.modes]
-        if len(self.names) > nv.EVAL_MAX_SCORES:
-            raise ValueError("Evaluator: %d scores, at most %d fit one record" % (len(self.names), nv.EVAL_MAX_SCORES))
+        self.names = score_names(list(self.gens), self.modes, bool(self.prdc_per_class))
+        most = nv.EVAL2_MAX_SCORES if self.prdc_per_class else nv.EVAL_MAX_SCORES
+        if len(self.names) > most:
+            raise ValueError("Evaluator: %d scores, at most %d fit one record" % (len(self.names), most))
         self.select = default_select(list(self.gens), self.modes) if select is None else str(select)
         if self.select not in self.names:
             raise ValueError("Evaluator: select %r is none of %s" % (self.select, self.names))
         self._select = self.names.index(self.select)
+        self.maximise = score_sense(self.select) == "max"
+        self._worst = float("-inf") if self.maximise else float("inf")
         self.pairs, self.seed, self.ring_len = int(pairs), int(seed), int(ring_len)
         if self.pairs < 1 or self.ring_len < 1:
             raise ValueError("Evaluator: pairs and ring_len must be >= 1")
@@ -124,6 +174,10 @@ class Evaluator:
         else:
             data = real.detach().cpu().numpy() if isinstance(real, torch.Tensor) else np.asarray(real)
             lab = real_labels.detach().cpu().numpy() if isinstance(real_labels, torch.Tensor) else np.asarray(real_labels)
+        if self.prdc_per_class:
+            self._prdc_setup(real, real_labels, first, t_size, trunc, trunc_mode)
+        else:
+            self.prdc_samplers, self.prdc_real, self.prdc_radii = {}, None, None
         rows = pair_rows(lab, self.n_classes, self.pairs)
         self.real = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32)[rows])).to(dev)
         self._pair_labels = np.arange(self.n)                  # every (fake, real) pair is a "class" of the kg_mmd call
@@ -135,7 +189,7 @@ class Evaluator:
         self.count = torch.zeros(1, dtype=torch.int64, device=dev)
         self.ring_val = torch.full((self.ring_len, n), float("nan"), dtype=torch.float32, device=dev)
         self.ring_iter = torch.full((self.ring_len, 2), -1, dtype=torch.int64, device=dev)
-        self.best_val = torch.full((1,), float("inf"), dtype=torch.float32, device=dev)
+        self.best_val = torch.full((1,), self._worst, dtype=torch.float32, device=dev)
         self.best_iter = torch.full((1,), -1, dtype=torch.int64, device=dev)
         self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self.n_evals = 0                     # host mirror of count
@@ -160,6 +214,58 @@ class Evaluator:
         self._scores = None
         self._graph = None
 
+    # ---- precision / recall / density / coverage -----------------------------------------------------------
+    def _prdc_setup(self, real, real_labels, first, t_size, trunc, trunc_mode):
+        """the real side, once: ``prdc_per_class`` samples of every class, class by class on the device, and their radii
+        (one kg_prdc_radii launch; deterministic, so not part of the state); per generator a second Sampler whose round
+        kg_prdc_sets reads in place"""
+        dev, K, P = self.device, self.n_classes, self.prdc_per_class
+        if real_labels is None and hasattr(real, "label") and hasattr(real, "data"):
+            data, _, _ = metrics.select_reference_samples(real, np.arange(K), int(t_size) if t_size is not None else int(first.t_size),
+                                                          per_class=P)
+        else:
+            data = real.detach().cpu().numpy() if isinstance(real, torch.Tensor) else np.asarray(real)
+            lab = real_labels.detach().cpu().numpy() if isinstance(real_labels, torch.Tensor) else np.asarray(real_labels)
+            data = np.asarray(data, dtype=np.float32)[class_rows(lab, K, P)]
+        self.prdc_real = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32))).to(dev)    # (K*P, C, t, V)
+        self._prdc_D = int(np.prod(self.prdc_real.shape[1:]))
+        self._prdc_rv = nv.PrdcView(self.prdc_real, P * self._prdc_D, self._prdc_D, 0)
+        self.prdc_samplers = {k: Sampler(G, qtd=P, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False)
+                              for k, G in self.gens.items()}
+        with torch.cuda.device(dev):
+            self.prdc_radii = nv.prdc_radii(self._prdc_rv, P, 1, self._prdc_D, K, self.prdc_k)
+            sets = min(len(self.gens), nv.PRDC_MAX_SETS)
+            nbytes = nv.prdc_sets_workspace_bytes(sets, P, P, 1, self._prdc_D, K, self.prdc_k)
+            self._prdc_ws = torch.empty(max(1, nbytes // 4), dtype=torch.int32, device=dev)
+
+    def _prdc_scores(self):
+        """the PRDC rounds of all generators, then ONE kg_prdc_sets per PRDC_MAX_SETS generators: the (nsets, 4) class means,
+        whose elements are the scores"""
+        K, P = self.n_classes, self.prdc_per_class
+        outs = []
+        for s in self.prdc_samplers.values():
+            s._round()
+            out = s._out                     # (P*K, C, T, V), row j*K + c = sample j of class c; read in place
+            _, C, T, V = out.shape
+            if tuple(out.shape[1:]) != tuple(self.prdc_real.shape[1:]) or not nv.is_plane(out):
+                raise ValueError("Evaluator: generated samples %s against real samples %s" % (
+                    tuple(out.shape[1:]), tuple(self.prdc_real.shape[1:])))
+            outs.append(out)
+        o = outs[0]
+        _, C, T, V = o.shape
+        sn, sc = nv._sn_sc(o)
+        if any(nv._sn_sc(q) != (sn, sc) for q in outs):
+            raise ValueError("Evaluator: the generators' rounds differ in their strides")
+        d_outer, d_inner, so = (1, C * T * V, 0) if C == 1 else (C, T * V, sc)
+        rv = self._prdc_rv if d_outer == 1 else self._prdc_rv._replace(so=T * V)
+        scores = []
+        for q in range(0, len(outs), nv.PRDC_MAX_SETS):
+            part = outs[q:q + nv.PRDC_MAX_SETS]
+            res = nv.prdc_sets(rv, part, sn, K * sn, so, self.prdc_radii, P, P, d_outer, d_inner, K, self.prdc_k,
+                               want_mean=True, ws=self._prdc_ws)
+            scores += [res["mean"][g, i:i + 1] for g in range(len(part)) for i in range(4)]
+        return scores
+
     # ---- the launch sequence -------------------------------------------------------------------------------------------
     def _round(self):
         """what a graph holds: per generator a Sampler round, the re-layout, kg_mmd per mode; then the record, then the
@@ -173,15 +279,23 @@ class Evaluator:
                 out = self._nchw[k]
             for mode in self.modes:
                 scores.append(metrics.calculate_mmd(out, self.real, self._pair_labels, mode).reshape(1))
-        nv.eval_record(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
-                       self.best_iter, self.flag)
+        if self.prdc_per_class:
+            scores += self._prdc_scores()
+            nv.eval_record2(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
+                            self.best_iter, self.flag, maximise=self.maximise)
+        else:
+            nv.eval_record(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
+                           self.best_iter, self.flag)
         nv.copy_if(self.flag, self._jobs)
         self._scores = scores                # (under capture: the graph's own memory, kept alive with it)
 
     def _state_tensors(self):
-        ts = [s.step_dev for s in self.samplers.values()]
+        ts = [s.step_dev for s in self._all_samplers()]
         ts += [self.count, self.ring_val, self.ring_iter, self.best_val, self.best_iter, self.flag, self.snap_flat]
         return ts + list(self.snap_buffers.values())
+
+    def _all_samplers(self):
+        return list(self.samplers.values()) + list(self.prdc_samplers.values())
 
     def _capture(self):
         """Single-stream capture, no parallel branches.  The warm-up rounds in front of it are real evaluations:
@@ -207,7 +321,7 @@ class Evaluator:
             self._graph.replay()
         else:
             self._round()
-        for s in self.samplers.values():
+        for s in self._all_samplers():
             s.step_count += 1
         self.n_evals += 1
 
@@ -236,7 +350,8 @@ class Evaluator:
                 "scores": np.concatenate([h[1] for h in self._hist]), "improved": np.concatenate([h[2] for h in self._hist])}
 
     def best(self) -> dict:
-        """{"value", "iteration"} of the best evaluation so far (+inf, -1 before the first finite one).  Synchronises."""
+        """{"value", "iteration"} of the best evaluation so far (+inf - or -inf when the deciding score is better when
+        larger -, -1 before the first finite one).  Synchronises."""
         return {"value": float(self.best_val.item()), "iteration": int(self.best_iter.item())}
 
     def best_generator(self):
@@ -261,13 +376,20 @@ class Evaluator:
     def state_dict(self) -> dict:
         rec = self.records()
         s0 = next(iter(self.samplers.values()))
-        return {"seed": self.seed, "step": s0.step_count, "pairs": self.pairs, "select": self.select, "modes": list(self.modes),
-                "names": list(self.names), "count": self.n_evals, "ring_val": self.ring_val.cpu(), "ring_iter": self.ring_iter.cpu(),
-                "best_val": self.best_val.cpu(), "best_iter": self.best_iter.cpu(),
-                "snapshot": {"flat": self.snap_flat.cpu(), "buffers": {k: b.cpu() for k, b in self.snap_buffers.items()}},
-                "records": {k: rec[k] for k in ("iteration", "scores", "improved")}}
+        sd = {"seed": self.seed, "step": s0.step_count, "pairs": self.pairs, "select": self.select, "modes": list(self.modes),
+              "names": list(self.names), "count": self.n_evals, "ring_val": self.ring_val.cpu(), "ring_iter": self.ring_iter.cpu(),
+              "best_val": self.best_val.cpu(), "best_iter": self.best_iter.cpu(),
+              "snapshot": {"flat": self.snap_flat.cpu(), "buffers": {k: b.cpu() for k, b in self.snap_buffers.items()}},
+              "records": {k: rec[k] for k in ("iteration", "scores", "improved")}}
+        if self.prdc_per_class:              # (the real radii are recomputed from the data: not part of the state)
+            sd["prdc"] = {"per_class": self.prdc_per_class, "k": self.prdc_k}
+        return sd
 
     def check_compatible(self, sd: dict) -> None:
+        mine = {"per_class": self.prdc_per_class, "k": self.prdc_k} if self.prdc_per_class else None
+        theirs = sd.get("prdc")
+        if (None if theirs is None else {k: int(v) for k, v in dict(theirs).items()}) != mine:
+            raise ValueError("Evaluator.load_state_dict: prdc is %r in the state, %r here" % (theirs, mine))
         for k, mine in (("pairs", self.pairs), ("select", self.select), ("modes", list(self.modes)), ("names", list(self.names))):
             if (list(sd[k]) if isinstance(mine, list) else sd[k]) != mine:
                 raise ValueError("Evaluator.load_state_dict: %s is %r in the state, %r here" % (k, sd[k], mine))
@@ -278,7 +400,7 @@ class Evaluator:
     def load_state_dict(self, sd: dict) -> None:
         """Continues bit for bit: the same draws, the same record, the same best so far and its snapshot."""
         self.check_compatible(sd)
-        for s in self.samplers.values():
+        for s in self._all_samplers():
             s.load_state_dict({"seed": sd["seed"], "step": sd["step"]})
         if int(sd["seed"]) != self.seed:
             self.seed, self._graph = int(sd["seed"]), None      # (the seed is a launch argument)
@@ -300,14 +422,14 @@ class Evaluator:
     def reset(self) -> None:
         """A fresh record (``TrainLoop.load_state_dict`` of a state without one); the Sampler counters start again at 0."""
         warnings.warn("Evaluator: the loaded state holds no evaluation record; it starts a fresh one")
-        for s in self.samplers.values():
+        for s in self._all_samplers():
             s.load_state_dict({"seed": self.seed, "step": 0})
         self.n_evals = self._flushed = 0
         self._hist = []
         self.count.zero_()
         self.ring_val.fill_(float("nan"))
         self.ring_iter.fill_(-1)
-        self.best_val.fill_(float("inf"))
+        self.best_val.fill_(self._worst)
         self.best_iter.fill_(-1)
         self.flag.zero_()
         self.snap_flat.zero_()

@@ -14,7 +14,15 @@ the averaged generator, both modes (four scores).
      tools/time_train_loop.py's.
 
 ``--only-eval N``: N evaluation replays and nothing else (the run to put under a kernel trace).
-    python tools/time_eval.py [--rounds 3] [--log FILE]"""
+``--prdc N`` (record: profiles/eval_prdc_time.log): instead of the above, the cost of scoring precision / recall /
+density / coverage on N samples per class inside an evaluation, at the NTU shapes (60 classes) and the H36M shapes (10 classes),
+live + ema, k = 5:
+  a. the PRDC part as a graph of its own - ONE kg_prdc_sets over both generators' rounds with the real radii cached - against
+     the same part built from one kg_prdc call per generator, alternating in one process: median of ``--replays`` event-timed
+     replays, ``--reps`` repetitions, spread = max - min of the medians; "faster" only if the gap exceeds the larger spread;
+  b. the whole evaluation replay with and without PRDC, and the Sampler round of classes x N samples alone with the device
+     memory it holds (``--eval-replays`` replays each).
+    python tools/time_eval.py [--rounds 3] [--prdc 100] [--log FILE]"""
 import argparse
 import os
 import statistics
@@ -27,7 +35,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kinetic_gan_amd  # noqa: F401,E402
+from kinetic_gan_amd import _native as nv  # noqa: E402
 from kinetic_gan_amd import metrics  # noqa: E402
+from kinetic_gan_amd.evaluate import Evaluator  # noqa: E402
+from kinetic_gan_amd.generator import Generator  # noqa: E402
 from kinetic_gan_amd.sample import Sampler  # noqa: E402
 from kinetic_gan_amd.train import ResidentDataset, TrainLoop, _capture  # noqa: E402
 from time_train_loop import BATCH, CFG, SyntheticFeeder, models, time_loop  # noqa: E402
@@ -50,12 +61,91 @@ def time_replays(graph, n):
     return ts
 
 
+PRDC_SHAPES = (("NTU", dict(latent=512, channels=3, n_classes=60, t_size=64, mlp=4, v=25, dataset="ntu")),
+               ("H36M", dict(latent=512, channels=2, n_classes=10, t_size=64, mlp=4, v=16, dataset="h36m")))
+
+
+def prdc_part(args, say, dev):
+    """``--prdc N``: see the module docstring"""
+    N, K5 = args.prdc, 5
+    for name, c in PRDC_SHAPES:
+        K = c["n_classes"]
+        gens = {}
+        for g, seed in (("live", 1234), ("ema", 4321)):      # two generators of different weights (no training needed here)
+            torch.manual_seed(seed)
+            gens[g] = Generator(c["latent"], c["channels"], K, c["t_size"], c["mlp"], dataset=c["dataset"]).to(dev)
+        rng = np.random.RandomState(0)
+        real = torch.as_tensor((rng.rand(K * N, c["channels"], c["t_size"], c["v"]) * 2 - 1).astype(np.float32))
+        labels = np.tile(np.arange(K), N)
+        say("%s shapes: %d classes x %d samples per class, D = %d, live + ema, k = %d" % (
+            name, K, N, c["channels"] * c["t_size"] * c["v"], K5))
+        # b. the Sampler round of K x N samples alone, and what it holds
+        torch.cuda.synchronize()
+        m0 = torch.cuda.memory_allocated(dev)
+        smp = {g: Sampler(G, qtd=N, seed=0) for g, G in gens.items()}
+        outs = {g: s.next()[0] for g, s in smp.items()}
+        torch.cuda.synchronize()
+        m1 = torch.cuda.memory_allocated(dev)
+        t_round = statistics.median(time_replays(smp["live"]._graph, args.eval_replays))
+        say("%s Sampler round of %d samples alone: %.4f ms (median of %d replays); the two Samplers hold %.1f MB of device memory" % (
+            name, K * N, t_round, args.eval_replays, (m1 - m0) / 1e6))
+        # a. the PRDC part: one kg_prdc_sets with cached radii against one kg_prdc per generator
+        ev = {"on": Evaluator(gens, real, labels, pairs=PAIRS, seed=0, prdc_per_class=N, prdc_k=K5),
+              "off": Evaluator(gens, real, labels, pairs=PAIRS, seed=0)}
+        e = ev["on"]
+        o = outs["live"]
+        _, C, T, V = o.shape
+        sn, sc = o.stride(0), o.stride(1)
+        rv = e._prdc_rv._replace(so=T * V)
+        fv = {g: nv.PrdcView(t, sn, K * sn, sc) for g, t in outs.items()}
+        ws1 = torch.empty(nv.prdc_workspace_bytes(N, N, C, T * V, K, K5) // 4, dtype=torch.int32, device=dev)
+        graphs = {"kg_prdc_sets, cached real radii": _capture(lambda: nv.prdc_sets(
+                      rv, list(outs.values()), sn, K * sn, sc, e.prdc_radii, N, N, C, T * V, K, K5, ws=e._prdc_ws)),
+                  "kg_prdc per generator": _capture(lambda: [nv.prdc(rv, v, N, N, C, T * V, K, K5, ws=ws1) for v in fv.values()])}
+        meds = {k: [] for k in graphs}
+        for r in range(args.reps):
+            for k, g in graphs.items():
+                ts = time_replays(g, args.replays)
+                meds[k].append(statistics.median(ts))
+                say("%s PRDC part, %-34s repetition %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
+                    name, k + ",", r, meds[k][-1], args.replays, min(ts), max(ts)))
+        m = {k: statistics.median(v) for k, v in meds.items()}
+        sp = {k: max(v) - min(v) for k, v in meds.items()}
+        a, b = list(graphs)
+        gap, wide = m[b] - m[a], max(sp.values())
+        verdict = "not separated" if abs(gap) <= wide else ("kg_prdc_sets is faster" if gap > 0 else "kg_prdc_sets is slower")
+        say("%s PRDC part: %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f); gap %+.4f ms against the larger spread %.4f ms: %s" % (
+            name, a, m[a], sp[a], b, m[b], sp[b], gap, wide, verdict))
+        # b. the whole evaluation replay with and without PRDC
+        for x in ev.values():
+            x.evaluate()                     # (captures)
+        torch.cuda.synchronize()
+        em = {k: [] for k in ev}
+        for r in range(args.reps):
+            for k, x in ev.items():
+                ts = time_replays(x._graph, args.eval_replays)
+                x.n_evals += args.eval_replays + 1
+                for s in x._all_samplers():
+                    s.step_count += args.eval_replays + 1
+                em[k].append(statistics.median(ts))
+        say("%s evaluation replay (%d pairs per class, avg and joint): without PRDC %.4f ms (spread %.4f), with PRDC %.4f ms "
+            "(spread %.4f): %+.4f ms (median of %d repetitions of %d replays)" % (
+                name, PAIRS, statistics.median(em["off"]), max(em["off"]) - min(em["off"]), statistics.median(em["on"]),
+                max(em["on"]) - min(em["on"]), statistics.median(em["on"]) - statistics.median(em["off"]), args.reps, args.eval_replays))
+        rec = e.records()
+        say("%s last recorded scores: %s" % (name, ", ".join("%s %.4f" % (n, v) for n, v in zip(rec["names"], rec["scores"][-1]))))
+        del ev, e, graphs, smp, outs, fv, gens
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--replays", type=int, default=200)
     ap.add_argument("--only-eval", type=int, default=0, help="this many evaluation replays and nothing else (for a kernel trace)")
+    ap.add_argument("--prdc", type=int, default=0, help="samples per class: time the PRDC part of an evaluation instead (DESIGN.md 17)")
+    ap.add_argument("--eval-replays", type=int, default=30, help="replays of a whole evaluation / a Sampler round under --prdc")
     ap.add_argument("--log", default=None, help="also write the lines to this file")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
@@ -67,6 +157,14 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
+    if args.prdc:
+        say("device %s" % torch.cuda.get_device_name(0))
+        prdc_part(args, say, dev)
+        if args.log:
+            os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
+            with open(args.log, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     feeder = SyntheticFeeder(64 * BATCH + 17, CFG["channels"], CFG["t_size"], CFG["v"], CFG["n_classes"])
     data = ResidentDataset(feeder, CFG["t_size"], dev)
     say("device %s; NTU-60 shapes, %d samples per iteration, a generator step in every iteration, %d resident samples; "
