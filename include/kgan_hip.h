@@ -792,6 +792,51 @@ int     kg_prdc_radii(const KgPrdcRadiiArgs* a, void* stream);
 int64_t kg_prdc_sets_workspace_bytes(const KgPrdcSetsArgs* a);   /* < 0 for invalid shapes                           */
 int     kg_prdc_sets(const KgPrdcSetsArgs* a, void* stream);
 
+/* ---- Frechet distance of pose / motion / caller features in fp64 (additive, ABI v9; DESIGN.md 18, csrc/kg_frechet.hip) -----
+ * For every class c: a real set of n and a fake set of m samples of `frames` frames, a frame being d = d_outer*d_inner <= 96
+ * floats read through strides (elements):
+ *   x_(i, f)[(o, e)] = real + c*r_sc + i*r_ss + f*r_sf + o*r_so + e      (o < d_outer, e < d_inner: the inner run is contiguous)
+ * and likewise the fake set.  The points of a set:
+ *   diff = 0 (pose):    x_(i, f),                 f < frames       P = n frames
+ *   diff = 1 (motion):  x_(i, f + 1) - x_(i, f),  f < frames - 1   P = n (frames - 1)     (the difference formed in fp64: exact)
+ * An (N, d) feature matrix is frames = 1, d_outer = 1, d_inner = d.  With X in {real R, fake F}, everything in fp64:
+ *   mu_X = the mean of the points,  S_X = their unbiased covariance (divided by P - 1)
+ *   S_R = V diag(l) V^T,  l clamped at 0,  G = V diag(sqrt l)             (it is always the REAL covariance that is decomposed)
+ *   H = sym(G^T S_F G),  e = the eigenvalues of H,  T = sum_i sqrt(max(e_i, 0))          (= tr sqrt(S_R S_F))
+ *   terms[c] = (|mu_R - mu_F|^2, tr S_R, tr S_F, T),   values[c] = FD = ((terms0 + terms1) + terms2) - 2 T
+ *   mean (optional) = the mean over classes of values (fp64 sum in class order)
+ *   sweeps[c] = the Jacobi sweeps of the two eigen-problems (S_R, H), the last, rotation-free one included; at most 40
+ * Four launches (three without mean): moments of chunks of points (centred on the set's first point, fp64 FMA chains in point
+ * order), merge (chunks summed in chunk order: the chunking depends on the shape alone, so two calls give the same bits),
+ * solve (one workgroup per class, both eigen-problems in LDS by cyclic Jacobi in the round-robin ordering, which depends on d
+ * alone), mean.  No atomics, no ticket.  ws = kg_frechet_workspace_bytes(a) bytes, 8-byte aligned: chunk partials, then mu
+ * (classes, 2, d) and S (classes, 2, d, d); its contents on entry do not matter.
+ * Every pointer is read when the launches run; nothing is synchronised; capturable on one stream.
+ * Rejected (< 0, kg_last_error() names the field) before any GPU call: null real / fake / values / terms / sweeps / ws;
+ * classes, n, m, d_outer or d_inner < 1; diff not 0 or 1; d above KG_FRECHET_MAX_DIM; frames < 1 + diff; P < 2 or P > 2^24 in
+ * either set; classes that need 2^24 workgroups or more in one launch; ws misaligned or ws_bytes too small.                */
+#define KG_FRECHET_MAX_DIM 96
+typedef struct KgFrechetArgs {
+    const float* real;  int64_t r_sc, r_ss, r_sf, r_so;   /* class, sample, frame, outer-dimension strides (elements)    */
+    const float* fake;  int64_t f_sc, f_ss, f_sf, f_so;
+    int32_t n, m;                   /* real / fake samples per class (n != m allowed)                                  */
+    int32_t frames;                 /* frames per sample                                                               */
+    int32_t diff;                   /* 0: a point is a frame, 1: the difference of two consecutive frames              */
+    int32_t d_outer, d_inner;       /* d = d_outer*d_inner; element (o, e) at + o*so + e                                */
+    int32_t classes;
+    double* values;                 /* (classes): FD                                                                   */
+    double* terms;                  /* (classes, 4): |dmu|^2, tr S_R, tr S_F, T                                        */
+    double* mean;                   /* (1) or NULL                                                                     */
+    int32_t* sweeps;                /* (classes, 2)                                                                    */
+    double* mu_real;                /* (classes, d) or NULL                                                            */
+    double* mu_fake;                /* (classes, d) or NULL                                                            */
+    double* cov_real;               /* (classes, d, d) or NULL                                                         */
+    double* cov_fake;               /* (classes, d, d) or NULL                                                         */
+    void* ws;  int64_t ws_bytes;
+} KgFrechetArgs;
+int64_t kg_frechet_workspace_bytes(const KgFrechetArgs* a);   /* < 0 for invalid shapes                              */
+int     kg_frechet(const KgFrechetArgs* a, void* stream);
+
 /* ---- inputs of one training iteration (additive, ABI v9; DESIGN.md 11, csrc/kg_input.hip) ---------------------------
  * kg_step_inputs writes, in ONE launch, every input of iteration s = *step and then stores s + 1 (last workgroup).
  * Batch: b = s mod batches_per_epoch, e = s div batches_per_epoch, row r_j = perm[(e & 1)*perm_stride + (b*world +

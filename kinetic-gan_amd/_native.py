@@ -331,6 +331,18 @@ class _PrdcSetsArgs(C.Structure):
                 ("counts", C.c_void_p), ("values", c_f32p), ("mean", c_f32p),
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
+FRECHET_MAX_DIM = 96
+
+
+class _FrechetArgs(C.Structure):
+    _fields_ = [("real", c_f32p), ("r_sc", C.c_int64), ("r_ss", C.c_int64), ("r_sf", C.c_int64), ("r_so", C.c_int64),
+                ("fake", c_f32p), ("f_sc", C.c_int64), ("f_ss", C.c_int64), ("f_sf", C.c_int64), ("f_so", C.c_int64),
+                ("n", C.c_int32), ("m", C.c_int32), ("frames", C.c_int32), ("diff", C.c_int32),
+                ("d_outer", C.c_int32), ("d_inner", C.c_int32), ("classes", C.c_int32),
+                ("values", C.c_void_p), ("terms", C.c_void_p), ("mean", C.c_void_p), ("sweeps", C.c_void_p),
+                ("mu_real", C.c_void_p), ("mu_fake", C.c_void_p), ("cov_real", C.c_void_p), ("cov_fake", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
 STEP_MAX_PLANES = 8
 STREAM_Z, STREAM_ALPHA, STREAM_NOISE_D, STREAM_NOISE_G = 0, 1, 2, 3
 
@@ -481,6 +493,8 @@ EXPORTS = {
     "kg_prdc_radii": (C.c_int, [C.POINTER(_PrdcRadiiArgs), C.c_void_p]),
     "kg_prdc_sets_workspace_bytes": (C.c_int64, [C.POINTER(_PrdcSetsArgs)]),
     "kg_prdc_sets": (C.c_int, [C.POINTER(_PrdcSetsArgs), C.c_void_p]),
+    "kg_frechet_workspace_bytes": (C.c_int64, [C.POINTER(_FrechetArgs)]),
+    "kg_frechet": (C.c_int, [C.POINTER(_FrechetArgs), C.c_void_p]),
     "kg_step_inputs": (C.c_int, [C.POINTER(_StepInputsArgs), C.c_void_p]),
     "kg_loss_append": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kg_adam_step_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
@@ -2365,6 +2379,86 @@ def prdc_sets(real: PrdcView, fakes: Sequence[torch.Tensor], f_sc: int, f_sp: in
     a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
     _count("kg_prdc_sets", 3.0 * nsets * (float(m) * m + float(n) * m) * d_outer * d_inner * classes)
     _check(lib.kg_prdc_sets(C.byref(a), _stream()), "kg_prdc_sets")
+    return out
+
+
+# ---- Frechet distance of pose / motion / caller features (kg_frechet.hip) -------------------------------------------------
+
+class FrechetView(NamedTuple):
+    """How kg_frechet walks one set: element (class c, sample i, frame f, outer o, inner e) sits at
+    t.data_ptr() + (c*sc + i*ss + f*sf + o*so + e) floats."""
+    t: torch.Tensor
+    sc: int
+    ss: int
+    sf: int
+    so: int
+
+
+def _frechet_extent_ok(v: FrechetView, samples: int, frames: int, d_outer: int, d_inner: int, classes: int) -> bool:
+    """every element kg_frechet will read lies inside the tensor's storage"""
+    if min(v.sc, v.ss, v.sf, v.so) < 0:
+        return False
+    last = (classes - 1) * v.sc + (samples - 1) * v.ss + (frames - 1) * v.sf + (d_outer - 1) * v.so + d_inner - 1
+    return v.t.storage_offset() + last < v.t.untyped_storage().nbytes() // 4
+
+
+def _frechet_shape(n: int, m: int, frames: int, diff: bool, d_outer: int, d_inner: int, classes: int) -> _FrechetArgs:
+    a = _FrechetArgs()
+    a.n, a.m, a.frames, a.diff = int(n), int(m), int(frames), int(bool(diff))
+    a.d_outer, a.d_inner, a.classes = int(d_outer), int(d_inner), int(classes)
+    return a
+
+
+def frechet_workspace_bytes(n: int, m: int, frames: int, diff: bool, d_outer: int, d_inner: int, classes: int) -> int:
+    """kg_frechet_workspace_bytes of a shape (RuntimeError naming the field for a shape kg_frechet rejects); no GPU call"""
+    nbytes = load_library().kg_frechet_workspace_bytes(C.byref(_frechet_shape(n, m, frames, diff, d_outer, d_inner, classes)))
+    if nbytes < 0:
+        _check(-1, "kg_frechet_workspace_bytes")
+    return nbytes
+
+
+def frechet(real: FrechetView, fake: FrechetView, n: int, m: int, frames: int, diff: bool, d_outer: int, d_inner: int,
+            classes: int, want_mean: bool = True, moments: bool = False, ws: Optional[torch.Tensor] = None) -> dict:
+    """Enqueue kg_frechet (moments, merge, solve and mean launch) on the current stream; no host synchronisation.
+    Returns dict(values (classes,) fp64, terms (classes, 4) fp64: |dmu|^2, tr S_r, tr S_f, T, sweeps (classes, 2) int32,
+    mean () fp64 or None) on the device; with ``moments`` also mu_real, mu_fake (classes, d) and cov_real, cov_fake
+    (classes, d, d) fp64.  ``ws``: a caller's contiguous float64 workspace of at least the needed bytes (its contents do
+    not matter), else one is taken with torch.empty."""
+    lib = load_library()
+    for v in (real, fake):
+        if v.t.dtype != torch.float32:
+            raise TypeError(f"kg_frechet: fp32 only, got {v.t.dtype}")
+    nbytes = frechet_workspace_bytes(n, m, frames, diff, d_outer, d_inner, classes)
+    _need_cuda(real.t, fake.t, ws)
+    for name, v, cnt in (("real", real, n), ("fake", fake, m)):
+        if not _frechet_extent_ok(v, cnt, frames, d_outer, d_inner, classes):
+            raise ValueError(f"kg_frechet: the strides of {name} reach outside its tensor")
+    dev = real.t.device
+    if ws is None:
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    elif not ws.is_contiguous() or ws.dtype != torch.float64:
+        raise ValueError("kg_frechet: ws must be a contiguous float64 tensor")
+    d = d_outer * d_inner
+    out = dict(values=torch.empty(classes, dtype=torch.float64, device=dev),
+               terms=torch.empty((classes, 4), dtype=torch.float64, device=dev),
+               sweeps=torch.empty((classes, 2), dtype=torch.int32, device=dev),
+               mean=torch.empty((), dtype=torch.float64, device=dev) if want_mean else None)
+    if moments:
+        out.update(mu_real=torch.empty((classes, d), dtype=torch.float64, device=dev),
+                   mu_fake=torch.empty((classes, d), dtype=torch.float64, device=dev),
+                   cov_real=torch.empty((classes, d, d), dtype=torch.float64, device=dev),
+                   cov_fake=torch.empty((classes, d, d), dtype=torch.float64, device=dev))
+    a = _frechet_shape(n, m, frames, diff, d_outer, d_inner, classes)
+    a.real, a.r_sc, a.r_ss, a.r_sf, a.r_so = real.t.data_ptr(), real.sc, real.ss, real.sf, real.so
+    a.fake, a.f_sc, a.f_ss, a.f_sf, a.f_so = fake.t.data_ptr(), fake.sc, fake.ss, fake.sf, fake.so
+    a.values, a.terms, a.sweeps, a.mean = out["values"].data_ptr(), out["terms"].data_ptr(), out["sweeps"].data_ptr(), \
+        _ptr(out["mean"])
+    a.mu_real, a.mu_fake = _ptr(out.get("mu_real")), _ptr(out.get("mu_fake"))
+    a.cov_real, a.cov_fake = _ptr(out.get("cov_real")), _ptr(out.get("cov_fake"))
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 8
+    pts = (n + m) * (frames - int(bool(diff)))
+    _count("kg_frechet", 2.0 * float(pts) * d * d * classes)
+    _check(lib.kg_frechet(C.byref(a), _stream()), "kg_frechet")
     return out
 
 

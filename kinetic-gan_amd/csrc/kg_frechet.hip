@@ -1,0 +1,484 @@
+// Frechet distance between the point sets of many classes in fp64 (see include/kgan_hip.h).  Per class: a real
+// and a fake set of P_r / P_f points of dimension d = d_outer * d_inner <= 96 - the frames of n / m samples (pose) or the
+// differences of consecutive frames (motion), read in place through strides.  Four launches:
+//
+// kg_frechet_moments_kernel: one workgroup = one chunk of the points of one (class, set).  The points are staged 32 at a
+//   time in LDS as doubles, CENTRED on the set's first point (the provisional shift: what is left of the one-pass
+//   cancellation is |mu - x_0|^2 against the variance, both of the order of the data's range), and every thread keeps a
+//   6 x 6 (d <= 48: 3 x 3) tile of sum (x - x_0)(x - x_0)^T in registers: one v_fma_f64 chain per entry in point order.
+//   The chunk's sum and second-moment matrix go to the workspace; nothing is accumulated across workgroups.
+// kg_frechet_merge_kernel: one thread per entry of S: the chunks' partials summed in chunk order (the chunking depends on
+//   the shape alone: the same bits on every call), S = (M2 - s s^T / P) / (P - 1), mu = x_0 + s / P.
+// kg_frechet_solve_kernel: one workgroup of 1024 threads per class.  S_r and its eigenvector matrix live in LDS as doubles
+//   (row stride m + 1, m = d rounded up to even: 2 x 96 x 97 x 8 = 148,992 bytes at d = 96).  Cyclic Jacobi with the
+//   round-robin parallel ordering: every step computes m / 2 disjoint rotations (phase 1) and applies them as independent
+//   2 x 2 blocks J_k^T B J_l, upper blocks computed and mirrored so the matrix stays symmetric bit for bit (phase 2): two
+//   barriers per step.  Then G = V sqrt(max(l, 0)), W = S_f G (S_f from the workspace) into the place of S_r,
+//   H = sym(G^T W) through registers into the same place, the eigenvalues of H by the same iteration without vectors,
+//   T = sum sqrt(max(e, 0)), and the four terms and FD of the class.
+// kg_frechet_mean_kernel: the class mean (fp64 sum in class order).
+// No atomics, no ticket, no scratch, no dynamically indexed private array; every launch on the caller's stream.
+#include <math.h>
+
+#include "kg_common.h"
+
+namespace {
+
+constexpr int FR_MAXD = KG_FRECHET_MAX_DIM;
+constexpr int FR_NT = 256;          // threads of a moments / merge workgroup: 16 x 16 register tiles
+constexpr int FR_KB = 32;           // points staged per batch
+constexpr int FR_MINCHUNK = 64;     // points of the smallest chunk
+constexpr int FR_TARGET = 1024;     // workgroups the moments launch aims at (4 of them fit a CU)
+constexpr int FR_SOLVE_NT = 1024;   // threads of the solving workgroup
+constexpr int FR_MAXSWEEPS = 40;
+constexpr long FR_MAX_POINTS = 1L << 24;
+constexpr long FR_MAX_GRID = 1L << 24;  // workgroups of one launch (exclusive): grid x 256 threads stays below 2^32
+constexpr int FR_MAXPAIRS = FR_MAXD / 2;
+constexpr int FR_HREG = FR_MAXD * FR_MAXD / FR_SOLVE_NT;    // entries of H a thread carries through the barrier
+static_assert(FR_MAXD % 16 == 0 && FR_MAXD % 2 == 0 && FR_HREG * FR_SOLVE_NT == FR_MAXD * FR_MAXD, "tile plan");
+
+struct FrSet {
+    const float* p;
+    long sc, ss, sf, so;        // class, sample, frame, outer strides (elements); the inner run is contiguous
+    int P;                      // points per class
+    int cs, nch;                // points per chunk (a multiple of FR_KB), chunks
+};
+
+struct FrDev {
+    FrSet set[2];               // 0 = real, 1 = fake
+    FastDiv inner, fr;          // j = o * d_inner + e;  point p = sample * fr + frame
+    int d, diff, classes;
+    double* part;               // ws: (classes, nch_r + nch_f, d + d*d)
+    double* mu;                 // ws: (classes, 2, d)
+    double* cov;                // ws: (classes, 2, d, d)
+    double* mu_out[2];          // the caller's arrays or null
+    double* cov_out[2];
+    double* values;  double* terms;  int32_t* sweeps;
+};
+
+// coordinate j of point (sample i, frame f) of a class, formed in fp64 (the motion difference is exact there)
+__device__ __forceinline__ double fr_coord(const float* base, const FrSet& X, int diff, long i, long f, unsigned o, unsigned e) {
+    const float* q = base + (i * X.ss + f * X.sf + (long)o * X.so + e);
+    return diff ? (double)q[X.sf] - (double)q[0] : (double)q[0];
+}
+
+template <int NR>
+__global__ __launch_bounds__(FR_NT) void kg_frechet_moments_kernel(FrDev a) {
+    constexpr int W = NR * 16;                      // columns a workgroup covers (d <= W)
+    __shared__ double pts[FR_KB][W];
+    __shared__ double shift[W];
+    const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
+    const unsigned per = (unsigned)(a.set[0].nch + a.set[1].nch);
+    const unsigned cls = blockIdx.x / per, t = blockIdx.x % per;
+    const int set = t >= (unsigned)a.set[0].nch ? 1 : 0;
+    const int chunk = (int)t - (set ? a.set[0].nch : 0);
+    const FrSet X = a.set[set];
+    const float* base = X.p + (long)cls * X.sc;
+    const int d = a.d;
+
+    for (int e = tid; e < FR_KB * W; e += FR_NT) pts[e / W][e % W] = 0.0;      // columns >= d stay zero
+    if (tid < W) {
+        double s = 0.0;
+        if (tid < d) {
+            unsigned o, r;
+            a.inner.divmod((unsigned)tid, o, r);
+            s = fr_coord(base, X, a.diff, 0, 0, o, r);
+        }
+        shift[tid] = s;
+    }
+    __syncthreads();
+
+    double acc[NR][NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int s = 0; s < NR; ++s) acc[r][s] = 0.0;
+    double sum = 0.0;
+
+    const int pbeg = chunk * X.cs, pend = min(X.P, pbeg + X.cs);
+    for (int p0 = pbeg; p0 < pend; p0 += FR_KB) {
+        // element e = (o, k, inner): a wave reads runs of d_inner floats of consecutive frames
+        for (int e = tid; e < FR_KB * d; e += FR_NT) {
+            unsigned q, v;
+            a.inner.divmod((unsigned)e, q, v);
+            const int k = (int)(q & (FR_KB - 1));
+            const unsigned o = q / FR_KB;
+            const int j = (int)(o * a.inner.d + v);
+            const int p = p0 + k;
+            double x = 0.0;
+            if (p < pend) {
+                unsigned i, f;
+                a.fr.divmod((unsigned)p, i, f);
+                x = fr_coord(base, X, a.diff, i, f, o, v) - shift[j];
+            }
+            pts[k][j] = x;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int k = 0; k < FR_KB; ++k) {
+            double xi[NR], yj[NR];
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                xi[r] = pts[k][r * 16 + ti];
+                yj[r] = pts[k][r * 16 + tj];
+            }
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+#pragma unroll
+                for (int s = 0; s < NR; ++s) acc[r][s] = fma(xi[r], yj[s], acc[r][s]);
+        }
+        if (tid < W) {
+            for (int k = 0; k < FR_KB; ++k) sum += pts[k][tid];
+        }
+        __syncthreads();
+    }
+
+    double* part = a.part + ((long)cls * per + t) * ((long)d + (long)d * d);
+    if (tid < d) part[tid] = sum;
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int s = 0; s < NR; ++s) {
+            const int ra = r * 16 + ti, cb = s * 16 + tj;
+            if (ra < d && cb < d) part[d + ra * d + cb] = acc[r][s];
+        }
+}
+
+__global__ __launch_bounds__(FR_NT) void kg_frechet_merge_kernel(FrDev a) {
+    const int d = a.d, dd = d * d;
+    const unsigned nb = (unsigned)((dd + FR_NT - 1) / FR_NT);
+    const unsigned cs = blockIdx.x / nb, tile = blockIdx.x % nb;        // cs = class * 2 + set
+    const unsigned cls = cs >> 1;
+    const int set = (int)(cs & 1);
+    const int entry = (int)tile * FR_NT + (int)threadIdx.x;
+    if (entry >= dd) return;
+    const int ra = entry / d, cb = entry % d;
+    const FrSet X = a.set[set];
+    const long per = a.set[0].nch + a.set[1].nch, stride = (long)d + dd;
+    const double* part = a.part + ((long)cls * per + (set ? a.set[0].nch : 0)) * stride;
+    double m2 = 0.0, sa = 0.0, sb = 0.0;
+    for (int c = 0; c < X.nch; ++c) {
+        const double* q = part + (long)c * stride;
+        m2 += q[d + entry];
+        sa += q[ra];
+        sb += q[cb];
+    }
+    const double P = (double)X.P;
+    const double cov = (m2 - (sa * sb) / P) / (P - 1.0);
+    a.cov[(long)cs * dd + entry] = cov;
+    if (a.cov_out[set] != nullptr) a.cov_out[set][(long)cls * dd + entry] = cov;
+    if (cb == 0) {
+        unsigned o, r;
+        a.inner.divmod((unsigned)ra, o, r);
+        const double mu = fr_coord(X.p + (long)cls * X.sc, X, a.diff, 0, 0, o, r) + sa / P;
+        a.mu[(long)cs * d + ra] = mu;
+        if (a.mu_out[set] != nullptr) a.mu_out[set][(long)cls * d + ra] = mu;
+    }
+}
+
+struct FrSmall {
+    double c[FR_MAXPAIRS], s[FR_MAXPAIRS], t[FR_MAXPAIRS];
+    int p[FR_MAXPAIRS], q[FR_MAXPAIRS], rot[FR_MAXPAIRS];
+    double root[FR_MAXD];       // sqrt(max(l, 0)) of S_r
+    double red[FR_SOLVE_NT / 64];
+    double thresh;
+    int any;
+};
+
+// Cyclic Jacobi, round-robin ordering, on the symmetric m x m matrix A (m even, row stride ld) in LDS; V (or null)
+// accumulates the rotations.  Returns the sweeps run (the last one applied no rotation unless the cap was met).
+__device__ int fr_jacobi(double* A, double* V, int m, int ld, int d, FrSmall& sm) {
+    const int tid = threadIdx.x, np = m >> 1;
+    {   // |a_pq| <= 2^-52 ||A||_F / d is left alone; the norm is taken once
+        double s = 0.0;
+        for (int e = tid; e < m * m; e += FR_SOLVE_NT) {
+            const double v = A[(e / m) * ld + (e % m)];
+            s = fma(v, v, s);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        if ((tid & 63) == 0) sm.red[tid >> 6] = s;
+        __syncthreads();
+        if (tid == 0) {
+            double tot = 0.0;
+            for (int w = 0; w < FR_SOLVE_NT / 64; ++w) tot += sm.red[w];
+            sm.thresh = 0x1p-52 * sqrt(tot) / (double)d;
+        }
+        __syncthreads();
+    }
+    const double thresh = sm.thresh;
+    int sweeps = 0;
+    for (int sweep = 0; sweep < FR_MAXSWEEPS; ++sweep) {
+        if (tid == 0) sm.any = 0;
+        __syncthreads();
+        for (int r = 0; r < m - 1; ++r) {
+            // phase 1: the rotations of this step's m / 2 disjoint pairs (circle method: m - 1 stays, the others turn)
+            if (tid < np) {
+                int p, q;
+                if (tid == 0) {
+                    p = r;  q = m - 1;
+                } else {
+                    p = (r + tid) % (m - 1);
+                    q = (r - tid + (m - 1)) % (m - 1);
+                }
+                if (p > q) { const int x = p; p = q; q = x; }
+                const double apq = A[p * ld + q];
+                double c = 1.0, s = 0.0, t = 0.0;
+                const int rot = fabs(apq) > thresh ? 1 : 0;
+                if (rot) {
+                    const double theta = (A[q * ld + q] - A[p * ld + p]) / (2.0 * apq);
+                    t = 1.0 / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));
+                    if (theta < 0.0) t = -t;
+                    c = 1.0 / sqrt(fma(t, t, 1.0));
+                    s = t * c;
+                    sm.any = 1;
+                }
+                sm.p[tid] = p;  sm.q[tid] = q;  sm.rot[tid] = rot;
+                sm.c[tid] = c;  sm.s[tid] = s;  sm.t[tid] = t;
+            }
+            __syncthreads();
+            // phase 2: A <- J^T A J as independent 2 x 2 blocks (k <= l computed, mirrored), V <- V J
+            for (int item = tid; item < np * np; item += FR_SOLVE_NT) {
+                const int k = item / np, l = item % np;
+                if (k > l || !(sm.rot[k] | sm.rot[l])) continue;
+                const int pk = sm.p[k], qk = sm.q[k];
+                if (k == l) {
+                    const double apq = A[pk * ld + qk], t = sm.t[k];
+                    A[pk * ld + pk] -= t * apq;
+                    A[qk * ld + qk] += t * apq;
+                    A[pk * ld + qk] = 0.0;
+                    A[qk * ld + pk] = 0.0;
+                    continue;
+                }
+                const int pl = sm.p[l], ql = sm.q[l];
+                const double ck = sm.c[k], sk = sm.s[k], cl = sm.c[l], sl = sm.s[l];
+                const double b00 = A[pk * ld + pl], b01 = A[pk * ld + ql], b10 = A[qk * ld + pl], b11 = A[qk * ld + ql];
+                const double r00 = ck * b00 - sk * b10, r01 = ck * b01 - sk * b11;      // rows: J_k^T B
+                const double r10 = sk * b00 + ck * b10, r11 = sk * b01 + ck * b11;
+                const double n00 = cl * r00 - sl * r01, n01 = sl * r00 + cl * r01;      // columns: (.) J_l
+                const double n10 = cl * r10 - sl * r11, n11 = sl * r10 + cl * r11;
+                A[pk * ld + pl] = n00;  A[pl * ld + pk] = n00;
+                A[pk * ld + ql] = n01;  A[ql * ld + pk] = n01;
+                A[qk * ld + pl] = n10;  A[pl * ld + qk] = n10;
+                A[qk * ld + ql] = n11;  A[ql * ld + qk] = n11;
+            }
+            if (V != nullptr) {
+                for (int item = tid; item < m * np; item += FR_SOLVE_NT) {
+                    const int i = item / np, l = item % np;
+                    if (!sm.rot[l]) continue;
+                    const int pl = sm.p[l], ql = sm.q[l];
+                    const double cl = sm.c[l], sl = sm.s[l];
+                    const double vp = V[i * ld + pl], vq = V[i * ld + ql];
+                    V[i * ld + pl] = cl * vp - sl * vq;
+                    V[i * ld + ql] = sl * vp + cl * vq;
+                }
+            }
+            __syncthreads();
+        }
+        sweeps = sweep + 1;
+        const int any = sm.any;
+        __syncthreads();
+        if (!any) break;
+    }
+    return sweeps;
+}
+
+__global__ __launch_bounds__(FR_SOLVE_NT) void kg_frechet_solve_kernel(FrDev a) {
+    extern __shared__ __attribute__((aligned(16))) double fr_lds[];
+    __shared__ FrSmall sm;
+    const int tid = threadIdx.x, d = a.d, dd = d * d;
+    const int m = d + (d & 1), ld = m + 1;
+    double* A = fr_lds;
+    double* V = fr_lds + m * ld;
+    const unsigned cls = blockIdx.x;
+    const double* Sr = a.cov + (long)(cls * 2) * dd;
+    const double* Sf = Sr + dd;
+
+    for (int e = tid; e < m * m; e += FR_SOLVE_NT) {
+        const int i = e / m, j = e % m;
+        A[i * ld + j] = (i < d && j < d) ? Sr[i * d + j] : 0.0;      // (odd d: one idle index, never rotated)
+        V[i * ld + j] = i == j ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    const int sweeps_r = fr_jacobi(A, V, m, ld, d, sm);
+
+    if (tid < m) sm.root[tid] = sqrt(fmax(A[tid * ld + tid], 0.0));
+    __syncthreads();
+    for (int e = tid; e < m * m; e += FR_SOLVE_NT) V[(e / m) * ld + (e % m)] *= sm.root[e % m];      // G = V sqrt(l)
+    __syncthreads();
+    for (int e = tid; e < m * m; e += FR_SOLVE_NT) {           // W = S_f G, in the place of S_r
+        const int i = e / m, j = e % m;
+        double w = 0.0;
+        if (i < d) {
+            for (int b = 0; b < d; ++b) w = fma(Sf[i * d + b], V[b * ld + j], w);
+        }
+        A[i * ld + j] = w;
+    }
+    __syncthreads();
+    double h[FR_HREG];                                          // H = sym(G^T W), upper entries, through registers
+#pragma unroll
+    for (int u = 0; u < FR_HREG; ++u) {
+        const int e = tid + u * FR_SOLVE_NT;
+        const int i = e / m, j = e % m;
+        double x = 0.0, y = 0.0;
+        if (e < m * m && i <= j) {
+            for (int b = 0; b < m; ++b) {
+                x = fma(V[b * ld + i], A[b * ld + j], x);
+                y = fma(V[b * ld + j], A[b * ld + i], y);
+            }
+        }
+        h[u] = 0.5 * (x + y);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < FR_HREG; ++u) {
+        const int e = tid + u * FR_SOLVE_NT;
+        const int i = e / m, j = e % m;
+        if (e < m * m && i <= j) {
+            A[i * ld + j] = h[u];
+            A[j * ld + i] = h[u];
+        }
+    }
+    __syncthreads();
+    const int sweeps_h = fr_jacobi(A, nullptr, m, ld, d, sm);
+
+    if (tid == 0) {
+        const double* mr = a.mu + (long)(cls * 2) * d;
+        const double* mf = mr + d;
+        double dmu2 = 0.0, trr = 0.0, trf = 0.0, T = 0.0;
+        for (int i = 0; i < d; ++i) {
+            const double df = mr[i] - mf[i];
+            dmu2 += df * df;
+            trr += Sr[i * d + i];
+            trf += Sf[i * d + i];
+        }
+        for (int i = 0; i < m; ++i) T += sqrt(fmax(A[i * ld + i], 0.0));
+        a.terms[cls * 4 + 0] = dmu2;
+        a.terms[cls * 4 + 1] = trr;
+        a.terms[cls * 4 + 2] = trf;
+        a.terms[cls * 4 + 3] = T;
+        a.values[cls] = ((dmu2 + trr) + trf) - 2.0 * T;
+        a.sweeps[cls * 2 + 0] = sweeps_r;
+        a.sweeps[cls * 2 + 1] = sweeps_h;
+    }
+}
+
+__global__ void kg_frechet_mean_kernel(const double* values, double* mean, int classes) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0;
+    for (int c = 0; c < classes; ++c) s += values[c];
+    *mean = s / (double)classes;
+}
+
+struct FrPlan {
+    long P[2];
+    int cs[2], nch[2];
+    long grid_moments, grid_merge;
+    int64_t part_doubles, ws_bytes;
+    int d, m, lds_solve;
+};
+
+// The chunking is a function of the shape alone: about FR_TARGET workgroups in all, chunks of at least FR_MINCHUNK points,
+// a multiple of the FR_KB points staged at a time.
+void frechet_plan(const KgFrechetArgs* a, FrPlan& p) {
+    const long fr = (long)a->frames - (a->diff ? 1 : 0);
+    p.P[0] = (long)a->n * fr;
+    p.P[1] = (long)a->m * fr;
+    p.d = a->d_outer * a->d_inner;
+    p.m = p.d + (p.d & 1);
+    const long per_set = FR_TARGET / (2L * a->classes) > 1 ? FR_TARGET / (2L * a->classes) : 1;
+    for (int s = 0; s < 2; ++s) {
+        long cs = (p.P[s] + per_set - 1) / per_set;
+        if (cs < FR_MINCHUNK) cs = FR_MINCHUNK;
+        cs = (cs + FR_KB - 1) / FR_KB * FR_KB;
+        p.cs[s] = (int)cs;
+        p.nch[s] = (int)((p.P[s] + cs - 1) / cs);
+    }
+    const long dd = (long)p.d * p.d;
+    p.grid_moments = (long)a->classes * (p.nch[0] + p.nch[1]);
+    p.grid_merge = (long)a->classes * 2 * ((dd + FR_NT - 1) / FR_NT);
+    p.part_doubles = (int64_t)p.grid_moments * (p.d + dd);
+    p.ws_bytes = 8 * (p.part_doubles + (int64_t)a->classes * 2 * (p.d + dd));
+    p.lds_solve = 2 * p.m * (p.m + 1) * 8;
+}
+
+int frechet_validate(const KgFrechetArgs* a, const char* who, FrPlan& p) {
+    KG_REQUIRE(a != nullptr, "%s: null args", who);
+    KG_REQUIRE(a->classes >= 1, "%s: classes=%d < 1", who, a->classes);
+    KG_REQUIRE(a->n >= 1, "%s: n=%d < 1", who, a->n);
+    KG_REQUIRE(a->m >= 1, "%s: m=%d < 1", who, a->m);
+    KG_REQUIRE(a->d_outer >= 1, "%s: d_outer=%d < 1", who, a->d_outer);
+    KG_REQUIRE(a->d_inner >= 1, "%s: d_inner=%d < 1", who, a->d_inner);
+    KG_REQUIRE(a->diff == 0 || a->diff == 1, "%s: diff=%d is neither 0 (pose) nor 1 (motion)", who, a->diff);
+    KG_REQUIRE((long)a->d_outer * a->d_inner <= KG_FRECHET_MAX_DIM, "%s: d = d_outer=%d x d_inner=%d above KG_FRECHET_MAX_DIM = %d",
+               who, a->d_outer, a->d_inner, KG_FRECHET_MAX_DIM);
+    KG_REQUIRE(a->frames >= 1 + a->diff, "%s: frames=%d < %d%s", who, a->frames, 1 + a->diff,
+               a->diff ? " (a motion point needs two frames)" : "");
+    const long fr = (long)a->frames - a->diff;
+    KG_REQUIRE((long)a->n * fr >= 2, "%s: n=%d gives P=%ld < 2 real points", who, a->n, (long)a->n * fr);
+    KG_REQUIRE((long)a->m * fr >= 2, "%s: m=%d gives P=%ld < 2 fake points", who, a->m, (long)a->m * fr);
+    KG_REQUIRE((long)a->n * fr <= FR_MAX_POINTS, "%s: n=%d x frames=%d gives P=%ld real points, above 2^24", who, a->n, a->frames,
+               (long)a->n * fr);
+    KG_REQUIRE((long)a->m * fr <= FR_MAX_POINTS, "%s: m=%d x frames=%d gives P=%ld fake points, above 2^24", who, a->m, a->frames,
+               (long)a->m * fr);
+    frechet_plan(a, p);
+    const long grid = p.grid_moments > p.grid_merge ? p.grid_moments : p.grid_merge;
+    KG_REQUIRE(grid < FR_MAX_GRID, "%s: classes=%d make %ld workgroups, one launch takes fewer than %ld", who, a->classes, grid,
+               FR_MAX_GRID);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t kg_frechet_workspace_bytes(const KgFrechetArgs* a) {
+    FrPlan p;
+    if (int rc = frechet_validate(a, "kg_frechet_workspace_bytes", p)) return rc;
+    return p.ws_bytes;
+}
+
+extern "C" int kg_frechet(const KgFrechetArgs* a, void* stream) {
+    FrPlan p;
+    if (int rc = frechet_validate(a, "kg_frechet", p)) return rc;
+    KG_REQUIRE(a->real != nullptr, "kg_frechet: null pointer real");
+    KG_REQUIRE(a->fake != nullptr, "kg_frechet: null pointer fake");
+    KG_REQUIRE(a->values != nullptr, "kg_frechet: null pointer values");
+    KG_REQUIRE(a->terms != nullptr, "kg_frechet: null pointer terms");
+    KG_REQUIRE(a->sweeps != nullptr, "kg_frechet: null pointer sweeps");
+    KG_REQUIRE(a->ws != nullptr, "kg_frechet: null pointer ws");
+    KG_REQUIRE(((uintptr_t)a->ws & 7) == 0, "kg_frechet: ws is not 8-byte aligned");
+    KG_REQUIRE(a->ws_bytes >= p.ws_bytes, "kg_frechet: ws_bytes=%lld < %lld (kg_frechet_workspace_bytes)", (long long)a->ws_bytes,
+               (long long)p.ws_bytes);
+
+    FrDev d = {};
+    d.set[0].p = a->real;  d.set[0].sc = a->r_sc;  d.set[0].ss = a->r_ss;  d.set[0].sf = a->r_sf;  d.set[0].so = a->r_so;
+    d.set[1].p = a->fake;  d.set[1].sc = a->f_sc;  d.set[1].ss = a->f_ss;  d.set[1].sf = a->f_sf;  d.set[1].so = a->f_so;
+    for (int s = 0; s < 2; ++s) {
+        d.set[s].P = (int)p.P[s];  d.set[s].cs = p.cs[s];  d.set[s].nch = p.nch[s];
+    }
+    d.inner = FastDiv::make((unsigned)a->d_inner);
+    d.fr = FastDiv::make((unsigned)(a->frames - a->diff));
+    d.d = p.d;  d.diff = a->diff;  d.classes = a->classes;
+    d.part = (double*)a->ws;
+    d.mu = d.part + p.part_doubles;
+    d.cov = d.mu + (long)a->classes * 2 * p.d;
+    d.mu_out[0] = a->mu_real;  d.mu_out[1] = a->mu_fake;
+    d.cov_out[0] = a->cov_real;  d.cov_out[1] = a->cov_fake;
+    d.values = a->values;  d.terms = a->terms;  d.sweeps = a->sweeps;
+    hipStream_t s = (hipStream_t)stream;
+
+    static unsigned long long attr_mask = 0;
+    if (kg_first_on_device(attr_mask)) KG_SET_DYN_LDS(kg_frechet_solve_kernel, 2 * FR_MAXD * (FR_MAXD + 1) * 8);
+
+    if (p.d <= 48) hipLaunchKernelGGL(kg_frechet_moments_kernel<3>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
+    else hipLaunchKernelGGL(kg_frechet_moments_kernel<6>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
+    if (int rc = kg_launch_status("kg_frechet_moments")) return rc;
+    hipLaunchKernelGGL(kg_frechet_merge_kernel, dim3((unsigned)p.grid_merge), dim3(FR_NT), 0, s, d);
+    if (int rc = kg_launch_status("kg_frechet_merge")) return rc;
+    hipLaunchKernelGGL(kg_frechet_solve_kernel, dim3((unsigned)a->classes), dim3(FR_SOLVE_NT), (size_t)p.lds_solve, s, d);
+    if (int rc = kg_launch_status("kg_frechet_solve")) return rc;
+    if (a->mean != nullptr) {
+        hipLaunchKernelGGL(kg_frechet_mean_kernel, dim3(1), dim3(64), 0, s, (const double*)a->values, a->mean, a->classes);
+        return kg_launch_status("kg_frechet_mean");
+    }
+    return 0;
+}

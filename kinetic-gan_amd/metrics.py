@@ -1,5 +1,6 @@
 """MMD evaluation of generated actions (evaluation/mmd-actions.py of the reference) on the kg_mmd HIP kernels, and
-precision / recall / density / coverage of sample sets on the kg_prdc kernels (``prdc``, at the end).
+precision / recall / density / coverage of sample sets on the kg_prdc kernels (``prdc``) and the Frechet distance of
+pose / motion / caller features in fp64 on the kg_frechet kernels (``frechet``, ``frechet_features``), at the end.
 
 The reference scores samples with a kernel two-sample statistic (MMD) under 14 RBF bandwidths 10^-4 .. 10^9: per class
 the first selected fake and real sample, each a set of V points (joints) per frame (``avg``: the mean over frames of
@@ -280,6 +281,87 @@ def prdc(gen, real, labels_gen=None, labels_real=None, k: int = 5, per_class: Op
         rv, gv = (v if v.so or C == 1 else v._replace(so=T * V) for v in (rv, gv))
         d_outer, d_inner = C, T * V
     return _native.prdc(rv, gv, n, m, d_outer, d_inner, classes, k, want_mean=True, per_point=per_point)
+
+
+FRECHET_MODES = ("pose", "motion")
+FRECHET_TERMS = ("dmu2", "tr_real", "tr_fake", "tr_sqrt")
+
+
+def _frechet_view(t: torch.Tensor, idx: np.ndarray) -> _native.FrechetView:
+    """view of the samples idx (classes, count) of t (N, C, T, V) on the device: read in place when idx is evenly spaced
+    along both axes, else gathered once; only the joint axis has to be contiguous (a crop in T is read in place)"""
+    K, cnt = idx.shape
+    ps = int(idx[0, 1] - idx[0, 0]) if cnt > 1 else 1
+    cs = int(idx[1, 0] - idx[0, 0]) if K > 1 else 0
+    even = ps > 0 and cs >= 0 and np.array_equal(idx, idx[0, 0] + cs * np.arange(K)[:, None] + ps * np.arange(cnt)[None, :])
+    if even:
+        base = int(idx[0, 0])
+    else:
+        t = t.index_select(0, torch.as_tensor(idx.reshape(-1), device=t.device))
+        base, ps, cs = 0, 1, cnt
+    if (t.shape[3] > 1 and t.stride(3) != 1) or min(t.stride()) < 0:
+        t = t.contiguous()
+    return _native.FrechetView(t[base], cs * t.stride(0), ps * t.stride(0), t.stride(2), t.stride(1))
+
+
+def frechet(gen, real, labels_gen=None, labels_real=None, mode: str = "pose", per_class: Optional[int] = None,
+            moments: bool = False) -> dict:
+    """Frechet distance per class between the frames (``pose``: a point is one frame, dimension C*V) or the frame
+    differences (``motion``: x[:, :, f + 1] - x[:, :, f], formed in fp64) of generated and real sequences, in fp64, in one
+    kg_frechet call (four launches):
+
+        FD = |mu_r - mu_f|^2 + tr S_r + tr S_f - 2 tr sqrt(S_r S_f)        (unbiased covariances)
+
+    gen (Nf, C, T, V), real (Nr, C, T, V): fake, real - prdc's argument order and prdc's conventions: labels one-hot
+    (N, K), class ids (N,) or None for one class; the first ``per_class`` samples of every class (default: all; ragged
+    classes raise ValueError); samples that lie evenly spaced in the batch are read in place, otherwise gathered once.
+    C*V must not exceed 96 and either set needs two points.  Returns device tensors: ``mean`` () fp64 - the plain mean over
+    classes -, ``values`` (K,), ``terms`` (K, 4) in the order FRECHET_TERMS, ``sweeps`` (K, 2) int32 (Jacobi sweeps of
+    the two eigen-problems); with ``moments`` also ``mu_real``, ``mu_fake`` (K, d) and ``cov_real``, ``cov_fake``
+    (K, d, d).  ``mode="both"`` returns {"pose": ..., "motion": ...} from two calls.  No host sync (labels that live on
+    the device are read once)."""
+    if mode == "both":
+        return {md: frechet(gen, real, labels_gen, labels_real, md, per_class, moments) for md in FRECHET_MODES}
+    if mode not in FRECHET_MODES:
+        raise ValueError("frechet: undefined mode %r ('pose', 'motion' or 'both')" % (mode,))
+    gen, real = _as_f32(gen), _as_f32(real)
+    if gen.dim() != 4 or real.dim() != 4:
+        raise ValueError("frechet: samples are (N, C, T, V), got %s and %s" % (tuple(gen.shape), tuple(real.shape)))
+    if gen.shape[1:] != real.shape[1:]:
+        raise ValueError("frechet: gen samples %s and real samples %s differ in shape" % (tuple(gen.shape[1:]),
+                                                                                         tuple(real.shape[1:])))
+    _, C, T, V = real.shape
+    diff = mode == "motion"
+    if C * V > _native.FRECHET_MAX_DIM:
+        raise ValueError("frechet: d = C*V = %d above %d" % (C * V, _native.FRECHET_MAX_DIM))
+    if T < 1 + diff:
+        raise ValueError("frechet: T=%d frames, mode %r needs %d" % (T, mode, 1 + diff))
+    lab_g, kg = _label_ids(labels_gen, gen.shape[0], "labels_gen")
+    lab_r, kr = _label_ids(labels_real, real.shape[0], "labels_real")
+    classes = max(kg, kr)
+    if classes < 1:
+        raise ValueError("frechet: no samples")
+    idx_r = _class_rows(lab_r, classes, per_class, "real")
+    idx_g = _class_rows(lab_g, classes, per_class, "fake")
+    n, m = idx_r.shape[1], idx_g.shape[1]
+    if min(n, m) * (T - diff) < 2:
+        raise ValueError("frechet: n=%d, m=%d samples of %d points each: either set needs two points" % (n, m, T - diff))
+    gen, real = _as_cuda(gen), _as_cuda(real)
+    return _native.frechet(_frechet_view(real, idx_r), _frechet_view(gen, idx_g), n, m, T, diff, C, V, classes,
+                           want_mean=True, moments=moments)
+
+
+def frechet_features(feat_gen, feat_real, labels_gen=None, labels_real=None, per_class: Optional[int] = None,
+                     moments: bool = False) -> dict:
+    """``frechet`` on (N, d) feature matrices of the caller's own extractor (d <= 96): a row is a point."""
+    feat_gen, feat_real = _as_f32(feat_gen), _as_f32(feat_real)
+    if feat_gen.dim() != 2 or feat_real.dim() != 2:
+        raise ValueError("frechet_features: features are (N, d), got %s and %s" % (tuple(feat_gen.shape),
+                                                                                   tuple(feat_real.shape)))
+    if feat_gen.shape[1] != feat_real.shape[1]:
+        raise ValueError("frechet_features: gen features %s and real features %s differ in shape"
+                         % (tuple(feat_gen.shape[1:]), tuple(feat_real.shape[1:])))
+    return frechet(feat_gen[:, None, None, :], feat_real[:, None, None, :], labels_gen, labels_real, "pose", per_class, moments)
 
 
 def select_reference_samples(feeder, classes: Optional[Sequence[int]] = None, t_size: int = 64, per_class: int = 100):
