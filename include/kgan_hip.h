@@ -156,6 +156,15 @@ typedef struct KgWgradArgs {
 
 int64_t kg_wgrad_workspace_bytes(const KgWgradArgs* a);   /* = splits * taps * M * Cin * 4                        */
 int     kg_wgrad(const KgWgradArgs* a, void* stream);
+/* tile variants of the weight-gradient kernels (output rows x input channels per workgroup), as the plan reports name them */
+#define KG_WGRAD_TILE_128x128 0
+#define KG_WGRAD_TILE_64x64   1
+#define KG_WGRAD_TILE_64x32   2
+#define KG_WGRAD_TILE_32x64   3
+#define KG_WGRAD_TILE_32x32   4
+/* tests / tuning (additive, ABI v9): the tile variant and the number of partial slabs kg_wgrad takes for `a` (the variant is
+ * always KG_WGRAD_TILE_64x64 today).  Geometry only: the pointers of `a` are not looked at.  Launches nothing.        */
+int     kg_wgrad_plan_info(const KgWgradArgs* a, int32_t* variant, int32_t* splits);
 
 /* The slab reductions of several deferred kg_wgrad launches in ONE launch (a backward pass produces the weight
  * gradients of all layers back to back; 17-19 reductions of a few microseconds each become one).              */
@@ -178,6 +187,10 @@ int     kg_wgrad_reduce_many(const KgWgradReduceJobs* jobs, void* stream);
  * (aten::convolution_backward's weight halves of all of discriminator.py:99-120 / generator.py:134-159).        */
 int64_t kg_wgrad_many_workspace_bytes(const KgWgradArgs* jobs, int32_t njobs);
 int     kg_wgrad_many(const KgWgradArgs* jobs, int32_t njobs, float* ws, int64_t ws_bytes, void* stream);
+/* tests / tuning (additive, ABI v9): variant[i] / splits[i] = the tile variant (KG_WGRAD_TILE_*) and the number of partial
+ * slabs job i of kg_wgrad_many(jobs, njobs, ...) takes (1 = the tile kernel writes dw itself) - the same walk over the jobs
+ * as the launch (cost target, coarser first half, KG_WGRAD_* switches).  Geometry only; launches nothing.               */
+int     kg_wgrad_many_plan(const KgWgradArgs* jobs, int32_t njobs, int32_t* variant, int32_t* splits);
 
 /* ---- spatial graph aggregation -------------------------------------------------------------------
  * A is (K, V, W) row-major fp32 in device memory (the effective adjacency A[lvl]*importance,

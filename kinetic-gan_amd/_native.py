@@ -79,6 +79,11 @@ class _WgradReduceJob(C.Structure):
 
 
 WGRAD_REDUCE_MAX_JOBS = 24
+# tile variants of the weight-gradient kernels (KG_WGRAD_TILE_* of kgan_hip.h: output rows x input channels per workgroup)
+WGRAD_TILE_128x128, WGRAD_TILE_64x64, WGRAD_TILE_64x32, WGRAD_TILE_32x64, WGRAD_TILE_32x32 = 0, 1, 2, 3, 4
+WGRAD_TILE_NAMES = {WGRAD_TILE_128x128: "128x128", WGRAD_TILE_64x64: "64x64", WGRAD_TILE_64x32: "64x32",
+                    WGRAD_TILE_32x64: "32x64", WGRAD_TILE_32x32: "32x32"}
+WGRAD_MAX_SPLITS = 128          # partial slabs of one layer (make_plan's cap; one more per extra operand pair at most)
 
 
 class _WgradReduceJobs(C.Structure):
@@ -427,9 +432,11 @@ EXPORTS = {
     "kg_conv_many_plan": (C.c_int, [C.POINTER(_ConvArgs), C.c_int32, C.POINTER(C.c_int32)]),
     "kg_wgrad_workspace_bytes": (C.c_int64, [C.POINTER(_WgradArgs)]),
     "kg_wgrad": (C.c_int, [C.POINTER(_WgradArgs), C.c_void_p]),
+    "kg_wgrad_plan_info": (C.c_int, [C.POINTER(_WgradArgs), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kg_wgrad_reduce_many": (C.c_int, [C.POINTER(_WgradReduceJobs), C.c_void_p]),
     "kg_wgrad_many_workspace_bytes": (C.c_int64, [C.POINTER(_WgradArgs), C.c_int32]),
     "kg_wgrad_many": (C.c_int, [C.POINTER(_WgradArgs), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "kg_wgrad_many_plan": (C.c_int, [C.POINTER(_WgradArgs), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kg_aggconv_supported": (C.c_int, [C.POINTER(_AggConvArgs)]),
     "kg_aggconv": (C.c_int, [C.POINTER(_AggConvArgs), C.c_void_p]),
     "kg_agg_expand": (C.c_int, [C.POINTER(_AggArgs), C.c_void_p]),
@@ -819,6 +826,9 @@ def conv_many(jobs: Sequence[dict]) -> list:
     return outs
 
 
+last_wgrad_plan = None    # set to a list to have wgrad() / wgrad_many() report (tile variant, splits) of every job, in call order
+
+
 def _wgrad_args(g, x, Cin, taps, tap_mode, t_stride, vmap, wv, dw, accumulate, extra, keep):
     """Fill a KgWgradArgs (without workspace) for one layer; tensors that must outlive the launch go to `keep`."""
     g = as_plane(g)
@@ -880,6 +890,10 @@ def wgrad(g: torch.Tensor, x: torch.Tensor, Cin: int, taps: int, tap_mode: int, 
         _check(-1, "kg_wgrad_workspace_bytes")
     ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=g.device)
     a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    if last_wgrad_plan is not None:      # tests / tuning: record the tile variant and the number of partial slabs
+        v, ns = C.c_int32(), C.c_int32()
+        _check(lib.kg_wgrad_plan_info(C.byref(a), C.byref(v), C.byref(ns)), "kg_wgrad_plan_info")
+        last_wgrad_plan[:] = [(v.value, ns.value)]
     if defer is not None:
         a.defer_reduce = 1
         per = taps * a.M * Cin
@@ -906,6 +920,10 @@ def wgrad_many(jobs: Sequence[dict]):
     nbytes = lib.kg_wgrad_many_workspace_bytes(arr, len(jobs))
     if nbytes < 0:
         _check(-1, "kg_wgrad_many_workspace_bytes")
+    if last_wgrad_plan is not None:      # tests / tuning: (tile variant, splits) of every job
+        v, ns = (C.c_int32 * len(jobs))(), (C.c_int32 * len(jobs))()
+        _check(lib.kg_wgrad_many_plan(arr, len(jobs), v, ns), "kg_wgrad_many_plan")
+        last_wgrad_plan[:] = list(zip(v, ns))
     ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=jobs[0]["g"].device)
     _check(lib.kg_wgrad_many(arr, len(jobs), ws.data_ptr(), ws.numel() * 4, _stream()), "kg_wgrad_many")
 

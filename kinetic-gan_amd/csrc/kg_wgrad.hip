@@ -58,6 +58,9 @@ inline int pair_N(const KgWgradArgs* a, int p) { return p == 0 ? a->N : a->extra
 // Fragment reads (round 4): ds_read_b128 on the small tiles, ds_read_b64 on V_BIG (wgrad_tile's RW; VGPRs 119 -> 125) -
 // a quarter / half of the LDS read instructions and waits per MFMA; critic pass 375 -> 361 us with both.
 enum { V_BIG = 0, V_6464, V_6432, V_3264, V_3232, V_COUNT };
+static_assert(V_BIG == KG_WGRAD_TILE_128x128 && V_6464 == KG_WGRAD_TILE_64x64 && V_6432 == KG_WGRAD_TILE_64x32 &&
+              V_3264 == KG_WGRAD_TILE_32x64 && V_3232 == KG_WGRAD_TILE_32x32, "variant numbers of kg_wgrad_many_plan (kgan_hip.h)");
+constexpr int V_SINGLE = V_6464;           // the tile of the single-layer kg_wgrad (kg_wgrad_plan_info reports it)
 #ifndef KG_WG_RW
 #define KG_WG_RW 4
 #endif
@@ -753,6 +756,14 @@ extern "C" int64_t kg_wgrad_workspace_bytes(const KgWgradArgs* a) {
     return (int64_t)splits * a->taps * a->M * a->Cin * (int64_t)sizeof(float);
 }
 
+extern "C" int kg_wgrad_plan_info(const KgWgradArgs* a, int32_t* variant, int32_t* splits) {
+    KG_REQUIRE(a != nullptr && variant != nullptr && splits != nullptr, "kg_wgrad_plan_info: null argument");
+    if (int rc = validate(a)) return rc;
+    *variant = V_SINGLE;
+    *splits = make_plan(a).splits;
+    return 0;
+}
+
 extern "C" int kg_wgrad(const KgWgradArgs* a, void* stream) {
     if (int rc = validate(a)) return rc;
     KG_REQUIRE(a->g && a->x && a->dw && a->ws, "kg_wgrad: null pointer");
@@ -764,8 +775,9 @@ extern "C" int kg_wgrad(const KgWgradArgs* a, void* stream) {
     dim3 grid(p.tiles_m * p.tiles_n, a->taps, p.splits);
     static const bool lds_ok = wgrad_lds_attr();
     (void)lds_ok;
-    if (kg_env().wgrad_split != 0) hipLaunchKernelGGL(kg_wgrad_bs_kernel, grid, dim3(NT), tile_lds_bs(V_6464), s, *a, p);
-    else                           hipLaunchKernelGGL(kg_wgrad_kernel, grid, dim3(NT), tile_lds(V_6464), s, *a, p);
+    static_assert(V_SINGLE == V_6464, "kg_wgrad_kernel / kg_wgrad_bs_kernel are the 64 x 64 tile");
+    if (kg_env().wgrad_split != 0) hipLaunchKernelGGL(kg_wgrad_bs_kernel, grid, dim3(NT), tile_lds_bs(V_SINGLE), s, *a, p);
+    else                           hipLaunchKernelGGL(kg_wgrad_kernel, grid, dim3(NT), tile_lds(V_SINGLE), s, *a, p);
     if (int rc = kg_launch_status("kg_wgrad")) return rc;
     if (a->defer_reduce) return 0;
     const long per = (long)a->taps * a->M * a->Cin;
@@ -799,7 +811,51 @@ Plan many_plan(const KgWgradArgs* a, float cost_target) {
     return make_plan(a, per < floor_ ? floor_ : per, t);
 }
 
+// The plan of every job of a multi-layer call, in the caller's order: each(i, variant, plan) -> 0 or an error code.  ONE
+// walk for kg_wgrad_many (which launches from it) and kg_wgrad_many_plan (which reports it).
+// (launch order = the caller's order; sorting the layers by workgroup cost, costliest first, measured 367 -> 379 us)
+// Workgroups are dispatched in index order as slots free up, so only the LAST ones shape the tail of the launch:
+// the layers in the first KG_WG_EARLYF of the pass's cost are cut into workgroups of KG_WG_EARLYX times the common
+// cost - half the partial slabs (and reduction traffic) for the wide layers a backward pass of D emits first.
+#ifndef KG_WG_EARLYX
+#define KG_WG_EARLYX 2.0f
+#endif
+#ifndef KG_WG_EARLYF
+#define KG_WG_EARLYF 0.5f
+#endif
+template <class F>
+int many_walk(const KgWgradArgs* jobs, int njobs, F&& each) {
+    const float target = many_cost_target(jobs, njobs);
+    const float total_cost = target * (float)(kg_env().wgrad_budget > 0 ? kg_env().wgrad_budget : 6144);
+    float cost_before = 0.f;
+    for (int i = 0; i < njobs; ++i) {
+        const int variant = tile_variant(&jobs[i]);
+        const float job_target = cost_before < KG_WG_EARLYF * total_cost ? target * KG_WG_EARLYX : target;
+        {
+            const Tile t = TILES[variant];
+            long chunks = 0;
+            for (int q = 0; q <= jobs[i].nextra; ++q) chunks += kg_cdiv((long)pair_N(&jobs[i], q) * jobs[i].T_out * jobs[i].V_out, t.pj);
+            cost_before += (float)((long)kg_cdiv(jobs[i].M, t.bm) * kg_cdiv(jobs[i].Cin, t.bn) * jobs[i].taps * chunks) * t.cost;
+        }
+        if (int rc = each(i, variant, many_plan(&jobs[i], job_target))) return rc;
+    }
+    return 0;
+}
+
 }  // namespace
+
+// (geometry only, like kg_wgrad_many_workspace_bytes: the operand and destination pointers do not enter the plan and may be null)
+extern "C" int kg_wgrad_many_plan(const KgWgradArgs* jobs, int32_t njobs, int32_t* variant, int32_t* splits) {
+    KG_REQUIRE(jobs != nullptr && njobs >= 1, "kg_wgrad_many_plan: no jobs");
+    KG_REQUIRE(variant != nullptr && splits != nullptr, "kg_wgrad_many_plan: null output");
+    for (int i = 0; i < njobs; ++i)
+        if (int rc = validate(&jobs[i])) return rc;
+    return many_walk(jobs, njobs, [&](int i, int v, const Plan& p) -> int {
+        variant[i] = v;
+        splits[i] = p.splits;
+        return 0;
+    });
+}
 
 extern "C" int64_t kg_wgrad_many_workspace_bytes(const KgWgradArgs* jobs, int32_t njobs) {
     if (jobs == nullptr || njobs < 1) { kg_set_error("kg_wgrad_many: no jobs"); return -1; }
@@ -822,7 +878,6 @@ extern "C" int kg_wgrad_many(const KgWgradArgs* jobs, int32_t njobs, float* ws, 
     }
     static const bool lds_ok = wgrad_lds_attr();
     (void)lds_ok;
-    const float target = many_cost_target(jobs, njobs);
     hipStream_t s = (hipStream_t)stream;
     int64_t off = 0;
     KgWgradReduceJobs rj;
@@ -851,30 +906,11 @@ extern "C" int kg_wgrad_many(const KgWgradArgs* jobs, int32_t njobs, float* ws, 
         rj.njobs = 0;
         return rc;
     };
-    // (launch order = the caller's order; sorting the layers by workgroup cost, costliest first, measured 367 -> 379 us)
-    // Workgroups are dispatched in index order as slots free up, so only the LAST ones shape the tail of the launch:
-    // the layers in the first KG_WG_EARLYF of the pass's cost are cut into workgroups of KG_WG_EARLYX times the common
-    // cost - half the partial slabs (and reduction traffic) for the wide layers a backward pass of D emits first.
-#ifndef KG_WG_EARLYX
-#define KG_WG_EARLYX 2.0f
-#endif
-#ifndef KG_WG_EARLYF
-#define KG_WG_EARLYF 0.5f
-#endif
-    const float total_cost = target * (float)(kg_env().wgrad_budget > 0 ? kg_env().wgrad_budget : 6144);
-    float cost_before = 0.f;
-    for (int i = 0; i < njobs; ++i) {
+    if (int rc = many_walk(jobs, njobs, [&](int i, int variant, const Plan& plan) -> int {
         ManyJob& j = m.job[m.njobs];
         j.a = jobs[i];
-        j.variant = tile_variant(&jobs[i]);
-        const float job_target = cost_before < KG_WG_EARLYF * total_cost ? target * KG_WG_EARLYX : target;
-        {
-            const Tile t = TILES[j.variant];
-            long chunks = 0;
-            for (int q = 0; q <= jobs[i].nextra; ++q) chunks += kg_cdiv((long)pair_N(&jobs[i], q) * jobs[i].T_out * jobs[i].V_out, t.pj);
-            cost_before += (float)((long)kg_cdiv(jobs[i].M, t.bm) * kg_cdiv(jobs[i].Cin, t.bn) * jobs[i].taps * chunks) * t.cost;
-        }
-        j.p = many_plan(&jobs[i], job_target);
+        j.variant = variant;
+        j.p = plan;
         lds = std::max(lds, bs ? tile_lds_bs(j.variant) : tile_lds(j.variant));
         const int64_t bytes = (int64_t)j.p.splits * j.a.taps * j.a.M * j.a.Cin * (int64_t)sizeof(float);
         KG_REQUIRE(ws != nullptr && off + bytes <= ws_bytes, "kg_wgrad_many: workspace %ld < %ld bytes", (long)ws_bytes,
@@ -898,7 +934,8 @@ extern "C" int kg_wgrad_many(const KgWgradArgs* jobs, int32_t njobs, float* ws, 
             if (int rc = flush_compute()) return rc;
         if (rj.njobs == KG_WGRAD_REDUCE_MAX_JOBS)
             if (int rc = flush_reduce()) return rc;
-    }
+        return 0;
+    })) return rc;
     return flush_reduce();
 }
 

@@ -76,6 +76,22 @@ int main(void) {
     for (int i = 0; i < 12; ++i) CHECK(kg_wgrad_workspace_bytes(&jobs[i]) > 0);
     int64_t wsb = kg_wgrad_many_workspace_bytes(jobs, 12);
     CHECK(wsb > 0);
+    {   /* the plan report walks the jobs as the launch does: every entry written, the slabs within the workspace query */
+        int32_t pv[12], ps[12];
+        int64_t need = 0;
+        memset(pv, 0xff, sizeof pv);
+        memset(ps, 0xff, sizeof ps);
+        CHECK(kg_wgrad_many_plan(jobs, 12, pv, ps) == 0);
+        for (int i = 0; i < 12; ++i) {
+            CHECK(pv[i] >= KG_WGRAD_TILE_128x128 && pv[i] <= KG_WGRAD_TILE_32x32 && ps[i] >= 1 && ps[i] <= 130);
+            need += (int64_t)ps[i] * jobs[i].taps * jobs[i].M * jobs[i].Cin * 4;
+            int32_t v1 = -1, s1 = -1;
+            CHECK(kg_wgrad_plan_info(&jobs[i], &v1, &s1) == 0 && v1 == KG_WGRAD_TILE_64x64);
+            CHECK(kg_wgrad_workspace_bytes(&jobs[i]) == (int64_t)s1 * jobs[i].taps * jobs[i].M * jobs[i].Cin * 4);
+        }
+        CHECK(need <= wsb);
+        CHECK(kg_wgrad_many_plan(0, 12, pv, ps) < 0 && kg_wgrad_many_plan(jobs, 12, 0, ps) < 0 && kg_wgrad_plan_info(&jobs[0], 0, 0) < 0);
+    }
     CHECK(kg_wgrad_many(jobs, 12, 0, 0, 0) < 0);                 /* no workspace: rejected before any launch */
     jobs[5].dw = jobs[2].dw;
     CHECK(kg_wgrad_many(jobs, 12, (float*)0x1000, wsb, 0) < 0 && strstr(kg_last_error(), "same dw") != 0);

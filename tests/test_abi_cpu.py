@@ -144,6 +144,46 @@ def test_wgrad_many_plan_bounds_without_gpu(lib):
     assert lib.kg_wgrad_many_workspace_bytes(arr, n) < 0 and b"taps" in lib.kg_last_error()
 
 
+def test_wgrad_plan_reports_validate_without_gpu(lib):
+    """kg_wgrad_many_plan / kg_wgrad_plan_info (additive, ABI v9): null or empty arguments are rejected by name, a bad layer
+    fails the whole call with the launcher's own message, a good one is planned on the host - nothing is launched - and the
+    plan agrees with the workspace the launcher asks for."""
+    import bench
+    v, s = (ctypes.c_int32 * 4)(), (ctypes.c_int32 * 4)()
+    arr = (_native._WgradArgs * 4)()
+    assert lib.kg_wgrad_many_plan(None, 1, v, s) < 0 and b"kg_wgrad_many_plan: no jobs" in lib.kg_last_error()
+    assert lib.kg_wgrad_many_plan(arr, 0, v, s) < 0 and b"kg_wgrad_many_plan: no jobs" in lib.kg_last_error()
+    assert lib.kg_wgrad_many_plan(arr, 4, None, s) < 0 and b"kg_wgrad_many_plan: null output" in lib.kg_last_error()
+    assert lib.kg_wgrad_many_plan(arr, 4, v, None) < 0 and b"kg_wgrad_many_plan: null output" in lib.kg_last_error()
+    assert lib.kg_wgrad_many_plan(arr, 4, v, s) < 0 and b"kg_wgrad: bad dims" in lib.kg_last_error()       # empty structs
+    one_v, one_s = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    assert lib.kg_wgrad_plan_info(None, ctypes.byref(one_v), ctypes.byref(one_s)) < 0 and b"kg_wgrad_plan_info: null" in lib.kg_last_error()
+    assert lib.kg_wgrad_plan_info(ctypes.byref(arr[0]), None, ctypes.byref(one_s)) < 0 and b"kg_wgrad_plan_info: null" in lib.kg_last_error()
+    assert lib.kg_wgrad_plan_info(ctypes.byref(arr[0]), ctypes.byref(one_v), None) < 0 and b"kg_wgrad_plan_info: null" in lib.kg_last_error()
+    assert lib.kg_wgrad_plan_info(ctypes.byref(arr[0]), ctypes.byref(one_v), ctypes.byref(one_s)) < 0 and b"bad dims" in lib.kg_last_error()
+    assert (one_v.value, one_s.value) == (-1, -1)
+    for i, (M, Cin, taps, t_out, V, st) in enumerate(bench.D_WGRAD_LAYERS[:4]):
+        a = arr[i]
+        a.N, a.M, a.T_out, a.V_out, a.Cin, a.T_in, a.V_in = 128, M, t_out, V, Cin, t_out * st, V
+        a.taps, a.tap_mode, a.t_stride = taps, _native.TAP_TIME, st
+        a.g_sC, a.g_sN, a.x_sC, a.x_sN = 128 * t_out * V, t_out * V, 128 * t_out * st * V, t_out * st * V
+    assert lib.kg_wgrad_many_plan(arr, 4, v, s) == 0
+    tiles = (_native.WGRAD_TILE_128x128, _native.WGRAD_TILE_64x64, _native.WGRAD_TILE_64x32, _native.WGRAD_TILE_32x64,
+             _native.WGRAD_TILE_32x32)
+    assert tiles == (0, 1, 2, 3, 4) and set(_native.WGRAD_TILE_NAMES) == set(tiles)
+    assert all(t in tiles for t in v) and all(1 <= n <= _native.WGRAD_MAX_SPLITS for n in s)
+    # the launch never needs more workspace than the query promises (the query plans every layer at the finer, later-half cost)
+    need = sum(4 * n * a.taps * a.M * a.Cin for n, a in zip(s, arr))
+    assert 0 < need <= lib.kg_wgrad_many_workspace_bytes(arr, 4)
+    for i in range(4):
+        assert lib.kg_wgrad_plan_info(ctypes.byref(arr[i]), ctypes.byref(one_v), ctypes.byref(one_s)) == 0
+        assert one_v.value == _native.WGRAD_TILE_64x64
+        assert lib.kg_wgrad_workspace_bytes(ctypes.byref(arr[i])) == 4 * one_s.value * arr[i].taps * arr[i].M * arr[i].Cin
+    arr[2].taps = 2
+    assert lib.kg_wgrad_many_plan(arr, 4, v, s) < 0 and b"taps" in lib.kg_last_error()
+    assert _native.last_wgrad_plan is None          # the hook is off unless a test switches it on
+
+
 def test_mapping_network_entry_points_validate_without_gpu(lib):
     """kg_linear_fwd / kg_linear_bwd / kg_embed_bwd (ABI v6): argument checking happens before any launch."""
     a = _native._LinearArgs()

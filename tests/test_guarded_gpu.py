@@ -9,7 +9,7 @@ differs between the two runs.  The kernel-level cases are the launches of tests/
 "against definition" tests) at their edge shapes - ragged M, Cin not a multiple of the tile, V = 1, N = 1 - so each also
 passes its own comparison with the definition under both patterns.
 
-Input-side variant (conv, aggconv, wgrad): the operands are handed over as guarded tensors too (storage offset 0, pattern A
+Input-side variant (conv, aggconv, wgrad, wgrad_many): the operands are handed over as guarded tensors too (storage offset 0, pattern A
 directly in front of and behind them) and the results must equal the run on plain operands bit for bit: any over-read - in
 front of a row (KgConvGroup.x_lead), past the end of `add` / `mask` / `x` - that reaches the output is a NaN there."""
 import collections
@@ -32,8 +32,9 @@ from tests import test_ema_gpu as te
 from tests import test_kernels_gpu as tk
 from tests import test_sampler_gpu as ts
 from tests import test_train_gpu as tt
+from tests import test_wgrad_tiles_gpu as tw
 from tests.guard import PATTERN_A, Guard
-from tests.util import CFG, build_pair
+from tests.util import CFG, ReloadingEnv, build_pair
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -41,7 +42,7 @@ DEV = "cuda:0"
 ENTRY = [n for n in prim_ref.NAMES + ["aggconv_label", "adam_step_ema", "step_inputs", "sample_inputs", "trunc_lerp",
                                       "loss_append", "bn_eval_coef", "genblock_infer", "mmd", "conv_pack"] if hasattr(nv, n)]
 SCRATCH_KEYS = {"ws", "keep", "args"}          # workspaces inside deferred-job records: scratch, not results
-GUARDED_OPERANDS = ("conv", "aggconv", "wgrad")
+GUARDED_OPERANDS = ("conv", "aggconv", "wgrad", "wgrad_many")
 # disc_trunk._d0_fused_route takes the fused block-0 route only while these two are the library's own functions (the CPU
 # tests swap in emulations): the model-level cases leave them unwrapped, so the production route runs
 IDENTITY_CHECKED = ("label_bias_fwd", "aggconv")
@@ -53,26 +54,7 @@ def _lib():
     nv.load_library()
 
 
-class Env:
-    """tests/test_kernels_gpu.py's `monkeypatch`: the library reads its KG_* switches when told to"""
-
-    def __init__(self, mp):
-        self.mp = mp
-
-    def setenv(self, k, v):
-        self.mp.setenv(k, v)
-        nv.reload_env()
-
-    def delenv(self, k, raising=True):
-        self.mp.delenv(k, raising)
-        nv.reload_env()
-
-    def undo(self):
-        self.mp.undo()
-        nv.reload_env()
-
-    def __getattr__(self, n):
-        return getattr(self.mp, n)
+Env = ReloadingEnv      # tests/test_kernels_gpu.py's `monkeypatch`: the library reads its KG_* switches when told to
 
 
 def _bits(t):
@@ -114,6 +96,9 @@ def _guard_operands(name, fn, args, kwargs):
                 a[k] = guarded_copy(a[k])
         if a.get("extra"):
             a["extra"] = [(guarded_copy(g), guarded_copy(x)) for g, x in a["extra"]]
+    elif name == "wgrad_many":
+        a["jobs"] = [dict(j, g=guarded_copy(j["g"]), x=guarded_copy(j["x"]), vmap=guarded_copy(j.get("vmap")),
+                          extra=[(guarded_copy(g), guarded_copy(x)) for g, x in j.get("extra", ())]) for j in a["jobs"]]
     return ba.args, ba.kwargs
 
 
@@ -152,6 +137,8 @@ class Recorder:
                 args, kwargs = _guard_operands(name, fn, args, kwargs)
             res = fn(*args, **kwargs)
             self._walk(res, "%s#%d result" % (name, n))
+            if name == "wgrad_many":           # (returns nothing: its results are the jobs' destinations)
+                self._walk([j["out"] for j in (args[0] if args else kwargs["jobs"])], "%s#%d out" % (name, n))
             return res
         return wrapped
 
@@ -249,6 +236,8 @@ KERNEL_CASES = {
     "wgrad vertex gather": _k(tk.test_wgrad_with_vertex_gather, expect=["wgrad"]),
     "wgrad_many": _k(tk.test_wgrad_many_layers_one_call, expect=["wgrad_many"]),
     "wgrad_many, several launches": _k(tk.test_wgrad_many_more_layers_than_one_launch_holds, expect=["wgrad_many"]),
+    "wgrad_many 128x128 tile, ragged rows and channels": _k(tw.test_big_tile_forced_at_small_column_counts, "forced 128x128: ragged 130x200, pairs", "fp32", expect=["wgrad_many"]),
+    "wgrad_many bf16-split tiles": _k(tw.test_small_tiles_all_in_one_call, "bf16split", expect=["wgrad_many"]),
     "aggconv ragged (M 33, Cin 40)": _k(tk.test_aggconv_fused_gcn, "ntu", 3, False, 9, 40, 33, 8, 0, expect=["aggconv"]),
     "aggconv block 0 weights inside their parent": _k(tk.test_aggconv_fused_gcn, "h36m", 0, True, 3, 2, 32, 32, 10, expect=["aggconv"]),
     "aggconv_label": _k(td.test_aggconv_label_vs_definition, "h36m", 10, 2, 13, 64, expect=["aggconv_label"]),
@@ -380,6 +369,9 @@ INPUT_SIDE = {
     "wgrad channel-block taps": _k(tk.test_wgrad, 2, 63, 32, 64, 11, 3, TAP_CHANBLOCK, 1),
     "wgrad operand pairs": _k(tk.test_wgrad_operand_pairs, (3, 5), 70, 65, 10, 7, 3, TAP_TIME, 2),
     "wgrad vertex gather": _k(tk.test_wgrad_with_vertex_gather),
+    "wgrad_many 128x128 tile, ragged rows and channels": _k(tw.test_big_tile_forced_at_small_column_counts, "forced 128x128: ragged 130x200, pairs", "fp32"),
+    "wgrad_many 128x128 tile, 129x255": _k(tw.test_big_tile_forced_at_small_column_counts, "forced 128x128: ragged 129x255, 70 columns", "bf16split"),
+    "wgrad_many bf16-split tiles": _k(tw.test_small_tiles_all_in_one_call, "bf16split"),
 }
 
 

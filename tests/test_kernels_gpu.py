@@ -12,6 +12,7 @@ from kinetic_gan_amd._native import TAP_CHANBLOCK, TAP_TIME, Group, WView
 from oracle import prim_ref as pr
 from tests import guard
 from tests.guard import guard_all  # noqa: F401  (autouse: every test of this module runs on poisoned, red-zoned buffers)
+from tests.util import ReloadingEnv
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
@@ -21,18 +22,7 @@ TOL = 2e-5
 def monkeypatch(monkeypatch):
     """the library caches its KG_* switches when it is loaded (no getenv on the launch path): every change of the
     environment made through this fixture is followed by kg_reload_env()"""
-    class Reloading:
-        def setenv(self, k, v):
-            monkeypatch.setenv(k, v)
-            nv.reload_env()
-
-        def delenv(self, k, raising=True):
-            monkeypatch.delenv(k, raising)
-            nv.reload_env()
-
-        def __getattr__(self, n):
-            return getattr(monkeypatch, n)
-    return Reloading()
+    return ReloadingEnv(monkeypatch)
 
 
 def pytest_generate_tests(metafunc):

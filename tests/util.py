@@ -31,6 +31,29 @@ def emulated_native():
         restore()
 
 
+class ReloadingEnv:
+    """pytest's `monkeypatch` for the library's KG_* switches: the library caches them when it is loaded (no getenv on the
+    launch path), so every change of the environment made through this wrapper is followed by kg_reload_env()"""
+
+    def __init__(self, monkeypatch):
+        self.mp = monkeypatch
+
+    def setenv(self, k, v):
+        self.mp.setenv(k, v)
+        _native.reload_env()
+
+    def delenv(self, k, raising=True):
+        self.mp.delenv(k, raising)
+        _native.reload_env()
+
+    def undo(self):
+        self.mp.undo()
+        _native.reload_env()
+
+    def __getattr__(self, n):
+        return getattr(self.mp, n)
+
+
 def build_pair(cfg_name, device="cpu", seed_g=1, seed_d=2):
     """(G, D) on the HIP path and (Go, Do) oracle modules with identical parameters."""
     c = CFG[cfg_name]
