@@ -850,6 +850,63 @@ typedef struct KgFrechetArgs {
 int64_t kg_frechet_workspace_bytes(const KgFrechetArgs* a);   /* < 0 for invalid shapes                              */
 int     kg_frechet(const KgFrechetArgs* a, void* stream);
 
+/* ---- several fake sets against ONE real set whose Frechet side is cached (additive, ABI v9; DESIGN.md 19, csrc/kg_frechet.hip)
+ * The Evaluator's case: the real set is fixed for a whole run and every named generator is scored against it.  Strides, diff,
+ * d_outer / d_inner, the fp64 arithmetic and the shape rules are those of kg_frechet; e = d + (d & 1) below.
+ * kg_frechet_real: the real side of ONE (data, diff) pair: mu_real (classes, d), tr_real (classes) = tr S_R, G (classes, e, e)
+ * = V diag(sqrt(max(l, 0))) of S_R row-major (the padding row and column of an odd d are zero), sweeps_real (classes).  Three
+ * launches: moments of the real set alone - chunked exactly as kg_frechet chunks the real set of a call with the same n,
+ * frames, diff and classes (that chunking depends on P_r and classes alone) -, merge, one workgroup per class running the
+ * Jacobi iteration with vectors.  The four arrays hold the bits kg_frechet forms internally.
+ * ws = kg_frechet_real_workspace_bytes(a) = 8 classes (nch_r + 1) (d + d*d) bytes, nch_r the real set's chunks.
+ * kg_frechet_sets: nsets (1..KG_FRECHET_MAX_SETS) fake sets fake[g] with shared strides and m against that cache, which is an
+ * INPUT read when the launches run; the real data is never touched.  Four launches whatever nsets is: moments of all fake
+ * sets (chunked as kg_frechet chunks a fake set of m samples), merge, one workgroup per (set, class) - W = S_F G, H = sym(G^T
+ * W), the Jacobi iteration without vectors, T, the terms and the FD with the loops of kg_frechet's solve -, finish (per set the
+ * class mean in fp64 and its fp32 rounding mean32, the word kg_eval_record2 reads).  For every set g, values[g], terms[g] and
+ * sweeps[g] equal, bit for bit, values, terms and sweeps[:, 1] of kg_frechet(real, fake[g]) on the same data, mean[g] its
+ * mean, and sweeps_real its sweeps[:, 0]; the grouping into sets shows in no bit.
+ * ws = kg_frechet_sets_workspace_bytes(a) = 8 nsets classes (nch_f + 1) (d + d*d) bytes, nch_f the chunks of one fake set.
+ * No atomics, no ticket, no scratch; the workspace contents on entry do not matter; every output word is written; nothing is
+ * synchronised; capturable on one stream.
+ * Rejected (< 0, kg_last_error() names the field) before any GPU call: what kg_frechet rejects for the side in question; nsets
+ * outside [1, KG_FRECHET_MAX_SETS]; a null fake[g] with g < nsets; a null cache or output pointer; ws null, misaligned or
+ * ws_bytes too small.                                                                                                        */
+#define KG_FRECHET_MAX_SETS 4
+typedef struct KgFrechetRealArgs {
+    const float* real;  int64_t r_sc, r_ss, r_sf, r_so;   /* class, sample, frame, outer-dimension strides (elements)    */
+    int32_t n;                      /* real samples per class                                                          */
+    int32_t frames, diff;
+    int32_t d_outer, d_inner;
+    int32_t classes;
+    double* mu_real;                /* (classes, d)                                                                    */
+    double* tr_real;                /* (classes)                                                                       */
+    double* G;                      /* (classes, e, e)                                                                 */
+    int32_t* sweeps_real;           /* (classes)                                                                       */
+    void* ws;  int64_t ws_bytes;
+} KgFrechetRealArgs;
+typedef struct KgFrechetSetsArgs {
+    const float* fake[KG_FRECHET_MAX_SETS];  int64_t f_sc, f_ss, f_sf, f_so;   /* fake[0 .. nsets): strides and m are shared */
+    int32_t nsets;
+    int32_t m;                      /* fake samples per class                                                          */
+    int32_t frames, diff;
+    int32_t d_outer, d_inner;
+    int32_t classes;
+    const double* mu_real;          /* INPUT: the cache of kg_frechet_real for the same frames, diff, d and classes    */
+    const double* tr_real;
+    const double* G;
+    double* values;                 /* (nsets, classes): FD                                                            */
+    double* terms;                  /* (nsets, classes, 4)                                                             */
+    int32_t* sweeps;                /* (nsets, classes): the sweeps of H                                               */
+    double* mean;                   /* (nsets)                                                                         */
+    float* mean32;                  /* (nsets): (float)mean                                                            */
+    void* ws;  int64_t ws_bytes;
+} KgFrechetSetsArgs;
+int64_t kg_frechet_real_workspace_bytes(const KgFrechetRealArgs* a);   /* < 0 for invalid shapes                     */
+int     kg_frechet_real(const KgFrechetRealArgs* a, void* stream);
+int64_t kg_frechet_sets_workspace_bytes(const KgFrechetSetsArgs* a);   /* < 0 for invalid shapes                     */
+int     kg_frechet_sets(const KgFrechetSetsArgs* a, void* stream);
+
 /* ---- inputs of one training iteration (additive, ABI v9; DESIGN.md 11, csrc/kg_input.hip) ---------------------------
  * kg_step_inputs writes, in ONE launch, every input of iteration s = *step and then stores s + 1 (last workgroup).
  * Batch: b = s mod batches_per_epoch, e = s div batches_per_epoch, row r_j = perm[(e & 1)*perm_stride + (b*world +

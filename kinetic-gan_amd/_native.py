@@ -348,6 +348,27 @@ class _FrechetArgs(C.Structure):
                 ("mu_real", C.c_void_p), ("mu_fake", C.c_void_p), ("cov_real", C.c_void_p), ("cov_fake", C.c_void_p),
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
+FRECHET_MAX_SETS = 4
+
+
+class _FrechetRealArgs(C.Structure):
+    _fields_ = [("real", c_f32p), ("r_sc", C.c_int64), ("r_ss", C.c_int64), ("r_sf", C.c_int64), ("r_so", C.c_int64),
+                ("n", C.c_int32), ("frames", C.c_int32), ("diff", C.c_int32),
+                ("d_outer", C.c_int32), ("d_inner", C.c_int32), ("classes", C.c_int32),
+                ("mu_real", C.c_void_p), ("tr_real", C.c_void_p), ("G", C.c_void_p), ("sweeps_real", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
+class _FrechetSetsArgs(C.Structure):
+    _fields_ = [("fake", c_f32p * FRECHET_MAX_SETS), ("f_sc", C.c_int64), ("f_ss", C.c_int64), ("f_sf", C.c_int64),
+                ("f_so", C.c_int64),
+                ("nsets", C.c_int32), ("m", C.c_int32), ("frames", C.c_int32), ("diff", C.c_int32),
+                ("d_outer", C.c_int32), ("d_inner", C.c_int32), ("classes", C.c_int32),
+                ("mu_real", C.c_void_p), ("tr_real", C.c_void_p), ("G", C.c_void_p),
+                ("values", C.c_void_p), ("terms", C.c_void_p), ("sweeps", C.c_void_p), ("mean", C.c_void_p),
+                ("mean32", c_f32p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
 STEP_MAX_PLANES = 8
 STREAM_Z, STREAM_ALPHA, STREAM_NOISE_D, STREAM_NOISE_G = 0, 1, 2, 3
 
@@ -502,6 +523,10 @@ EXPORTS = {
     "kg_prdc_sets": (C.c_int, [C.POINTER(_PrdcSetsArgs), C.c_void_p]),
     "kg_frechet_workspace_bytes": (C.c_int64, [C.POINTER(_FrechetArgs)]),
     "kg_frechet": (C.c_int, [C.POINTER(_FrechetArgs), C.c_void_p]),
+    "kg_frechet_real_workspace_bytes": (C.c_int64, [C.POINTER(_FrechetRealArgs)]),
+    "kg_frechet_real": (C.c_int, [C.POINTER(_FrechetRealArgs), C.c_void_p]),
+    "kg_frechet_sets_workspace_bytes": (C.c_int64, [C.POINTER(_FrechetSetsArgs)]),
+    "kg_frechet_sets": (C.c_int, [C.POINTER(_FrechetSetsArgs), C.c_void_p]),
     "kg_step_inputs": (C.c_int, [C.POINTER(_StepInputsArgs), C.c_void_p]),
     "kg_loss_append": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kg_adam_step_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
@@ -2477,6 +2502,118 @@ def frechet(real: FrechetView, fake: FrechetView, n: int, m: int, frames: int, d
     pts = (n + m) * (frames - int(bool(diff)))
     _count("kg_frechet", 2.0 * float(pts) * d * d * classes)
     _check(lib.kg_frechet(C.byref(a), _stream()), "kg_frechet")
+    return out
+
+
+def _frechet_real_shape(n: int, frames: int, diff: bool, d_outer: int, d_inner: int, classes: int) -> _FrechetRealArgs:
+    a = _FrechetRealArgs()
+    a.n, a.frames, a.diff = int(n), int(frames), int(bool(diff))
+    a.d_outer, a.d_inner, a.classes = int(d_outer), int(d_inner), int(classes)
+    return a
+
+
+def frechet_real_workspace_bytes(n: int, frames: int, diff: bool, d_outer: int, d_inner: int, classes: int) -> int:
+    """kg_frechet_real_workspace_bytes of a shape = 8 classes (nch_r + 1) (d + d*d) (RuntimeError naming the field for a
+    shape kg_frechet_real rejects); no GPU call"""
+    nbytes = load_library().kg_frechet_real_workspace_bytes(C.byref(_frechet_real_shape(n, frames, diff, d_outer, d_inner, classes)))
+    if nbytes < 0:
+        _check(-1, "kg_frechet_real_workspace_bytes")
+    return nbytes
+
+
+def frechet_real(view: FrechetView, n: int, frames: int, diff: bool, d_outer: int, d_inner: int, classes: int,
+                 ws: Optional[torch.Tensor] = None) -> dict:
+    """Enqueue kg_frechet_real: the real side of one (data, diff) pair, once (moments, merge and one Jacobi solve with
+    vectors per class; three launches, no host synchronisation).  Returns the cache ``frechet_sets`` reads, a dict of
+    device tensors: mu_real (classes, d), tr_real (classes), G (classes, e, e) fp64 with e = d + (d & 1), sweeps_real
+    (classes) int32 - the bits ``frechet`` forms internally for the same real set."""
+    if view.t.dtype != torch.float32:
+        raise TypeError(f"kg_frechet_real: fp32 only, got {view.t.dtype}")
+    nbytes = frechet_real_workspace_bytes(n, frames, diff, d_outer, d_inner, classes)
+    _need_cuda(view.t, ws)
+    if not _frechet_extent_ok(view, n, frames, d_outer, d_inner, classes):
+        raise ValueError("kg_frechet_real: the strides of real reach outside its tensor")
+    dev = view.t.device
+    if ws is None:
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    elif not ws.is_contiguous() or ws.dtype != torch.float64:
+        raise ValueError("kg_frechet_real: ws must be a contiguous float64 tensor")
+    d = d_outer * d_inner
+    e = d + (d & 1)
+    out = dict(mu_real=torch.empty((classes, d), dtype=torch.float64, device=dev),
+               tr_real=torch.empty(classes, dtype=torch.float64, device=dev),
+               G=torch.empty((classes, e, e), dtype=torch.float64, device=dev),
+               sweeps_real=torch.empty(classes, dtype=torch.int32, device=dev))
+    a = _frechet_real_shape(n, frames, diff, d_outer, d_inner, classes)
+    a.real, a.r_sc, a.r_ss, a.r_sf, a.r_so = view.t.data_ptr(), view.sc, view.ss, view.sf, view.so
+    a.mu_real, a.tr_real, a.G, a.sweeps_real = (out[k].data_ptr() for k in ("mu_real", "tr_real", "G", "sweeps_real"))
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 8
+    _count("kg_frechet_real", 2.0 * float(n * (frames - int(bool(diff)))) * d * d * classes)
+    _check(load_library().kg_frechet_real(C.byref(a), _stream()), "kg_frechet_real")
+    return out
+
+
+def _frechet_sets_shape(nsets: int, m: int, frames: int, diff: bool, d_outer: int, d_inner: int, classes: int) -> _FrechetSetsArgs:
+    a = _FrechetSetsArgs()
+    a.nsets, a.m, a.frames, a.diff = int(nsets), int(m), int(frames), int(bool(diff))
+    a.d_outer, a.d_inner, a.classes = int(d_outer), int(d_inner), int(classes)
+    return a
+
+
+def frechet_sets_workspace_bytes(nsets: int, m: int, frames: int, diff: bool, d_outer: int, d_inner: int, classes: int) -> int:
+    """kg_frechet_sets_workspace_bytes of a shape = 8 nsets classes (nch_f + 1) (d + d*d) (RuntimeError naming the field
+    for a shape kg_frechet_sets rejects); no GPU call"""
+    nbytes = load_library().kg_frechet_sets_workspace_bytes(
+        C.byref(_frechet_sets_shape(nsets, m, frames, diff, d_outer, d_inner, classes)))
+    if nbytes < 0:
+        _check(-1, "kg_frechet_sets_workspace_bytes")
+    return nbytes
+
+
+def frechet_sets(cache: dict, fakes: Sequence[torch.Tensor], f_sc: int, f_ss: int, f_sf: int, f_so: int, m: int, frames: int,
+                 diff: bool, d_outer: int, d_inner: int, classes: int, ws: Optional[torch.Tensor] = None) -> dict:
+    """Enqueue kg_frechet_sets: the ``fakes`` (1..FRECHET_MAX_SETS fp32 tensors walked with the shared strides f_sc / f_ss /
+    f_sf / f_so) against the ``cache`` of ``frechet_real`` for the same frames, diff, d and classes; four launches whatever
+    the number of sets, no host synchronisation, the real data is not read.  Returns dict(values (nsets, classes), terms
+    (nsets, classes, 4), mean (nsets) fp64, sweeps (nsets, classes) int32, mean32 (nsets) fp32) on the device; every entry
+    of set g equals, bit for bit, that of ``frechet(real, fakes[g])`` (sweeps: its column 1).  ``ws`` as in ``frechet``."""
+    lib = load_library()
+    fakes = list(fakes)
+    for t in fakes:
+        if t.dtype != torch.float32:
+            raise TypeError(f"kg_frechet_sets: fp32 only, got {t.dtype}")
+    nsets = len(fakes)
+    nbytes = frechet_sets_workspace_bytes(nsets, m, frames, diff, d_outer, d_inner, classes)
+    d = d_outer * d_inner
+    e = d + (d & 1)
+    mu_real, tr_real, G = cache["mu_real"], cache["tr_real"], cache["G"]
+    _need_cuda(mu_real, tr_real, G, ws, *fakes)
+    for g, t in enumerate(fakes):
+        if not _frechet_extent_ok(FrechetView(t, f_sc, f_ss, f_sf, f_so), m, frames, d_outer, d_inner, classes):
+            raise ValueError(f"kg_frechet_sets: the strides of fake set {g} reach outside its tensor")
+    for name, t, cnt in (("mu_real", mu_real, classes * d), ("tr_real", tr_real, classes), ("G", G, classes * e * e)):
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != cnt:
+            raise ValueError(f"kg_frechet_sets: cache entry {name} must be a contiguous float64 tensor of {cnt} elements")
+    dev = fakes[0].device
+    if ws is None:
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    elif not ws.is_contiguous() or ws.dtype != torch.float64:
+        raise ValueError("kg_frechet_sets: ws must be a contiguous float64 tensor")
+    out = dict(values=torch.empty((nsets, classes), dtype=torch.float64, device=dev),
+               terms=torch.empty((nsets, classes, 4), dtype=torch.float64, device=dev),
+               sweeps=torch.empty((nsets, classes), dtype=torch.int32, device=dev),
+               mean=torch.empty(nsets, dtype=torch.float64, device=dev),
+               mean32=torch.empty(nsets, dtype=torch.float32, device=dev))
+    a = _frechet_sets_shape(nsets, m, frames, diff, d_outer, d_inner, classes)
+    for g, t in enumerate(fakes):
+        a.fake[g] = t.data_ptr()
+    a.f_sc, a.f_ss, a.f_sf, a.f_so = int(f_sc), int(f_ss), int(f_sf), int(f_so)
+    a.mu_real, a.tr_real, a.G = mu_real.data_ptr(), tr_real.data_ptr(), G.data_ptr()
+    a.values, a.terms, a.sweeps = out["values"].data_ptr(), out["terms"].data_ptr(), out["sweeps"].data_ptr()
+    a.mean, a.mean32 = out["mean"].data_ptr(), out["mean32"].data_ptr()
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 8
+    _count("kg_frechet_sets", 2.0 * nsets * float(m * (frames - int(bool(diff)))) * d * d * classes)
+    _check(lib.kg_frechet_sets(C.byref(a), _stream()), "kg_frechet_sets")
     return out
 
 

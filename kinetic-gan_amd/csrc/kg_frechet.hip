@@ -18,6 +18,14 @@
 //   T = sum sqrt(max(e, 0)), and the four terms and FD of the class.
 // kg_frechet_mean_kernel: the class mean (fp64 sum in class order).
 // No atomics, no ticket, no scratch, no dynamically indexed private array; every launch on the caller's stream.
+//
+// The Evaluator's split: the real set of a run never changes, so kg_frechet_real runs the moments and merge
+// launch on the real set alone (the chunking kg_frechet gives it) and kg_frechet_real_solve_kernel - the first half of the
+// solve - and keeps mu_r, tr S_r, G and the sweeps; kg_frechet_sets runs the moments and merge launch on up to
+// KG_FRECHET_MAX_SETS fake sets (the chunking kg_frechet gives a fake set), kg_frechet_sets_solve_kernel - the second half
+// of the solve, one workgroup per (set, class), G read from the cache into the place where kg_frechet_solve_kernel forms
+// it - and kg_frechet_sets_finish_kernel.  The moments and merge kernels walk a list of sets; every sum keeps its order,
+// so each output is, bit for bit, that of kg_frechet(real, fake[g]).
 #include <math.h>
 
 #include "kg_common.h"
@@ -34,6 +42,8 @@ constexpr int FR_MAXSWEEPS = 40;
 constexpr long FR_MAX_POINTS = 1L << 24;
 constexpr long FR_MAX_GRID = 1L << 24;  // workgroups of one launch (exclusive): grid x 256 threads stays below 2^32
 constexpr int FR_MAXPAIRS = FR_MAXD / 2;
+constexpr int FR_MAXSETS = KG_FRECHET_MAX_SETS;     // sets of one moments / merge launch (kg_frechet: real, fake)
+static_assert(FR_MAXSETS >= 2, "kg_frechet's launches hold the real and the fake set");
 constexpr int FR_HREG = FR_MAXD * FR_MAXD / FR_SOLVE_NT;    // entries of H a thread carries through the barrier
 static_assert(FR_MAXD % 16 == 0 && FR_MAXD % 2 == 0 && FR_HREG * FR_SOLVE_NT == FR_MAXD * FR_MAXD, "tile plan");
 
@@ -42,17 +52,19 @@ struct FrSet {
     long sc, ss, sf, so;        // class, sample, frame, outer strides (elements); the inner run is contiguous
     int P;                      // points per class
     int cs, nch;                // points per chunk (a multiple of FR_KB), chunks
+    int ch0;                    // chunks of the sets in front of this one
 };
 
 struct FrDev {
-    FrSet set[2];               // 0 = real, 1 = fake
+    FrSet set[FR_MAXSETS];      // kg_frechet: 0 = real, 1 = fake; kg_frechet_real: the real set; kg_frechet_sets: the fake sets
+    int nset, per;              // sets in use, chunks of all of them (of one class)
     FastDiv inner, fr;          // j = o * d_inner + e;  point p = sample * fr + frame
     int d, diff, classes;
-    double* part;               // ws: (classes, nch_r + nch_f, d + d*d)
-    double* mu;                 // ws: (classes, 2, d)
-    double* cov;                // ws: (classes, 2, d, d)
-    double* mu_out[2];          // the caller's arrays or null
-    double* cov_out[2];
+    double* part;               // ws: (classes, per, d + d*d)
+    double* mu;                 // ws: (classes, nset, d)
+    double* cov;                // ws: (classes, nset, d, d)
+    double* mu_out[FR_MAXSETS]; // the caller's arrays or null
+    double* cov_out[FR_MAXSETS];
     double* values;  double* terms;  int32_t* sweeps;
 };
 
@@ -68,11 +80,12 @@ __global__ __launch_bounds__(FR_NT) void kg_frechet_moments_kernel(FrDev a) {
     __shared__ double pts[FR_KB][W];
     __shared__ double shift[W];
     const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
-    const unsigned per = (unsigned)(a.set[0].nch + a.set[1].nch);
+    const unsigned per = (unsigned)a.per;
     const unsigned cls = blockIdx.x / per, t = blockIdx.x % per;
-    const int set = t >= (unsigned)a.set[0].nch ? 1 : 0;
-    const int chunk = (int)t - (set ? a.set[0].nch : 0);
+    int set = 0;
+    while (set + 1 < a.nset && t >= (unsigned)a.set[set + 1].ch0) ++set;
     const FrSet X = a.set[set];
+    const int chunk = (int)t - X.ch0;
     const float* base = X.p + (long)cls * X.sc;
     const int d = a.d;
 
@@ -147,15 +160,15 @@ __global__ __launch_bounds__(FR_NT) void kg_frechet_moments_kernel(FrDev a) {
 __global__ __launch_bounds__(FR_NT) void kg_frechet_merge_kernel(FrDev a) {
     const int d = a.d, dd = d * d;
     const unsigned nb = (unsigned)((dd + FR_NT - 1) / FR_NT);
-    const unsigned cs = blockIdx.x / nb, tile = blockIdx.x % nb;        // cs = class * 2 + set
-    const unsigned cls = cs >> 1;
-    const int set = (int)(cs & 1);
+    const unsigned cs = blockIdx.x / nb, tile = blockIdx.x % nb;        // cs = class * nset + set
+    const unsigned cls = cs / (unsigned)a.nset;
+    const int set = (int)(cs % (unsigned)a.nset);
     const int entry = (int)tile * FR_NT + (int)threadIdx.x;
     if (entry >= dd) return;
     const int ra = entry / d, cb = entry % d;
     const FrSet X = a.set[set];
-    const long per = a.set[0].nch + a.set[1].nch, stride = (long)d + dd;
-    const double* part = a.part + ((long)cls * per + (set ? a.set[0].nch : 0)) * stride;
+    const long per = a.per, stride = (long)d + dd;
+    const double* part = a.part + ((long)cls * per + X.ch0) * stride;
     double m2 = 0.0, sa = 0.0, sb = 0.0;
     for (int c = 0; c < X.nch; ++c) {
         const double* q = part + (long)c * stride;
@@ -370,6 +383,141 @@ __global__ void kg_frechet_mean_kernel(const double* values, double* mean, int c
     *mean = s / (double)classes;
 }
 
+// ---- the real side alone, and several fake sets against its cache -----------------------------------------
+
+struct FrRealDev {
+    const double* cov;          // ws: (classes, d, d), the merge launch's S_r
+    int d;
+    double* G;                  // (classes, m, m)
+    double* tr;                 // (classes)
+    int32_t* sweeps;            // (classes)
+};
+
+// The first half of kg_frechet_solve_kernel: S_r = V diag(l) V^T, G = V sqrt(max(l, 0)) - the words that kernel holds in LDS
+// when it forms W -, tr S_r in its order, the sweeps.
+__global__ __launch_bounds__(FR_SOLVE_NT) void kg_frechet_real_solve_kernel(FrRealDev a) {
+    extern __shared__ __attribute__((aligned(16))) double fr_lds[];
+    __shared__ FrSmall sm;
+    const int tid = threadIdx.x, d = a.d, dd = d * d;
+    const int m = d + (d & 1), ld = m + 1;
+    double* A = fr_lds;
+    double* V = fr_lds + m * ld;
+    const unsigned cls = blockIdx.x;
+    const double* Sr = a.cov + (long)cls * dd;
+
+    for (int e = tid; e < m * m; e += FR_SOLVE_NT) {
+        const int i = e / m, j = e % m;
+        A[i * ld + j] = (i < d && j < d) ? Sr[i * d + j] : 0.0;
+        V[i * ld + j] = i == j ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    const int sweeps_r = fr_jacobi(A, V, m, ld, d, sm);
+
+    if (tid < m) sm.root[tid] = sqrt(fmax(A[tid * ld + tid], 0.0));
+    __syncthreads();
+    double* G = a.G + (long)cls * m * m;
+    for (int e = tid; e < m * m; e += FR_SOLVE_NT) G[e] = V[(e / m) * ld + (e % m)] * sm.root[e % m];
+    if (tid == 0) {
+        double trr = 0.0;
+        for (int i = 0; i < d; ++i) trr += Sr[i * d + i];
+        a.tr[cls] = trr;
+        a.sweeps[cls] = sweeps_r;
+    }
+}
+
+struct FrSetsDev {
+    const double* mu;           // ws: (classes, nsets, d)
+    const double* cov;          // ws: (classes, nsets, d, d)
+    const double* mu_real;      // the cache: (classes, d), (classes), (classes, m, m)
+    const double* tr_real;
+    const double* G;
+    int d, nsets, classes;
+    double* values;  double* terms;  int32_t* sweeps;       // (nsets, classes), (nsets, classes, 4), (nsets, classes)
+};
+
+// The second half of kg_frechet_solve_kernel for one (set, class): G from the cache, then W, H, the eigenvalues of H, T and
+// the terms with that kernel's loops.
+__global__ __launch_bounds__(FR_SOLVE_NT) void kg_frechet_sets_solve_kernel(FrSetsDev a) {
+    extern __shared__ __attribute__((aligned(16))) double fr_lds[];
+    __shared__ FrSmall sm;
+    const int tid = threadIdx.x, d = a.d, dd = d * d;
+    const int m = d + (d & 1), ld = m + 1;
+    double* A = fr_lds;
+    double* V = fr_lds + m * ld;
+    const unsigned g = blockIdx.x / (unsigned)a.classes, cls = blockIdx.x % (unsigned)a.classes;
+    const double* Sf = a.cov + ((long)cls * a.nsets + g) * dd;
+    const double* G = a.G + (long)cls * m * m;
+
+    for (int e = tid; e < m * m; e += FR_SOLVE_NT) V[(e / m) * ld + (e % m)] = G[e];
+    __syncthreads();
+    for (int e = tid; e < m * m; e += FR_SOLVE_NT) {           // W = S_f G
+        const int i = e / m, j = e % m;
+        double w = 0.0;
+        if (i < d) {
+            for (int b = 0; b < d; ++b) w = fma(Sf[i * d + b], V[b * ld + j], w);
+        }
+        A[i * ld + j] = w;
+    }
+    __syncthreads();
+    double h[FR_HREG];                                          // H = sym(G^T W), upper entries, through registers
+#pragma unroll
+    for (int u = 0; u < FR_HREG; ++u) {
+        const int e = tid + u * FR_SOLVE_NT;
+        const int i = e / m, j = e % m;
+        double x = 0.0, y = 0.0;
+        if (e < m * m && i <= j) {
+            for (int b = 0; b < m; ++b) {
+                x = fma(V[b * ld + i], A[b * ld + j], x);
+                y = fma(V[b * ld + j], A[b * ld + i], y);
+            }
+        }
+        h[u] = 0.5 * (x + y);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < FR_HREG; ++u) {
+        const int e = tid + u * FR_SOLVE_NT;
+        const int i = e / m, j = e % m;
+        if (e < m * m && i <= j) {
+            A[i * ld + j] = h[u];
+            A[j * ld + i] = h[u];
+        }
+    }
+    __syncthreads();
+    const int sweeps_h = fr_jacobi(A, nullptr, m, ld, d, sm);
+
+    if (tid == 0) {
+        const double* mr = a.mu_real + (long)cls * d;
+        const double* mf = a.mu + ((long)cls * a.nsets + g) * d;
+        double dmu2 = 0.0, trf = 0.0, T = 0.0;
+        for (int i = 0; i < d; ++i) {
+            const double df = mr[i] - mf[i];
+            dmu2 += df * df;
+            trf += Sf[i * d + i];
+        }
+        const double trr = a.tr_real[cls];
+        for (int i = 0; i < m; ++i) T += sqrt(fmax(A[i * ld + i], 0.0));
+        const long o = (long)g * a.classes + cls;
+        a.terms[o * 4 + 0] = dmu2;
+        a.terms[o * 4 + 1] = trr;
+        a.terms[o * 4 + 2] = trf;
+        a.terms[o * 4 + 3] = T;
+        a.values[o] = ((dmu2 + trr) + trf) - 2.0 * T;
+        a.sweeps[o] = sweeps_h;
+    }
+}
+
+// per set: the class mean as kg_frechet_mean_kernel forms it, and its fp32 rounding (the word kg_eval_record2 reads)
+__global__ void kg_frechet_sets_finish_kernel(const double* values, double* mean, float* mean32, int classes, int nsets) {
+    const int g = (int)threadIdx.x;
+    if (blockIdx.x != 0 || g >= nsets) return;
+    double s = 0.0;
+    for (int c = 0; c < classes; ++c) s += values[(long)g * classes + c];
+    const double mu = s / (double)classes;
+    mean[g] = mu;
+    mean32[g] = (float)mu;
+}
+
 struct FrPlan {
     long P[2];
     int cs[2], nch[2];
@@ -402,11 +550,13 @@ void frechet_plan(const KgFrechetArgs* a, FrPlan& p) {
     p.lds_solve = 2 * p.m * (p.m + 1) * 8;
 }
 
-int frechet_validate(const KgFrechetArgs* a, const char* who, FrPlan& p) {
+// sides: 1 = the real set, 2 = the fake set(s), 3 = both (kg_frechet); nset: sets of the moments / merge launches.  A call
+// for one side alone is handed the other side's count equal to its own, so only its own field is ever named.
+int frechet_validate(const KgFrechetArgs* a, const char* who, FrPlan& p, int sides = 3, int nset = 2) {
     KG_REQUIRE(a != nullptr, "%s: null args", who);
     KG_REQUIRE(a->classes >= 1, "%s: classes=%d < 1", who, a->classes);
-    KG_REQUIRE(a->n >= 1, "%s: n=%d < 1", who, a->n);
-    KG_REQUIRE(a->m >= 1, "%s: m=%d < 1", who, a->m);
+    KG_REQUIRE(!(sides & 1) || a->n >= 1, "%s: n=%d < 1", who, a->n);
+    KG_REQUIRE(!(sides & 2) || a->m >= 1, "%s: m=%d < 1", who, a->m);
     KG_REQUIRE(a->d_outer >= 1, "%s: d_outer=%d < 1", who, a->d_outer);
     KG_REQUIRE(a->d_inner >= 1, "%s: d_inner=%d < 1", who, a->d_inner);
     KG_REQUIRE(a->diff == 0 || a->diff == 1, "%s: diff=%d is neither 0 (pose) nor 1 (motion)", who, a->diff);
@@ -415,13 +565,21 @@ int frechet_validate(const KgFrechetArgs* a, const char* who, FrPlan& p) {
     KG_REQUIRE(a->frames >= 1 + a->diff, "%s: frames=%d < %d%s", who, a->frames, 1 + a->diff,
                a->diff ? " (a motion point needs two frames)" : "");
     const long fr = (long)a->frames - a->diff;
-    KG_REQUIRE((long)a->n * fr >= 2, "%s: n=%d gives P=%ld < 2 real points", who, a->n, (long)a->n * fr);
-    KG_REQUIRE((long)a->m * fr >= 2, "%s: m=%d gives P=%ld < 2 fake points", who, a->m, (long)a->m * fr);
-    KG_REQUIRE((long)a->n * fr <= FR_MAX_POINTS, "%s: n=%d x frames=%d gives P=%ld real points, above 2^24", who, a->n, a->frames,
-               (long)a->n * fr);
-    KG_REQUIRE((long)a->m * fr <= FR_MAX_POINTS, "%s: m=%d x frames=%d gives P=%ld fake points, above 2^24", who, a->m, a->frames,
-               (long)a->m * fr);
+    KG_REQUIRE(!(sides & 1) || (long)a->n * fr >= 2, "%s: n=%d gives P=%ld < 2 real points", who, a->n, (long)a->n * fr);
+    KG_REQUIRE(!(sides & 2) || (long)a->m * fr >= 2, "%s: m=%d gives P=%ld < 2 fake points", who, a->m, (long)a->m * fr);
+    KG_REQUIRE(!(sides & 1) || (long)a->n * fr <= FR_MAX_POINTS, "%s: n=%d x frames=%d gives P=%ld real points, above 2^24", who,
+               a->n, a->frames, (long)a->n * fr);
+    KG_REQUIRE(!(sides & 2) || (long)a->m * fr <= FR_MAX_POINTS, "%s: m=%d x frames=%d gives P=%ld fake points, above 2^24", who,
+               a->m, a->frames, (long)a->m * fr);
     frechet_plan(a, p);
+    if (sides != 3) {           // nset sets of ONE side, each with the chunking kg_frechet gives that side
+        const int s = sides == 1 ? 0 : 1;
+        const long dd = (long)p.d * p.d;
+        p.grid_moments = (long)a->classes * nset * p.nch[s];
+        p.grid_merge = (long)a->classes * nset * ((dd + FR_NT - 1) / FR_NT);
+        p.part_doubles = (int64_t)p.grid_moments * (p.d + dd);
+        p.ws_bytes = 8 * (p.part_doubles + (int64_t)a->classes * nset * (p.d + dd));
+    }
     const long grid = p.grid_moments > p.grid_merge ? p.grid_moments : p.grid_merge;
     KG_REQUIRE(grid < FR_MAX_GRID, "%s: classes=%d make %ld workgroups, one launch takes fewer than %ld", who, a->classes, grid,
                FR_MAX_GRID);
@@ -455,6 +613,8 @@ extern "C" int kg_frechet(const KgFrechetArgs* a, void* stream) {
     for (int s = 0; s < 2; ++s) {
         d.set[s].P = (int)p.P[s];  d.set[s].cs = p.cs[s];  d.set[s].nch = p.nch[s];
     }
+    d.set[1].ch0 = p.nch[0];
+    d.nset = 2;  d.per = p.nch[0] + p.nch[1];
     d.inner = FastDiv::make((unsigned)a->d_inner);
     d.fr = FastDiv::make((unsigned)(a->frames - a->diff));
     d.d = p.d;  d.diff = a->diff;  d.classes = a->classes;
@@ -481,4 +641,136 @@ extern "C" int kg_frechet(const KgFrechetArgs* a, void* stream) {
         return kg_launch_status("kg_frechet_mean");
     }
     return 0;
+}
+
+// ---- the real side once, several fake sets per call --------------------------------------------------------
+
+namespace {
+
+// kg_frechet's shape checks and chunking for ONE side: the other side's count is a copy, so it never decides anything
+KgFrechetArgs frechet_side_shape(int count, int frames, int diff, int d_outer, int d_inner, int classes) {
+    KgFrechetArgs f = {};
+    f.n = count;  f.m = count;  f.frames = frames;  f.diff = diff;
+    f.d_outer = d_outer;  f.d_inner = d_inner;  f.classes = classes;
+    return f;
+}
+
+int frechet_real_validate(const KgFrechetRealArgs* a, const char* who, FrPlan& p) {
+    KG_REQUIRE(a != nullptr, "%s: null args", who);
+    const KgFrechetArgs f = frechet_side_shape(a->n, a->frames, a->diff, a->d_outer, a->d_inner, a->classes);
+    return frechet_validate(&f, who, p, 1, 1);
+}
+
+int frechet_sets_validate(const KgFrechetSetsArgs* a, const char* who, FrPlan& p) {
+    KG_REQUIRE(a != nullptr, "%s: null args", who);
+    KG_REQUIRE(a->nsets >= 1 && a->nsets <= KG_FRECHET_MAX_SETS, "%s: nsets=%d outside [1, %d]", who, a->nsets, KG_FRECHET_MAX_SETS);
+    const KgFrechetArgs f = frechet_side_shape(a->m, a->frames, a->diff, a->d_outer, a->d_inner, a->classes);
+    if (int rc = frechet_validate(&f, who, p, 2, a->nsets)) return rc;
+    KG_REQUIRE((long)a->nsets * a->classes < FR_MAX_GRID, "%s: nsets=%d x classes=%d make %ld workgroups, one launch takes fewer than %ld",
+               who, a->nsets, a->classes, (long)a->nsets * a->classes, FR_MAX_GRID);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t kg_frechet_real_workspace_bytes(const KgFrechetRealArgs* a) {
+    FrPlan p;
+    if (int rc = frechet_real_validate(a, "kg_frechet_real_workspace_bytes", p)) return rc;
+    return p.ws_bytes;
+}
+
+extern "C" int kg_frechet_real(const KgFrechetRealArgs* a, void* stream) {
+    FrPlan p;
+    if (int rc = frechet_real_validate(a, "kg_frechet_real", p)) return rc;
+    KG_REQUIRE(a->real != nullptr, "kg_frechet_real: null pointer real");
+    KG_REQUIRE(a->mu_real != nullptr, "kg_frechet_real: null pointer mu_real");
+    KG_REQUIRE(a->tr_real != nullptr, "kg_frechet_real: null pointer tr_real");
+    KG_REQUIRE(a->G != nullptr, "kg_frechet_real: null pointer G");
+    KG_REQUIRE(a->sweeps_real != nullptr, "kg_frechet_real: null pointer sweeps_real");
+    KG_REQUIRE(a->ws != nullptr, "kg_frechet_real: null pointer ws");
+    KG_REQUIRE(((uintptr_t)a->ws & 7) == 0, "kg_frechet_real: ws is not 8-byte aligned");
+    KG_REQUIRE(a->ws_bytes >= p.ws_bytes, "kg_frechet_real: ws_bytes=%lld < %lld (kg_frechet_real_workspace_bytes)",
+               (long long)a->ws_bytes, (long long)p.ws_bytes);
+
+    FrDev d = {};
+    d.set[0].p = a->real;  d.set[0].sc = a->r_sc;  d.set[0].ss = a->r_ss;  d.set[0].sf = a->r_sf;  d.set[0].so = a->r_so;
+    d.set[0].P = (int)p.P[0];  d.set[0].cs = p.cs[0];  d.set[0].nch = p.nch[0];
+    d.nset = 1;  d.per = p.nch[0];
+    d.inner = FastDiv::make((unsigned)a->d_inner);
+    d.fr = FastDiv::make((unsigned)(a->frames - a->diff));
+    d.d = p.d;  d.diff = a->diff;  d.classes = a->classes;
+    d.part = (double*)a->ws;
+    d.mu = d.part + p.part_doubles;
+    d.cov = d.mu + (long)a->classes * p.d;
+    d.mu_out[0] = a->mu_real;
+    FrRealDev r = {};
+    r.cov = d.cov;  r.d = p.d;  r.G = a->G;  r.tr = a->tr_real;  r.sweeps = a->sweeps_real;
+    hipStream_t s = (hipStream_t)stream;
+
+    static unsigned long long attr_mask = 0;
+    if (kg_first_on_device(attr_mask)) KG_SET_DYN_LDS(kg_frechet_real_solve_kernel, 2 * FR_MAXD * (FR_MAXD + 1) * 8);
+
+    if (p.d <= 48) hipLaunchKernelGGL(kg_frechet_moments_kernel<3>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
+    else hipLaunchKernelGGL(kg_frechet_moments_kernel<6>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
+    if (int rc = kg_launch_status("kg_frechet_real moments")) return rc;
+    hipLaunchKernelGGL(kg_frechet_merge_kernel, dim3((unsigned)p.grid_merge), dim3(FR_NT), 0, s, d);
+    if (int rc = kg_launch_status("kg_frechet_real merge")) return rc;
+    hipLaunchKernelGGL(kg_frechet_real_solve_kernel, dim3((unsigned)a->classes), dim3(FR_SOLVE_NT), (size_t)p.lds_solve, s, r);
+    return kg_launch_status("kg_frechet_real solve");
+}
+
+extern "C" int64_t kg_frechet_sets_workspace_bytes(const KgFrechetSetsArgs* a) {
+    FrPlan p;
+    if (int rc = frechet_sets_validate(a, "kg_frechet_sets_workspace_bytes", p)) return rc;
+    return p.ws_bytes;
+}
+
+extern "C" int kg_frechet_sets(const KgFrechetSetsArgs* a, void* stream) {
+    FrPlan p;
+    if (int rc = frechet_sets_validate(a, "kg_frechet_sets", p)) return rc;
+    for (int g = 0; g < a->nsets; ++g) KG_REQUIRE(a->fake[g] != nullptr, "kg_frechet_sets: null pointer fake[%d]", g);
+    KG_REQUIRE(a->mu_real != nullptr, "kg_frechet_sets: null pointer mu_real");
+    KG_REQUIRE(a->tr_real != nullptr, "kg_frechet_sets: null pointer tr_real");
+    KG_REQUIRE(a->G != nullptr, "kg_frechet_sets: null pointer G");
+    KG_REQUIRE(a->values != nullptr, "kg_frechet_sets: null pointer values");
+    KG_REQUIRE(a->terms != nullptr, "kg_frechet_sets: null pointer terms");
+    KG_REQUIRE(a->sweeps != nullptr, "kg_frechet_sets: null pointer sweeps");
+    KG_REQUIRE(a->mean != nullptr, "kg_frechet_sets: null pointer mean");
+    KG_REQUIRE(a->mean32 != nullptr, "kg_frechet_sets: null pointer mean32");
+    KG_REQUIRE(a->ws != nullptr, "kg_frechet_sets: null pointer ws");
+    KG_REQUIRE(((uintptr_t)a->ws & 7) == 0, "kg_frechet_sets: ws is not 8-byte aligned");
+    KG_REQUIRE(a->ws_bytes >= p.ws_bytes, "kg_frechet_sets: ws_bytes=%lld < %lld (kg_frechet_sets_workspace_bytes)",
+               (long long)a->ws_bytes, (long long)p.ws_bytes);
+
+    FrDev d = {};
+    for (int g = 0; g < a->nsets; ++g) {
+        d.set[g].p = a->fake[g];  d.set[g].sc = a->f_sc;  d.set[g].ss = a->f_ss;  d.set[g].sf = a->f_sf;  d.set[g].so = a->f_so;
+        d.set[g].P = (int)p.P[1];  d.set[g].cs = p.cs[1];  d.set[g].nch = p.nch[1];  d.set[g].ch0 = g * p.nch[1];
+    }
+    d.nset = a->nsets;  d.per = a->nsets * p.nch[1];
+    d.inner = FastDiv::make((unsigned)a->d_inner);
+    d.fr = FastDiv::make((unsigned)(a->frames - a->diff));
+    d.d = p.d;  d.diff = a->diff;  d.classes = a->classes;
+    d.part = (double*)a->ws;
+    d.mu = d.part + p.part_doubles;
+    d.cov = d.mu + (long)a->classes * a->nsets * p.d;
+    FrSetsDev v = {};
+    v.mu = d.mu;  v.cov = d.cov;  v.mu_real = a->mu_real;  v.tr_real = a->tr_real;  v.G = a->G;
+    v.d = p.d;  v.nsets = a->nsets;  v.classes = a->classes;
+    v.values = a->values;  v.terms = a->terms;  v.sweeps = a->sweeps;
+    hipStream_t s = (hipStream_t)stream;
+
+    static unsigned long long attr_mask = 0;
+    if (kg_first_on_device(attr_mask)) KG_SET_DYN_LDS(kg_frechet_sets_solve_kernel, 2 * FR_MAXD * (FR_MAXD + 1) * 8);
+
+    if (p.d <= 48) hipLaunchKernelGGL(kg_frechet_moments_kernel<3>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
+    else hipLaunchKernelGGL(kg_frechet_moments_kernel<6>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
+    if (int rc = kg_launch_status("kg_frechet_sets moments")) return rc;
+    hipLaunchKernelGGL(kg_frechet_merge_kernel, dim3((unsigned)p.grid_merge), dim3(FR_NT), 0, s, d);
+    if (int rc = kg_launch_status("kg_frechet_sets merge")) return rc;
+    hipLaunchKernelGGL(kg_frechet_sets_solve_kernel, dim3((unsigned)(a->nsets * a->classes)), dim3(FR_SOLVE_NT), (size_t)p.lds_solve, s, v);
+    if (int rc = kg_launch_status("kg_frechet_sets solve")) return rc;
+    hipLaunchKernelGGL(kg_frechet_sets_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)a->values, a->mean, a->mean32,
+                       a->classes, a->nsets);
+    return kg_launch_status("kg_frechet_sets finish");
 }

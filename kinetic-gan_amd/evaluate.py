@@ -24,6 +24,12 @@ k-th-neighbour radii were computed once, at construction (kg_prdc_radii).  The r
 ``"<g>/precision"``, ``"<g>/recall"``, ``"<g>/density"``, ``"<g>/coverage"`` per generator and goes through
 kg_eval_record2, which knows the sense of the deciding score: the four new names are better when larger.
 
+With ``frechet_per_class > 0`` it also scores the Frechet pose and / or motion distance: a round of
+``frechet_per_class`` samples per class from every generator - the PRDC round itself when both options ask for the same
+count, else a round of its own -, read in place by ONE kg_frechet_sets call per mode (four launches for all generators)
+against the real side's cache, which kg_frechet_real computed once per mode at construction.  The record then ends with
+``"<g>/pose_fd"`` / ``"<g>/motion_fd"`` per generator (smaller is better) and goes through kg_eval_record2.
+
 Nothing synchronises the host; everything is read through pointers when the launches run, so the captured evaluation
 follows the training replays in between.  ``records()``, ``best()`` and ``state_dict()`` read the device; the Evaluator
 never writes to a generator.  Definitions the tests pin this against: tests/eval_def.py.
@@ -68,12 +74,14 @@ def score_sense(name: str) -> str:
     return "max" if str(name).rsplit("/", 1)[-1] in metrics.PRDC_NAMES else "min"
 
 
-def score_names(generators: Sequence[str], modes: Sequence[str], prdc: bool = False) -> list:
+def score_names(generators: Sequence[str], modes: Sequence[str], prdc: bool = False, frechet: Sequence[str] = ()) -> list:
     """The record's columns: ``"<g>/<mode>"`` generator by generator, then - with precision / recall / density / coverage
-    on - ``"<g>/<name>"`` generator by generator in the order of ``metrics.PRDC_NAMES``"""
+    on - ``"<g>/<name>"`` generator by generator in the order of ``metrics.PRDC_NAMES``, then - with the Frechet modes
+    ``frechet`` (of ``metrics.FRECHET_MODES``) - ``"<g>/pose_fd"`` and / or ``"<g>/motion_fd"`` generator by generator"""
     names = ["%s/%s" % (g, m) for g in generators for m in modes]
     if prdc:
         names += ["%s/%s" % (g, q) for g in generators for q in metrics.PRDC_NAMES]
+    names += ["%s/%s_fd" % (g, f) for g in generators for f in frechet]
     return names
 
 
@@ -119,15 +127,24 @@ class Evaluator:
     ``"<generator>/<mode>"``; ``select`` names the one that decides (default: ``default_select``).  ``iteration``: a
     one-element int64 device tensor read when an evaluation runs (``TrainLoop.step_dev``), None records -1.
     ``prdc_per_class`` (0: off): also score precision / recall / density / coverage with ``prdc_k`` neighbours on that many
-    fake and real samples per class (``"<generator>/precision"`` ...; ``select`` may name one of them: larger is better)."""
+    fake and real samples per class (``"<generator>/precision"`` ...; ``select`` may name one of them: larger is better).
+    ``frechet_per_class`` (0: off): also score the Frechet distance of the ``frechet_modes`` (``"pose"``, ``"motion"``) on
+    that many fake and real samples per class (``"<generator>/pose_fd"``, ``"<generator>/motion_fd"``; smaller is better)."""
 
     def __init__(self, generators: Dict[str, torch.nn.Module], real, real_labels=None, pairs: int = 10,
                  modes: Sequence[str] = ("avg", "joint"), select: Optional[str] = None, seed: int = 0,
                  trunc: Optional[float] = None, trunc_mode: str = "-", iteration: Optional[torch.Tensor] = None,
                  ring_len: int = 1024, use_graph: bool = True, t_size: Optional[int] = None, prdc_per_class: int = 0,
-                 prdc_k: int = 5):
+                 prdc_k: int = 5, frechet_per_class: int = 0, frechet_modes: Sequence[str] = ("pose", "motion")):
         if not generators:
             raise ValueError("Evaluator: at least one generator")
+        self.frechet_per_class = int(frechet_per_class)
+        if self.frechet_per_class < 0:
+            raise ValueError("Evaluator: frechet_per_class=%d < 0" % self.frechet_per_class)
+        # (the modes in the order of metrics.FRECHET_MODES, whatever order they were asked for in)
+        self.frechet_modes = tuple(f for f in metrics.FRECHET_MODES if f in tuple(frechet_modes)) if self.frechet_per_class else ()
+        if self.frechet_per_class and (not self.frechet_modes or set(frechet_modes) - set(metrics.FRECHET_MODES)):
+            raise ValueError("Evaluator: frechet_modes %r: one or more of %s" % (tuple(frechet_modes), metrics.FRECHET_MODES))
         self.prdc_per_class, self.prdc_k = int(prdc_per_class), int(prdc_k)
         if self.prdc_per_class < 0:
             raise ValueError("Evaluator: prdc_per_class=%d < 0" % self.prdc_per_class)
@@ -143,8 +160,8 @@ class Evaluator:
         if not self.modes:
             raise ValueError("Evaluator: at least one mode")
         self.gens = dict(generators)
-        self.names = score_names(list(self.gens), self.modes, bool(self.prdc_per_class))
-        most = nv.EVAL2_MAX_SCORES if self.prdc_per_class else nv.EVAL_MAX_SCORES
+        self.names = score_names(list(self.gens), self.modes, bool(self.prdc_per_class), self.frechet_modes)
+        most = nv.EVAL2_MAX_SCORES if self.prdc_per_class or self.frechet_per_class else nv.EVAL_MAX_SCORES
         if len(self.names) > most:
             raise ValueError("Evaluator: %d scores, at most %d fit one record" % (len(self.names), most))
         self.select = default_select(list(self.gens), self.modes) if select is None else str(select)
@@ -178,6 +195,10 @@ class Evaluator:
             self._prdc_setup(real, real_labels, first, t_size, trunc, trunc_mode)
         else:
             self.prdc_samplers, self.prdc_real, self.prdc_radii = {}, None, None
+        if self.frechet_per_class:
+            self._frechet_setup(real, real_labels, first, t_size, trunc, trunc_mode)
+        else:
+            self.frechet_samplers, self.frechet_real, self.frechet_cache = {}, None, {}
         rows = pair_rows(lab, self.n_classes, self.pairs)
         self.real = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32)[rows])).to(dev)
         self._pair_labels = np.arange(self.n)                  # every (fake, real) pair is a "class" of the kg_mmd call
@@ -266,6 +287,68 @@ class Evaluator:
             scores += [res["mean"][g, i:i + 1] for g in range(len(part)) for i in range(4)]
         return scores
 
+    # ---- Frechet pose / motion distance --------------------------------------------------------------------
+    def _frechet_setup(self, real, real_labels, first, t_size, trunc, trunc_mode):
+        """the real side, once: ``frechet_per_class`` samples of every class, class by class on the device, and per mode
+        their cache (one kg_frechet_real call; deterministic, so not part of the state); per generator a Sampler of its
+        own whose round kg_frechet_sets reads in place - unless the PRDC round has the same count and is read instead"""
+        dev, K, P = self.device, self.n_classes, self.frechet_per_class
+        if real_labels is None and hasattr(real, "label") and hasattr(real, "data"):
+            data, _, _ = metrics.select_reference_samples(real, np.arange(K), int(t_size) if t_size is not None else int(first.t_size),
+                                                          per_class=P)
+        else:
+            data = real.detach().cpu().numpy() if isinstance(real, torch.Tensor) else np.asarray(real)
+            lab = real_labels.detach().cpu().numpy() if isinstance(real_labels, torch.Tensor) else np.asarray(real_labels)
+            data = np.asarray(data, dtype=np.float32)[class_rows(lab, K, P)]
+        self.frechet_real = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32))).to(dev)    # (K*P, C, t, V)
+        _, C, T, V = self.frechet_real.shape
+        if C * V > nv.FRECHET_MAX_DIM:
+            raise ValueError("Evaluator: frechet needs d = C*V = %d <= %d" % (C * V, nv.FRECHET_MAX_DIM))
+        if "motion" in self.frechet_modes and T < 2:
+            raise ValueError("Evaluator: frechet mode 'motion' needs two frames, the samples have %d" % T)
+        self._frechet_shared = self.prdc_per_class == P
+        self.frechet_samplers = {} if self._frechet_shared else {
+            k: Sampler(G, qtd=P, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False) for k, G in self.gens.items()}
+        D = C * T * V
+        rv = nv.FrechetView(self.frechet_real, P * D, D, V, T * V if C > 1 else 0)
+        with torch.cuda.device(dev):
+            self.frechet_cache = {f: nv.frechet_real(rv, P, T, f == "motion", C, V, K) for f in self.frechet_modes}
+            sets = min(len(self.gens), nv.FRECHET_MAX_SETS)
+            nbytes = max(nv.frechet_sets_workspace_bytes(sets, P, T, f == "motion", C, V, K) for f in self.frechet_modes)
+            self._frechet_ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+
+    def _frechet_scores(self):
+        """the Frechet rounds of all generators (the PRDC rounds when they are shared), then per mode ONE kg_frechet_sets per
+        FRECHET_MAX_SETS generators: the mean32 words, which are the scores - generator by generator, mode by mode"""
+        K, P = self.n_classes, self.frechet_per_class
+        outs = []
+        for k in self.gens:
+            if self._frechet_shared:
+                out = self.prdc_samplers[k]._out         # this evaluation's PRDC round: no third round
+            else:
+                s = self.frechet_samplers[k]
+                s._round()
+                out = s._out                 # (P*K, C, T, V), row j*K + c = sample j of class c; read in place
+            if tuple(out.shape[1:]) != tuple(self.frechet_real.shape[1:]) or not nv.is_plane(out):
+                raise ValueError("Evaluator: generated samples %s against real samples %s" % (
+                    tuple(out.shape[1:]), tuple(self.frechet_real.shape[1:])))
+            outs.append(out)
+        _, C, T, V = outs[0].shape
+        sn, sc = nv._sn_sc(outs[0])
+        if any(nv._sn_sc(q) != (sn, sc) for q in outs):
+            raise ValueError("Evaluator: the generators' rounds differ in their strides")
+        so = sc if C > 1 else 0
+        per_mode = {}
+        for f in self.frechet_modes:
+            words = []
+            for q in range(0, len(outs), nv.FRECHET_MAX_SETS):
+                part = outs[q:q + nv.FRECHET_MAX_SETS]
+                res = nv.frechet_sets(self.frechet_cache[f], part, sn, K * sn, V, so, P, T, f == "motion", C, V, K,
+                                      ws=self._frechet_ws)
+                words += [res["mean32"][g:g + 1] for g in range(len(part))]
+            per_mode[f] = words
+        return [per_mode[f][g] for g in range(len(outs)) for f in self.frechet_modes]
+
     # ---- the launch sequence -------------------------------------------------------------------------------------------
     def _round(self):
         """what a graph holds: per generator a Sampler round, the re-layout, kg_mmd per mode; then the record, then the
@@ -281,6 +364,9 @@ class Evaluator:
                 scores.append(metrics.calculate_mmd(out, self.real, self._pair_labels, mode).reshape(1))
         if self.prdc_per_class:
             scores += self._prdc_scores()
+        if self.frechet_per_class:
+            scores += self._frechet_scores()
+        if self.prdc_per_class or self.frechet_per_class:
             nv.eval_record2(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
                             self.best_iter, self.flag, maximise=self.maximise)
         else:
@@ -295,7 +381,7 @@ class Evaluator:
         return ts + list(self.snap_buffers.values())
 
     def _all_samplers(self):
-        return list(self.samplers.values()) + list(self.prdc_samplers.values())
+        return list(self.samplers.values()) + list(self.prdc_samplers.values()) + list(self.frechet_samplers.values())
 
     def _capture(self):
         """Single-stream capture, no parallel branches.  The warm-up rounds in front of it are real evaluations:
@@ -383,6 +469,8 @@ class Evaluator:
               "records": {k: rec[k] for k in ("iteration", "scores", "improved")}}
         if self.prdc_per_class:              # (the real radii are recomputed from the data: not part of the state)
             sd["prdc"] = {"per_class": self.prdc_per_class, "k": self.prdc_k}
+        if self.frechet_per_class:           # (the real side's cache is recomputed from the data: not part of the state)
+            sd["frechet"] = {"per_class": self.frechet_per_class, "modes": list(self.frechet_modes)}
         return sd
 
     def check_compatible(self, sd: dict) -> None:
@@ -390,6 +478,10 @@ class Evaluator:
         theirs = sd.get("prdc")
         if (None if theirs is None else {k: int(v) for k, v in dict(theirs).items()}) != mine:
             raise ValueError("Evaluator.load_state_dict: prdc is %r in the state, %r here" % (theirs, mine))
+        mine = {"per_class": self.frechet_per_class, "modes": list(self.frechet_modes)} if self.frechet_per_class else None
+        theirs = sd.get("frechet")
+        if (None if theirs is None else {"per_class": int(dict(theirs)["per_class"]), "modes": list(dict(theirs)["modes"])}) != mine:
+            raise ValueError("Evaluator.load_state_dict: frechet is %r in the state, %r here" % (theirs, mine))
         for k, mine in (("pairs", self.pairs), ("select", self.select), ("modes", list(self.modes)), ("names", list(self.names))):
             if (list(sd[k]) if isinstance(mine, list) else sd[k]) != mine:
                 raise ValueError("Evaluator.load_state_dict: %s is %r in the state, %r here" % (k, sd[k], mine))

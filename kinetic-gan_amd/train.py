@@ -121,7 +121,8 @@ class TrainLoop:
                  run_ahead: int = 16, ema_decay: Optional[float] = None, ema_warmup: float = 10.0,
                  eval_interval: Optional[int] = None, eval_pairs: int = 10, eval_select: Optional[str] = None,
                  eval_modes=("avg", "joint"), eval_trunc: Optional[float] = None, eval_trunc_mode: str = "-",
-                 eval_data: Optional[Feeder] = None, eval_prdc: int = 0, eval_prdc_k: int = 5):
+                 eval_data: Optional[Feeder] = None, eval_prdc: int = 0, eval_prdc_k: int = 5,
+                 eval_frechet: int = 0, eval_frechet_modes=("pose", "motion")):
         self.G, self.D = G, D
         self.device = next(G.parameters()).device
         if self.device.type != "cuda":
@@ -192,6 +193,7 @@ class TrainLoop:
         # iteration - it scores the live (and the averaged) generator, appends to a record on the device and snapshots the
         # best-scoring weights there.  Off: no launch, no file, no state key is added.  eval_prdc (0: off):
         # the evaluation also scores precision / recall / density / coverage on that many samples per class.
+        # eval_frechet (0: off): and the Frechet distance of eval_frechet_modes on that many samples per class.
         self.eval_interval = int(eval_interval) if eval_interval else None
         self.evaluator = None
         if self.eval_interval:
@@ -202,7 +204,8 @@ class TrainLoop:
             self.evaluator = Evaluator(gens, eval_data if eval_data is not None else feeder, pairs=eval_pairs, modes=eval_modes,
                                        select=eval_select, seed=self.seed, trunc=eval_trunc, trunc_mode=eval_trunc_mode,
                                        iteration=self.step_dev, use_graph=self.use_graph, t_size=self.t,
-                                       prdc_per_class=eval_prdc, prdc_k=eval_prdc_k)
+                                       prdc_per_class=eval_prdc, prdc_k=eval_prdc_k, frechet_per_class=eval_frechet,
+                                       frechet_modes=eval_frechet_modes)
 
     # ---- schedule ------------------------------------------------------------------------------------------------
     @property

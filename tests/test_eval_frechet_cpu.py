@@ -1,0 +1,321 @@
+"""Frechet pose / motion distance inside the Evaluator, without a GPU: declaration / export / ctypes mirrors of
+kg_frechet_real and kg_frechet_sets, their workspace formulas, their host-side rejections, score names and senses, the
+state's compatibility rules and the command line's flags."""
+import ctypes
+import importlib.util
+import os
+import re
+import subprocess
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import kinetic_gan_amd  # noqa: F401
+from kinetic_gan_amd import _native, build, evaluate, metrics
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRY_POINTS = (("kg_frechet_real_workspace_bytes", "KgFrechetRealArgs", 1), ("kg_frechet_real", "KgFrechetRealArgs", 2),
+                ("kg_frechet_sets_workspace_bytes", "KgFrechetSetsArgs", 1), ("kg_frechet_sets", "KgFrechetSetsArgs", 2))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    build.build()
+    return _native.load_library()
+
+
+# ---- declaration, export, mirrors ----------------------------------------------------------------------------------------
+
+def test_header_declares_and_library_exports(lib):
+    txt = open(os.path.join(ROOT, "include", "kgan_hip.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    raw = ctypes.CDLL(_native.LIB_PATH)
+    for name, arg, nargs in ENTRY_POINTS:
+        assert re.search(r"\b%s\s*\(\s*const %s\*" % (name, arg), code), "%s is not declared in kgan_hip.h" % name
+        assert hasattr(raw, name) and getattr(lib, name) is not None
+        assert len(_native.EXPORTS[name][1]) == nargs
+    assert "#define KG_FRECHET_MAX_SETS 4" in txt and _native.FRECHET_MAX_SETS == 4
+    assert "#define KG_FRECHET_MAX_DIM 96" in txt and _native.FRECHET_MAX_DIM == 96
+    assert all(callable(getattr(_native, f)) for f in ("frechet_real", "frechet_real_workspace_bytes", "frechet_sets",
+                                                        "frechet_sets_workspace_bytes"))
+
+
+def test_abi_version_unchanged(lib):
+    assert lib.kg_abi_version() == 9
+
+
+@pytest.mark.parametrize("cname,mirror", [("KgFrechetRealArgs", "_FrechetRealArgs"), ("KgFrechetSetsArgs", "_FrechetSetsArgs"),
+                                          ("KgFrechetArgs", "_FrechetArgs")])
+def test_structs_match_header(tmp_path, cname, mirror):
+    st = getattr(_native, mirror)
+    fields = [n for n, _ in st._fields_]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "kgan_hip.h"\nint main(void){ printf("%%zu", sizeof(%s));' % cname
+    src += "".join(' printf(" %%zu", offsetof(%s, %s));' % (cname, n) for n in fields) + " return 0; }"
+    c = tmp_path / "s.c"
+    c.write_text(src)
+    exe = str(tmp_path / "s")
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe])
+    got = [int(v) for v in subprocess.check_output([exe]).split()]
+    assert got[0] == ctypes.sizeof(st)
+    assert got[1:] == [getattr(st, n).offset for n in fields]
+
+
+# ---- workspace queries ---------------------------------------------------------------------------------------------------
+
+def chunks(P, classes):
+    """the documented chunking of one set of P points (csrc/kg_frechet.hip, frechet_plan): about 1024 workgroups for the two
+    sets of all classes, chunks of at least 64 points, a multiple of the 32 points staged at a time"""
+    per_set = max(1024 // (2 * classes), 1)
+    cs = max(-(-P // per_set), 64)
+    cs = -(-cs // 32) * 32
+    return -(-P // cs)
+
+
+SHAPES = [  # n, m, frames, diff, d_outer, d_inner, classes
+    (2, 2, 2, 1, 1, 1, 1), (5, 4, 8, 0, 3, 5, 3), (5, 9, 16, 0, 3, 5, 2), (37, 29, 64, 1, 3, 25, 1), (100, 80, 64, 0, 3, 25, 60),
+    (4096, 1000, 64, 1, 3, 32, 7)]
+
+
+@pytest.mark.parametrize("n,m,frames,diff,d_outer,d_inner,classes", SHAPES)
+def test_workspace_formulas(lib, n, m, frames, diff, d_outer, d_inner, classes):
+    """real: 8 classes (nch_r + 1) (d + d*d); sets: 8 nsets classes (nch_f + 1) (d + d*d); and the two sides of ONE
+    kg_frechet call add up to its workspace: the chunking of either side is the one kg_frechet uses"""
+    d = d_outer * d_inner
+    fr = frames - diff
+    real = _native.frechet_real_workspace_bytes(n, frames, diff, d_outer, d_inner, classes)
+    assert real == 8 * classes * (chunks(n * fr, classes) + 1) * (d + d * d)
+    for nsets in (1, 2, 3, 4):
+        sets = _native.frechet_sets_workspace_bytes(nsets, m, frames, diff, d_outer, d_inner, classes)
+        assert sets == 8 * nsets * classes * (chunks(m * fr, classes) + 1) * (d + d * d)
+    one = _native.frechet_sets_workspace_bytes(1, m, frames, diff, d_outer, d_inner, classes)
+    assert real + one == _native.frechet_workspace_bytes(n, m, frames, diff, d_outer, d_inner, classes)
+
+
+def test_ragged_chunk_shapes_of_the_gpu_tests():
+    """tests/test_eval_frechet_gpu.py: 80 and 144 pose points per class of 2 classes are 2 and 3 chunks of 64"""
+    assert chunks(5 * 16, 2) == 2 and chunks(9 * 16, 2) == 3 and chunks(5 * 15, 2) == 2 and chunks(9 * 15, 2) == 3
+
+
+@pytest.mark.parametrize("mode", ("pose", "motion"))
+def test_definition_brackets_of_the_gpu_shapes_stay_under_the_caps(mode):
+    """tests/test_eval_frechet_gpu.py holds kg_frechet_sets against the float64 definition within the definition's own
+    end-to-end bracket; with the seed chosen there every bracket stays under frechet_def.caps (reference_sets asserts it)"""
+    import eval_frechet_def
+    for nsets, K, n, m, t, C, V in eval_frechet_def.DEF_SHAPES:
+        real, fakes = eval_frechet_def.make_sets(eval_frechet_def.SEED, nsets, K, n, m, C, t, V)
+        refs = eval_frechet_def.reference_sets(real, fakes, mode)
+        assert len(refs) == nsets and all(len(per) == K and np.isfinite(mean) for per, mean in refs)
+    assert {s[5] * s[6] for s in eval_frechet_def.DEF_SHAPES} == {15, 75, 96}
+
+
+# ---- rejections without a GPU call ---------------------------------------------------------------------------------------
+
+def _real_args():
+    a = _native._FrechetRealArgs()
+    a.real = 0x1000
+    a.r_sc, a.r_ss, a.r_sf, a.r_so = 100 * 4800, 4800, 25, 1600
+    a.n, a.frames, a.diff, a.d_outer, a.d_inner, a.classes = 100, 64, 1, 3, 25, 60
+    a.mu_real, a.tr_real, a.G, a.sweeps_real, a.ws = 0x2000, 0x3000, 0x4000, 0x5000, 0x6000
+    return a
+
+
+REAL_SHAPE = ("n", "frames", "diff", "d_outer", "d_inner", "classes")
+
+
+@pytest.mark.parametrize("field,value,needle", [
+    ("real", None, b"null pointer real"), ("mu_real", None, b"null pointer mu_real"), ("tr_real", None, b"null pointer tr_real"),
+    ("G", None, b"null pointer G"), ("sweeps_real", None, b"null pointer sweeps_real"), ("ws", None, b"null pointer ws"),
+    ("ws", 0x6004, b"not 8-byte aligned"), ("ws_bytes", 64, b"ws_bytes=64"),
+    ("n", 0, b"n=0"), ("classes", 0, b"classes=0"), ("d_outer", 0, b"d_outer=0"), ("d_inner", -1, b"d_inner=-1"),
+    ("diff", 2, b"diff=2"), ("d_inner", 33, b"d_inner=33 above KG_FRECHET_MAX_DIM"), ("frames", 1, b"frames=1 < 2"),
+    ("n", (1 << 24) // 63 + 1, b"real points, above 2^24"), ("classes", 1 << 24, b"fewer than 16777216")])
+def test_kg_frechet_real_rejects_bad_arguments_without_gpu(lib, field, value, needle):
+    a = _real_args()
+    need = lib.kg_frechet_real_workspace_bytes(ctypes.byref(a))
+    assert need == 8 * 60 * (chunks(100 * 63, 60) + 1) * (75 + 75 * 75)
+    a.ws_bytes = need
+    setattr(a, field, value)
+    if field in REAL_SHAPE:
+        assert lib.kg_frechet_real_workspace_bytes(ctypes.byref(a)) < 0
+        assert needle in lib.kg_last_error(), lib.kg_last_error()
+    assert lib.kg_frechet_real(ctypes.byref(a), None) < 0
+    assert b"kg_frechet_real" in lib.kg_last_error() and needle in lib.kg_last_error(), lib.kg_last_error()
+    assert lib.kg_frechet_real(None, None) < 0 and lib.kg_frechet_real_workspace_bytes(None) < 0
+
+
+def test_kg_frechet_real_one_point_is_rejected(lib):
+    a = _real_args()
+    a.n, a.frames = 1, 2                      # one sample of two frames: one motion point
+    assert lib.kg_frechet_real(ctypes.byref(a), None) < 0
+    assert b"n=1 gives P=1 < 2 real points" in lib.kg_last_error()
+
+
+def _sets_args(nsets=2):
+    a = _native._FrechetSetsArgs()
+    for g in range(nsets):
+        a.fake[g] = 0x1000 + 0x100 * g
+    a.f_sc, a.f_ss, a.f_sf, a.f_so = 1600, 60 * 1600, 25, 6000 * 1600
+    a.nsets, a.m, a.frames, a.diff, a.d_outer, a.d_inner, a.classes = nsets, 90, 64, 0, 3, 25, 60
+    a.mu_real, a.tr_real, a.G = 0x2000, 0x3000, 0x4000
+    a.values, a.terms, a.sweeps, a.mean, a.mean32, a.ws = 0x5000, 0x6000, 0x7000, 0x8000, 0x9000, 0xa000
+    return a
+
+
+SETS_SHAPE = ("nsets", "m", "frames", "diff", "d_outer", "d_inner", "classes")
+
+
+@pytest.mark.parametrize("field,value,needle", [
+    ("fake0", None, b"null pointer fake[0]"), ("fake1", None, b"null pointer fake[1]"),
+    ("mu_real", None, b"null pointer mu_real"), ("tr_real", None, b"null pointer tr_real"), ("G", None, b"null pointer G"),
+    ("values", None, b"null pointer values"), ("terms", None, b"null pointer terms"), ("sweeps", None, b"null pointer sweeps"),
+    ("mean", None, b"null pointer mean"), ("mean32", None, b"null pointer mean32"), ("ws", None, b"null pointer ws"),
+    ("ws", 0xa004, b"not 8-byte aligned"), ("ws_bytes", 64, b"ws_bytes=64"),
+    ("nsets", 0, b"nsets=0"), ("nsets", 5, b"nsets=5"), ("m", 0, b"m=0"), ("classes", 0, b"classes=0"),
+    ("d_outer", 0, b"d_outer=0"), ("d_inner", 0, b"d_inner=0"), ("diff", -1, b"diff=-1"),
+    ("d_outer", 4, b"d_outer=4 x d_inner=25 above KG_FRECHET_MAX_DIM"), ("frames", 0, b"frames=0 < 1"),
+    ("m", (1 << 24) // 64 + 1, b"fake points, above 2^24"), ("classes", 1 << 24, b"fewer than 16777216")])
+def test_kg_frechet_sets_rejects_bad_arguments_without_gpu(lib, field, value, needle):
+    a = _sets_args()
+    need = lib.kg_frechet_sets_workspace_bytes(ctypes.byref(a))
+    assert need == 8 * 2 * 60 * (chunks(90 * 64, 60) + 1) * (75 + 75 * 75)
+    a.ws_bytes = need
+    if field.startswith("fake"):
+        a.fake[int(field[4:])] = None
+    else:
+        setattr(a, field, value)
+    if field in SETS_SHAPE:
+        assert lib.kg_frechet_sets_workspace_bytes(ctypes.byref(a)) < 0
+        assert needle in lib.kg_last_error(), lib.kg_last_error()
+    assert lib.kg_frechet_sets(ctypes.byref(a), None) < 0
+    assert b"kg_frechet_sets" in lib.kg_last_error() and needle in lib.kg_last_error(), lib.kg_last_error()
+    assert lib.kg_frechet_sets(None, None) < 0 and lib.kg_frechet_sets_workspace_bytes(None) < 0
+
+
+def test_kg_frechet_sets_reads_only_the_first_nsets_pointers_and_names_its_own_count(lib):
+    a = _sets_args(nsets=2)                     # fake[2], fake[3] are null and not asked for
+    a.ws_bytes = lib.kg_frechet_sets_workspace_bytes(ctypes.byref(a))
+    a.m, a.frames, a.diff = 1, 2, 1             # one motion point per class: the fake count is named, never "n"
+    assert lib.kg_frechet_sets(ctypes.byref(a), None) < 0
+    assert b"m=1 gives P=1 < 2 fake points" in lib.kg_last_error() and b"n=" not in lib.kg_last_error()
+
+
+def test_bindings_refuse_cpu_tensors_and_wrong_dtypes():
+    x = torch.zeros(2, 10, 3, 4, 5)
+    v = _native.FrechetView(x, 600, 60, 5, 20)
+    with pytest.raises(RuntimeError, match="GPU only"):
+        _native.frechet_real(v, 10, 4, False, 3, 5, 2)
+    with pytest.raises(TypeError, match="fp32 only"):
+        _native.frechet_real(v._replace(t=x.double()), 10, 4, False, 3, 5, 2)
+    with pytest.raises(RuntimeError, match="n=0"):
+        _native.frechet_real(v, 0, 4, False, 3, 5, 2)
+    cache = dict(mu_real=torch.zeros(2, 15, dtype=torch.float64), tr_real=torch.zeros(2, dtype=torch.float64),
+                 G=torch.zeros(2, 16, 16, dtype=torch.float64))
+    with pytest.raises(RuntimeError, match="GPU only"):
+        _native.frechet_sets(cache, [x, x], 600, 60, 5, 20, 10, 4, False, 3, 5, 2)
+    with pytest.raises(TypeError, match="fp32 only"):
+        _native.frechet_sets(cache, [x.double()], 600, 60, 5, 20, 10, 4, False, 3, 5, 2)
+    with pytest.raises(RuntimeError, match="nsets=5"):
+        _native.frechet_sets(cache, [x] * 5, 600, 60, 5, 20, 10, 4, False, 3, 5, 2)
+    with pytest.raises(RuntimeError, match="nsets=0"):
+        _native.frechet_sets(cache, [], 600, 60, 5, 20, 10, 4, False, 3, 5, 2)
+
+
+# ---- names, senses, arguments --------------------------------------------------------------------------------------------
+
+def test_score_names_and_senses():
+    names = evaluate.score_names(["live", "ema"], ("avg", "joint"), prdc=True, frechet=("pose", "motion"))
+    assert names == ["live/avg", "live/joint", "ema/avg", "ema/joint",
+                     "live/precision", "live/recall", "live/density", "live/coverage",
+                     "ema/precision", "ema/recall", "ema/density", "ema/coverage",
+                     "live/pose_fd", "live/motion_fd", "ema/pose_fd", "ema/motion_fd"]
+    assert len(names) == 16 <= _native.EVAL2_MAX_SCORES
+    assert evaluate.score_names(["live", "ema"], ("avg", "joint"), prdc=True) == names[:12]           # today's lists
+    assert evaluate.score_names(["live", "ema"], ("avg", "joint")) == names[:4]
+    assert evaluate.score_names(["live", "ema"], ("avg", "joint"), False, ()) == names[:4]
+    assert evaluate.score_names(["a", "b"], ("avg",), frechet=("motion",)) == ["a/avg", "b/avg", "a/motion_fd", "b/motion_fd"]
+    assert [evaluate.score_sense(n) for n in names] == ["min"] * 4 + ["max"] * 8 + ["min"] * 4
+    assert evaluate.score_sense("g/pose_fd") == "min" and evaluate.score_sense("g/motion_fd") == "min"
+    assert metrics.FRECHET_MODES == ("pose", "motion")
+
+
+def test_evaluator_argument_errors_without_device():
+    gens = {"a": object()}
+    with pytest.raises(ValueError, match="frechet_per_class=-1"):
+        evaluate.Evaluator(gens, None, frechet_per_class=-1)
+    with pytest.raises(ValueError, match="frechet_modes"):
+        evaluate.Evaluator(gens, None, frechet_per_class=8, frechet_modes=("pose", "speed"))
+    with pytest.raises(ValueError, match="frechet_modes"):
+        evaluate.Evaluator(gens, None, frechet_per_class=8, frechet_modes=())
+    with pytest.raises(ValueError, match="select 'a/motion_fd' is none of"):                 # a Frechet name with Frechet off
+        evaluate.Evaluator(gens, None, select="a/motion_fd")
+    with pytest.raises(ValueError, match="select 'a/motion_fd' is none of"):                 # ... or with that mode off
+        evaluate.Evaluator(gens, None, select="a/motion_fd", frechet_per_class=8, frechet_modes=("pose",))
+    with pytest.raises(ValueError, match="40 scores, at most 32"):                           # the over-capacity error stays
+        evaluate.Evaluator({str(i): object() for i in range(5)}, None, prdc_per_class=8, prdc_k=3, frechet_per_class=8)
+    with pytest.raises(ValueError, match="36 scores, at most 32"):                           # Frechet alone: kg_eval_record2's room
+        evaluate.Evaluator({str(i): object() for i in range(9)}, None, frechet_per_class=8)
+    with pytest.raises(ValueError, match="10 scores, at most 8"):                            # off: the limit of kg_eval_record
+        evaluate.Evaluator({str(i): object() for i in range(5)}, None)
+
+
+# ---- the state -----------------------------------------------------------------------------------------------------------
+
+def _stub(prdc=0, frechet=0, modes=("pose", "motion")):
+    """what Evaluator.check_compatible reads of an Evaluator (none of it lives on a device here)"""
+    names = evaluate.score_names(["a"], ("avg",), bool(prdc), modes if frechet else ())
+    return types.SimpleNamespace(prdc_per_class=prdc, prdc_k=3, frechet_per_class=frechet, frechet_modes=tuple(modes) if frechet else (),
+                                 pairs=2, select="a/avg", modes=("avg",), names=names, ring_val=torch.zeros(8, len(names)),
+                                 snap_flat=torch.zeros(5), snap_buffers={"b": torch.zeros(1)})
+
+
+def _state(ev):
+    """a state as Evaluator.state_dict lays it out; the parent's format has no "frechet" key"""
+    sd = {"seed": 0, "step": 0, "pairs": ev.pairs, "select": ev.select, "modes": list(ev.modes), "names": list(ev.names), "count": 0,
+          "ring_val": torch.zeros_like(ev.ring_val), "snapshot": {"flat": torch.zeros(5), "buffers": {"b": torch.zeros(1)}}}
+    if ev.prdc_per_class:
+        sd["prdc"] = {"per_class": ev.prdc_per_class, "k": ev.prdc_k}
+    if ev.frechet_per_class:
+        sd["frechet"] = {"per_class": ev.frechet_per_class, "modes": list(ev.frechet_modes)}
+    return sd
+
+
+def test_state_compatibility():
+    check = evaluate.Evaluator.check_compatible
+    off, on = _stub(), _stub(frechet=8)
+    check(off, _state(off))                                     # the parent's format into an Evaluator without the option
+    assert "frechet" not in _state(off) and "frechet" not in _state(_stub(prdc=8))
+    check(_stub(prdc=8), _state(_stub(prdc=8)))
+    check(on, _state(on))
+    check(_stub(prdc=8, frechet=8), _state(_stub(prdc=8, frechet=8)))
+    check(on, dict(_state(on), frechet={"per_class": np.int64(8), "modes": ("pose", "motion")}))     # as a file gives them back
+    for ev, sd in ((off, _state(on)), (on, _state(off)), (on, _state(_stub(frechet=9))), (on, _state(_stub(frechet=8, modes=("pose",)))),
+                   (_stub(frechet=8, modes=("motion",)), _state(_stub(frechet=8, modes=("pose",))))):
+        with pytest.raises(ValueError, match="frechet is"):
+            check(ev, sd)
+    with pytest.raises(ValueError, match="prdc is"):            # (the PRDC rule is untouched)
+        check(_stub(prdc=8, frechet=8), _state(on))
+
+
+# ---- the command ---------------------------------------------------------------------------------------------------------
+
+def test_train_command_flags():
+    spec = importlib.util.spec_from_file_location("kg_tools_train", os.path.join(ROOT, "tools", "train.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    opt = mod.parse_args(["--data_path", "d", "--label_path", "l"])
+    assert opt.eval_frechet == 0 and opt.eval_frechet_modes == ["pose", "motion"]          # off by default
+    opt = mod.parse_args(["--data_path", "d", "--label_path", "l", "--eval_interval", "100", "--eval_frechet", "50",
+                          "--eval_frechet_modes", "motion", "--eval_select", "ema/motion_fd"])
+    assert (opt.eval_frechet, opt.eval_frechet_modes, opt.eval_select) == (50, ["motion"], "ema/motion_fd")
+    with pytest.raises(SystemExit):
+        mod.parse_args(["--data_path", "d", "--label_path", "l", "--eval_frechet_modes", "speed"])
+
+
+def test_time_eval_tool_flags():
+    spec = importlib.util.spec_from_file_location("kg_tools_time_eval", os.path.join(ROOT, "tools", "time_eval.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert mod.parse_args([]).frechet == 0
+    assert mod.parse_args(["--frechet", "20"]).frechet == 20

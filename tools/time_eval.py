@@ -22,7 +22,13 @@ live + ema, k = 5:
      replays, ``--reps`` repetitions, spread = max - min of the medians; "faster" only if the gap exceeds the larger spread;
   b. the whole evaluation replay with and without PRDC, and the Sampler round of classes x N samples alone with the device
      memory it holds (``--eval-replays`` replays each).
-    python tools/time_eval.py [--rounds 3] [--prdc 100] [--log FILE]"""
+``--frechet N`` (record: profiles/eval_frechet_time.log): instead of the above, the cost of scoring the Frechet
+pose and motion distance on N samples per class inside an evaluation, at the NTU and the H36M shapes, live + ema.  ONE
+evaluation replay three ways - with Frechet through kg_frechet_sets (the real side cached), with the same columns composed
+from one kg_frechet call per generator and mode (the real moments and the Jacobi solve of S_R repeated every time), and
+without Frechet - alternating in one process: ``--rounds`` rounds, each the median of ``--eval-replays`` event-timed replays
+per variant; spread = max - min of the medians; "faster" only if the gap exceeds the larger spread.
+    python tools/time_eval.py [--rounds 3] [--prdc 100 | --frechet 100] [--log FILE]"""
 import argparse
 import os
 import statistics
@@ -138,16 +144,97 @@ def prdc_part(args, say, dev):
         torch.cuda.empty_cache()
 
 
-def main():
+class ComposedFrechetEvaluator(Evaluator):
+    """the Frechet columns as they would be without kg_frechet_sets: per generator and mode one kg_frechet call against the
+    real samples themselves, its fp64 mean rounded to the fp32 word the record reads (the same bits, more work)"""
+
+    def _frechet_scores(self):
+        K, P = self.n_classes, self.frechet_per_class
+        outs = []
+        for k in self.gens:
+            s = self.frechet_samplers[k]
+            s._round()
+            outs.append(s._out)
+        _, C, T, V = outs[0].shape
+        sn, sc = nv._sn_sc(outs[0])
+        D = C * T * V
+        rv = nv.FrechetView(self.frechet_real, P * D, D, V, T * V if C > 1 else 0)
+        if getattr(self, "_composed_ws", None) is None:
+            self._composed_ws = torch.empty(nv.frechet_workspace_bytes(P, P, T, True, C, V, K) // 8 + nv.frechet_workspace_bytes(
+                P, P, T, False, C, V, K) // 8, dtype=torch.float64, device=self.device)
+        scores = []
+        for o in outs:
+            fv = nv.FrechetView(o, sn, K * sn, V, sc if C > 1 else 0)
+            for f in self.frechet_modes:
+                res = nv.frechet(rv, fv, P, P, T, f == "motion", C, V, K, want_mean=True, ws=self._composed_ws)
+                scores.append(res["mean"].to(torch.float32).reshape(1))
+        return scores
+
+
+def frechet_part(args, say, dev):
+    """``--frechet N``: see the module docstring"""
+    N = args.frechet
+    for name, c in PRDC_SHAPES:
+        K = c["n_classes"]
+        gens = {}
+        for g, seed in (("live", 1234), ("ema", 4321)):      # two generators of different weights (no training needed here)
+            torch.manual_seed(seed)
+            gens[g] = Generator(c["latent"], c["channels"], K, c["t_size"], c["mlp"], dataset=c["dataset"]).to(dev)
+        rng = np.random.RandomState(0)
+        real = torch.as_tensor((rng.rand(K * N, c["channels"], c["t_size"], c["v"]) * 2 - 1).astype(np.float32))
+        labels = np.tile(np.arange(K), N)
+        say("%s shapes: %d classes x %d samples per class of %d frames, d = %d, live + ema, pose and motion" % (
+            name, K, N, c["t_size"], c["channels"] * c["v"]))
+        ev = {"kg_frechet_sets, cached real side": Evaluator(gens, real, labels, pairs=PAIRS, seed=0, frechet_per_class=N),
+              "kg_frechet per generator and mode": ComposedFrechetEvaluator(gens, real, labels, pairs=PAIRS, seed=0, frechet_per_class=N),
+              "without Frechet": Evaluator(gens, real, labels, pairs=PAIRS, seed=0)}
+        for x in ev.values():
+            x.evaluate()                     # (captures)
+        torch.cuda.synchronize()
+        em = {k: [] for k in ev}
+        for r in range(args.rounds):
+            for k, x in ev.items():
+                ts = time_replays(x._graph, args.eval_replays)
+                x.n_evals += args.eval_replays + 1
+                for s in x._all_samplers():
+                    s.step_count += args.eval_replays + 1
+                em[k].append(statistics.median(ts))
+                say("%s evaluation replay, %-36s round %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
+                    name, k + ",", r, em[k][-1], args.eval_replays, min(ts), max(ts)))
+        m = {k: statistics.median(v) for k, v in em.items()}
+        sp = {k: max(v) - min(v) for k, v in em.items()}
+        a, b, off = list(ev)
+        gap, wide = m[b] - m[a], max(sp[a], sp[b])
+        verdict = "not separated" if abs(gap) <= wide else ("kg_frechet_sets is faster" if gap > 0 else "kg_frechet_sets is slower")
+        say("%s evaluation replay: %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f)" % (
+            name, a, m[a], sp[a], b, m[b], sp[b], off, m[off], sp[off]))
+        say("%s Frechet columns cost %+.4f ms through kg_frechet_sets, %+.4f ms composed; gap %+.4f ms against the larger spread "
+            "%.4f ms: %s" % (name, m[a] - m[off], m[b] - m[off], gap, wide, verdict))
+        ra, rb = ev[a].records(), ev[b].records()
+        say("%s the two routes record the same bits: %s; last scores: %s" % (
+            name, np.array_equal(ra["scores"].view(np.uint32), rb["scores"].view(np.uint32)),
+            ", ".join("%s %.6g" % (n, v) for n, v in zip(ra["names"], ra["scores"][-1]))))
+        del ev, gens
+        torch.cuda.empty_cache()
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--replays", type=int, default=200)
     ap.add_argument("--only-eval", type=int, default=0, help="this many evaluation replays and nothing else (for a kernel trace)")
     ap.add_argument("--prdc", type=int, default=0, help="samples per class: time the PRDC part of an evaluation instead (DESIGN.md 17)")
-    ap.add_argument("--eval-replays", type=int, default=30, help="replays of a whole evaluation / a Sampler round under --prdc")
+    ap.add_argument("--frechet", type=int, default=0,
+                    help="samples per class: time the Frechet part of an evaluation instead (DESIGN.md 19)")
+    ap.add_argument("--eval-replays", type=int, default=30,
+                    help="replays of a whole evaluation / a Sampler round under --prdc and --frechet")
     ap.add_argument("--log", default=None, help="also write the lines to this file")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -157,9 +244,12 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    if args.prdc:
+    if args.prdc or args.frechet:
         say("device %s" % torch.cuda.get_device_name(0))
-        prdc_part(args, say, dev)
+        if args.prdc:
+            prdc_part(args, say, dev)
+        else:
+            frechet_part(args, say, dev)
         if args.log:
             os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
             with open(args.log, "w") as fh:

@@ -10,7 +10,9 @@ inside the generator's Adam launch: also writes ``models/generator_ema_<n>.pth``
 inside the loop: writes ``metrics.csv`` and ``models/generator_best.pth``, the weights of the best-scoring evaluation;
 ``--eval_pairs``, ``--eval_select``, ``--eval_trunc``, ``--eval_trunc_mode``, ``--eval_data_path`` / ``--eval_label_path``;
 ``--eval_prdc N`` also scores precision / recall / density / coverage on N samples per class with ``--eval_prdc_k`` neighbours:
-eight more ``metrics.csv`` columns, and ``--eval_select`` may name one, e.g. ``ema/coverage``)."""
+eight more ``metrics.csv`` columns, and ``--eval_select`` may name one, e.g. ``ema/coverage``; ``--eval_frechet N`` also scores
+the Frechet pose / motion distance on N samples per class, ``--eval_frechet_modes`` choosing between them: up to four more
+columns, and ``--eval_select`` may name one, e.g. ``ema/motion_fd``)."""
 import argparse
 import os
 import sys
@@ -61,10 +63,15 @@ def parse_args(argv=None):
     p.add_argument("--eval_pairs", type=int, default=10, help="(fake, real) pairs per class of one evaluation")
     p.add_argument("--eval_select", type=str, default=None,
                    help="the score that picks the best weights, '<live|ema>/<avg|joint>' (default: ema/avg with --ema_decay, else live/avg); "
-                        "with --eval_prdc also '<live|ema>/<precision|recall|density|coverage>' (larger is better)")
+                        "with --eval_prdc also '<live|ema>/<precision|recall|density|coverage>' (larger is better); "
+                        "with --eval_frechet also '<live|ema>/<pose_fd|motion_fd>' (smaller is better)")
     p.add_argument("--eval_prdc", type=int, default=0,
                    help="samples per class on which an evaluation also scores precision / recall / density / coverage (0 = off)")
     p.add_argument("--eval_prdc_k", type=int, default=5, help="neighbours of --eval_prdc")
+    p.add_argument("--eval_frechet", type=int, default=0,
+                   help="samples per class on which an evaluation also scores the Frechet pose / motion distance (0 = off)")
+    p.add_argument("--eval_frechet_modes", type=str, nargs="+", default=["pose", "motion"], choices=["pose", "motion"],
+                   help="the Frechet distances of --eval_frechet")
     p.add_argument("--eval_trunc", type=float, default=None, help="truncation factor of the evaluation's samples")
     p.add_argument("--eval_trunc_mode", type=str, default="-", help="'-' none, 'z' or 'w' truncation of the evaluation's samples")
     p.add_argument("--eval_data_path", type=str, default=None, help="real samples of the evaluation (default: the training data)")
@@ -98,7 +105,8 @@ def main(argv=None):
                      ring_len=max(4096, opt.log_interval), ema_decay=opt.ema_decay or None, ema_warmup=opt.ema_warmup,
                      eval_interval=opt.eval_interval or None, eval_pairs=opt.eval_pairs, eval_select=opt.eval_select,
                      eval_trunc=opt.eval_trunc, eval_trunc_mode=opt.eval_trunc_mode, eval_data=eval_data,
-                     eval_prdc=opt.eval_prdc, eval_prdc_k=opt.eval_prdc_k)
+                     eval_prdc=opt.eval_prdc, eval_prdc_k=opt.eval_prdc_k, eval_frechet=opt.eval_frechet,
+                     eval_frechet_modes=tuple(opt.eval_frechet_modes))
     print("dataset: %d samples, %d batches per epoch, %s (%.1f MB cropped)" % (
         len(feeder), loop.bpe, "streamed" if loop.streaming else "resident on the device", loop.resident.nbytes / 1e6))
     if opt.resume:
