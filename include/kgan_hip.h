@@ -857,13 +857,15 @@ int     kg_frechet(const KgFrechetArgs* a, void* stream);
  * = V diag(sqrt(max(l, 0))) of S_R row-major (the padding row and column of an odd d are zero), sweeps_real (classes).  Three
  * launches: moments of the real set alone - chunked exactly as kg_frechet chunks the real set of a call with the same n,
  * frames, diff and classes (that chunking depends on P_r and classes alone) -, merge, one workgroup per class running the
- * Jacobi iteration with vectors.  The four arrays hold the bits kg_frechet forms internally.
+ * Jacobi iteration with vectors: the device function kg_frechet's solve runs first.  The four arrays hold the bits kg_frechet
+ * forms internally.
  * ws = kg_frechet_real_workspace_bytes(a) = 8 classes (nch_r + 1) (d + d*d) bytes, nch_r the real set's chunks.
  * kg_frechet_sets: nsets (1..KG_FRECHET_MAX_SETS) fake sets fake[g] with shared strides and m against that cache, which is an
  * INPUT read when the launches run; the real data is never touched.  Four launches whatever nsets is: moments of all fake
  * sets (chunked as kg_frechet chunks a fake set of m samples), merge, one workgroup per (set, class) - W = S_F G, H = sym(G^T
- * W), the Jacobi iteration without vectors, T, the terms and the FD with the loops of kg_frechet's solve -, finish (per set the
- * class mean in fp64 and its fp32 rounding mean32, the word kg_eval_record2 reads).  For every set g, values[g], terms[g] and
+ * W), the Jacobi iteration without vectors, T, the terms and the FD: the device function kg_frechet's solve runs second, not a
+ * copy of it -, finish (per set the class mean in fp64 and its fp32 rounding mean32, the word kg_eval_record2 reads).
+ * For every set g, values[g], terms[g] and
  * sweeps[g] equal, bit for bit, values, terms and sweeps[:, 1] of kg_frechet(real, fake[g]) on the same data, mean[g] its
  * mean, and sweeps_real its sweeps[:, 0]; the grouping into sets shows in no bit.
  * ws = kg_frechet_sets_workspace_bytes(a) = 8 nsets classes (nch_f + 1) (d + d*d) bytes, nch_f the chunks of one fake set.
@@ -1039,8 +1041,8 @@ int kg_eval_record(const KgEvalRecordArgs* a, void* stream);
  *                                                                  keeps the earlier snapshot
  * The host initialises *best_val = -inf when maximising, +inf otherwise.  Everything else is the definition above (ring
  * rows, [iteration, improved] in int64, *flag, *count, one thread of one small workgroup); with maximise = 0 and nscores <=
- * KG_EVAL_MAX_SCORES it leaves the same bits as kg_eval_record.  Call site: evaluate.Evaluator._round when precision /
- * recall / density / coverage are recorded (live + ema x 6 scores = 12 > 8).                                          */
+ * KG_EVAL_MAX_SCORES it leaves the same bits as kg_eval_record (one kernel template, one launcher).  Call site:
+ * evaluate.Evaluator._round when precision / recall / density / coverage are recorded (live + ema x 6 scores = 12 > 8). */
 #define KG_EVAL2_MAX_SCORES 32
 typedef struct KgEvalRecord2Args {
     const float* scores[KG_EVAL2_MAX_SCORES];  /* device: one fp32 each                                               */

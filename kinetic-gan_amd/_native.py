@@ -2830,6 +2830,35 @@ def trunc_lerp(x: torch.Tensor, t: torch.Tensor, truncation: float) -> torch.Ten
 
 # ---- scoring during training (kg_eval.hip; evaluate.Evaluator) --------------------------------------------------------------
 
+def _eval_record_args(struct, most: int, who: str, scores, select, iteration, count, ring_val, ring_iter, best_val, best_iter, flag):
+    """The tensor checks and the struct fill of ``eval_record`` / ``eval_record2``: an instance of ``struct`` (room for
+    ``most`` scores) with every field the two share; ``who`` is the entry point's name in the messages."""
+    _need_cuda(iteration, count, ring_val, ring_iter, best_val, best_iter, flag, *scores)
+    for t in scores:
+        if t.dtype != torch.float32 or t.numel() != 1:
+            raise TypeError("%s: one-element fp32 scores expected" % who)
+    for t in (iteration, count, best_iter):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != 1):
+            raise TypeError("%s: one-element int64 iteration / count / best_iter expected" % who)
+    if best_val.dtype != torch.float32 or best_val.numel() != 1 or flag.dtype != torch.int32 or flag.numel() != 1:
+        raise TypeError("%s: one-element fp32 best_val and int32 flag expected" % who)
+    if ring_val.dtype != torch.float32 or ring_iter.dtype != torch.int64 or not ring_val.is_contiguous() or \
+            not ring_iter.is_contiguous():
+        raise TypeError("%s: contiguous ring_val fp32 and ring_iter int64 expected" % who)
+    n = len(scores)
+    ring_len = ring_val.shape[0] if ring_val.dim() == 2 else 0
+    if ring_val.dim() != 2 or ring_iter.dim() != 2 or (ring_len and (ring_val.shape[1] != n or tuple(ring_iter.shape) != (ring_len, 2))):
+        raise ValueError("%s: ring_val (len, nscores) and ring_iter (len, 2) expected" % who)
+    a = struct()
+    for i, t in enumerate(scores[:most]):   # (more than fit: the library names nscores)
+        a.scores[i] = t.data_ptr()
+    a.nscores, a.select, a.ring_len = n, int(select), ring_len
+    a.iter, a.count = _ptr(iteration), count.data_ptr()
+    a.ring_val, a.ring_iter = ring_val.data_ptr(), ring_iter.data_ptr()
+    a.best_val, a.best_iter, a.flag = best_val.data_ptr(), best_iter.data_ptr(), flag.data_ptr()
+    return a
+
+
 def eval_record(scores: Sequence[torch.Tensor], select: int, iteration: Optional[torch.Tensor], count: torch.Tensor,
                 ring_val: torch.Tensor, ring_iter: torch.Tensor, best_val: torch.Tensor, best_iter: torch.Tensor,
                 flag: torch.Tensor) -> None:
@@ -2837,29 +2866,8 @@ def eval_record(scores: Sequence[torch.Tensor], select: int, iteration: Optional
     (len, nscores) fp32 and ``ring_iter`` (len, 2) int64 = [iteration, improved]; ``flag`` (int32) = scores[select] <
     best_val (strict), and then best_val / best_iter (int64) take the score and ``iteration[0]`` (int64; None: -1);
     ``count`` (int64) is advanced."""
-    _need_cuda(iteration, count, ring_val, ring_iter, best_val, best_iter, flag, *scores)
-    for t in scores:
-        if t.dtype != torch.float32 or t.numel() != 1:
-            raise TypeError("kg_eval_record: one-element fp32 scores expected")
-    for t in (iteration, count, best_iter):
-        if t is not None and (t.dtype != torch.int64 or t.numel() != 1):
-            raise TypeError("kg_eval_record: one-element int64 iteration / count / best_iter expected")
-    if best_val.dtype != torch.float32 or best_val.numel() != 1 or flag.dtype != torch.int32 or flag.numel() != 1:
-        raise TypeError("kg_eval_record: one-element fp32 best_val and int32 flag expected")
-    if ring_val.dtype != torch.float32 or ring_iter.dtype != torch.int64 or not ring_val.is_contiguous() or \
-            not ring_iter.is_contiguous():
-        raise TypeError("kg_eval_record: contiguous ring_val fp32 and ring_iter int64 expected")
-    n = len(scores)
-    ring_len = ring_val.shape[0] if ring_val.dim() == 2 else 0
-    if ring_val.dim() != 2 or ring_iter.dim() != 2 or (ring_len and (ring_val.shape[1] != n or tuple(ring_iter.shape) != (ring_len, 2))):
-        raise ValueError("kg_eval_record: ring_val (len, nscores) and ring_iter (len, 2) expected")
-    a = _EvalRecordArgs()
-    for i, t in enumerate(scores[:EVAL_MAX_SCORES]):
-        a.scores[i] = t.data_ptr()
-    a.nscores, a.select, a.ring_len = n, int(select), ring_len
-    a.iter, a.count = _ptr(iteration), count.data_ptr()
-    a.ring_val, a.ring_iter = ring_val.data_ptr(), ring_iter.data_ptr()
-    a.best_val, a.best_iter, a.flag = best_val.data_ptr(), best_iter.data_ptr(), flag.data_ptr()
+    a = _eval_record_args(_EvalRecordArgs, EVAL_MAX_SCORES, "kg_eval_record", scores, select, iteration, count, ring_val, ring_iter,
+                          best_val, best_iter, flag)
     _check(load_library().kg_eval_record(C.byref(a), _stream()), "kg_eval_record")
 
 
@@ -2868,29 +2876,9 @@ def eval_record2(scores: Sequence[torch.Tensor], select: int, iteration: Optiona
                  flag: torch.Tensor, maximise: bool = False) -> None:
     """Enqueue kg_eval_record2: ``eval_record`` for up to EVAL2_MAX_SCORES scores and with a sense - ``maximise``: ``flag``
     = scores[select] > best_val (strict; the host starts best_val at -inf), else scores[select] < best_val."""
-    _need_cuda(iteration, count, ring_val, ring_iter, best_val, best_iter, flag, *scores)
-    for t in scores:
-        if t.dtype != torch.float32 or t.numel() != 1:
-            raise TypeError("kg_eval_record2: one-element fp32 scores expected")
-    for t in (iteration, count, best_iter):
-        if t is not None and (t.dtype != torch.int64 or t.numel() != 1):
-            raise TypeError("kg_eval_record2: one-element int64 iteration / count / best_iter expected")
-    if best_val.dtype != torch.float32 or best_val.numel() != 1 or flag.dtype != torch.int32 or flag.numel() != 1:
-        raise TypeError("kg_eval_record2: one-element fp32 best_val and int32 flag expected")
-    if ring_val.dtype != torch.float32 or ring_iter.dtype != torch.int64 or not ring_val.is_contiguous() or \
-            not ring_iter.is_contiguous():
-        raise TypeError("kg_eval_record2: contiguous ring_val fp32 and ring_iter int64 expected")
-    n = len(scores)
-    ring_len = ring_val.shape[0] if ring_val.dim() == 2 else 0
-    if ring_val.dim() != 2 or ring_iter.dim() != 2 or (ring_len and (ring_val.shape[1] != n or tuple(ring_iter.shape) != (ring_len, 2))):
-        raise ValueError("kg_eval_record2: ring_val (len, nscores) and ring_iter (len, 2) expected")
-    a = _EvalRecord2Args()
-    for i, t in enumerate(scores[:EVAL2_MAX_SCORES]):
-        a.scores[i] = t.data_ptr()
-    a.nscores, a.select, a.ring_len, a.maximise = n, int(select), ring_len, 1 if maximise else 0
-    a.iter, a.count = _ptr(iteration), count.data_ptr()
-    a.ring_val, a.ring_iter = ring_val.data_ptr(), ring_iter.data_ptr()
-    a.best_val, a.best_iter, a.flag = best_val.data_ptr(), best_iter.data_ptr(), flag.data_ptr()
+    a = _eval_record_args(_EvalRecord2Args, EVAL2_MAX_SCORES, "kg_eval_record2", scores, select, iteration, count, ring_val,
+                          ring_iter, best_val, best_iter, flag)
+    a.maximise = 1 if maximise else 0
     _check(load_library().kg_eval_record2(C.byref(a), _stream()), "kg_eval_record2")
 
 

@@ -1,7 +1,8 @@
 // Scoring the generator during training (include/kgan_hip.h; evaluate.Evaluator):
 //   kg_eval_record : ONE thread compares the deciding score of an evaluation with the best so far, appends the evaluation
 //                    to the device record and leaves the decision in `flag`
-//   kg_eval_record2: the same kernel with room for KG_EVAL2_MAX_SCORES scores and a sense (larger or smaller is better)
+//   kg_eval_record2: the same kernel template and the same launcher (eval_record_launch) with room for KG_EVAL2_MAX_SCORES
+//                    scores and a sense (larger or smaller is better)
 //   kg_copy_if     : a grid that only READS that decision and, when it is set, copies a table of word runs - the snapshot
 //                    of the best-scoring weights, taken by the device with no host synchronisation
 // Two launches on purpose: one writer of the decision, then readers of it, with a launch boundary in between - there is no
@@ -81,63 +82,53 @@ __global__ __launch_bounds__(CP_NT) void kg_copy_if_kernel(const CopyJobs a) {
 
 }  // namespace
 
+namespace {
+
+// Both record entry points: the checks, the kernel's arguments and the launch of kg_eval_record_kernel<MAXS>; `who` is the
+// entry point's name in the messages
+template <int MAXS>
+int eval_record_launch(const char* who, const float* const* scores, int nscores, int select, int maximise, const int64_t* iter,
+                       int64_t* count, float* ring_val, int64_t* ring_iter, int64_t ring_len, float* best_val, int64_t* best_iter,
+                       int32_t* flag, void* stream) {
+    KG_REQUIRE(nscores >= 1 && nscores <= MAXS, "%s: nscores=%d outside [1, %d]", who, nscores, MAXS);
+    KG_REQUIRE(select >= 0 && select < nscores, "%s: select=%d outside [0, nscores=%d)", who, select, nscores);
+    KG_REQUIRE(ring_len >= 1, "%s: ring_len=%lld < 1", who, (long long)ring_len);
+    EvalRecDev<MAXS> d = {};
+    for (int i = 0; i < nscores; ++i) {
+        KG_REQUIRE(scores[i] != nullptr, "%s: null score %d", who, i);
+        d.scores[i] = scores[i];
+    }
+    KG_REQUIRE(count != nullptr && ring_val != nullptr && ring_iter != nullptr, "%s: null count / ring_val / ring_iter", who);
+    KG_REQUIRE(best_val != nullptr && best_iter != nullptr && flag != nullptr, "%s: null best_val / best_iter / flag", who);
+    d.nscores = nscores;
+    d.select = select;
+    d.maximise = maximise;
+    d.iter = (const long long*)iter;
+    d.count = (long long*)count;
+    d.ring_val = ring_val;
+    d.ring_iter = (long long*)ring_iter;
+    d.ring_len = (long)ring_len;
+    d.best_val = best_val;
+    d.best_iter = (long long*)best_iter;
+    d.flag = flag;
+    hipLaunchKernelGGL(kg_eval_record_kernel<MAXS>, dim3(1), dim3(64), 0, (hipStream_t)stream, d);
+    return kg_launch_status(who);
+}
+
+}  // namespace
+
 extern "C" int kg_eval_record(const KgEvalRecordArgs* a, void* stream) {
     KG_REQUIRE(a != nullptr, "kg_eval_record: null arguments");
-    KG_REQUIRE(a->nscores >= 1 && a->nscores <= KG_EVAL_MAX_SCORES, "kg_eval_record: nscores=%d outside [1, %d]", a->nscores,
-               KG_EVAL_MAX_SCORES);
-    KG_REQUIRE(a->select >= 0 && a->select < a->nscores, "kg_eval_record: select=%d outside [0, nscores=%d)", a->select, a->nscores);
-    KG_REQUIRE(a->ring_len >= 1, "kg_eval_record: ring_len=%lld < 1", (long long)a->ring_len);
-    EvalRecDev<KG_EVAL_MAX_SCORES> d = {};
-    for (int i = 0; i < a->nscores; ++i) {
-        KG_REQUIRE(a->scores[i] != nullptr, "kg_eval_record: null score %d", i);
-        d.scores[i] = a->scores[i];
-    }
-    KG_REQUIRE(a->count != nullptr && a->ring_val != nullptr && a->ring_iter != nullptr,
-               "kg_eval_record: null count / ring_val / ring_iter");
-    KG_REQUIRE(a->best_val != nullptr && a->best_iter != nullptr && a->flag != nullptr,
-               "kg_eval_record: null best_val / best_iter / flag");
-    d.nscores = a->nscores;
-    d.select = a->select;
-    d.iter = (const long long*)a->iter;
-    d.count = (long long*)a->count;
-    d.ring_val = a->ring_val;
-    d.ring_iter = (long long*)a->ring_iter;
-    d.ring_len = (long)a->ring_len;
-    d.best_val = a->best_val;
-    d.best_iter = (long long*)a->best_iter;
-    d.flag = a->flag;
-    hipLaunchKernelGGL(kg_eval_record_kernel<KG_EVAL_MAX_SCORES>, dim3(1), dim3(64), 0, (hipStream_t)stream, d);
-    return kg_launch_status("kg_eval_record");
+    return eval_record_launch<KG_EVAL_MAX_SCORES>("kg_eval_record", a->scores, a->nscores, a->select, /*maximise=*/0, a->iter,
+                                                  a->count, a->ring_val, a->ring_iter, a->ring_len, a->best_val, a->best_iter,
+                                                  a->flag, stream);
 }
 
 extern "C" int kg_eval_record2(const KgEvalRecord2Args* a, void* stream) {
     KG_REQUIRE(a != nullptr, "kg_eval_record2: null arguments");
-    KG_REQUIRE(a->nscores >= 1 && a->nscores <= KG_EVAL2_MAX_SCORES, "kg_eval_record2: nscores=%d outside [1, %d]", a->nscores,
-               KG_EVAL2_MAX_SCORES);
-    KG_REQUIRE(a->select >= 0 && a->select < a->nscores, "kg_eval_record2: select=%d outside [0, nscores=%d)", a->select, a->nscores);
-    KG_REQUIRE(a->ring_len >= 1, "kg_eval_record2: ring_len=%lld < 1", (long long)a->ring_len);
-    EvalRecDev<KG_EVAL2_MAX_SCORES> d = {};
-    for (int i = 0; i < a->nscores; ++i) {
-        KG_REQUIRE(a->scores[i] != nullptr, "kg_eval_record2: null score %d", i);
-        d.scores[i] = a->scores[i];
-    }
-    KG_REQUIRE(a->count != nullptr && a->ring_val != nullptr && a->ring_iter != nullptr,
-               "kg_eval_record2: null count / ring_val / ring_iter");
-    KG_REQUIRE(a->best_val != nullptr && a->best_iter != nullptr && a->flag != nullptr,
-               "kg_eval_record2: null best_val / best_iter / flag");
-    d.nscores = a->nscores;
-    d.select = a->select;
-    d.maximise = a->maximise != 0 ? 1 : 0;
-    d.iter = (const long long*)a->iter;
-    d.count = (long long*)a->count;
-    d.ring_val = a->ring_val;
-    d.ring_iter = (long long*)a->ring_iter;
-    d.ring_len = (long)a->ring_len;
-    d.best_val = a->best_val;
-    d.best_iter = (long long*)a->best_iter;
-    d.flag = a->flag;
-    hipLaunchKernelGGL(kg_eval_record_kernel<KG_EVAL2_MAX_SCORES>, dim3(1), dim3(64), 0, (hipStream_t)stream, d);
-    return kg_launch_status("kg_eval_record2");
+    return eval_record_launch<KG_EVAL2_MAX_SCORES>("kg_eval_record2", a->scores, a->nscores, a->select, a->maximise != 0 ? 1 : 0,
+                                                   a->iter, a->count, a->ring_val, a->ring_iter, a->ring_len, a->best_val,
+                                                   a->best_iter, a->flag, stream);
 }
 
 extern "C" int kg_copy_if(const int32_t* flag, const KgCopyJob* jobs, int32_t njobs, void* stream) {

@@ -20,12 +20,13 @@
 // No atomics, no ticket, no scratch, no dynamically indexed private array; every launch on the caller's stream.
 //
 // The Evaluator's split: the real set of a run never changes, so kg_frechet_real runs the moments and merge
-// launch on the real set alone (the chunking kg_frechet gives it) and kg_frechet_real_solve_kernel - the first half of the
-// solve - and keeps mu_r, tr S_r, G and the sweeps; kg_frechet_sets runs the moments and merge launch on up to
-// KG_FRECHET_MAX_SETS fake sets (the chunking kg_frechet gives a fake set), kg_frechet_sets_solve_kernel - the second half
-// of the solve, one workgroup per (set, class), G read from the cache into the place where kg_frechet_solve_kernel forms
-// it - and kg_frechet_sets_finish_kernel.  The moments and merge kernels walk a list of sets; every sum keeps its order,
-// so each output is, bit for bit, that of kg_frechet(real, fake[g]).
+// launch on the real set alone (the chunking kg_frechet gives it) and kg_frechet_real_solve_kernel, and keeps mu_r, tr S_r,
+// G and the sweeps; kg_frechet_sets runs the moments and merge launch on up to KG_FRECHET_MAX_SETS fake sets (the chunking
+// kg_frechet gives a fake set), kg_frechet_sets_solve_kernel - one workgroup per (set, class), G read from the cache into the
+// place where kg_frechet_solve_kernel forms it - and kg_frechet_sets_finish_kernel.  The solve is written once, as two
+// device functions: fr_real_half (S_r -> V, sqrt(l)) and fr_fake_half (G, S_f -> the terms).  kg_frechet_solve_kernel calls
+// both, the real kernel the first, the sets kernel the second: shared code, not mirrored code.  The moments and merge kernels
+// walk a list of sets; every sum keeps its order, so each output is, bit for bit, that of kg_frechet(real, fake[g]).
 #include <math.h>
 
 #include "kg_common.h"
@@ -296,17 +297,14 @@ __device__ int fr_jacobi(double* A, double* V, int m, int ld, int d, FrSmall& sm
     return sweeps;
 }
 
-__global__ __launch_bounds__(FR_SOLVE_NT) void kg_frechet_solve_kernel(FrDev a) {
-    extern __shared__ __attribute__((aligned(16))) double fr_lds[];
-    __shared__ FrSmall sm;
-    const int tid = threadIdx.x, d = a.d, dd = d * d;
-    const int m = d + (d & 1), ld = m + 1;
-    double* A = fr_lds;
-    double* V = fr_lds + m * ld;
-    const unsigned cls = blockIdx.x;
-    const double* Sr = a.cov + (long)(cls * 2) * dd;
-    const double* Sf = Sr + dd;
+// The solve of one class in two halves, each written ONCE: kg_frechet_solve_kernel runs both, kg_frechet_real_solve_kernel
+// the real half, kg_frechet_sets_solve_kernel the fake half on the G of the cache.  A, V: the two m x m matrices (m = d
+// rounded up to even, row stride ld = m + 1) in dynamic LDS.
 
+// Real half: S_r = V diag(l) V^T.  Leaves V and sm.root[] = sqrt(max(l, 0)) behind a barrier and returns the sweeps;
+// G = V sqrt(l) is the caller's one loop over V[..] * sm.root[..] - in place, or on the way to global memory.
+__device__ __forceinline__ int fr_real_half(const double* __restrict__ Sr, double* A, double* V, int m, int ld, int d, FrSmall& sm) {
+    const int tid = threadIdx.x;
     for (int e = tid; e < m * m; e += FR_SOLVE_NT) {
         const int i = e / m, j = e % m;
         A[i * ld + j] = (i < d && j < d) ? Sr[i * d + j] : 0.0;      // (odd d: one idle index, never rotated)
@@ -317,8 +315,18 @@ __global__ __launch_bounds__(FR_SOLVE_NT) void kg_frechet_solve_kernel(FrDev a) 
 
     if (tid < m) sm.root[tid] = sqrt(fmax(A[tid * ld + tid], 0.0));
     __syncthreads();
-    for (int e = tid; e < m * m; e += FR_SOLVE_NT) V[(e / m) * ld + (e % m)] *= sm.root[e % m];      // G = V sqrt(l)
-    __syncthreads();
+    return sweeps_r;
+}
+
+// Fake half: V holds G (behind a barrier).  W = S_f G into A, H = sym(G^T W) through registers into A, the eigenvalues of
+// H, T, and thread 0 stores the four terms and FD at index o and the sweeps of H at sweeps[slot].  tr S_r is summed from
+// Sr's diagonal, or - Sr null - read from *trr_given.
+__device__ __forceinline__ void fr_fake_half(double* A, double* V, int m, int ld, int d, FrSmall& sm,
+                                             const double* __restrict__ mr, const double* __restrict__ mf,
+                                             const double* __restrict__ Sf, const double* __restrict__ Sr,
+                                             const double* __restrict__ trr_given, double* __restrict__ terms,
+                                             double* __restrict__ values, int32_t* __restrict__ sweeps, long o, long slot) {
+    const int tid = threadIdx.x;
     for (int e = tid; e < m * m; e += FR_SOLVE_NT) {           // W = S_f G, in the place of S_r
         const int i = e / m, j = e % m;
         double w = 0.0;
@@ -356,24 +364,40 @@ __global__ __launch_bounds__(FR_SOLVE_NT) void kg_frechet_solve_kernel(FrDev a) 
     const int sweeps_h = fr_jacobi(A, nullptr, m, ld, d, sm);
 
     if (tid == 0) {
-        const double* mr = a.mu + (long)(cls * 2) * d;
-        const double* mf = mr + d;
         double dmu2 = 0.0, trr = 0.0, trf = 0.0, T = 0.0;
         for (int i = 0; i < d; ++i) {
             const double df = mr[i] - mf[i];
             dmu2 += df * df;
-            trr += Sr[i * d + i];
+            if (Sr != nullptr) trr += Sr[i * d + i];
             trf += Sf[i * d + i];
         }
+        if (Sr == nullptr) trr = *trr_given;
         for (int i = 0; i < m; ++i) T += sqrt(fmax(A[i * ld + i], 0.0));
-        a.terms[cls * 4 + 0] = dmu2;
-        a.terms[cls * 4 + 1] = trr;
-        a.terms[cls * 4 + 2] = trf;
-        a.terms[cls * 4 + 3] = T;
-        a.values[cls] = ((dmu2 + trr) + trf) - 2.0 * T;
-        a.sweeps[cls * 2 + 0] = sweeps_r;
-        a.sweeps[cls * 2 + 1] = sweeps_h;
+        terms[o * 4 + 0] = dmu2;
+        terms[o * 4 + 1] = trr;
+        terms[o * 4 + 2] = trf;
+        terms[o * 4 + 3] = T;
+        values[o] = ((dmu2 + trr) + trf) - 2.0 * T;
+        sweeps[slot] = sweeps_h;
     }
+}
+
+__global__ __launch_bounds__(FR_SOLVE_NT) void kg_frechet_solve_kernel(FrDev a) {
+    extern __shared__ __attribute__((aligned(16))) double fr_lds[];
+    __shared__ FrSmall sm;
+    const int tid = threadIdx.x, d = a.d, dd = d * d;
+    const int m = d + (d & 1), ld = m + 1;
+    double* A = fr_lds;
+    double* V = fr_lds + m * ld;
+    const unsigned cls = blockIdx.x;
+    const double* Sr = a.cov + (long)(cls * 2) * dd;
+    const double* mr = a.mu + (long)(cls * 2) * d;
+
+    const int sweeps_r = fr_real_half(Sr, A, V, m, ld, d, sm);
+    for (int e = tid; e < m * m; e += FR_SOLVE_NT) V[(e / m) * ld + (e % m)] *= sm.root[e % m];      // G = V sqrt(l)
+    __syncthreads();
+    if (tid == 0) a.sweeps[cls * 2 + 0] = sweeps_r;
+    fr_fake_half(A, V, m, ld, d, sm, mr, mr + d, Sr + dd, Sr, nullptr, a.terms, a.values, a.sweeps, cls, cls * 2 + 1);
 }
 
 __global__ void kg_frechet_mean_kernel(const double* values, double* mean, int classes) {
@@ -393,8 +417,8 @@ struct FrRealDev {
     int32_t* sweeps;            // (classes)
 };
 
-// The first half of kg_frechet_solve_kernel: S_r = V diag(l) V^T, G = V sqrt(max(l, 0)) - the words that kernel holds in LDS
-// when it forms W -, tr S_r in its order, the sweeps.
+// The real half alone: G = V sqrt(max(l, 0)) - the words kg_frechet_solve_kernel holds in LDS when it enters the fake half -,
+// tr S_r in that kernel's order, the sweeps.
 __global__ __launch_bounds__(FR_SOLVE_NT) void kg_frechet_real_solve_kernel(FrRealDev a) {
     extern __shared__ __attribute__((aligned(16))) double fr_lds[];
     __shared__ FrSmall sm;
@@ -405,16 +429,7 @@ __global__ __launch_bounds__(FR_SOLVE_NT) void kg_frechet_real_solve_kernel(FrRe
     const unsigned cls = blockIdx.x;
     const double* Sr = a.cov + (long)cls * dd;
 
-    for (int e = tid; e < m * m; e += FR_SOLVE_NT) {
-        const int i = e / m, j = e % m;
-        A[i * ld + j] = (i < d && j < d) ? Sr[i * d + j] : 0.0;
-        V[i * ld + j] = i == j ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    const int sweeps_r = fr_jacobi(A, V, m, ld, d, sm);
-
-    if (tid < m) sm.root[tid] = sqrt(fmax(A[tid * ld + tid], 0.0));
-    __syncthreads();
+    const int sweeps_r = fr_real_half(Sr, A, V, m, ld, d, sm);
     double* G = a.G + (long)cls * m * m;
     for (int e = tid; e < m * m; e += FR_SOLVE_NT) G[e] = V[(e / m) * ld + (e % m)] * sm.root[e % m];
     if (tid == 0) {
@@ -435,8 +450,7 @@ struct FrSetsDev {
     double* values;  double* terms;  int32_t* sweeps;       // (nsets, classes), (nsets, classes, 4), (nsets, classes)
 };
 
-// The second half of kg_frechet_solve_kernel for one (set, class): G from the cache, then W, H, the eigenvalues of H, T and
-// the terms with that kernel's loops.
+// The fake half alone for one (set, class): G from the cache into the place where kg_frechet_solve_kernel forms it.
 __global__ __launch_bounds__(FR_SOLVE_NT) void kg_frechet_sets_solve_kernel(FrSetsDev a) {
     extern __shared__ __attribute__((aligned(16))) double fr_lds[];
     __shared__ FrSmall sm;
@@ -445,66 +459,13 @@ __global__ __launch_bounds__(FR_SOLVE_NT) void kg_frechet_sets_solve_kernel(FrSe
     double* A = fr_lds;
     double* V = fr_lds + m * ld;
     const unsigned g = blockIdx.x / (unsigned)a.classes, cls = blockIdx.x % (unsigned)a.classes;
-    const double* Sf = a.cov + ((long)cls * a.nsets + g) * dd;
+    const long fs = (long)cls * a.nsets + g, o = (long)g * a.classes + cls;     // in the workspace; in the outputs
     const double* G = a.G + (long)cls * m * m;
 
     for (int e = tid; e < m * m; e += FR_SOLVE_NT) V[(e / m) * ld + (e % m)] = G[e];
     __syncthreads();
-    for (int e = tid; e < m * m; e += FR_SOLVE_NT) {           // W = S_f G
-        const int i = e / m, j = e % m;
-        double w = 0.0;
-        if (i < d) {
-            for (int b = 0; b < d; ++b) w = fma(Sf[i * d + b], V[b * ld + j], w);
-        }
-        A[i * ld + j] = w;
-    }
-    __syncthreads();
-    double h[FR_HREG];                                          // H = sym(G^T W), upper entries, through registers
-#pragma unroll
-    for (int u = 0; u < FR_HREG; ++u) {
-        const int e = tid + u * FR_SOLVE_NT;
-        const int i = e / m, j = e % m;
-        double x = 0.0, y = 0.0;
-        if (e < m * m && i <= j) {
-            for (int b = 0; b < m; ++b) {
-                x = fma(V[b * ld + i], A[b * ld + j], x);
-                y = fma(V[b * ld + j], A[b * ld + i], y);
-            }
-        }
-        h[u] = 0.5 * (x + y);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < FR_HREG; ++u) {
-        const int e = tid + u * FR_SOLVE_NT;
-        const int i = e / m, j = e % m;
-        if (e < m * m && i <= j) {
-            A[i * ld + j] = h[u];
-            A[j * ld + i] = h[u];
-        }
-    }
-    __syncthreads();
-    const int sweeps_h = fr_jacobi(A, nullptr, m, ld, d, sm);
-
-    if (tid == 0) {
-        const double* mr = a.mu_real + (long)cls * d;
-        const double* mf = a.mu + ((long)cls * a.nsets + g) * d;
-        double dmu2 = 0.0, trf = 0.0, T = 0.0;
-        for (int i = 0; i < d; ++i) {
-            const double df = mr[i] - mf[i];
-            dmu2 += df * df;
-            trf += Sf[i * d + i];
-        }
-        const double trr = a.tr_real[cls];
-        for (int i = 0; i < m; ++i) T += sqrt(fmax(A[i * ld + i], 0.0));
-        const long o = (long)g * a.classes + cls;
-        a.terms[o * 4 + 0] = dmu2;
-        a.terms[o * 4 + 1] = trr;
-        a.terms[o * 4 + 2] = trf;
-        a.terms[o * 4 + 3] = T;
-        a.values[o] = ((dmu2 + trr) + trf) - 2.0 * T;
-        a.sweeps[o] = sweeps_h;
-    }
+    fr_fake_half(A, V, m, ld, d, sm, a.mu_real + (long)cls * d, a.mu + fs * d, a.cov + fs * dd, nullptr, a.tr_real + cls,
+                 a.terms, a.values, a.sweeps, o, o);
 }
 
 // per set: the class mean as kg_frechet_mean_kernel forms it, and its fp32 rounding (the word kg_eval_record2 reads)
@@ -586,6 +547,41 @@ int frechet_validate(const KgFrechetArgs* a, const char* who, FrPlan& p, int sid
     return 0;
 }
 
+// set `side` (0 = real, 1 = fake) of the plan read through the caller's strides; ch0: the chunks in front of it
+FrSet frechet_set(const float* x, long sc, long ss, long sf, long so, const FrPlan& p, int side, int ch0) {
+    FrSet X;
+    X.p = x;  X.sc = sc;  X.ss = ss;  X.sf = sf;  X.so = so;
+    X.P = (int)p.P[side];  X.cs = p.cs[side];  X.nch = p.nch[side];  X.ch0 = ch0;
+    return X;
+}
+
+// what every launcher fills alike: the index arithmetic, the shape, and the workspace laid out for nset sets
+void frechet_fill(FrDev& d, const FrPlan& p, int nset, int d_inner, int frames, int diff, int classes, void* ws) {
+    d.nset = nset;
+    d.inner = FastDiv::make((unsigned)d_inner);
+    d.fr = FastDiv::make((unsigned)(frames - diff));
+    d.d = p.d;  d.diff = diff;  d.classes = classes;
+    d.part = (double*)ws;
+    d.mu = d.part + p.part_doubles;
+    d.cov = d.mu + (long)classes * nset * p.d;
+}
+
+// the moments and the merge launch; the status strings are the entry point's own
+int frechet_moments_merge(const FrDev& d, const FrPlan& p, hipStream_t s, const char* moments, const char* merge) {
+    if (p.d <= 48) hipLaunchKernelGGL(kg_frechet_moments_kernel<3>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
+    else hipLaunchKernelGGL(kg_frechet_moments_kernel<6>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
+    if (int rc = kg_launch_status(moments)) return rc;
+    hipLaunchKernelGGL(kg_frechet_merge_kernel, dim3((unsigned)p.grid_merge), dim3(FR_NT), 0, s, d);
+    return kg_launch_status(merge);
+}
+
+// a solve kernel takes the LDS of d = FR_MAXD: asked for once per device, before the kernel's first launch there
+#define FR_SOLVE_LDS(kern_)                                                                               \
+    do {                                                                                                  \
+        static unsigned long long mask_ = 0;                                                              \
+        if (kg_first_on_device(mask_)) KG_SET_DYN_LDS(kern_, 2 * FR_MAXD * (FR_MAXD + 1) * 8);            \
+    } while (0)
+
 }  // namespace
 
 extern "C" int64_t kg_frechet_workspace_bytes(const KgFrechetArgs* a) {
@@ -608,32 +604,17 @@ extern "C" int kg_frechet(const KgFrechetArgs* a, void* stream) {
                (long long)p.ws_bytes);
 
     FrDev d = {};
-    d.set[0].p = a->real;  d.set[0].sc = a->r_sc;  d.set[0].ss = a->r_ss;  d.set[0].sf = a->r_sf;  d.set[0].so = a->r_so;
-    d.set[1].p = a->fake;  d.set[1].sc = a->f_sc;  d.set[1].ss = a->f_ss;  d.set[1].sf = a->f_sf;  d.set[1].so = a->f_so;
-    for (int s = 0; s < 2; ++s) {
-        d.set[s].P = (int)p.P[s];  d.set[s].cs = p.cs[s];  d.set[s].nch = p.nch[s];
-    }
-    d.set[1].ch0 = p.nch[0];
-    d.nset = 2;  d.per = p.nch[0] + p.nch[1];
-    d.inner = FastDiv::make((unsigned)a->d_inner);
-    d.fr = FastDiv::make((unsigned)(a->frames - a->diff));
-    d.d = p.d;  d.diff = a->diff;  d.classes = a->classes;
-    d.part = (double*)a->ws;
-    d.mu = d.part + p.part_doubles;
-    d.cov = d.mu + (long)a->classes * 2 * p.d;
+    frechet_fill(d, p, 2, a->d_inner, a->frames, a->diff, a->classes, a->ws);
+    d.set[0] = frechet_set(a->real, a->r_sc, a->r_ss, a->r_sf, a->r_so, p, 0, 0);
+    d.set[1] = frechet_set(a->fake, a->f_sc, a->f_ss, a->f_sf, a->f_so, p, 1, p.nch[0]);
+    d.per = p.nch[0] + p.nch[1];
     d.mu_out[0] = a->mu_real;  d.mu_out[1] = a->mu_fake;
     d.cov_out[0] = a->cov_real;  d.cov_out[1] = a->cov_fake;
     d.values = a->values;  d.terms = a->terms;  d.sweeps = a->sweeps;
     hipStream_t s = (hipStream_t)stream;
 
-    static unsigned long long attr_mask = 0;
-    if (kg_first_on_device(attr_mask)) KG_SET_DYN_LDS(kg_frechet_solve_kernel, 2 * FR_MAXD * (FR_MAXD + 1) * 8);
-
-    if (p.d <= 48) hipLaunchKernelGGL(kg_frechet_moments_kernel<3>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
-    else hipLaunchKernelGGL(kg_frechet_moments_kernel<6>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
-    if (int rc = kg_launch_status("kg_frechet_moments")) return rc;
-    hipLaunchKernelGGL(kg_frechet_merge_kernel, dim3((unsigned)p.grid_merge), dim3(FR_NT), 0, s, d);
-    if (int rc = kg_launch_status("kg_frechet_merge")) return rc;
+    FR_SOLVE_LDS(kg_frechet_solve_kernel);
+    if (int rc = frechet_moments_merge(d, p, s, "kg_frechet_moments", "kg_frechet_merge")) return rc;
     hipLaunchKernelGGL(kg_frechet_solve_kernel, dim3((unsigned)a->classes), dim3(FR_SOLVE_NT), (size_t)p.lds_solve, s, d);
     if (int rc = kg_launch_status("kg_frechet_solve")) return rc;
     if (a->mean != nullptr) {
@@ -693,28 +674,16 @@ extern "C" int kg_frechet_real(const KgFrechetRealArgs* a, void* stream) {
                (long long)a->ws_bytes, (long long)p.ws_bytes);
 
     FrDev d = {};
-    d.set[0].p = a->real;  d.set[0].sc = a->r_sc;  d.set[0].ss = a->r_ss;  d.set[0].sf = a->r_sf;  d.set[0].so = a->r_so;
-    d.set[0].P = (int)p.P[0];  d.set[0].cs = p.cs[0];  d.set[0].nch = p.nch[0];
-    d.nset = 1;  d.per = p.nch[0];
-    d.inner = FastDiv::make((unsigned)a->d_inner);
-    d.fr = FastDiv::make((unsigned)(a->frames - a->diff));
-    d.d = p.d;  d.diff = a->diff;  d.classes = a->classes;
-    d.part = (double*)a->ws;
-    d.mu = d.part + p.part_doubles;
-    d.cov = d.mu + (long)a->classes * p.d;
+    frechet_fill(d, p, 1, a->d_inner, a->frames, a->diff, a->classes, a->ws);
+    d.set[0] = frechet_set(a->real, a->r_sc, a->r_ss, a->r_sf, a->r_so, p, 0, 0);
+    d.per = p.nch[0];
     d.mu_out[0] = a->mu_real;
     FrRealDev r = {};
     r.cov = d.cov;  r.d = p.d;  r.G = a->G;  r.tr = a->tr_real;  r.sweeps = a->sweeps_real;
     hipStream_t s = (hipStream_t)stream;
 
-    static unsigned long long attr_mask = 0;
-    if (kg_first_on_device(attr_mask)) KG_SET_DYN_LDS(kg_frechet_real_solve_kernel, 2 * FR_MAXD * (FR_MAXD + 1) * 8);
-
-    if (p.d <= 48) hipLaunchKernelGGL(kg_frechet_moments_kernel<3>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
-    else hipLaunchKernelGGL(kg_frechet_moments_kernel<6>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
-    if (int rc = kg_launch_status("kg_frechet_real moments")) return rc;
-    hipLaunchKernelGGL(kg_frechet_merge_kernel, dim3((unsigned)p.grid_merge), dim3(FR_NT), 0, s, d);
-    if (int rc = kg_launch_status("kg_frechet_real merge")) return rc;
+    FR_SOLVE_LDS(kg_frechet_real_solve_kernel);
+    if (int rc = frechet_moments_merge(d, p, s, "kg_frechet_real moments", "kg_frechet_real merge")) return rc;
     hipLaunchKernelGGL(kg_frechet_real_solve_kernel, dim3((unsigned)a->classes), dim3(FR_SOLVE_NT), (size_t)p.lds_solve, s, r);
     return kg_launch_status("kg_frechet_real solve");
 }
@@ -743,31 +712,17 @@ extern "C" int kg_frechet_sets(const KgFrechetSetsArgs* a, void* stream) {
                (long long)a->ws_bytes, (long long)p.ws_bytes);
 
     FrDev d = {};
-    for (int g = 0; g < a->nsets; ++g) {
-        d.set[g].p = a->fake[g];  d.set[g].sc = a->f_sc;  d.set[g].ss = a->f_ss;  d.set[g].sf = a->f_sf;  d.set[g].so = a->f_so;
-        d.set[g].P = (int)p.P[1];  d.set[g].cs = p.cs[1];  d.set[g].nch = p.nch[1];  d.set[g].ch0 = g * p.nch[1];
-    }
-    d.nset = a->nsets;  d.per = a->nsets * p.nch[1];
-    d.inner = FastDiv::make((unsigned)a->d_inner);
-    d.fr = FastDiv::make((unsigned)(a->frames - a->diff));
-    d.d = p.d;  d.diff = a->diff;  d.classes = a->classes;
-    d.part = (double*)a->ws;
-    d.mu = d.part + p.part_doubles;
-    d.cov = d.mu + (long)a->classes * a->nsets * p.d;
+    frechet_fill(d, p, a->nsets, a->d_inner, a->frames, a->diff, a->classes, a->ws);
+    for (int g = 0; g < a->nsets; ++g) d.set[g] = frechet_set(a->fake[g], a->f_sc, a->f_ss, a->f_sf, a->f_so, p, 1, g * p.nch[1]);
+    d.per = a->nsets * p.nch[1];
     FrSetsDev v = {};
     v.mu = d.mu;  v.cov = d.cov;  v.mu_real = a->mu_real;  v.tr_real = a->tr_real;  v.G = a->G;
     v.d = p.d;  v.nsets = a->nsets;  v.classes = a->classes;
     v.values = a->values;  v.terms = a->terms;  v.sweeps = a->sweeps;
     hipStream_t s = (hipStream_t)stream;
 
-    static unsigned long long attr_mask = 0;
-    if (kg_first_on_device(attr_mask)) KG_SET_DYN_LDS(kg_frechet_sets_solve_kernel, 2 * FR_MAXD * (FR_MAXD + 1) * 8);
-
-    if (p.d <= 48) hipLaunchKernelGGL(kg_frechet_moments_kernel<3>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
-    else hipLaunchKernelGGL(kg_frechet_moments_kernel<6>, dim3((unsigned)p.grid_moments), dim3(FR_NT), 0, s, d);
-    if (int rc = kg_launch_status("kg_frechet_sets moments")) return rc;
-    hipLaunchKernelGGL(kg_frechet_merge_kernel, dim3((unsigned)p.grid_merge), dim3(FR_NT), 0, s, d);
-    if (int rc = kg_launch_status("kg_frechet_sets merge")) return rc;
+    FR_SOLVE_LDS(kg_frechet_sets_solve_kernel);
+    if (int rc = frechet_moments_merge(d, p, s, "kg_frechet_sets moments", "kg_frechet_sets merge")) return rc;
     hipLaunchKernelGGL(kg_frechet_sets_solve_kernel, dim3((unsigned)(a->nsets * a->classes)), dim3(FR_SOLVE_NT), (size_t)p.lds_solve, s, v);
     if (int rc = kg_launch_status("kg_frechet_sets solve")) return rc;
     hipLaunchKernelGGL(kg_frechet_sets_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)a->values, a->mean, a->mean32,

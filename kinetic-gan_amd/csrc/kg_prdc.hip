@@ -323,31 +323,42 @@ struct PrdcPlan {
 // moves to 64-tiles from about 1500 x 1500 points (and 6 classes of 600 x 600 do); the radii launch has one per ROW tile
 // only, so it stays on 32-tiles until classes * (n + m) reaches about 32768 points - one class of 4096 + 4096 gives 128
 // row tiles of 64 and runs its radii on 32-tiles.  The protocol's 60 x (100 + 100) runs both launches on 32-tiles.
-PrdcPlan prdc_plan(const KgPrdcArgs* a) {
+int prdc_edge(long groups64) { return groups64 >= 512 ? 64 : 32; }
+
+// gc: (set, class) pairs; n_radii: the real rows of the radii launch (n: kg_prdc, 0: kg_prdc_sets, whose real radii are given)
+PrdcPlan prdc_plan(long gc, int n_radii, int n, int m) {
     PrdcPlan p;
-    const long c = a->classes;
-    const long r64 = c * ((long)kg_cdiv(a->n, 64) + kg_cdiv(a->m, 64));
-    p.ti_radii = r64 >= 512 ? 64 : 32;
-    p.grid_radii = c * ((long)kg_cdiv(a->n, p.ti_radii) + kg_cdiv(a->m, p.ti_radii));
-    const long x64 = c * (long)kg_cdiv(a->n, 64) * kg_cdiv(a->m, 64);
-    p.ti_cross = x64 >= 512 ? 64 : 32;
-    p.grid_cross = c * (long)kg_cdiv(a->n, p.ti_cross) * kg_cdiv(a->m, p.ti_cross);
+    p.ti_radii = prdc_edge(gc * ((long)kg_cdiv(n_radii, 64) + kg_cdiv(m, 64)));
+    p.grid_radii = gc * ((long)kg_cdiv(n_radii, p.ti_radii) + kg_cdiv(m, p.ti_radii));
+    p.ti_cross = prdc_edge(gc * kg_cdiv(n, 64) * kg_cdiv(m, 64));
+    p.grid_cross = gc * kg_cdiv(n, p.ti_cross) * kg_cdiv(m, p.ti_cross);
     return p;
+}
+PrdcPlan prdc_plan(const KgPrdcArgs* a) { return prdc_plan(a->classes, a->n, a->n, a->m); }
+
+// The shape requirements of every entry point, in the order their callers are told about them.  m null: one set alone
+// (kg_prdc_radii).
+int prdc_check_shape(const char* who, int n, const int32_t* m, int classes, int d_outer, int d_inner, int k) {
+    KG_REQUIRE(n >= 1, "%s: n=%d < 1", who, n);
+    KG_REQUIRE(m == nullptr || *m >= 1, "%s: m=%d < 1", who, m ? *m : 0);
+    KG_REQUIRE(classes >= 1, "%s: classes=%d < 1", who, classes);
+    KG_REQUIRE(d_outer >= 1, "%s: d_outer=%d < 1", who, d_outer);
+    KG_REQUIRE(d_inner >= 1, "%s: d_inner=%d < 1", who, d_inner);
+    KG_REQUIRE((long)d_outer * d_inner <= 0x7fffffffL, "%s: d_outer=%d x d_inner=%d does not fit 31 bits", who, d_outer, d_inner);
+    KG_REQUIRE(k >= 1 && k <= KG_PRDC_MAX_K, "%s: k=%d outside [1, %d]", who, k, KG_PRDC_MAX_K);
+    KG_REQUIRE(n <= KG_PRDC_MAX_POINTS, "%s: n=%d above the cap of %d points per class", who, n, KG_PRDC_MAX_POINTS);
+    if (m == nullptr) {
+        KG_REQUIRE(k <= n - 1, "%s: k=%d > n=%d - 1 neighbours", who, k, n);
+        return 0;
+    }
+    KG_REQUIRE(*m <= KG_PRDC_MAX_POINTS, "%s: m=%d above the cap of %d points per class", who, *m, KG_PRDC_MAX_POINTS);
+    KG_REQUIRE(k <= (n < *m ? n : *m) - 1, "%s: k=%d > min(n=%d, m=%d) - 1 neighbours", who, k, n, *m);
+    return 0;
 }
 
 int prdc_validate(const KgPrdcArgs* a, const char* who) {
     KG_REQUIRE(a != nullptr, "%s: null args", who);
-    KG_REQUIRE(a->n >= 1, "%s: n=%d < 1", who, a->n);
-    KG_REQUIRE(a->m >= 1, "%s: m=%d < 1", who, a->m);
-    KG_REQUIRE(a->classes >= 1, "%s: classes=%d < 1", who, a->classes);
-    KG_REQUIRE(a->d_outer >= 1, "%s: d_outer=%d < 1", who, a->d_outer);
-    KG_REQUIRE(a->d_inner >= 1, "%s: d_inner=%d < 1", who, a->d_inner);
-    KG_REQUIRE((long)a->d_outer * a->d_inner <= 0x7fffffffL, "%s: d_outer=%d x d_inner=%d does not fit 31 bits", who, a->d_outer,
-               a->d_inner);
-    KG_REQUIRE(a->k >= 1 && a->k <= KG_PRDC_MAX_K, "%s: k=%d outside [1, %d]", who, a->k, KG_PRDC_MAX_K);
-    KG_REQUIRE(a->n <= KG_PRDC_MAX_POINTS, "%s: n=%d above the cap of %d points per class", who, a->n, KG_PRDC_MAX_POINTS);
-    KG_REQUIRE(a->m <= KG_PRDC_MAX_POINTS, "%s: m=%d above the cap of %d points per class", who, a->m, KG_PRDC_MAX_POINTS);
-    KG_REQUIRE(a->k <= (a->n < a->m ? a->n : a->m) - 1, "%s: k=%d > min(n=%d, m=%d) - 1 neighbours", who, a->k, a->n, a->m);
+    if (int rc = prdc_check_shape(who, a->n, &a->m, a->classes, a->d_outer, a->d_inner, a->k)) return rc;
     const PrdcPlan p = prdc_plan(a);
     // gridDim.x * blockDim.x has to stay below 2^32 for the runtime to take the launch: below 2^24 workgroups of 256 threads
     KG_REQUIRE(p.grid_radii < PR_MAX_GRID && p.grid_cross < PR_MAX_GRID,
@@ -365,6 +376,18 @@ void prdc_launch_radii(const PrdcDev& d, long grid, hipStream_t s) {
 template <int TI, int MI>
 void prdc_launch_cross(const PrdcDev& d, long grid, hipStream_t s) {
     hipLaunchKernelGGL((kg_prdc_cross_kernel<TI, MI>), dim3((unsigned)grid), dim3(PR_NT), 0, s, d);
+}
+
+// the finish launch on the flag / hit words of d; `what`: the entry point's name for the launch in the messages
+int prdc_finish(const PrdcDev& d, int32_t* hits_out, uint8_t* flags_out, int32_t* counts, float* values, float* mean,
+                hipStream_t s, const char* what) {
+    PrdcFin fin;
+    fin.flags = d.flags;  fin.hits = d.hits;
+    fin.hits_out = hits_out;  fin.flags_out = flags_out;
+    fin.counts = counts;  fin.values = values;  fin.mean = mean;
+    fin.n = d.set[0].n;  fin.m = d.set[1].n;  fin.classes = d.classes;  fin.k = d.k;  fin.nsets = d.nsets;
+    hipLaunchKernelGGL(kg_prdc_finish_kernel, dim3(1), dim3(PR_FIN), 0, s, fin);
+    return kg_launch_status(what);
 }
 
 }  // namespace
@@ -408,47 +431,21 @@ extern "C" int kg_prdc(const KgPrdcArgs* a, void* stream) {
     else prdc_launch_cross<64, 4>(d, p.grid_cross, s);
     if (int rc = kg_launch_status("kg_prdc_cross")) return rc;
 
-    PrdcFin fin;
-    fin.flags = d.flags;  fin.hits = d.hits;
-    fin.hits_out = a->fake_hits;  fin.flags_out = a->real_flags;
-    fin.counts = a->counts;  fin.values = a->values;  fin.mean = a->mean;
-    fin.n = a->n;  fin.m = a->m;  fin.classes = a->classes;  fin.k = a->k;  fin.nsets = 1;
-    hipLaunchKernelGGL(kg_prdc_finish_kernel, dim3(1), dim3(PR_FIN), 0, s, fin);
-    return kg_launch_status("kg_prdc_finish");
+    return prdc_finish(d, a->fake_hits, a->real_flags, a->counts, a->values, a->mean, s, "kg_prdc_finish");
 }
 
 // ---- one set's radii alone; several fake sets against one real set with given radii ------------------------
 
 namespace {
 
-// The rule of prdc_plan with the workgroups these launches really have: row tiles of ONE set (kg_prdc_radii), of the
-// nsets fake sets (kg_prdc_sets, radii), tiles of nsets x classes x (n x m) (kg_prdc_sets, cross).
-int prdc_edge(long groups64) { return groups64 >= 512 ? 64 : 32; }
-
-PrdcPlan prdc_sets_plan(const KgPrdcSetsArgs* a) {
-    PrdcPlan p;
-    const long gc = (long)a->nsets * a->classes;
-    p.ti_radii = prdc_edge(gc * kg_cdiv(a->m, 64));
-    p.grid_radii = gc * kg_cdiv(a->m, p.ti_radii);
-    p.ti_cross = prdc_edge(gc * kg_cdiv(a->n, 64) * kg_cdiv(a->m, 64));
-    p.grid_cross = gc * kg_cdiv(a->n, p.ti_cross) * kg_cdiv(a->m, p.ti_cross);
-    return p;
-}
+// The rule of prdc_plan with the workgroups these launches really have: row tiles of the nsets fake sets (radii), tiles of
+// nsets x classes x (n x m) (cross).
+PrdcPlan prdc_sets_plan(const KgPrdcSetsArgs* a) { return prdc_plan((long)a->nsets * a->classes, 0, a->n, a->m); }
 
 int prdc_sets_validate(const KgPrdcSetsArgs* a, const char* who) {
     KG_REQUIRE(a != nullptr, "%s: null args", who);
     KG_REQUIRE(a->nsets >= 1 && a->nsets <= KG_PRDC_MAX_SETS, "%s: nsets=%d outside [1, %d]", who, a->nsets, KG_PRDC_MAX_SETS);
-    KG_REQUIRE(a->n >= 1, "%s: n=%d < 1", who, a->n);
-    KG_REQUIRE(a->m >= 1, "%s: m=%d < 1", who, a->m);
-    KG_REQUIRE(a->classes >= 1, "%s: classes=%d < 1", who, a->classes);
-    KG_REQUIRE(a->d_outer >= 1, "%s: d_outer=%d < 1", who, a->d_outer);
-    KG_REQUIRE(a->d_inner >= 1, "%s: d_inner=%d < 1", who, a->d_inner);
-    KG_REQUIRE((long)a->d_outer * a->d_inner <= 0x7fffffffL, "%s: d_outer=%d x d_inner=%d does not fit 31 bits", who, a->d_outer,
-               a->d_inner);
-    KG_REQUIRE(a->k >= 1 && a->k <= KG_PRDC_MAX_K, "%s: k=%d outside [1, %d]", who, a->k, KG_PRDC_MAX_K);
-    KG_REQUIRE(a->n <= KG_PRDC_MAX_POINTS, "%s: n=%d above the cap of %d points per class", who, a->n, KG_PRDC_MAX_POINTS);
-    KG_REQUIRE(a->m <= KG_PRDC_MAX_POINTS, "%s: m=%d above the cap of %d points per class", who, a->m, KG_PRDC_MAX_POINTS);
-    KG_REQUIRE(a->k <= (a->n < a->m ? a->n : a->m) - 1, "%s: k=%d > min(n=%d, m=%d) - 1 neighbours", who, a->k, a->n, a->m);
+    if (int rc = prdc_check_shape(who, a->n, &a->m, a->classes, a->d_outer, a->d_inner, a->k)) return rc;
     const PrdcPlan p = prdc_sets_plan(a);
     KG_REQUIRE(p.grid_radii < PR_MAX_GRID && p.grid_cross < PR_MAX_GRID,
                "%s: nsets=%d x classes=%d x tiles of n=%d x m=%d make %ld workgroups, one launch takes fewer than %ld", who, a->nsets,
@@ -465,15 +462,7 @@ int64_t prdc_sets_ws_bytes(const KgPrdcSetsArgs* a) {
 extern "C" int kg_prdc_radii(const KgPrdcRadiiArgs* a, void* stream) {
     const char* who = "kg_prdc_radii";
     KG_REQUIRE(a != nullptr, "%s: null args", who);
-    KG_REQUIRE(a->n >= 1, "%s: n=%d < 1", who, a->n);
-    KG_REQUIRE(a->classes >= 1, "%s: classes=%d < 1", who, a->classes);
-    KG_REQUIRE(a->d_outer >= 1, "%s: d_outer=%d < 1", who, a->d_outer);
-    KG_REQUIRE(a->d_inner >= 1, "%s: d_inner=%d < 1", who, a->d_inner);
-    KG_REQUIRE((long)a->d_outer * a->d_inner <= 0x7fffffffL, "%s: d_outer=%d x d_inner=%d does not fit 31 bits", who, a->d_outer,
-               a->d_inner);
-    KG_REQUIRE(a->k >= 1 && a->k <= KG_PRDC_MAX_K, "%s: k=%d outside [1, %d]", who, a->k, KG_PRDC_MAX_K);
-    KG_REQUIRE(a->n <= KG_PRDC_MAX_POINTS, "%s: n=%d above the cap of %d points per class", who, a->n, KG_PRDC_MAX_POINTS);
-    KG_REQUIRE(a->k <= a->n - 1, "%s: k=%d > n=%d - 1 neighbours", who, a->k, a->n);
+    if (int rc = prdc_check_shape(who, a->n, nullptr, a->classes, a->d_outer, a->d_inner, a->k)) return rc;
     const int ti = prdc_edge((long)a->classes * kg_cdiv(a->n, 64));
     const long grid = (long)a->classes * kg_cdiv(a->n, ti);
     KG_REQUIRE(grid < PR_MAX_GRID, "%s: classes=%d x row tiles of n=%d make %ld workgroups, one launch takes fewer than %ld", who,
@@ -534,11 +523,5 @@ extern "C" int kg_prdc_sets(const KgPrdcSetsArgs* a, void* stream) {
     else prdc_launch_cross<64, 4>(d, p.grid_cross, s);
     if (int rc = kg_launch_status("kg_prdc_sets_cross")) return rc;
 
-    PrdcFin fin;
-    fin.flags = d.flags;  fin.hits = d.hits;
-    fin.hits_out = a->fake_hits;  fin.flags_out = a->real_flags;
-    fin.counts = a->counts;  fin.values = a->values;  fin.mean = a->mean;
-    fin.n = a->n;  fin.m = a->m;  fin.classes = a->classes;  fin.k = a->k;  fin.nsets = a->nsets;
-    hipLaunchKernelGGL(kg_prdc_finish_kernel, dim3(1), dim3(PR_FIN), 0, s, fin);
-    return kg_launch_status("kg_prdc_sets_finish");
+    return prdc_finish(d, a->fake_hits, a->real_flags, a->counts, a->values, a->mean, s, "kg_prdc_sets_finish");
 }

@@ -138,22 +138,8 @@ class Evaluator:
                  prdc_k: int = 5, frechet_per_class: int = 0, frechet_modes: Sequence[str] = ("pose", "motion")):
         if not generators:
             raise ValueError("Evaluator: at least one generator")
-        self.frechet_per_class = int(frechet_per_class)
-        if self.frechet_per_class < 0:
-            raise ValueError("Evaluator: frechet_per_class=%d < 0" % self.frechet_per_class)
-        # (the modes in the order of metrics.FRECHET_MODES, whatever order they were asked for in)
-        self.frechet_modes = tuple(f for f in metrics.FRECHET_MODES if f in tuple(frechet_modes)) if self.frechet_per_class else ()
-        if self.frechet_per_class and (not self.frechet_modes or set(frechet_modes) - set(metrics.FRECHET_MODES)):
-            raise ValueError("Evaluator: frechet_modes %r: one or more of %s" % (tuple(frechet_modes), metrics.FRECHET_MODES))
-        self.prdc_per_class, self.prdc_k = int(prdc_per_class), int(prdc_k)
-        if self.prdc_per_class < 0:
-            raise ValueError("Evaluator: prdc_per_class=%d < 0" % self.prdc_per_class)
-        if self.prdc_per_class and not 1 <= self.prdc_k <= min(nv.PRDC_MAX_K, self.prdc_per_class - 1):
-            raise ValueError("Evaluator: prdc_k=%d outside [1, min(%d, prdc_per_class=%d - 1)]" % (
-                self.prdc_k, nv.PRDC_MAX_K, self.prdc_per_class))
-        if self.prdc_per_class > nv.PRDC_MAX_POINTS:
-            raise ValueError("Evaluator: prdc_per_class=%d above the cap of %d points per class" % (
-                self.prdc_per_class, nv.PRDC_MAX_POINTS))
+        self._check_frechet_options(frechet_per_class, frechet_modes)
+        self._check_prdc_options(prdc_per_class, prdc_k)
         self.modes = tuple(modes)
         for m in self.modes:
             metrics._check_mode(m)
@@ -184,23 +170,17 @@ class Evaluator:
         self.n_classes, self.n = s0.n_classes, s0.n
         if any(s.n_classes != self.n_classes for s in self.samplers.values()):
             raise ValueError("Evaluator: the generators differ in their number of classes")
-        # the real side, once: row j*K + c = the j-th selected real sample of class c (the Sampler's label order)
-        if real_labels is None and hasattr(real, "label") and hasattr(real, "data"):
-            data, lab, _ = metrics.select_reference_samples(real, np.arange(self.n_classes),
-                                                            int(t_size) if t_size is not None else int(first.t_size), per_class=self.pairs)
-        else:
-            data = real.detach().cpu().numpy() if isinstance(real, torch.Tensor) else np.asarray(real)
-            lab = real_labels.detach().cpu().numpy() if isinstance(real_labels, torch.Tensor) else np.asarray(real_labels)
+        t_size = int(t_size) if t_size is not None else int(first.t_size)
         if self.prdc_per_class:
-            self._prdc_setup(real, real_labels, first, t_size, trunc, trunc_mode)
+            self._prdc_setup(real, real_labels, t_size, trunc, trunc_mode)
         else:
             self.prdc_samplers, self.prdc_real, self.prdc_radii = {}, None, None
         if self.frechet_per_class:
-            self._frechet_setup(real, real_labels, first, t_size, trunc, trunc_mode)
+            self._frechet_setup(real, real_labels, t_size, trunc, trunc_mode)
         else:
             self.frechet_samplers, self.frechet_real, self.frechet_cache = {}, None, {}
-        rows = pair_rows(lab, self.n_classes, self.pairs)
-        self.real = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32)[rows])).to(dev)
+        # the real side, once: row j*K + c = the j-th selected real sample of class c (the Sampler's label order)
+        self.real = torch.as_tensor(self._select_real(real, real_labels, self.pairs, "pairs", t_size)).to(dev)
         self._pair_labels = np.arange(self.n)                  # every (fake, real) pair is a "class" of the kg_mmd call
         self._nchw = None
         if "joint" in self.modes and self.real.shape[1] > 1 and self.real.shape[2] > 1:
@@ -235,20 +215,65 @@ class Evaluator:
         self._scores = None
         self._graph = None
 
+    def _check_frechet_options(self, frechet_per_class, frechet_modes):
+        self.frechet_per_class = int(frechet_per_class)
+        if self.frechet_per_class < 0:
+            raise ValueError("Evaluator: frechet_per_class=%d < 0" % self.frechet_per_class)
+        # (the modes in the order of metrics.FRECHET_MODES, whatever order they were asked for in)
+        self.frechet_modes = tuple(f for f in metrics.FRECHET_MODES if f in tuple(frechet_modes)) if self.frechet_per_class else ()
+        if self.frechet_per_class and (not self.frechet_modes or set(frechet_modes) - set(metrics.FRECHET_MODES)):
+            raise ValueError("Evaluator: frechet_modes %r: one or more of %s" % (tuple(frechet_modes), metrics.FRECHET_MODES))
+
+    def _check_prdc_options(self, prdc_per_class, prdc_k):
+        self.prdc_per_class, self.prdc_k = int(prdc_per_class), int(prdc_k)
+        if self.prdc_per_class < 0:
+            raise ValueError("Evaluator: prdc_per_class=%d < 0" % self.prdc_per_class)
+        if self.prdc_per_class and not 1 <= self.prdc_k <= min(nv.PRDC_MAX_K, self.prdc_per_class - 1):
+            raise ValueError("Evaluator: prdc_k=%d outside [1, min(%d, prdc_per_class=%d - 1)]" % (
+                self.prdc_k, nv.PRDC_MAX_K, self.prdc_per_class))
+        if self.prdc_per_class > nv.PRDC_MAX_POINTS:
+            raise ValueError("Evaluator: prdc_per_class=%d above the cap of %d points per class" % (
+                self.prdc_per_class, nv.PRDC_MAX_POINTS))
+
+    def _select_real(self, real, real_labels, per_class, order, t_size) -> np.ndarray:
+        """The first ``per_class`` real samples of every class as one contiguous fp32 host array (n_classes * per_class, C,
+        t, V): from a ``Feeder`` (``metrics.select_reference_samples``, cropped to ``t_size``) or from ``real`` with
+        ``real_labels``.  ``order="pairs"``: the Sampler's row order (``pair_rows``); ``"classes"``: class by class
+        (``class_rows``; a Feeder's selection is in that order already, so it is left as it is)."""
+        K = self.n_classes
+        if real_labels is None and hasattr(real, "label") and hasattr(real, "data"):
+            data, lab, _ = metrics.select_reference_samples(real, np.arange(K), t_size, per_class=per_class)
+        else:
+            data = real.detach().cpu().numpy() if isinstance(real, torch.Tensor) else np.asarray(real)
+            lab = real_labels.detach().cpu().numpy() if isinstance(real_labels, torch.Tensor) else np.asarray(real_labels)
+        rows = (pair_rows if order == "pairs" else class_rows)(lab, K, per_class)
+        return np.ascontiguousarray(np.asarray(data, dtype=np.float32)[rows])
+
+    def _checked_rounds(self, samplers_or_outs, real_shape):
+        """One round of every Sampler given (a tensor given instead is a round that has been run already: the PRDC round the
+        Frechet scores share), each (P*K, C, T, V) with row j*K + c = sample j of class c and read in place - so it has to
+        have the real side's sample shape, be a plane, and all of them the same strides.  Returns (outs, sn, sc)."""
+        outs = []
+        for out in samplers_or_outs:
+            if not torch.is_tensor(out):
+                out._round()
+                out = out._out
+            if tuple(out.shape[1:]) != tuple(real_shape[1:]) or not nv.is_plane(out):
+                raise ValueError("Evaluator: generated samples %s against real samples %s" % (
+                    tuple(out.shape[1:]), tuple(real_shape[1:])))
+            outs.append(out)
+        sn, sc = nv._sn_sc(outs[0])
+        if any(nv._sn_sc(q) != (sn, sc) for q in outs):
+            raise ValueError("Evaluator: the generators' rounds differ in their strides")
+        return outs, sn, sc
+
     # ---- precision / recall / density / coverage (DESIGN.md 17) -----------------------------------------------------------
-    def _prdc_setup(self, real, real_labels, first, t_size, trunc, trunc_mode):
+    def _prdc_setup(self, real, real_labels, t_size, trunc, trunc_mode):
         """the real side, once: ``prdc_per_class`` samples of every class, class by class on the device, and their radii
         (one kg_prdc_radii launch; deterministic, so not part of the state); per generator a second Sampler whose round
         kg_prdc_sets reads in place"""
         dev, K, P = self.device, self.n_classes, self.prdc_per_class
-        if real_labels is None and hasattr(real, "label") and hasattr(real, "data"):
-            data, _, _ = metrics.select_reference_samples(real, np.arange(K), int(t_size) if t_size is not None else int(first.t_size),
-                                                          per_class=P)
-        else:
-            data = real.detach().cpu().numpy() if isinstance(real, torch.Tensor) else np.asarray(real)
-            lab = real_labels.detach().cpu().numpy() if isinstance(real_labels, torch.Tensor) else np.asarray(real_labels)
-            data = np.asarray(data, dtype=np.float32)[class_rows(lab, K, P)]
-        self.prdc_real = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32))).to(dev)    # (K*P, C, t, V)
+        self.prdc_real = torch.as_tensor(self._select_real(real, real_labels, P, "classes", t_size)).to(dev)    # (K*P, C, t, V)
         self._prdc_D = int(np.prod(self.prdc_real.shape[1:]))
         self._prdc_rv = nv.PrdcView(self.prdc_real, P * self._prdc_D, self._prdc_D, 0)
         self.prdc_samplers = {k: Sampler(G, qtd=P, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False)
@@ -263,20 +288,8 @@ class Evaluator:
         """the PRDC rounds of all generators, then ONE kg_prdc_sets per PRDC_MAX_SETS generators: the (nsets, 4) class means,
         whose elements are the scores"""
         K, P = self.n_classes, self.prdc_per_class
-        outs = []
-        for s in self.prdc_samplers.values():
-            s._round()
-            out = s._out                     # (P*K, C, T, V), row j*K + c = sample j of class c; read in place
-            _, C, T, V = out.shape
-            if tuple(out.shape[1:]) != tuple(self.prdc_real.shape[1:]) or not nv.is_plane(out):
-                raise ValueError("Evaluator: generated samples %s against real samples %s" % (
-                    tuple(out.shape[1:]), tuple(self.prdc_real.shape[1:])))
-            outs.append(out)
-        o = outs[0]
-        _, C, T, V = o.shape
-        sn, sc = nv._sn_sc(o)
-        if any(nv._sn_sc(q) != (sn, sc) for q in outs):
-            raise ValueError("Evaluator: the generators' rounds differ in their strides")
+        outs, sn, sc = self._checked_rounds(self.prdc_samplers.values(), self.prdc_real.shape)
+        _, C, T, V = outs[0].shape
         d_outer, d_inner, so = (1, C * T * V, 0) if C == 1 else (C, T * V, sc)
         rv = self._prdc_rv if d_outer == 1 else self._prdc_rv._replace(so=T * V)
         scores = []
@@ -288,19 +301,12 @@ class Evaluator:
         return scores
 
     # ---- Frechet pose / motion distance --------------------------------------------------------------------
-    def _frechet_setup(self, real, real_labels, first, t_size, trunc, trunc_mode):
+    def _frechet_setup(self, real, real_labels, t_size, trunc, trunc_mode):
         """the real side, once: ``frechet_per_class`` samples of every class, class by class on the device, and per mode
         their cache (one kg_frechet_real call; deterministic, so not part of the state); per generator a Sampler of its
         own whose round kg_frechet_sets reads in place - unless the PRDC round has the same count and is read instead"""
         dev, K, P = self.device, self.n_classes, self.frechet_per_class
-        if real_labels is None and hasattr(real, "label") and hasattr(real, "data"):
-            data, _, _ = metrics.select_reference_samples(real, np.arange(K), int(t_size) if t_size is not None else int(first.t_size),
-                                                          per_class=P)
-        else:
-            data = real.detach().cpu().numpy() if isinstance(real, torch.Tensor) else np.asarray(real)
-            lab = real_labels.detach().cpu().numpy() if isinstance(real_labels, torch.Tensor) else np.asarray(real_labels)
-            data = np.asarray(data, dtype=np.float32)[class_rows(lab, K, P)]
-        self.frechet_real = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32))).to(dev)    # (K*P, C, t, V)
+        self.frechet_real = torch.as_tensor(self._select_real(real, real_labels, P, "classes", t_size)).to(dev)  # (K*P, C, t, V)
         _, C, T, V = self.frechet_real.shape
         if C * V > nv.FRECHET_MAX_DIM:
             raise ValueError("Evaluator: frechet needs d = C*V = %d <= %d" % (C * V, nv.FRECHET_MAX_DIM))
@@ -321,22 +327,10 @@ class Evaluator:
         """the Frechet rounds of all generators (the PRDC rounds when they are shared), then per mode ONE kg_frechet_sets per
         FRECHET_MAX_SETS generators: the mean32 words, which are the scores - generator by generator, mode by mode"""
         K, P = self.n_classes, self.frechet_per_class
-        outs = []
-        for k in self.gens:
-            if self._frechet_shared:
-                out = self.prdc_samplers[k]._out         # this evaluation's PRDC round: no third round
-            else:
-                s = self.frechet_samplers[k]
-                s._round()
-                out = s._out                 # (P*K, C, T, V), row j*K + c = sample j of class c; read in place
-            if tuple(out.shape[1:]) != tuple(self.frechet_real.shape[1:]) or not nv.is_plane(out):
-                raise ValueError("Evaluator: generated samples %s against real samples %s" % (
-                    tuple(out.shape[1:]), tuple(self.frechet_real.shape[1:])))
-            outs.append(out)
+        # (shared: this evaluation's PRDC rounds, no third round)
+        rounds = [s._out for s in self.prdc_samplers.values()] if self._frechet_shared else self.frechet_samplers.values()
+        outs, sn, sc = self._checked_rounds(rounds, self.frechet_real.shape)
         _, C, T, V = outs[0].shape
-        sn, sc = nv._sn_sc(outs[0])
-        if any(nv._sn_sc(q) != (sn, sc) for q in outs):
-            raise ValueError("Evaluator: the generators' rounds differ in their strides")
         so = sc if C > 1 else 0
         per_mode = {}
         for f in self.frechet_modes:
