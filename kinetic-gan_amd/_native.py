@@ -7,6 +7,22 @@ raises.  (tests/ swap these functions for torch emulations to exercise the autog
 on a CPU-only box; the product never does.)
 
 "Plane tensor" = logical (N, C, T, V) tensor whose (t, v) plane is contiguous; see kgan_hip.h.
+
+How an entry point is bound - the idioms are written once:
+  * ``_Foo`` mirrors the header's ``KgFoo`` field for field, ``X`` its ``#define KG_X`` (tests/test_abi_cpu.py compares every
+    size, offset and constant with the compiled header).
+  * ``_bind(a, field, prefix, t)`` writes a plane operand (pointer, <prefix>_sN, <prefix>_sC); ``_plane(t)`` makes the
+    KgPlane-typed fields of the fused generator block.  Special addressing (a broadcast operand, an offset output) is
+    spelled out where it happens.
+  * ``_query`` asks a ``*_bytes`` size query and raises the library's message when it answers < 0; ``_workspace`` also
+    allocates the scratch and attaches it (and the ticket counters of ``_sync_buffer``) to the struct, or hands it to a
+    ``*_many`` launcher's (ws, bytes) arguments.
+  * A struct that a single and a ``_many`` entry point share has ONE filler (``_conv_args``, ``_wgrad_args``,
+    ``_rowsum_fill``, ``_bn_fwd_fill``, ``_bn_bwd_fill``, ``_gp_args``, ``_head_args``); the ``_many`` form loops over it.
+  * ``_dest`` checks a flat fp32 destination, ``_chunks`` walks a job table in launches of at most X_MAX_JOBS entries.
+  * Lifetime: a tensor whose pointer sits in a struct must stay referenced until the launch call has returned (stream order
+    protects it afterwards).  ``as_plane`` / ``contiguous`` copies and scratch tensors have no other owner, so the helpers
+    RETURN what they bound and the callers hold it (``keep`` / ``held`` / ``ws``) - these names look unused and are not.
 """
 from __future__ import annotations
 
@@ -673,6 +689,59 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _bind(a, field: str, pre: str, t: torch.Tensor, convert: bool = False) -> torch.Tensor:
+    """Bind a plane tensor to a struct: a.<field> = its pointer, a.<pre>_sN / a.<pre>_sC = its strides.  ``convert``: through
+    as_plane first.  Returns the tensor that was bound - the caller holds it until the launch is enqueued."""
+    if convert:
+        t = as_plane(t)
+    setattr(a, field, t.data_ptr())
+    sn, sc = _sn_sc(t)
+    setattr(a, pre + "_sN", sn)
+    setattr(a, pre + "_sC", sc)
+    return t
+
+
+def _query(query: str, a, count: Optional[int] = None) -> int:
+    """The bytes the library's size query ``query`` answers for the filled struct ``a`` (for the ``count`` structs of the array
+    ``a``: the *_many launchers); an answer < 0 raises the library's message through _check."""
+    fn = getattr(load_library(), query)
+    nbytes = fn(C.byref(a)) if count is None else fn(a, count)
+    if nbytes < 0:
+        _check(-1, query)
+    return nbytes
+
+
+def _workspace(query: str, a, device, count: Optional[int] = None, tickets: Optional[str] = None, lazy: bool = False):
+    """_query, then allocate that much fp32 scratch.  One struct: a.ws / a.ws_bytes are set, and with ``tickets`` ("counters" /
+    "sync") a.<tickets> / a.<tickets>_len name the stream's ticket counters.  An array of ``count`` structs: the caller passes
+    ws.data_ptr(), ws.numel() * 4 to its launcher.  ``lazy``: a launch that needs no scratch gets none - nothing is allocated
+    or set (the library's plan reads these fields) and None is returned.  The caller holds the result until its launch."""
+    nbytes = _query(query, a, count)
+    if lazy and nbytes == 0:
+        return None
+    ws = torch.empty(nbytes // 4 if lazy else max(1, nbytes // 4), dtype=torch.float32, device=device)
+    if count is None:
+        a.ws, a.ws_bytes = ws.data_ptr(), nbytes if lazy else ws.numel() * 4
+        if tickets is not None:
+            sync = _sync_buffer(device)
+            setattr(a, tickets, sync.data_ptr())
+            setattr(a, tickets + "_len", sync.numel())
+    return ws
+
+
+def _dest(t: torch.Tensor, n: int, msg: str) -> torch.Tensor:
+    """a destination the kernels write flat: contiguous fp32 of n elements, else ValueError(msg)"""
+    if t.numel() != n or not t.is_contiguous() or t.dtype != torch.float32:
+        raise ValueError(msg)
+    return t
+
+
+def _chunks(jobs: Sequence, most: int):
+    """the job table in runs of at most ``most`` entries: one launch each"""
+    for i in range(0, len(jobs), most):
+        yield jobs[i:i + most]
+
+
 # ---- weight addressing -------------------------------------------------------------------------------
 
 class WView(NamedTuple):
@@ -727,8 +796,7 @@ def _conv_args(groups: Sequence[Group], N: int, M: int, T_out: int, V_out: int,
         _need_cuda(x, w, g.vmap)
         keep += [x, w]
         cg = a.g[i]
-        cg.x = x.data_ptr()
-        cg.x_sN, cg.x_sC = _sn_sc(x)
+        _bind(cg, "x", "x", x)
         cg.Cin, cg.T_in, cg.V_in = g.Cin, x.shape[2], x.shape[3]
         cg.x_lead = min(int(x.storage_offset()), 1 << 20)
         cg.vmap = _ptr(g.vmap)
@@ -753,10 +821,7 @@ def _conv_args(groups: Sequence[Group], N: int, M: int, T_out: int, V_out: int,
     _need_cuda(bias0, bias1, add)
     a.bias0, a.bias1 = _ptr(bias0), _ptr(bias1)
     if add is not None:
-        add = as_plane(add)
-        keep.append(add)
-        a.add = add.data_ptr()
-        a.a_sN, a.a_sC = _sn_sc(add)
+        keep.append(_bind(a, "add", "a", add, True))
     a.a_tstride = add_tstride
     a.act, a.slope = act, slope
     if mask is not None:
@@ -764,9 +829,7 @@ def _conv_args(groups: Sequence[Group], N: int, M: int, T_out: int, V_out: int,
         _need_cuda(mask)
         if tuple(mask.shape) != (N, M, T_out, V_out):
             raise ValueError(f"conv: mask shape {tuple(mask.shape)} != output shape {(N, M, T_out, V_out)}")
-        keep.append(mask)
-        a.mask = mask.data_ptr()
-        a.m_sN, a.m_sC = _sn_sc(mask)
+        keep.append(_bind(a, "mask", "m", mask))
     _count("kg_conv", 2.0 * M * sum(g.taps * g.Cin for g in groups) * N * T_out * V_out)
     return a, out, keep
 
@@ -777,9 +840,7 @@ def conv_pack(groups: Sequence[Group], N: int, M: int, T_out: int, V_out: int, o
     size) until the weights change; ``out``: a buffer of an earlier call to refill in place."""
     lib = load_library()
     a, _, keep = _conv_args(groups, N, M, T_out, V_out, alloc_out=False)
-    nbytes = lib.kg_conv_pack_bytes(C.byref(a))
-    if nbytes < 0:
-        _check(-1, "kg_conv_pack_bytes")
+    nbytes = _query("kg_conv_pack_bytes", a)
     if nbytes == 0:
         return None
     if out is None:
@@ -803,14 +864,9 @@ def conv(groups: Sequence[Group], N: int, M: int, T_out: int, V_out: int,
         t, ns = C.c_int32(), C.c_int32()
         lib.kg_conv_plan_info(C.byref(a), C.byref(t), C.byref(ns))
         last_conv_plan[:] = [t.value, ns.value]
-    nbytes = lib.kg_conv_workspace_bytes(C.byref(a))
-    if nbytes < 0:
-        _check(-1, "kg_conv_workspace_bytes")
-    if nbytes > 0:
-        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=groups[0].x.device)
-        a.ws, a.ws_bytes = ws.data_ptr(), nbytes
-        sync = _sync_buffer(groups[0].x.device)     # a K-split launch completes its tiles itself (no epilogue launch)
-        a.sync, a.sync_len = sync.data_ptr(), sync.numel()
+    # (scratch only for a K-split launch, which completes its tiles itself through the ticket counters: no epilogue launch;
+    #  ws and keep are held until the launch below is enqueued)
+    ws = _workspace("kg_conv_workspace_bytes", a, groups[0].x.device, tickets="sync", lazy=True)
     _check(lib.kg_conv(C.byref(a), _stream()), "kg_conv")
     return out
 
@@ -825,24 +881,15 @@ def conv_many(jobs: Sequence[dict]) -> list:
     lib = load_library()
     if len(jobs) == 1:
         return [conv(**jobs[0])]
-    outs, keep = [], []
-    for i0 in range(0, len(jobs), CONV_MANY_MAX):
-        chunk = jobs[i0:i0 + CONV_MANY_MAX]
+    outs, keep = [], []          # keep: converted operands and scratch of every job, held until its launch is enqueued
+    for chunk in _chunks(jobs, CONV_MANY_MAX):
         arr = (_ConvArgs * len(chunk))()
         for i, j in enumerate(chunk):
             a, out, kp = _conv_args(**j)
-            nbytes = lib.kg_conv_workspace_bytes(C.byref(a))
-            if nbytes < 0:
-                _check(-1, "kg_conv_workspace_bytes")
-            if nbytes > 0:          # (only used when the call falls back to one launch per job)
-                ws = torch.empty(nbytes // 4, dtype=torch.float32, device=out.device)
-                a.ws, a.ws_bytes = ws.data_ptr(), nbytes
-                sync = _sync_buffer(out.device)
-                a.sync, a.sync_len = sync.data_ptr(), sync.numel()
-                kp.append(ws)
+            # (the scratch is only used when the call falls back to one launch per job)
+            keep += kp + [_workspace("kg_conv_workspace_bytes", a, out.device, tickets="sync", lazy=True)]
             arr[i] = a
             outs.append(out)
-            keep += kp
         if last_conv_plan is not None:       # tests: the shared launch's tile, or -1 (one launch per job)
             t = C.c_int32()
             lib.kg_conv_many_plan(arr, len(chunk), C.byref(t))
@@ -861,10 +908,8 @@ def _wgrad_args(g, x, Cin, taps, tap_mode, t_stride, vmap, wv, dw, accumulate, e
     _need_cuda(g, x, vmap, dw)
     a = _WgradArgs()
     a.N, a.M, a.T_out, a.V_out = g.shape
-    a.g = g.data_ptr()
-    a.g_sN, a.g_sC = _sn_sc(g)
-    a.x = x.data_ptr()
-    a.x_sN, a.x_sC = _sn_sc(x)
+    _bind(a, "g", "g", g)
+    _bind(a, "x", "x", x)
     a.Cin, a.T_in, a.V_in = Cin, x.shape[2], x.shape[3]
     a.vmap = _ptr(vmap)
     a.taps, a.tap_mode, a.t_stride = taps, tap_mode, t_stride
@@ -879,10 +924,8 @@ def _wgrad_args(g, x, Cin, taps, tap_mode, t_stride, vmap, wv, dw, accumulate, e
         keep += [ge, xe]
         e = a.extra[i]
         e.N = ge.shape[0]
-        e.g = ge.data_ptr()
-        e.g_sN, e.g_sC = _sn_sc(ge)
-        e.x = xe.data_ptr()
-        e.x_sN, e.x_sC = _sn_sc(xe)
+        _bind(e, "g", "g", ge)
+        _bind(e, "x", "x", xe)
     a.nextra = len(extra)
     a.dw = dw.data_ptr()
     a.accumulate = int(accumulate)
@@ -905,16 +948,10 @@ def wgrad(g: torch.Tensor, x: torch.Tensor, Cin: int, taps: int, tap_mode: int, 
             raise ValueError("wgrad: accumulate needs out")
         dw = torch.empty(w_numel, dtype=torch.float32, device=g.device)
     else:
-        dw = out
-        if dw.numel() != w_numel or not dw.is_contiguous() or dw.dtype != torch.float32:
-            raise ValueError("wgrad: out must be a contiguous fp32 tensor of the weight's size")
-    keep = []
+        dw = _dest(out, w_numel, "wgrad: out must be a contiguous fp32 tensor of the weight's size")
+    keep = []                # the converted operands, held until the launch is enqueued
     a = _wgrad_args(g, x, Cin, taps, tap_mode, t_stride, vmap, wv, dw, accumulate, extra, keep)
-    nbytes = lib.kg_wgrad_workspace_bytes(C.byref(a))
-    if nbytes < 0:
-        _check(-1, "kg_wgrad_workspace_bytes")
-    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=g.device)
-    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    ws = _workspace("kg_wgrad_workspace_bytes", a, g.device)
     if last_wgrad_plan is not None:      # tests / tuning: record the tile variant and the number of partial slabs
         v, ns = C.c_int32(), C.c_int32()
         _check(lib.kg_wgrad_plan_info(C.byref(a), C.byref(v), C.byref(ns)), "kg_wgrad_plan_info")
@@ -923,7 +960,7 @@ def wgrad(g: torch.Tensor, x: torch.Tensor, Cin: int, taps: int, tap_mode: int, 
         a.defer_reduce = 1
         per = taps * a.M * Cin
         defer.append(dict(ws=ws, dw=dw, w_sT=wv.sT, w_sO=wv.sO, w_sI=wv.sI, taps=taps, M=a.M, Cin=Cin,
-                          splits=max(1, nbytes // (4 * per)), accumulate=int(accumulate)))
+                          splits=max(1, ws.numel() // per), accumulate=int(accumulate)))
     _check(lib.kg_wgrad(C.byref(a), _stream()), "kg_wgrad")
     return dw
 
@@ -935,29 +972,25 @@ def wgrad_many(jobs: Sequence[dict]):
     if not jobs:
         return
     arr = (_WgradArgs * len(jobs))()
-    keep = []
+    keep = []                # the converted operands of every job, held until the launch is enqueued
     for i, j in enumerate(jobs):
         dw = j["out"]
         if not dw.is_contiguous() or dw.dtype != torch.float32:
             raise ValueError("wgrad_many: out must be a contiguous fp32 tensor")
         arr[i] = _wgrad_args(j["g"], j["x"], j["Cin"], j["taps"], j["tap_mode"], j["t_stride"], j.get("vmap"),
                              j["wv"], dw, j.get("accumulate", False), j.get("extra", ()), keep)
-    nbytes = lib.kg_wgrad_many_workspace_bytes(arr, len(jobs))
-    if nbytes < 0:
-        _check(-1, "kg_wgrad_many_workspace_bytes")
+    ws = _workspace("kg_wgrad_many_workspace_bytes", arr, jobs[0]["g"].device, len(jobs))
     if last_wgrad_plan is not None:      # tests / tuning: (tile variant, splits) of every job
         v, ns = (C.c_int32 * len(jobs))(), (C.c_int32 * len(jobs))()
         _check(lib.kg_wgrad_many_plan(arr, len(jobs), v, ns), "kg_wgrad_many_plan")
         last_wgrad_plan[:] = list(zip(v, ns))
-    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=jobs[0]["g"].device)
     _check(lib.kg_wgrad_many(arr, len(jobs), ws.data_ptr(), ws.numel() * 4, _stream()), "kg_wgrad_many")
 
 
 def wgrad_reduce_many(jobs: list):
     """Finish the deferred kg_wgrad calls recorded in `jobs` (see wgrad(defer=...)): one launch per 24 jobs."""
     lib = load_library()
-    for i in range(0, len(jobs), WGRAD_REDUCE_MAX_JOBS):
-        chunk = jobs[i:i + WGRAD_REDUCE_MAX_JOBS]
+    for chunk in _chunks(jobs, WGRAD_REDUCE_MAX_JOBS):
         js = _WgradReduceJobs()
         js.njobs = len(chunk)
         for k, j in enumerate(chunk):
@@ -995,11 +1028,8 @@ def agg_expand(x: torch.Tensor, A: torch.Tensor, rep: int = 1) -> torch.Tensor:
     assert va == v, (A.shape, x.shape)
     a = _agg_args(n, c, k, v, w, t, rep, A)
     a.a_transposed = tr
-    a.x = x.data_ptr()
-    a.x_sN, a.x_sC = _sn_sc(x)
-    out = new_plane(n, k * c, t * rep, w, x.device)
-    a.out = out.data_ptr()
-    a.o_sN, a.o_sC = _sn_sc(out)
+    _bind(a, "x", "x", x)
+    out = _bind(a, "out", "o", new_plane(n, k * c, t * rep, w, x.device))
     _count("kg_agg", 2.0 * k * v * w * c * n * t * rep)
     _check(lib.kg_agg_expand(C.byref(a), _stream()), "kg_agg_expand")
     return out
@@ -1036,27 +1066,20 @@ def _aggconv_args(x, A, nbr, pcount, w, wv, M, add, add_tstride, want_xa):
     assert va == v and nbr.dtype == torch.int32 and tuple(nbr.shape) == (k, wd, AGGCONV_P), (A.shape, x.shape, nbr.shape)
     a = _AggConvArgs()
     a.N, a.Cin, a.M, a.T, a.V, a.W, a.K = n, c, M, t, v, wd, k
-    a.x = x.data_ptr()
-    a.x_sN, a.x_sC = _sn_sc(x)
+    _bind(a, "x", "x", x)
     a.a, a.a_transposed = A.data_ptr(), tr
     a.nbr = nbr.data_ptr()
     for i in range(3):
         a.pcount[i] = int(pcount[i]) if i < k else 0
     a.w = w.data_ptr()
     a.w_sT, a.w_sO, a.w_sI = wv.sT, wv.sO, wv.sI
-    out = new_plane(n, M, t, wd, x.device)
-    a.out = out.data_ptr()
-    a.o_sN, a.o_sC = _sn_sc(out)
+    out = _bind(a, "out", "o", new_plane(n, M, t, wd, x.device))
     if add is not None:
-        add = as_plane(add)
-        a.add = add.data_ptr()
-        a.a_sN, a.a_sC = _sn_sc(add)
+        add = _bind(a, "add", "a", add, True)
     a.a_tstride = add_tstride
     xa = None
     if want_xa:
-        xa = new_plane(n, k * c, t, wd, x.device)
-        a.xa = xa.data_ptr()
-        a.xa_sN, a.xa_sC = _sn_sc(xa)
+        xa = _bind(a, "xa", "xa", new_plane(n, k * c, t, wd, x.device))
     # (the operands are returned with the args: x / A / w / add may be converted copies that must outlive the launch)
     return a, out, xa, 2.0 * M * k * c * n * t * wd, (x, A, w, add)
 
@@ -1101,23 +1124,18 @@ def agg_reduce(y: torch.Tensor, A: torch.Tensor, fold: int = 1, res: Optional[to
     c = kc // k
     a = _agg_args(n, c, k, v, w, tin // fold, fold, A)
     a.a_transposed = tr
-    a.x = y.data_ptr()
-    a.x_sN, a.x_sC = _sn_sc(y)
-    out = new_plane(n, c, tin // fold, w, y.device)
-    a.out = out.data_ptr()
-    a.o_sN, a.o_sC = _sn_sc(out)
+    _bind(a, "x", "x", y)
+    out = _bind(a, "out", "o", new_plane(n, c, tin // fold, w, y.device))
     if res is not None:
         res = as_plane(res)
         assert fold == 1 and res.shape[0] == n and res.shape[1] == c, (res.shape, out.shape)
-        a.res = res.data_ptr()
-        a.r_sN, a.r_sC = _sn_sc(res)
+        _bind(a, "res", "r", res)
         a.r_T, a.r_V, a.r_tstride = res.shape[2], res.shape[3], res_tstride
         a.r_inv = _ptr(res_inv)
     if mask is not None:
         mask = as_plane(mask)
         assert fold == 1 and tuple(mask.shape) == tuple(out.shape), (mask.shape, out.shape)
-        a.mask = mask.data_ptr()
-        a.m_sN, a.m_sC = _sn_sc(mask)
+        _bind(a, "mask", "m", mask)
     a.slope = slope
     _count("kg_agg", 2.0 * k * v * w * c * n * tin)
     _check(lib.kg_agg_reduce(C.byref(a), _stream()), "kg_agg_reduce")
@@ -1142,16 +1160,10 @@ def agg_outer(x: torch.Tensor, y: torch.Tensor, K: int, rep: int = 1, out: Optio
         raise ValueError("agg_outer: out must be a contiguous fp32 (K, V, W) tensor")
     a = _agg_args(n, c, K, v, w, t, rep, out)
     a.a = None
-    a.x = x.data_ptr()
-    a.x_sN, a.x_sC = _sn_sc(x)
-    a.y = y.data_ptr()
-    a.y_sN, a.y_sC = _sn_sc(y)
+    _bind(a, "x", "x", x)
+    _bind(a, "y", "y", y)
     a.out = out.data_ptr()
-    nbytes = lib.kg_agg_outer_workspace_bytes(C.byref(a))
-    if nbytes < 0:
-        _check(-1, "kg_agg_outer_workspace_bytes")
-    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=x.device)
-    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    ws = _workspace("kg_agg_outer_workspace_bytes", a, x.device)
     _count("kg_agg", 2.0 * K * v * w * c * n * t * rep)
     if defer is not None:
         # nothing is launched now: the record keeps the operands and the scratch alive until agg_outer_finish
@@ -1191,8 +1203,7 @@ def gen_adj_prepare(jobs: Sequence[dict]):
     job: dict(a (K, V, V), imp (K, V, V) | None, u (Vc, V) | None, aeff (K, V, V) out, b (K, Vc, V) out), all
     contiguous fp32."""
     lib = load_library()
-    for i in range(0, len(jobs), GEN_ADJ_MAX_JOBS):
-        chunk = jobs[i:i + GEN_ADJ_MAX_JOBS]
+    for chunk in _chunks(jobs, GEN_ADJ_MAX_JOBS):
         arr = (_GenPrepJob * len(chunk))()
         for q, j in enumerate(chunk):
             ts = (j["a"], j.get("imp"), j.get("u"), j["aeff"], j["b"])
@@ -1228,22 +1239,16 @@ def gen_expand(y: Optional[torch.Tensor], A: Optional[torch.Tensor], U: Optional
         k = A.shape[0] if A is not None else B.shape[0]
         assert y.shape[1] == k * C_out and (A is None or tuple(A.shape) == (k, v, v)), (y.shape, C_out)
         a.C, a.K = C_out, k
-        a.y = y.data_ptr()
-        a.y_sN, a.y_sC = _sn_sc(y)
-        z = new_plane(n, C_out, tc * rep, v, y.device)
-        a.z = z.data_ptr()
-        a.z_sN, a.z_sC = _sn_sc(z)
+        _bind(a, "y", "y", y)
+        z = _bind(a, "z", "z", new_plane(n, C_out, tc * rep, v, y.device))
         _count("kg_agg", 2.0 * k * vc * v * C_out * n * tc)
     if rs is not None:
         rs = as_plane(rs)
         assert tuple(rs.shape[2:]) == (tc, vc) and rs.shape[0] == n
         a.Cr = rs.shape[1]
-        a.rs = rs.data_ptr()
-        a.rs_sN, a.rs_sC = _sn_sc(rs)
+        _bind(a, "rs", "rs", rs)
         a.rbias = _ptr(rbias)
-        r = new_plane(n, rs.shape[1], tc * rep, v, rs.device)
-        a.r = r.data_ptr()
-        a.r_sN, a.r_sC = _sn_sc(r)
+        r = _bind(a, "r", "r", new_plane(n, rs.shape[1], tc * rep, v, rs.device))
         _count("kg_agg", 2.0 * vc * v * rs.shape[1] * n * tc)
     _check(lib.kg_gen_expand(C.byref(a), _stream()), "kg_gen_expand")
     return z, r
@@ -1272,29 +1277,20 @@ def gen_fold(gz: Optional[torch.Tensor], A: Optional[torch.Tensor], U: Optional[
         gz = as_plane(gz)
         c = gz.shape[1]
         a.C, a.K = c, K
-        a.z = gz.data_ptr()
-        a.z_sN, a.z_sC = _sn_sc(gz)
+        _bind(a, "z", "z", gz)
         gy = y_out if y_out is not None else new_plane(n, K * c, tc, vc, gz.device)
         assert tuple(gy.shape) == (n, K * c, tc, vc) and is_plane(gy)
-        a.y_out = gy.data_ptr()
-        a.y_sN, a.y_sC = _sn_sc(gy)
+        _bind(a, "y_out", "y", gy)
         if want_zf:
-            if rep == 1:
-                zf = gz
-            else:
-                zf = new_plane(n, c, tc, v, gz.device)
-                a.zf = zf.data_ptr()
-                a.zf_sN, a.zf_sC = _sn_sc(zf)
+            zf = gz if rep == 1 else _bind(a, "zf", "zf", new_plane(n, c, tc, v, gz.device))
         _count("kg_agg", 2.0 * K * vc * v * c * n * tf)
     if gr is not None:
         gr = as_plane(gr)
         a.Cr = gr.shape[1]
-        a.r = gr.data_ptr()
-        a.r_sN, a.r_sC = _sn_sc(gr)
+        _bind(a, "r", "r", gr)
         grs = rs_out if rs_out is not None else new_plane(n, gr.shape[1], tc, vc, gr.device)
         assert tuple(grs.shape) == (n, gr.shape[1], tc, vc) and is_plane(grs)
-        a.rs_out = grs.data_ptr()
-        a.rs_sN, a.rs_sC = _sn_sc(grs)
+        _bind(a, "rs_out", "rs", grs)
         _count("kg_agg", 2.0 * vc * v * gr.shape[1] * n * tf)
     _check(lib.kg_gen_fold(C.byref(a), _stream()), "kg_gen_fold")
     return gy, grs, zf
@@ -1316,22 +1312,17 @@ def gen_tail_bwd(g, out, act: int, u=None, bn_t=None, r=None, bn_r=None, noise=N
     sinks = sinks or {}
     a = _GenTailArgs()
     a.N, a.C, a.T, a.V, a.act, a.slope = n, c, t, v, act, slope
-    a.g = g.data_ptr()
-    a.g_sN, a.g_sC = _sn_sc(g)
-    a.out = out.data_ptr()
-    a.o_sN, a.o_sC = _sn_sc(out)
+    _bind(a, "g", "g", g)
+    _bind(a, "out", "o", out)
     keep = [g, out]
     if bn_t is not None:
         u = as_plane(u)
         gam, mean, rstd = (_vec(q, c, "gen_tail_bwd") for q in bn_t)
-        a.u = u.data_ptr()
-        a.u_sN, a.u_sC = _sn_sc(u)
+        _bind(a, "u", "u", u)
         a.gamma_t, a.mean_t, a.rstd_t = _ptr(gam), mean.data_ptr(), rstd.data_ptr()
         keep += [u, gam, mean, rstd]
     if r is not None:
-        r = as_plane(r)
-        a.r = r.data_ptr()
-        a.r_sN, a.r_sC = _sn_sc(r)
+        r = _bind(a, "r", "r", r, True)
         keep.append(r)
         if bn_r is not None:
             gam, mean, rstd = (_vec(q, c, "gen_tail_bwd") for q in bn_r)
@@ -1358,26 +1349,14 @@ def gen_tail_bwd(g, out, act: int, u=None, bn_t=None, r=None, bn_r=None, noise=N
     if not have_coef:
         if c > SYNC_LEN:
             raise ValueError("gen_tail_bwd: %d channels exceed the %d ticket counters" % (c, SYNC_LEN))
-        nbytes = lib.kg_gen_tail_workspace_bytes(C.byref(a))
-        if nbytes < 0:
-            _check(-1, "kg_gen_tail_workspace_bytes")
-        ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=g.device)
-        sync = _sync_buffer(g.device)
-        a.ws, a.ws_bytes, a.counters, a.counters_len = ws.data_ptr(), ws.numel() * 4, sync.data_ptr(), sync.numel()
+        ws = _workspace("kg_gen_tail_workspace_bytes", a, g.device, tickets="counters")
         _check(lib.kg_gen_tail_stats(C.byref(a), _stream()), "kg_gen_tail_stats")
     if stats_only:
         return coef
-    du = new_plane(n, c, t, v, g.device)
-    a.du = du.data_ptr()
-    a.du_sN, a.du_sC = _sn_sc(du)
+    du = _bind(a, "du", "du", new_plane(n, c, t, v, g.device))
     dr = None
     if r is not None:
-        if bn_t is None and bn_r is None:
-            dr = du
-        else:
-            dr = new_plane(n, c, t, v, g.device)
-            a.dr = dr.data_ptr()
-            a.dr_sN, a.dr_sC = _sn_sc(dr)
+        dr = du if bn_t is None and bn_r is None else _bind(a, "dr", "dr", new_plane(n, c, t, v, g.device))
     _check(lib.kg_gen_tail_apply(C.byref(a), _stream()), "kg_gen_tail_apply")
     return du, dr
 
@@ -1386,8 +1365,7 @@ def gen_adj_finish(jobs: Sequence[dict]):
     """d edge_importance of several generator blocks in one launch (kg_gen_adj_finish).  Each job: dict(dbt (Kd, V, Vc)
     contiguous, u (Vc, V) | None, a (K, V, V) | None, out (K, V, V) contiguous view, accumulate)."""
     lib = load_library()
-    for i in range(0, len(jobs), GEN_ADJ_MAX_JOBS):
-        chunk = jobs[i:i + GEN_ADJ_MAX_JOBS]
+    for chunk in _chunks(jobs, GEN_ADJ_MAX_JOBS):
         arr = (_GenAdjJob * len(chunk))()
         for q, j in enumerate(chunk):
             dbt, out = j["dbt"], j["out"]
@@ -1538,12 +1516,7 @@ def genblock_fwd(d: GenBlockDims, *, x=None, pend=None, wg, wr=None, br=None, wt
             noise, nw = noise.contiguous(), nw.reshape(-1).contiguous()
             a.noise, a.nw = noise.data_ptr(), nw.data_ptr()
     else:
-        nbytes = lib.kg_genblock_workspace_bytes(C.byref(a))
-        if nbytes < 0:
-            _check(-1, "kg_genblock_workspace_bytes")
-        ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-        sync = _sync_buffer(dev)
-        a.ws, a.ws_bytes, a.counters, a.counters_len = ws.data_ptr(), ws.numel() * 4, sync.data_ptr(), sync.numel()
+        ws = _workspace("kg_genblock_workspace_bytes", a, dev, tickets="counters")
     _count("kg_genblock", 2.0 * n * (Mh * d.Cin * d.Tc * d.Vc + 3 * d.C * d.C * d.T * d.V) +
            2.0 * n * (d.Kp + (1 if d.res_kind else 0)) * d.Vc * d.V * d.C * d.Tc)
     _check(lib.kg_genblock_fwd(C.byref(a), _stream()), "kg_genblock_fwd")
@@ -1619,18 +1592,29 @@ def genblock_bwd(d: GenBlockDims, *, g, out, u=None, r=None, coef, wg, wr=None, 
         a.dgamma_r, a.dbeta_r, a.dnw = _ptr(sinks.get("gamma_r")), _ptr(sinks.get("beta_r")), _ptr(sinks.get("nw"))
         pcoef = torch.empty((6, d.Cin), dtype=torch.float32, device=dev)
         a.pcoef = pcoef.data_ptr()
-        nbytes = lib.kg_genblock_bwd_workspace_bytes(C.byref(a))
-        if nbytes < 0:
-            _check(-1, "kg_genblock_bwd_workspace_bytes")
-        ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-        sync = _sync_buffer(dev)
-        a.ws, a.ws_bytes, a.counters, a.counters_len = ws.data_ptr(), ws.numel() * 4, sync.data_ptr(), sync.numel()
+        ws = _workspace("kg_genblock_bwd_workspace_bytes", a, dev, tickets="counters")
     _count("kg_genblock", 2.0 * n * (Mh * d.Cin * d.Tc * d.Vc + 3 * d.C * d.C * d.T * d.V) +
            2.0 * n * (d.Kp + (1 if d.res_kind else 0)) * d.Vc * d.V * d.C * d.T)
     _check(lib.kg_genblock_bwd(C.byref(a), _stream()), "kg_genblock_bwd")
     if dr is None and d.res_kind != 0:
         dr = du
     return dict(du=du, dr=dr, gyc=gyc, zf=zf, gx=gx, pcoef=pcoef)
+
+
+def _rowsum_fill(a, x, y, want_second: int, out, out2, accumulate: int):
+    """Fill one KgRowsumArgs (without shift and workspace) from the plane tensor x; returns the tensors it bound."""
+    n, c, t, v = x.shape
+    a.N, a.C, a.T, a.V = n, c, t, v
+    _bind(a, "x", "x", x)
+    if y is not None:
+        if y.shape[1] == 1 and c > 1:          # one plane for all channels: channel stride 0
+            y = y.contiguous()
+            a.y, a.y_sN, a.y_sC = y.data_ptr(), t * v, 0
+        else:
+            y = _bind(a, "y", "y", y, True)
+    a.want_second = want_second      # 1: both rows; 2: the product row alone
+    a.out, a.out2, a.accumulate = out.data_ptr(), _ptr(out2), accumulate
+    return x, y
 
 
 def rowsum(x: torch.Tensor, y: Optional[torch.Tensor] = None, second: bool = False,
@@ -1642,43 +1626,22 @@ def rowsum(x: torch.Tensor, y: Optional[torch.Tensor] = None, second: bool = Fal
     lib = load_library()
     x = as_plane(x)
     _need_cuda(x, y, shift)
-    n, c, t, v = x.shape
+    c = x.shape[1]
     a = _RowsumArgs()
     if shift is not None:
         shift = shift.reshape(-1).contiguous()
         a.shift = shift.data_ptr()
-    a.N, a.C, a.T, a.V = n, c, t, v
-    a.x = x.data_ptr()
-    a.x_sN, a.x_sC = _sn_sc(x)
-    keep = None
-    if y is not None:
-        if y.shape[1] == 1 and c > 1:
-            keep = y.contiguous()
-            a.y, a.y_sN, a.y_sC = keep.data_ptr(), t * v, 0
-        else:
-            keep = as_plane(y)
-            a.y = keep.data_ptr()
-            a.y_sN, a.y_sC = _sn_sc(keep)
-    a.want_second = int(second)      # True: both rows; 2: the product row alone
     rows = 2 if int(second) == 1 else 1
     if out is None:
         if accumulate:
             raise ValueError("rowsum: accumulate needs out")
         out = torch.empty((rows, c), dtype=torch.float32, device=x.device)
     else:
-        if out.numel() != rows * c or not out.is_contiguous() or out.dtype != torch.float32:
-            raise ValueError("rowsum: out must be a contiguous fp32 tensor of %d elements" % (rows * c))
-        _need_cuda(out)
-    a.out = out.data_ptr()
-    a.accumulate = int(accumulate)
+        _need_cuda(_dest(out, rows * c, "rowsum: out must be a contiguous fp32 tensor of %d elements" % (rows * c)))
     if out2 is not None:
-        if out2.numel() != rows * c or not out2.is_contiguous() or out2.dtype != torch.float32:
-            raise ValueError("rowsum: out2 must be a contiguous fp32 tensor of %d elements" % (rows * c))
-        _need_cuda(out2)
-        a.out2 = out2.data_ptr()
-    nbytes = lib.kg_rowsum_workspace_bytes(C.byref(a))
-    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=x.device)
-    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        _need_cuda(_dest(out2, rows * c, "rowsum: out2 must be a contiguous fp32 tensor of %d elements" % (rows * c)))
+    held = _rowsum_fill(a, x, y, int(second), out, out2, int(accumulate))
+    ws = _workspace("kg_rowsum_workspace_bytes", a, x.device)
     _check(lib.kg_rowsum(C.byref(a), _stream()), "kg_rowsum")
     return out
 
@@ -1691,48 +1654,25 @@ def rowsum_many(jobs: Sequence[dict]):
     if not jobs:
         return
     arr = (_RowsumArgs * len(jobs))()
-    keep = []
+    held = []                # the tensors every job bound (converted copies among them), until the launch is enqueued
     for i, j in enumerate(jobs):
         x = as_plane(j["x"])
-        out, out2 = j["out"], j.get("out2")
+        out, out2, y = j["out"], j.get("out2"), j.get("y")
         _need_cuda(x, out, out2)
-        n, c, t, v = x.shape
         for o in (out, out2):
-            if o is not None and (o.numel() != c or not o.is_contiguous() or o.dtype != torch.float32):
-                raise ValueError("rowsum_many: destinations must be contiguous fp32 vectors of C elements")
-        keep.append(x)
-        a = arr[i]
-        a.N, a.C, a.T, a.V = n, c, t, v
-        a.x = x.data_ptr()
-        a.x_sN, a.x_sC = _sn_sc(x)
-        y = j.get("y")
-        if y is not None:
-            _need_cuda(y)
-            if y.shape[1] == 1 and c > 1:
-                y = y.contiguous()
-                a.y, a.y_sN, a.y_sC = y.data_ptr(), t * v, 0
-            else:
-                y = as_plane(y)
-                a.y = y.data_ptr()
-                a.y_sN, a.y_sC = _sn_sc(y)
-            keep.append(y)
-            a.want_second = 2
-        a.out, a.out2 = out.data_ptr(), _ptr(out2)
-        a.accumulate = int(bool(j.get("accumulate", False)))
-    nbytes = lib.kg_rowsum_many_workspace_bytes(arr, len(jobs))
-    if nbytes < 0:
-        _check(-1, "kg_rowsum_many_workspace_bytes")
-    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=jobs[0]["x"].device)
+            if o is not None:
+                _dest(o, x.shape[1], "rowsum_many: destinations must be contiguous fp32 vectors of C elements")
+        _need_cuda(y)
+        held.append(_rowsum_fill(arr[i], x, y, 0 if y is None else 2, out, out2, int(bool(j.get("accumulate", False)))))
+    ws = _workspace("kg_rowsum_many_workspace_bytes", arr, jobs[0]["x"].device, len(jobs))
     _check(lib.kg_rowsum_many(arr, len(jobs), ws.data_ptr(), ws.numel() * 4, _stream()), "kg_rowsum_many")
 
 
 def _elt_args(x, out, act, slope):
     a = _EltArgs()
     a.N, a.C, a.T, a.V = x.shape
-    a.x = x.data_ptr()
-    a.x_sN, a.x_sC = _sn_sc(x)
-    a.out = out.data_ptr()
-    a.o_sN, a.o_sC = _sn_sc(out)
+    _bind(a, "x", "x", x)
+    _bind(a, "out", "o", out)
     a.act, a.slope = act, slope
     return a
 
@@ -1744,8 +1684,7 @@ def act_bwd(g: torch.Tensor, ref: torch.Tensor, act: int, slope: float = 0.2) ->
     _need_cuda(g, ref)
     out = new_plane(*g.shape, g.device)
     a = _elt_args(g, out, act, slope)
-    a.r = ref.data_ptr()
-    a.r_sN, a.r_sC = _sn_sc(ref)
+    _bind(a, "r", "r", ref)
     _check(lib.kg_act_bwd(C.byref(a), _stream()), "kg_act_bwd")
     return out
 
@@ -1766,9 +1705,7 @@ def affine_act(x, sx=None, bx=None, r=None, sr=None, br=None, noise=None, nw=Non
         raise ValueError("affine_act: out must be a plane tensor of x's shape")
     a = _elt_args(x, out, act, slope)
     if r is not None:
-        r = as_plane(r)
-        a.r = r.data_ptr()
-        a.r_sN, a.r_sC = _sn_sc(r)
+        r = _bind(a, "r", "r", r, True)
     if noise is not None:
         noise = noise.contiguous()
         a.noise = noise.data_ptr()
@@ -1778,15 +1715,20 @@ def affine_act(x, sx=None, bx=None, r=None, sr=None, br=None, noise=None, nw=Non
     return out
 
 
+def _gp_args(g):
+    """KgGpArgs of the per-sample gradients g (a plane tensor)"""
+    a = _GpArgs()
+    a.N, a.C, a.T, a.V = g.shape
+    _bind(a, "g", "g", g)
+    return a
+
+
 def gp_fwd(g: torch.Tensor):
     """(nrm (N,), gp ()) of the WGAN-GP penalty for per-sample gradients g (N, C, T, V): kg_gp_fwd"""
     lib = load_library()
     g = as_plane(g)
     _need_cuda(g)
-    a = _GpArgs()
-    a.N, a.C, a.T, a.V = g.shape
-    a.g = g.data_ptr()
-    a.g_sN, a.g_sC = _sn_sc(g)
+    a = _gp_args(g)
     nrm = torch.empty(g.shape[0], dtype=torch.float32, device=g.device)
     gp = torch.empty((), dtype=torch.float32, device=g.device)
     a.nrm, a.gp = nrm.data_ptr(), gp.data_ptr()
@@ -1800,24 +1742,33 @@ def gp_bwd(g: torch.Tensor, nrm: torch.Tensor, gout: torch.Tensor) -> torch.Tens
     g = as_plane(g)
     gout = gout.reshape(1).contiguous()
     _need_cuda(g, nrm, gout)
-    a = _GpArgs()
-    a.N, a.C, a.T, a.V = g.shape
-    a.g = g.data_ptr()
-    a.g_sN, a.g_sC = _sn_sc(g)
+    a = _gp_args(g)
     a.nrm, a.gout = nrm.data_ptr(), gout.data_ptr()
-    out = new_plane(*g.shape, g.device)
-    a.out = out.data_ptr()
-    a.o_sN, a.o_sC = _sn_sc(out)
+    out = _bind(a, "out", "o", new_plane(*g.shape, g.device))
     _check(lib.kg_gp_bwd(C.byref(a), _stream()), "kg_gp_bwd")
     return out
 
 
 def _vec(t: Optional[torch.Tensor], c: int, what: str):
-    if t is None:
-        return None
-    if t.numel() != c or not t.is_contiguous() or t.dtype != torch.float32:
-        raise ValueError(f"{what}: expected a contiguous fp32 vector of {c} elements")
-    return t
+    return None if t is None else _dest(t, c, f"{what}: expected a contiguous fp32 vector of {c} elements")
+
+
+def _bn_fwd_fill(a, who: str, x, gamma, beta, running_mean, running_var, nbt, momentum, eps, training, groups: Optional[int] = None):
+    """Fill one KgBnArgs for the forward statistics of the plane tensor x (``groups`` batches stacked along N; None: the
+    single form, whose coefficients are (4, C)); returns the coefficient tensor it allocated."""
+    n, c, t, v = x.shape
+    vecs = [_vec(q, c, who) for q in (gamma, beta, running_mean, running_var)]
+    _need_cuda(x, *vecs, nbt)
+    a.N, a.C, a.T, a.V = n // (groups or 1), c, t, v
+    _bind(a, "x", "x", x)
+    a.gamma, a.beta, a.running_mean, a.running_var = [_ptr(q) for q in vecs]
+    if nbt is not None:
+        assert nbt.dtype == torch.int64
+        a.num_batches_tracked = nbt.data_ptr()
+    a.momentum, a.eps, a.training = float(momentum), float(eps), int(bool(training))
+    coef = torch.empty((4, c) if groups is None else (groups, 4, c), dtype=torch.float32, device=x.device)
+    a.coef = coef.data_ptr()
+    return coef
 
 
 def bn_fwd(x: torch.Tensor, gamma, beta, running_mean, running_var, num_batches_tracked, training: bool,
@@ -1826,22 +1777,22 @@ def bn_fwd(x: torch.Tensor, gamma, beta, running_mean, running_var, num_batches_
     [scale, shift, mean, rstd]; training mode updates the running statistics in place (torch semantics)."""
     lib = load_library()
     x = as_plane(x)
-    n, c, t, v = x.shape
-    vecs = [_vec(q, c, "bn_fwd") for q in (gamma, beta, running_mean, running_var)]
-    _need_cuda(x, *vecs, num_batches_tracked)
     a = _BnArgs()
-    a.N, a.C, a.T, a.V = n, c, t, v
-    a.x = x.data_ptr()
-    a.x_sN, a.x_sC = _sn_sc(x)
-    a.gamma, a.beta, a.running_mean, a.running_var = [_ptr(q) for q in vecs]
-    if num_batches_tracked is not None:
-        assert num_batches_tracked.dtype == torch.int64
-        a.num_batches_tracked = num_batches_tracked.data_ptr()
-    a.momentum, a.eps, a.training = float(momentum), float(eps), int(bool(training))
-    coef = torch.empty((4, c), dtype=torch.float32, device=x.device)
-    a.coef = coef.data_ptr()
+    coef = _bn_fwd_fill(a, "bn_fwd", x, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, training)
     _check(lib.kg_bn_fwd(C.byref(a), _stream()), "kg_bn_fwd")
     return coef
+
+
+def _bn_many(who: str, arr, coefs):
+    """the shared end of bn_fwd_many / bn_bwd_many: ticket-counter limit, scratch and the launch of lib.kg_<who>"""
+    total_c = sum(cf.shape[-1] for cf in coefs)
+    if total_c > SYNC_LEN:
+        raise ValueError("%s: %d channels exceed the %d ticket counters" % (who, total_c, SYNC_LEN))
+    ws = _workspace("kg_%s_workspace_bytes" % who, arr, coefs[0].device if coefs else None, len(arr))   # (no jobs: its message)
+    sync = _sync_buffer(coefs[0].device)
+    _check(getattr(load_library(), "kg_" + who)(arr, len(arr), ws.data_ptr(), ws.numel() * 4, sync.data_ptr(), sync.numel(),
+                                               _stream()), "kg_" + who)
+    return coefs
 
 
 def bn_fwd_many(jobs: Sequence[dict]):
@@ -1849,64 +1800,41 @@ def bn_fwd_many(jobs: Sequence[dict]):
     running_mean, running_var, num_batches_tracked, momentum, eps, groups): x holds ``groups`` independent batches
     stacked along N; returns one (groups, 4, C) tensor [scale, shift, mean, rstd] per job, the running statistics
     updated batch by batch as ``groups`` bn_fwd calls would."""
-    lib = load_library()
     arr = (_BnJob * len(jobs))()
-    keep, coefs = [], []
-    total_c = 0
+    xs, coefs = [], []          # xs: the (converted) inputs, held until the launch is enqueued
     for i, j in enumerate(jobs):
         x = as_plane(j["x"])
-        n, c, t, v = x.shape
         groups = int(j.get("groups", 1))
-        if n % groups:
-            raise ValueError("bn_fwd_many: N=%d is not a multiple of groups=%d" % (n, groups))
-        vecs = [_vec(j.get(k), c, "bn_fwd_many") for k in ("gamma", "beta", "running_mean", "running_var")]
-        nbt = j.get("num_batches_tracked")
-        _need_cuda(x, *vecs, nbt)
-        a = arr[i].a
-        a.N, a.C, a.T, a.V = n // groups, c, t, v
-        a.x = x.data_ptr()
-        a.x_sN, a.x_sC = _sn_sc(x)
-        a.gamma, a.beta, a.running_mean, a.running_var = [_ptr(q) for q in vecs]
-        if nbt is not None:
-            assert nbt.dtype == torch.int64
-            a.num_batches_tracked = nbt.data_ptr()
-        a.momentum, a.eps, a.training = float(j["momentum"]), float(j["eps"]), 1
-        coef = torch.empty((groups, 4, c), dtype=torch.float32, device=x.device)
-        a.coef = coef.data_ptr()
+        if x.shape[0] % groups:
+            raise ValueError("bn_fwd_many: N=%d is not a multiple of groups=%d" % (x.shape[0], groups))
+        coefs.append(_bn_fwd_fill(arr[i].a, "bn_fwd_many", x, j.get("gamma"), j.get("beta"), j.get("running_mean"),
+                                  j.get("running_var"), j.get("num_batches_tracked"), j["momentum"], j["eps"], True, groups))
         arr[i].groups = groups
-        keep += [x] + vecs
-        coefs.append(coef)
-        total_c += c
-    if total_c > SYNC_LEN:
-        raise ValueError("bn_fwd_many: %d channels exceed the %d ticket counters" % (total_c, SYNC_LEN))
-    nbytes = lib.kg_bn_fwd_many_workspace_bytes(arr, len(jobs))
-    if nbytes < 0:
-        _check(-1, "kg_bn_fwd_many_workspace_bytes")
-    dev = coefs[0].device
-    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-    sync = _sync_buffer(dev)
-    _check(lib.kg_bn_fwd_many(arr, len(jobs), ws.data_ptr(), ws.numel() * 4, sync.data_ptr(), sync.numel(), _stream()),
-           "kg_bn_fwd_many")
-    return coefs
+        xs.append(x)
+    return _bn_many("bn_fwd_many", arr, coefs)
+
+
+def _bn_bwd_fill(a, who: str, g, x, gamma, mean, rstd, training):
+    """Fill one KgBnArgs for the backward coefficients; returns ((5, C) coefficient tensor, the tensors it bound)."""
+    g, x = as_plane(g), as_plane(x)
+    n, c, t, v = x.shape
+    gamma, mean, rstd = _vec(gamma, c, who), _vec(mean, c, who), _vec(rstd, c, who)
+    _need_cuda(g, x, gamma, mean, rstd)
+    a.N, a.C, a.T, a.V = n, c, t, v
+    _bind(a, "x", "x", x)
+    _bind(a, "g", "g", g)
+    a.gamma, a.mean, a.rstd = _ptr(gamma), _ptr(mean), _ptr(rstd)
+    a.training = int(bool(training))
+    coef = torch.empty((5, c), dtype=torch.float32, device=x.device)
+    a.coef = coef.data_ptr()
+    return coef, (g, x)
 
 
 def bn_bwd(g: torch.Tensor, x: torch.Tensor, gamma, mean: torch.Tensor, rstd: torch.Tensor, training: bool) -> torch.Tensor:
     """(5, C) = [a, b, c, dgamma, dbeta] of the BatchNorm2d backward (dL/dx = a*g + b*x + c), one launch."""
     lib = load_library()
-    g, x = as_plane(g), as_plane(x)
-    n, c, t, v = x.shape
-    gamma, mean, rstd = _vec(gamma, c, "bn_bwd"), _vec(mean, c, "bn_bwd"), _vec(rstd, c, "bn_bwd")
-    _need_cuda(g, x, gamma, mean, rstd)
     a = _BnArgs()
-    a.N, a.C, a.T, a.V = n, c, t, v
-    a.x = x.data_ptr()
-    a.x_sN, a.x_sC = _sn_sc(x)
-    a.g = g.data_ptr()
-    a.g_sN, a.g_sC = _sn_sc(g)
-    a.gamma, a.mean, a.rstd = _ptr(gamma), _ptr(mean), _ptr(rstd)
-    a.training = int(bool(training))
-    coef = torch.empty((5, c), dtype=torch.float32, device=x.device)
-    a.coef = coef.data_ptr()
+    coef, held = _bn_bwd_fill(a, "bn_bwd", g, x, gamma, mean, rstd, training)
     _check(lib.kg_bn_bwd(C.byref(a), _stream()), "kg_bn_bwd")
     return coef
 
@@ -1914,39 +1842,11 @@ def bn_bwd(g: torch.Tensor, x: torch.Tensor, gamma, mean: torch.Tensor, rstd: to
 def bn_bwd_many(jobs: Sequence[dict]):
     """bn_bwd of up to four layers in ONE launch (chunked partial sums, many workgroups per channel): each job
     dict(g, x, gamma, mean, rstd, training) -> its (5, C) coefficients [a, b, c, dgamma, dbeta]."""
-    lib = load_library()
     arr = (_BnArgs * len(jobs))()
-    keep, coefs = [], []
-    total_c = 0
-    for i, j in enumerate(jobs):
-        g, x = as_plane(j["g"]), as_plane(j["x"])
-        n, c, t, v = x.shape
-        gamma, mean, rstd = _vec(j.get("gamma"), c, "bn_bwd_many"), _vec(j["mean"], c, "bn_bwd_many"), _vec(j["rstd"], c, "bn_bwd_many")
-        _need_cuda(g, x, gamma, mean, rstd)
-        a = arr[i]
-        a.N, a.C, a.T, a.V = n, c, t, v
-        a.x = x.data_ptr()
-        a.x_sN, a.x_sC = _sn_sc(x)
-        a.g = g.data_ptr()
-        a.g_sN, a.g_sC = _sn_sc(g)
-        a.gamma, a.mean, a.rstd = _ptr(gamma), _ptr(mean), _ptr(rstd)
-        a.training = int(bool(j["training"]))
-        coef = torch.empty((5, c), dtype=torch.float32, device=x.device)
-        a.coef = coef.data_ptr()
-        keep += [g, x, gamma, mean, rstd]
-        coefs.append(coef)
-        total_c += c
-    if total_c > SYNC_LEN:
-        raise ValueError("bn_bwd_many: %d channels exceed the %d ticket counters" % (total_c, SYNC_LEN))
-    nbytes = lib.kg_bn_bwd_many_workspace_bytes(arr, len(jobs))
-    if nbytes < 0:
-        _check(-1, "kg_bn_bwd_many_workspace_bytes")
-    dev = coefs[0].device
-    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
-    sync = _sync_buffer(dev)
-    _check(lib.kg_bn_bwd_many(arr, len(jobs), ws.data_ptr(), ws.numel() * 4, sync.data_ptr(), sync.numel(), _stream()),
-           "kg_bn_bwd_many")
-    return coefs
+    # (every job's coefficients and the tensors it bound, the latter held until the launch is enqueued)
+    filled = [_bn_bwd_fill(arr[i], "bn_bwd_many", j["g"], j["x"], j.get("gamma"), j["mean"], j["rstd"], j["training"])
+              for i, j in enumerate(jobs)]
+    return _bn_many("bn_bwd_many", arr, [coef for coef, _ in filled])
 
 
 def adam_step(p, g, m, v, lr, b1, b2, eps, step_t: torch.Tensor, grad_scale: float = 1.0, zero_grad: bool = False):
@@ -1980,23 +1880,27 @@ def adam_step_ema(p, g, m, v, e, lr, b1, b2, eps, step_t: torch.Tensor, grad_sca
 
 # ---- container-level fusions around the discriminator's blocks (kg_disc.hip) ---------------------------------------------
 
-def _head_args(h, w):
-    h = as_plane(h)
+def _head_args(h, w=None, gv=None):
+    """KgHeadArgs with the operands the three head entry points share: h (N, C, T, V), the Linear weight w (C values) and the
+    per-sample gradient gv (N values, flat); returns (args, h as bound)."""
     a = _HeadArgs()
+    h = _bind(a, "h", "h", h, True)
     a.N, a.C, a.T, a.V = h.shape
-    a.h = h.data_ptr()
-    a.h_sN, a.h_sC = _sn_sc(h)
-    w = w.reshape(-1)
-    assert w.is_contiguous() and w.numel() == h.shape[1]
-    a.w = w.data_ptr()
-    return a, h, w
+    if w is not None:
+        w = w.reshape(-1)
+        assert w.is_contiguous() and w.numel() == h.shape[1]
+        a.w = w.data_ptr()
+    if gv is not None:
+        assert gv.numel() == h.shape[0]
+        a.gv = gv.data_ptr()
+    return a, h
 
 
 def head_fwd(h: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
     """v (N,) = b + mean_{t,v}(h) @ w: global average pool + Linear(latent, 1) (kg_head_fwd)"""
     lib = load_library()
     _need_cuda(h, w, b)
-    a, h, w = _head_args(h, w)
+    a, h = _head_args(h, w)
     a.b = _ptr(b)
     v = torch.empty(h.shape[0], dtype=torch.float32, device=h.device)
     a.v = v.data_ptr()
@@ -2009,13 +1913,9 @@ def head_bwd(gv: torch.Tensor, w: torch.Tensor, h: torch.Tensor, masked: bool = 
     lib = load_library()
     gv = gv.reshape(-1).contiguous()
     _need_cuda(gv, w, h)
-    a, h, w = _head_args(h, w)
-    assert gv.numel() == h.shape[0]
-    a.gv = gv.data_ptr()
+    a, h = _head_args(h, w, gv)
     a.masked, a.slope = int(bool(masked)), slope
-    g = new_plane(*h.shape, h.device)
-    a.g = g.data_ptr()
-    a.g_sN, a.g_sC = _sn_sc(g)
+    g = _bind(a, "g", "g", new_plane(*h.shape, h.device))
     _check(lib.kg_head_bwd(C.byref(a), _stream()), "kg_head_bwd")
     return g
 
@@ -2025,10 +1925,8 @@ def head_wgrad(x: torch.Tensor, gv: torch.Tensor, dw: torch.Tensor, db: Optional
     lib = load_library()
     gv = gv.reshape(-1).contiguous()
     _need_cuda(x, gv, dw, db)
-    a, x, _ = _head_args(x, dw)
-    assert gv.numel() == x.shape[0] and dw.is_contiguous() and (db is None or db.numel() == 1)
-    a.w = None
-    a.gv = gv.data_ptr()
+    a, x = _head_args(x, None, gv)
+    assert dw.is_contiguous() and dw.numel() == x.shape[1] and (db is None or db.numel() == 1)
     a.dw, a.db, a.accumulate = dw.data_ptr(), _ptr(db), int(bool(accumulate))
     _check(lib.kg_head_wgrad(C.byref(a), _stream()), "kg_head_wgrad")
 
@@ -2053,11 +1951,7 @@ def label_bias_fwd(labels, emb, wg, K: int, C_out: int, cin: int, J: int, ak) ->
     a = _label_bias_args(labels, emb, wg, K, C_out, cin, J, ak)
     zl = torch.empty((labels.numel(), C_out, 1, ak.shape[2]), dtype=torch.float32, device=emb.device)
     a.zl = zl.data_ptr()
-    nbytes = lib.kg_label_bias_workspace_bytes(C.byref(a))
-    if nbytes < 0:
-        _check(-1, "kg_label_bias_workspace_bytes")
-    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=emb.device)
-    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    ws = _workspace("kg_label_bias_workspace_bytes", a, emb.device)
     _check(lib.kg_label_bias_fwd(C.byref(a), _stream()), "kg_label_bias_fwd")
     return zl
 
@@ -2072,17 +1966,12 @@ def label_bias_bwd(gz, labels, emb, wg, K: int, C_out: int, cin: int, J: int, ak
     a = _label_bias_args(labels, emb, wg, K, C_out, cin, J, ak)
     assert gz.shape[0] == labels.numel() and gz.shape[1] == C_out and gz.shape[3] == ak.shape[2]
     a.T = gz.shape[2]
-    a.gz = gz.data_ptr()
-    a.gz_sN, a.gz_sC = _sn_sc(gz)
+    _bind(a, "gz", "gz", gz)
     for t in (demb, dw, dak):
         assert t is None or t.is_contiguous()
     a.demb, a.dw, a.dak = _ptr(demb), _ptr(dw), _ptr(dak)
     a.accumulate, a.dak_accumulate = int(bool(accumulate)), int(bool(dak_accumulate))
-    nbytes = lib.kg_label_bias_workspace_bytes(C.byref(a))
-    if nbytes < 0:
-        _check(-1, "kg_label_bias_workspace_bytes")
-    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=gz.device)
-    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    ws = _workspace("kg_label_bias_workspace_bytes", a, gz.device)
     _check(lib.kg_label_bias_bwd(C.byref(a), _stream()), "kg_label_bias_bwd")
 
 
@@ -2097,10 +1986,10 @@ def mix3(real: torch.Tensor, fake: torch.Tensor, alpha: torch.Tensor) -> torch.T
     out = torch.empty((3 * n, c, t, v), dtype=torch.float32, device=real.device)
     a = _MixArgs()
     a.N, a.C, a.T, a.V = n, c, t, v
-    a.real, a.fake, a.alpha, a.out = real.data_ptr(), fake.data_ptr(), alpha.data_ptr(), out.data_ptr()
-    a.r_sN, a.r_sC = _sn_sc(real)
-    a.f_sN, a.f_sC = _sn_sc(fake)
-    a.o_sN, a.o_sC = c * t * v, t * v
+    _bind(a, "real", "r", real)
+    _bind(a, "fake", "f", fake)
+    a.alpha = alpha.data_ptr()
+    a.out, a.o_sN, a.o_sC = out.data_ptr(), c * t * v, t * v          # (NCHW-contiguous, not channel-major)
     _check(lib.kg_mix3(C.byref(a), _stream()), "kg_mix3")
     return out
 
@@ -2248,9 +2137,7 @@ def mmd(x: MmdView, y: MmdView, m: int, n: int, dim: int, groups: int, classes: 
     a.m, a.n, a.dim, a.groups, a.classes, a.nbw = int(m), int(n), int(dim), int(groups), int(classes), len(bws)
     for i, b in enumerate(bws[:MMD_MAX_BW]):
         a.bw[i] = b
-    nbytes = lib.kg_mmd_workspace_bytes(C.byref(a))
-    if nbytes < 0:
-        _check(-1, "kg_mmd_workspace_bytes")
+    nbytes = _query("kg_mmd_workspace_bytes", a)
     for name, v, p in (("x", x, m), ("y", y, n)):
         if not _mmd_extent_ok(v, p, dim, groups, classes):
             raise ValueError(f"kg_mmd: the strides of {name} reach outside its tensor")
@@ -2291,10 +2178,7 @@ def prdc_workspace_bytes(n: int, m: int, d_outer: int, d_inner: int, classes: in
     """kg_prdc_workspace_bytes of a shape (RuntimeError naming the field for a shape kg_prdc rejects); no GPU call"""
     a = _PrdcArgs()
     a.n, a.m, a.d_outer, a.d_inner, a.classes, a.k = int(n), int(m), int(d_outer), int(d_inner), int(classes), int(k)
-    nbytes = load_library().kg_prdc_workspace_bytes(C.byref(a))
-    if nbytes < 0:
-        _check(-1, "kg_prdc_workspace_bytes")
-    return nbytes
+    return _query("kg_prdc_workspace_bytes", a)
 
 
 def prdc(real: PrdcView, fake: PrdcView, n: int, m: int, d_outer: int, d_inner: int, classes: int, k: int,
@@ -2350,8 +2234,8 @@ def prdc_radii(x: PrdcView, n: int, d_outer: int, d_inner: int, classes: int, k:
         raise ValueError("kg_prdc_radii: the strides of x reach outside its tensor")
     if out is None:
         out = torch.empty((max(classes, 0), max(n, 0)), dtype=torch.float32, device=x.t.device)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != classes * n:
-        raise ValueError("kg_prdc_radii: out must be a contiguous fp32 tensor of classes * n elements")
+    else:
+        _dest(out, classes * n, "kg_prdc_radii: out must be a contiguous fp32 tensor of classes * n elements")
     a = _PrdcRadiiArgs()
     a.x, a.sc, a.sp, a.so = x.t.data_ptr(), x.sc, x.sp, x.so
     a.n, a.d_outer, a.d_inner, a.classes, a.k = int(n), int(d_outer), int(d_inner), int(classes), int(k)
@@ -2367,10 +2251,7 @@ def prdc_sets_workspace_bytes(nsets: int, n: int, m: int, d_outer: int, d_inner:
     a = _PrdcSetsArgs()
     a.nsets, a.n, a.m = int(nsets), int(n), int(m)
     a.d_outer, a.d_inner, a.classes, a.k = int(d_outer), int(d_inner), int(classes), int(k)
-    nbytes = load_library().kg_prdc_sets_workspace_bytes(C.byref(a))
-    if nbytes < 0:
-        _check(-1, "kg_prdc_sets_workspace_bytes")
-    return nbytes
+    return _query("kg_prdc_sets_workspace_bytes", a)
 
 
 def prdc_sets(real: PrdcView, fakes: Sequence[torch.Tensor], f_sc: int, f_sp: int, f_so: int, radii_real: torch.Tensor,
@@ -2454,10 +2335,7 @@ def _frechet_shape(n: int, m: int, frames: int, diff: bool, d_outer: int, d_inne
 
 def frechet_workspace_bytes(n: int, m: int, frames: int, diff: bool, d_outer: int, d_inner: int, classes: int) -> int:
     """kg_frechet_workspace_bytes of a shape (RuntimeError naming the field for a shape kg_frechet rejects); no GPU call"""
-    nbytes = load_library().kg_frechet_workspace_bytes(C.byref(_frechet_shape(n, m, frames, diff, d_outer, d_inner, classes)))
-    if nbytes < 0:
-        _check(-1, "kg_frechet_workspace_bytes")
-    return nbytes
+    return _query("kg_frechet_workspace_bytes", _frechet_shape(n, m, frames, diff, d_outer, d_inner, classes))
 
 
 def frechet(real: FrechetView, fake: FrechetView, n: int, m: int, frames: int, diff: bool, d_outer: int, d_inner: int,
@@ -2515,10 +2393,7 @@ def _frechet_real_shape(n: int, frames: int, diff: bool, d_outer: int, d_inner: 
 def frechet_real_workspace_bytes(n: int, frames: int, diff: bool, d_outer: int, d_inner: int, classes: int) -> int:
     """kg_frechet_real_workspace_bytes of a shape = 8 classes (nch_r + 1) (d + d*d) (RuntimeError naming the field for a
     shape kg_frechet_real rejects); no GPU call"""
-    nbytes = load_library().kg_frechet_real_workspace_bytes(C.byref(_frechet_real_shape(n, frames, diff, d_outer, d_inner, classes)))
-    if nbytes < 0:
-        _check(-1, "kg_frechet_real_workspace_bytes")
-    return nbytes
+    return _query("kg_frechet_real_workspace_bytes", _frechet_real_shape(n, frames, diff, d_outer, d_inner, classes))
 
 
 def frechet_real(view: FrechetView, n: int, frames: int, diff: bool, d_outer: int, d_inner: int, classes: int,
@@ -2563,11 +2438,7 @@ def _frechet_sets_shape(nsets: int, m: int, frames: int, diff: bool, d_outer: in
 def frechet_sets_workspace_bytes(nsets: int, m: int, frames: int, diff: bool, d_outer: int, d_inner: int, classes: int) -> int:
     """kg_frechet_sets_workspace_bytes of a shape = 8 nsets classes (nch_f + 1) (d + d*d) (RuntimeError naming the field
     for a shape kg_frechet_sets rejects); no GPU call"""
-    nbytes = load_library().kg_frechet_sets_workspace_bytes(
-        C.byref(_frechet_sets_shape(nsets, m, frames, diff, d_outer, d_inner, classes)))
-    if nbytes < 0:
-        _check(-1, "kg_frechet_sets_workspace_bytes")
-    return nbytes
+    return _query("kg_frechet_sets_workspace_bytes", _frechet_sets_shape(nsets, m, frames, diff, d_outer, d_inner, classes))
 
 
 def frechet_sets(cache: dict, fakes: Sequence[torch.Tensor], f_sc: int, f_ss: int, f_sf: int, f_so: int, m: int, frames: int,
@@ -2891,8 +2762,7 @@ def copy_if(flag: torch.Tensor, jobs: Sequence[Tuple[torch.Tensor, torch.Tensor]
     _need_cuda(flag)
     lib = load_library()
     jobs = list(jobs)
-    for q in range(0, len(jobs), COPY_IF_MAX_JOBS):
-        part = jobs[q:q + COPY_IF_MAX_JOBS]
+    for part in _chunks(jobs, COPY_IF_MAX_JOBS):
         arr = (_CopyJob * len(part))()
         for i, (src, dst) in enumerate(part):
             _need_cuda(src, dst)

@@ -9,6 +9,8 @@ import pytest
 import kinetic_gan_amd  # noqa: F401
 from kinetic_gan_amd import _native, build
 
+import abi_layout
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -38,30 +40,34 @@ def test_info_calls(lib):
     assert lib.kg_arch() == b"gfx950"
 
 
+# every `#define KG_*` of the header that deliberately has no `_native` counterpart (KG_X <-> X); a name missing from both
+# fails test_constants_match_header: a silently skipped name would hide a drift
+DEFINES_WITHOUT_MIRROR = []
+
+
 def test_struct_sizes_match_header():
-    """ctypes mirrors must have the C layout: compile a tiny C program against the header."""
-    import subprocess
-    import tempfile
-    src = r'''
-#include <stdio.h>
-#include "kgan_hip.h"
-int main(void){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(KgConvGroup), sizeof(KgConvArgs),
-  sizeof(KgWgradArgs), sizeof(KgAggArgs), sizeof(KgRowsumArgs), sizeof(KgEltArgs), sizeof(KgBnArgs), sizeof(KgWgradPair),
-  sizeof(KgWgradReduceJob), sizeof(KgWgradReduceJobs), sizeof(KgAggConvArgs)); printf(" %zu %zu %zu %zu %zu %zu %zu\n", sizeof(KgGpArgs), sizeof(KgOuterSumJob), sizeof(KgOuterSumJobs), sizeof(KgBnJob), sizeof(KgGenArgs), sizeof(KgGenAdjJob), sizeof(KgGenPrepJob)); printf(" %zu %zu %zu %zu\n", sizeof(KgHeadArgs), sizeof(KgLabelBiasArgs), sizeof(KgMixArgs), sizeof(KgMaskedAdjArgs)); printf(" %zu %zu\n", sizeof(KgGenTailArgs), sizeof(KgLinearArgs)); printf(" %zu %zu %zu %zu\n", sizeof(KgPlane), sizeof(KgGenBnLayer), sizeof(KgGenBlockArgs), sizeof(KgGenBlockBwdArgs)); return 0; }'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        sizes = [int(v) for v in subprocess.check_output([exe]).split()]
-    mine = [ctypes.sizeof(t) for t in (_native._ConvGroup, _native._ConvArgs, _native._WgradArgs,
-                                       _native._AggArgs, _native._RowsumArgs, _native._EltArgs, _native._BnArgs,
-                                       _native._WgradPair, _native._WgradReduceJob, _native._WgradReduceJobs,
-                                       _native._AggConvArgs, _native._GpArgs, _native._OuterSumJob, _native._OuterSumJobs,
-                                       _native._BnJob, _native._GenArgs, _native._GenAdjJob, _native._GenPrepJob, _native._HeadArgs,
-                                       _native._LabelBiasArgs, _native._MixArgs, _native._MaskedAdjArgs, _native._GenTailArgs, _native._LinearArgs,
-                                       _native._Plane, _native._GenBnLayer, _native._GenBlockArgs, _native._GenBlockBwdArgs)]
-    assert sizes == mine
+    """ctypes mirrors must have the C layout: every ctypes.Structure of _native is a struct of the header (`_Foo` <-> `KgFoo`)
+    and the other way round, with the header's size and the header's offset of every field (tests/abi_layout.py compiles one
+    C program against the header)."""
+    mirrors = abi_layout.mirrors()
+    assert sorted(mirrors) == abi_layout.header_structs()
+    assert len(mirrors) >= 42
+    checked = 0
+    for cname in sorted(mirrors):
+        abi_layout.assert_mirror(cname)
+        checked += len(abi_layout.header_layout(cname))
+    assert checked >= 802       # sizeof of 42 structs + offsetof of their 760 fields
+
+
+def test_constants_match_header():
+    """every `#define KG_X` integer constant of the header equals `_native.X`; the ones without a counterpart are listed"""
+    consts = abi_layout.header_constants()
+    assert sorted(consts) == abi_layout.header_defines() and len(consts) >= 22
+    assert consts["KG_ABI_VERSION"] == _native.ABI_VERSION
+    missing = sorted(k for k in consts if not hasattr(_native, k[3:]))
+    assert missing == sorted(DEFINES_WITHOUT_MIRROR)
+    bad = {k: (v, getattr(_native, k[3:])) for k, v in consts.items() if hasattr(_native, k[3:]) and getattr(_native, k[3:]) != v}
+    assert not bad, "(header, _native) differ at %s" % bad
 
 
 def integration_md_stub(lib_path):
@@ -85,14 +91,7 @@ def integration_md_stub(lib_path):
 
 
 def header_sizeof(name):
-    import subprocess
-    import tempfile
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write('#include <stdio.h>\n#include "kgan_hip.h"\nint main(void){ printf("%%zu\\n", sizeof(%s)); return 0; }' % name)
-        exe = os.path.join(d, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        return int(subprocess.check_output([exe]))
+    return abi_layout.header_layout(name)["sizeof"]
 
 
 def test_integration_md_stub(lib):

@@ -15,6 +15,7 @@ import kinetic_gan_amd  # noqa: F401
 from kinetic_gan_amd import _native, build, evaluate, metrics
 from kinetic_gan_amd.feeder import Feeder
 
+import abi_layout
 import eval_def
 import train_def
 
@@ -79,16 +80,11 @@ def test_entry_points_declared_exported_bound(lib):
     assert callable(_native.eval_record) and callable(_native.copy_if)
 
 
-def test_struct_sizes_match_header(tmp_path):
-    import subprocess
-    c = tmp_path / "s.c"
-    c.write_text('#include <stdio.h>\n#include "kgan_hip.h"\nint main(void){ printf("%zu %zu %d %d\\n", sizeof(KgEvalRecordArgs), '
-                 'sizeof(KgCopyJob), KG_EVAL_MAX_SCORES, KG_COPY_IF_MAX_JOBS); return 0; }')
-    exe = str(tmp_path / "s")
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe])
-    got = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert got == [ctypes.sizeof(_native._EvalRecordArgs), ctypes.sizeof(_native._CopyJob), _native.EVAL_MAX_SCORES,
-                   _native.COPY_IF_MAX_JOBS]
+def test_struct_sizes_match_header():
+    for cname in ("KgEvalRecordArgs", "KgCopyJob"):
+        abi_layout.assert_mirror(cname)
+    consts = abi_layout.header_constants()
+    assert [consts["KG_EVAL_MAX_SCORES"], consts["KG_COPY_IF_MAX_JOBS"]] == [_native.EVAL_MAX_SCORES, _native.COPY_IF_MAX_JOBS]
     assert _native.COPY_IF_MAX_JOBS >= 32
 
 

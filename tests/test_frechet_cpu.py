@@ -3,8 +3,6 @@ recorded results and against closed forms, the caps on the tolerances of the sha
 kg_frechet and metrics.frechet, and the ctypes mirror of KgFrechetArgs."""
 import ctypes
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -14,6 +12,7 @@ import kinetic_gan_amd  # noqa: F401
 from kinetic_gan_amd import _native, build
 from kinetic_gan_amd import metrics
 
+import abi_layout
 import frechet_def
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -157,17 +156,7 @@ def test_header_declares_and_library_exports(lib):
 
 
 def test_frechet_struct_matches_header():
-    fields = [n for n, _ in _native._FrechetArgs._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "kgan_hip.h"\nint main(void){ printf("%zu", sizeof(KgFrechetArgs));'
-    src += "".join(' printf(" %%zu", offsetof(KgFrechetArgs, %s));' % n for n in fields) + " return 0; }"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert got[0] == ctypes.sizeof(_native._FrechetArgs)
-    assert got[1:] == [getattr(_native._FrechetArgs, n).offset for n in fields]
+    abi_layout.assert_mirror("KgFrechetArgs")
 
 
 def _valid_args():

@@ -3,8 +3,6 @@
 of kg_mmd and the ctypes mirror of KgMmdArgs."""
 import ctypes
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -15,6 +13,7 @@ from kinetic_gan_amd import _native, build
 from kinetic_gan_amd import metrics
 from kinetic_gan_amd.feeder import Feeder
 
+import abi_layout
 import mmd_def
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -184,15 +183,5 @@ def test_kg_mmd_m1_is_valid(lib):
 
 
 def test_mmd_struct_matches_header():
-    fields = [n for n, _ in _native._MmdArgs._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "kgan_hip.h"\nint main(void){ printf("%zu", sizeof(KgMmdArgs));'
-    src += "".join(' printf(" %%zu", offsetof(KgMmdArgs, %s));' % n for n in fields) + " return 0; }"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert got[0] == ctypes.sizeof(_native._MmdArgs)
-    assert got[1:] == [getattr(_native._MmdArgs, n).offset for n in fields]
+    abi_layout.assert_mirror("KgMmdArgs")
     assert _native.MMD_MAX_BW == 16

@@ -2,8 +2,6 @@
 example, the argument checks of kg_prdc and metrics.prdc, the workspace size and the ctypes mirror of KgPrdcArgs."""
 import ctypes
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ import kinetic_gan_amd  # noqa: F401
 from kinetic_gan_amd import _native, build
 from kinetic_gan_amd import metrics
 
+import abi_layout
 import prdc_def
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,17 +37,7 @@ def test_abi_version_unchanged(lib):
 
 
 def test_prdc_struct_matches_header():
-    fields = [n for n, _ in _native._PrdcArgs._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "kgan_hip.h"\nint main(void){ printf("%zu", sizeof(KgPrdcArgs));'
-    src += "".join(' printf(" %%zu", offsetof(KgPrdcArgs, %s));' % n for n in fields) + " return 0; }"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert got[0] == ctypes.sizeof(_native._PrdcArgs)
-    assert got[1:] == [getattr(_native._PrdcArgs, n).offset for n in fields]
+    abi_layout.assert_mirror("KgPrdcArgs")
 
 
 def _valid_args():

@@ -3,7 +3,6 @@ the random streams against Random123's known answers, the counter layout, the ba
 n_critic schedule, and the C ABI of the new entry points."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ from kinetic_gan_amd import _native, build
 from kinetic_gan_amd import train as ktrain
 from kinetic_gan_amd.feeder import DeviceBatches, Feeder
 
+import abi_layout
 import train_def
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -113,22 +113,10 @@ def test_step_inputs_abi():
     lib = _native.load_library()
     assert hasattr(lib, "kg_step_inputs") and hasattr(lib, "kg_loss_append")
     assert lib.kg_abi_version() == 9
-    S = _native._StepInputsArgs
-    names = [n for n, _ in S._fields_]
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "kgan_hip.h"\nint main(void){ printf("%zu", sizeof(KgStepInputsArgs));\n'
-    prog += "".join('printf(" %%zu", offsetof(KgStepInputsArgs, %s));\n' % n for n in names)
-    prog += 'printf(" %d %d %d %d %d\\n", KG_STEP_MAX_PLANES, KG_STREAM_Z, KG_STREAM_ALPHA, KG_STREAM_NOISE_D, KG_STREAM_NOISE_G); return 0; }\n'
-    import tempfile
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(d, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        vals = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert vals[0] == ctypes.sizeof(S)
-    assert vals[1:1 + len(names)] == [getattr(S, n).offset for n in names]
-    assert vals[1 + len(names):] == [_native.STEP_MAX_PLANES, _native.STREAM_Z, _native.STREAM_ALPHA, _native.STREAM_NOISE_D,
-                                     _native.STREAM_NOISE_G]
+    abi_layout.assert_mirror("KgStepInputsArgs")
+    consts = abi_layout.header_constants()
+    assert [consts[k] for k in ("KG_STEP_MAX_PLANES", "KG_STREAM_Z", "KG_STREAM_ALPHA", "KG_STREAM_NOISE_D", "KG_STREAM_NOISE_G")] == \
+        [_native.STEP_MAX_PLANES, _native.STREAM_Z, _native.STREAM_ALPHA, _native.STREAM_NOISE_D, _native.STREAM_NOISE_G]
     assert (train_def.STREAM_Z, train_def.STREAM_ALPHA, train_def.STREAM_NOISE_D, train_def.STREAM_NOISE_G) == (0, 1, 2, 3)
 
 
