@@ -1069,6 +1069,59 @@ int kg_eval_record2(const KgEvalRecord2Args* a, void* stream);
 typedef struct KgCopyJob { const void* src;  void* dst;  int64_t nwords; } KgCopyJob;
 int kg_copy_if(const int32_t* flag, const KgCopyJob* jobs, int32_t njobs, void* stream);
 
+/* ---- action classifier head (additive, ABI v9; DESIGN.md 20, csrc/kg_cls.hip) ------------------------------------------
+ * The head of classifier.Classifier on the last st_gcn block's output h (N, C, T, V), P = T V, read in place through
+ * (h_sN, h_sC) - the trunk's channel-major planes and an NCHW tensor alike:
+ *   pooled[n, c] = (sum_{t,v} h[n, c, t, v]) / P                          (t, v) in index order
+ *   feat[n, f]   = lrelu_slope(b1[f] + sum_c w1[f, c] pooled[n, c])       w1 (F, C), F <= KG_FRECHET_MAX_DIM
+ *   logits[n, l] = b2[l] + sum_f w2[l, f] feat[n, f]                      w2 (L, F)
+ *   pred[n]      = lowest class index holding the largest logit: start at class 0, replace on a strict '>' (NaN never wins)
+ *   loss_per_sample[n] = (m + log sum_l exp(logits[n, l] - m)) - logits[n, y_n],  m = max_l logits[n, l]
+ *                        NaN when y_n is outside [0, L): such a sample is never counted correct and reads nothing
+ *   loss = (1/N) sum_n loss_per_sample[n]        correct = #{n : 0 <= y_n < L and pred[n] == y_n}
+ * kg_cls_head_fwd: a workgroup owns KG_CLS_TILE samples (w1 is read once per tile) and writes pooled, feat, logits, pred
+ *   and - with labels - loss_per_sample; then ONE workgroup finishes loss (fp64, sample-index order, rounded once) and
+ *   correct.  No exchange between the workgroups of a launch: no tickets, no atomics - two calls give the same bits.
+ *   labels == NULL: features, logits and predictions only (loss_per_sample, loss, correct are not touched).
+ * kg_cls_head_bwd: from the scalar top gradient *gtop (device memory), the forward's feat / logits and the labels:
+ *   dlogits[n, l] = ((softmax(logits[n])[l] - [l == y_n]) * gtop) / N     (NaN for a label outside [0, L))
+ *   dfeat[n, f]   = (sum_l w2[l, f] dlogits[n, l]) * lrelu'(feat[n, f])   lrelu'(o) = o > 0 ? 1 : slope
+ *   dpooled[n, c] = sum_f w1[f, c] dfeat[n, f]
+ *   g[n, c, t, v] = dpooled[n, c] / P * (masked ? lrelu'(h[n, c, t, v]) : 1)      (the contract of kg_head_bwd)
+ *   dlogits (N, L) and dfeat (N, F) go to the workspace, in this order.
+ * kg_cls_head_wgrad: from the workspace kg_cls_head_bwd filled, pooled and feat:
+ *   dw2[l, f] (+)= sum_n dlogits[n, l] feat[n, f]      db2[l] (+)= sum_n dlogits[n, l]
+ *   dw1[f, c] (+)= sum_n dfeat[n, f] pooled[n, c]      db1[f] (+)= sum_n dfeat[n, f]
+ *   every output element is summed over n in index order by one thread; `accumulate` as in kg_head_wgrad.
+ * ws: kg_cls_head_workspace_bytes(a) = 4 N (L + F) bytes.  A null operand, N, T, V < 1, C outside [1, KG_CLS_MAX_C],
+ * F outside [1, KG_FRECHET_MAX_DIM], L outside [1, KG_CLS_MAX_CLASSES] or a small workspace are rejected on the host
+ * (< 0, kg_last_error() names the entry point) before anything is launched.                                          */
+#define KG_CLS_TILE 4
+#define KG_CLS_MAX_C 1024
+#define KG_CLS_MAX_CLASSES 1024
+typedef struct KgClsHeadArgs {
+    int32_t N, C, T, V, F, L;
+    const float* h;  int64_t h_sN, h_sC;        /* (N, C, T, V) plane tensor; bwd: read only when `masked`            */
+    const float* w1;  const float* b1;          /* fc1: (F, C), (F)                                                    */
+    const float* w2;  const float* b2;          /* fcn: (L, F), (L)                                                    */
+    const int64_t* labels;                      /* (N) or NULL (fwd only)                                              */
+    float slope;  int32_t masked;
+    float* pooled;                              /* (N, C)   fwd: out; wgrad: in                                        */
+    float* feat;                                /* (N, F)   fwd: out; bwd, wgrad: in                                   */
+    float* logits;                              /* (N, L)   fwd: out; bwd: in                                          */
+    float* loss_per_sample;                     /* (N)      fwd with labels                                            */
+    int32_t* pred;                              /* (N)      fwd                                                        */
+    float* loss;  int32_t* correct;             /* (1), (1) fwd with labels                                            */
+    const float* gtop;                          /* bwd: (1) d(objective) / d loss, on the device                       */
+    float* g;  int64_t g_sN, g_sC;              /* bwd: (N, C, T, V) plane tensor                                      */
+    float* dw1;  float* db1;  float* dw2;  float* db2;  int32_t accumulate;      /* wgrad                             */
+    void* ws;  int64_t ws_bytes;
+} KgClsHeadArgs;
+int64_t kg_cls_head_workspace_bytes(const KgClsHeadArgs* a);   /* < 0 for invalid shapes                              */
+int     kg_cls_head_fwd(const KgClsHeadArgs* a, void* stream);
+int     kg_cls_head_bwd(const KgClsHeadArgs* a, void* stream);
+int     kg_cls_head_wgrad(const KgClsHeadArgs* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

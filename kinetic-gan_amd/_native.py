@@ -453,6 +453,25 @@ class _CopyJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("nwords", C.c_int64)]
 
 
+CLS_TILE = 4
+CLS_MAX_C = 1024
+CLS_MAX_CLASSES = 1024
+
+
+class _ClsHeadArgs(C.Structure):
+    _fields_ = [("N", C.c_int32), ("C", C.c_int32), ("T", C.c_int32), ("V", C.c_int32), ("F", C.c_int32), ("L", C.c_int32),
+                ("h", c_f32p), ("h_sN", C.c_int64), ("h_sC", C.c_int64),
+                ("w1", c_f32p), ("b1", c_f32p), ("w2", c_f32p), ("b2", c_f32p),
+                ("labels", C.c_void_p),
+                ("slope", C.c_float), ("masked", C.c_int32),
+                ("pooled", c_f32p), ("feat", c_f32p), ("logits", c_f32p), ("loss_per_sample", c_f32p),
+                ("pred", C.c_void_p), ("loss", c_f32p), ("correct", C.c_void_p),
+                ("gtop", c_f32p),
+                ("g", c_f32p), ("g_sN", C.c_int64), ("g_sC", C.c_int64),
+                ("dw1", c_f32p), ("db1", c_f32p), ("dw2", c_f32p), ("db2", c_f32p), ("accumulate", C.c_int32),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
 EXPORTS = {
     "kg_abi_version": (C.c_int, []),
     "kg_arch": (C.c_char_p, []),
@@ -558,6 +577,10 @@ EXPORTS = {
     "kg_eval_record": (C.c_int, [C.POINTER(_EvalRecordArgs), C.c_void_p]),
     "kg_eval_record2": (C.c_int, [C.POINTER(_EvalRecord2Args), C.c_void_p]),
     "kg_copy_if": (C.c_int, [C.c_void_p, C.POINTER(_CopyJob), C.c_int32, C.c_void_p]),
+    "kg_cls_head_workspace_bytes": (C.c_int64, [C.POINTER(_ClsHeadArgs)]),
+    "kg_cls_head_fwd": (C.c_int, [C.POINTER(_ClsHeadArgs), C.c_void_p]),
+    "kg_cls_head_bwd": (C.c_int, [C.POINTER(_ClsHeadArgs), C.c_void_p]),
+    "kg_cls_head_wgrad": (C.c_int, [C.POINTER(_ClsHeadArgs), C.c_void_p]),
 }
 
 _lib = None
@@ -1929,6 +1952,94 @@ def head_wgrad(x: torch.Tensor, gv: torch.Tensor, dw: torch.Tensor, db: Optional
     assert dw.is_contiguous() and dw.numel() == x.shape[1] and (db is None or db.numel() == 1)
     a.dw, a.db, a.accumulate = dw.data_ptr(), _ptr(db), int(bool(accumulate))
     _check(lib.kg_head_wgrad(C.byref(a), _stream()), "kg_head_wgrad")
+
+
+# ---- the action classifier's head (kg_cls.hip; classifier.Classifier) -----------------------------------------------------
+
+def _cls_head_args(n: int, c: int, t: int, v: int, f: int, l: int, slope: float = 0.2) -> _ClsHeadArgs:
+    a = _ClsHeadArgs()
+    a.N, a.C, a.T, a.V, a.F, a.L, a.slope = int(n), int(c), int(t), int(v), int(f), int(l), float(slope)
+    return a
+
+
+def _cls_flat(t: torch.Tensor, n: int, dtype, what: str) -> torch.Tensor:
+    if t.numel() != n or not t.is_contiguous() or t.dtype != dtype:
+        raise ValueError(f"kg_cls_head: {what} must be contiguous {dtype} of {n} elements")
+    return t
+
+
+def cls_head_workspace_bytes(n: int, c: int, t: int, v: int, f: int, l: int) -> int:
+    """bytes of the scratch kg_cls_head_bwd fills and kg_cls_head_wgrad reads: 4 N (L + F)"""
+    return _query("kg_cls_head_workspace_bytes", _cls_head_args(n, c, t, v, f, l))
+
+
+def cls_head_fwd(h: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                 labels: Optional[torch.Tensor] = None, slope: float = 0.2) -> dict:
+    """Global average pool -> fc1 + LeakyReLU -> fcn -> argmax and, with ``labels`` (N,) int64, the softmax cross-entropy
+    (kg_cls_head_fwd; no host synchronisation).  Returns dict(pooled (N, C), feat (N, F), logits (N, L), pred (N,) int32) and
+    with labels loss_per_sample (N,), loss (0-d), correct (0-d int32); else those three are None."""
+    lib = load_library()
+    _need_cuda(h, w1, b1, w2, b2, labels)
+    f, l = w1.shape[0], w2.shape[0]
+    a = _cls_head_args(*h.shape, f, l, slope)
+    h = _bind(a, "h", "h", h, True)
+    n, c = h.shape[0], h.shape[1]
+    a.w1, a.b1 = _cls_flat(w1, f * c, torch.float32, "w1").data_ptr(), _cls_flat(b1, f, torch.float32, "b1").data_ptr()
+    a.w2, a.b2 = _cls_flat(w2, l * f, torch.float32, "w2").data_ptr(), _cls_flat(b2, l, torch.float32, "b2").data_ptr()
+    dev = h.device
+    out = dict(pooled=torch.empty((n, c), dtype=torch.float32, device=dev),
+               feat=torch.empty((n, f), dtype=torch.float32, device=dev),
+               logits=torch.empty((n, l), dtype=torch.float32, device=dev),
+               pred=torch.empty(n, dtype=torch.int32, device=dev),
+               loss_per_sample=None, loss=None, correct=None)
+    a.pooled, a.feat, a.logits, a.pred = (out[k].data_ptr() for k in ("pooled", "feat", "logits", "pred"))
+    if labels is not None:
+        a.labels = _cls_flat(labels, n, torch.int64, "labels").data_ptr()
+        out["loss_per_sample"] = torch.empty(n, dtype=torch.float32, device=dev)
+        out["loss"] = torch.empty((), dtype=torch.float32, device=dev)
+        out["correct"] = torch.empty((), dtype=torch.int32, device=dev)
+        a.loss_per_sample, a.loss, a.correct = (out[k].data_ptr() for k in ("loss_per_sample", "loss", "correct"))
+    _check(lib.kg_cls_head_fwd(C.byref(a), _stream()), "kg_cls_head_fwd")
+    return out
+
+
+def cls_head_bwd(gtop: torch.Tensor, h: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, labels: torch.Tensor,
+                 feat: torch.Tensor, logits: torch.Tensor, masked: bool = True, slope: float = 0.2):
+    """The head's backward pass from the one-element device tensor ``gtop`` = d objective / d loss (kg_cls_head_bwd).  Returns
+    (g, ws): the trunk's top gradient (N, C, T, V) - times lrelu'(h) when ``masked`` - and the workspace holding dlogits
+    (N, L) and dfeat (N, F), the operand of cls_head_wgrad."""
+    lib = load_library()
+    _need_cuda(gtop, h, w1, w2, labels, feat, logits)
+    f, l = w1.shape[0], w2.shape[0]
+    a = _cls_head_args(*h.shape, f, l, slope)
+    h = _bind(a, "h", "h", h, True)
+    n, c = h.shape[0], h.shape[1]
+    a.w1, a.w2 = _cls_flat(w1, f * c, torch.float32, "w1").data_ptr(), _cls_flat(w2, l * f, torch.float32, "w2").data_ptr()
+    a.labels = _cls_flat(labels, n, torch.int64, "labels").data_ptr()
+    a.feat, a.logits = _cls_flat(feat, n * f, torch.float32, "feat").data_ptr(), _cls_flat(logits, n * l, torch.float32, "logits").data_ptr()
+    a.gtop, a.masked = _cls_flat(gtop, 1, torch.float32, "gtop").data_ptr(), int(bool(masked))
+    g = _bind(a, "g", "g", new_plane(*h.shape, h.device))
+    ws = _workspace("kg_cls_head_workspace_bytes", a, h.device)
+    _check(lib.kg_cls_head_bwd(C.byref(a), _stream()), "kg_cls_head_bwd")
+    return g, ws
+
+
+def cls_head_wgrad(ws: torch.Tensor, pooled: torch.Tensor, feat: torch.Tensor, n_classes: int, dw1: torch.Tensor, db1: torch.Tensor,
+                   dw2: torch.Tensor, db2: torch.Tensor, accumulate: bool = True) -> None:
+    """dw1 (F, C), db1 (F), dw2 (L, F), db2 (L) (+)= the head's parameter gradients from the workspace cls_head_bwd filled
+    and the forward's pooled (N, C) / feat (N, F) (kg_cls_head_wgrad)."""
+    lib = load_library()
+    _need_cuda(ws, pooled, feat, dw1, db1, dw2, db2)
+    (n, c), f, l = pooled.shape, feat.shape[1], int(n_classes)
+    a = _cls_head_args(n, c, 1, 1, f, l)
+    a.pooled, a.feat = _cls_flat(pooled, n * c, torch.float32, "pooled").data_ptr(), _cls_flat(feat, n * f, torch.float32, "feat").data_ptr()
+    a.dw1, a.db1 = _cls_flat(dw1, f * c, torch.float32, "dw1").data_ptr(), _cls_flat(db1, f, torch.float32, "db1").data_ptr()
+    a.dw2, a.db2 = _cls_flat(dw2, l * f, torch.float32, "dw2").data_ptr(), _cls_flat(db2, l, torch.float32, "db2").data_ptr()
+    a.accumulate = int(bool(accumulate))
+    if ws.dtype != torch.float32 or not ws.is_contiguous():
+        raise ValueError("kg_cls_head_wgrad: the workspace of cls_head_bwd expected")
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    _check(lib.kg_cls_head_wgrad(C.byref(a), _stream()), "kg_cls_head_wgrad")
 
 
 def _label_bias_args(labels, emb, wg, K, C_out, cin, J, ak):

@@ -364,6 +364,50 @@ def frechet_features(feat_gen, feat_real, labels_gen=None, labels_real=None, per
     return frechet(feat_gen[:, None, None, :], feat_real[:, None, None, :], labels_gen, labels_real, "pose", per_class, moments)
 
 
+def _classifier_pass(clf, x, ids: Optional[np.ndarray], batch: int):
+    """features (N, d) and the correct count (0-d int64 on the device, None without labels) of x in chunks of ``batch``"""
+    dev = next(clf.parameters()).device
+    x = torch.as_tensor(x) if not torch.is_tensor(x) else x
+    feats, correct = [], None
+    with torch.no_grad():
+        for lo in range(0, x.shape[0], batch):
+            xb = x[lo:lo + batch].to(dev, dtype=torch.float32)
+            yb = None if ids is None else torch.as_tensor(ids[lo:lo + batch], dtype=torch.int64).to(dev)
+            out = clf.classify(xb, yb)
+            feats.append(out["features"])
+            if yb is not None:
+                c = out["correct"].to(torch.int64)
+                correct = c if correct is None else correct + c
+    return torch.cat(feats, 0), correct
+
+
+def classifier_scores(clf, gen, labels_gen, real, labels_real=None, per_class: Optional[int] = None, batch: int = 512,
+                      class_fd: bool = True) -> dict:
+    """The protocol of Action2Motion / ACTOR with a ``classifier.Classifier`` trained on the user's own data:
+    ``accuracy`` (and the integer ``correct``) - the recognition accuracy of the generated samples ``gen`` (N, C, T, V)
+    against their conditioning labels; ``accuracy_real`` when ``labels_real`` is given; ``feature_fd`` - the Frechet distance
+    of all generated against all real features as one set (``frechet_features`` without labels); with ``labels_real``
+    also ``feature_fd_class_mean`` / ``feature_fd_per_class`` (``frechet_features`` with both label vectors and
+    ``per_class``; ``class_fd=False`` leaves these two out).  Labels are one-hot rows or class ids.  Features are computed in chunks of ``batch`` without autograd;
+    the Frechet values stay fp64 device tensors, the accuracies are host numbers (one read); ``features_gen`` /
+    ``features_real`` (N, d) are handed back as well."""
+    n_g, n_r = int(gen.shape[0]), int(real.shape[0])
+    ids_g, _ = _label_ids(labels_gen, n_g, "labels_gen")
+    ids_r = None if labels_real is None else _label_ids(labels_real, n_r, "labels_real")[0]
+    feat_g, cor_g = _classifier_pass(clf, gen, ids_g, batch)
+    feat_r, cor_r = _classifier_pass(clf, real, ids_r, batch)
+    out = {"correct": int(cor_g), "features_gen": feat_g, "features_real": feat_r}
+    out["accuracy"] = out["correct"] / float(n_g)
+    if cor_r is not None:
+        out["correct_real"] = int(cor_r)
+        out["accuracy_real"] = out["correct_real"] / float(n_r)
+    out["feature_fd"] = frechet_features(feat_g, feat_r)["mean"]
+    if ids_r is not None and class_fd:
+        res = frechet_features(feat_g, feat_r, ids_g, ids_r, per_class)
+        out["feature_fd_class_mean"], out["feature_fd_per_class"] = res["mean"], res["values"]
+    return out
+
+
 def select_reference_samples(feeder, classes: Optional[Sequence[int]] = None, t_size: int = 64, per_class: int = 100):
     """The sample selection of mmd-actions.py:131-163, vectorised on the label vector.
 
