@@ -1122,6 +1122,41 @@ int     kg_cls_head_fwd(const KgClsHeadArgs* a, void* stream);
 int     kg_cls_head_bwd(const KgClsHeadArgs* a, void* stream);
 int     kg_cls_head_wgrad(const KgClsHeadArgs* a, void* stream);
 
+/* ---- classifier scores of up to four sets (additive, ABI v9; DESIGN.md 21, csrc/kg_cls.hip) ----------------------------
+ * From the features feat[s] (N, F; fp32, shared row stride feat_ld >= F) and predictions pred[s] (N) of nsets sets that
+ * share the labels (N) and two tables of row-index pairs - div_pairs (Sd, 2) and mm_pairs (K*Sl, 2), class-major:
+ *   dist[s, p]             = sqrt(sum_f ((double)feat[s][i_p, f] - (double)feat[s][j_p, f])^2)
+ *                            p over the Sd diversity pairs, then the K*Sl multimodality pairs; an index outside [0, N)
+ *                            gives NaN and nothing is read for the pair
+ *   diversity[s]           = (sum_{p < Sd} dist[s, p]) / Sd                     fp64, index order, one division
+ *   multimodality[s]       = (sum over the K*Sl pairs, index order) / (K*Sl)
+ *   correct_per_class[s,c] = #{n : labels[n] == c and pred[s][n] == c}          a label outside [0, K) counts nowhere
+ *   count_per_class[c]     = #{n : labels[n] == c}
+ *   correct[s]             = sum_c correct_per_class[s, c];   accuracy[s] = (double)correct[s] / N
+ *   scores64 (nsets, 3)    = [accuracy, diversity, multimodality];   scores = its fp32 rounding, once
+ * Two launches: a wave per (set, pair) writes dist (lane-strided fp64 squares, a shuffle tree, one sqrt); then ONE workgroup
+ * per set tallies the integers in LDS (integer adds only) and ONE thread adds the two means in index order.  No tickets,
+ * no polled words, no atomics on global memory; every output element has one owner (count_per_class: the workgroup of set
+ * 0) and is written on every call - two calls give the same bits.  No scratch beyond dist.  A null operand, nsets outside
+ * [1, KG_CLS_MAX_SETS], N < 1, F outside [1, KG_FRECHET_MAX_DIM], K outside [1, KG_CLS_MAX_CLASSES], Sd < 1, Sl < 1 or
+ * feat_ld < F are rejected on the host (< 0, kg_last_error() names the entry point) before anything is launched.        */
+#define KG_CLS_MAX_SETS 4
+typedef struct KgClsScoresArgs {
+    int32_t nsets, N, F, K, Sd, Sl;
+    int64_t feat_ld;
+    const float* feat[KG_CLS_MAX_SETS];         /* (N, F) rows feat_ld floats apart                                    */
+    const int32_t* pred[KG_CLS_MAX_SETS];       /* (N)                                                                 */
+    const int64_t* labels;                      /* (N)                                                                 */
+    const int32_t* div_pairs;                   /* (Sd, 2)                                                             */
+    const int32_t* mm_pairs;                    /* (K*Sl, 2), class-major                                              */
+    double* dist;                               /* out: (nsets, Sd + K*Sl)                                             */
+    double* scores64;  float* scores;           /* out: (nsets, 3), (nsets, 3)                                         */
+    int32_t* correct;                           /* out: (nsets)                                                        */
+    int32_t* correct_per_class;                 /* out: (nsets, K)                                                     */
+    int32_t* count_per_class;                   /* out: (K)                                                            */
+} KgClsScoresArgs;
+int     kg_cls_scores(const KgClsScoresArgs* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

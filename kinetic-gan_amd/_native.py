@@ -472,6 +472,18 @@ class _ClsHeadArgs(C.Structure):
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
+CLS_MAX_SETS = 4
+
+
+class _ClsScoresArgs(C.Structure):
+    _fields_ = [("nsets", C.c_int32), ("N", C.c_int32), ("F", C.c_int32), ("K", C.c_int32), ("Sd", C.c_int32), ("Sl", C.c_int32),
+                ("feat_ld", C.c_int64),
+                ("feat", c_f32p * CLS_MAX_SETS), ("pred", C.c_void_p * CLS_MAX_SETS),
+                ("labels", C.c_void_p), ("div_pairs", C.c_void_p), ("mm_pairs", C.c_void_p),
+                ("dist", C.c_void_p), ("scores64", C.c_void_p), ("scores", c_f32p),
+                ("correct", C.c_void_p), ("correct_per_class", C.c_void_p), ("count_per_class", C.c_void_p)]
+
+
 EXPORTS = {
     "kg_abi_version": (C.c_int, []),
     "kg_arch": (C.c_char_p, []),
@@ -581,6 +593,7 @@ EXPORTS = {
     "kg_cls_head_fwd": (C.c_int, [C.POINTER(_ClsHeadArgs), C.c_void_p]),
     "kg_cls_head_bwd": (C.c_int, [C.POINTER(_ClsHeadArgs), C.c_void_p]),
     "kg_cls_head_wgrad": (C.c_int, [C.POINTER(_ClsHeadArgs), C.c_void_p]),
+    "kg_cls_scores": (C.c_int, [C.POINTER(_ClsScoresArgs), C.c_void_p]),
 }
 
 _lib = None
@@ -1974,12 +1987,15 @@ def cls_head_workspace_bytes(n: int, c: int, t: int, v: int, f: int, l: int) -> 
 
 
 def cls_head_fwd(h: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
-                 labels: Optional[torch.Tensor] = None, slope: float = 0.2) -> dict:
+                 labels: Optional[torch.Tensor] = None, slope: float = 0.2, feat_out: Optional[torch.Tensor] = None,
+                 pred_out: Optional[torch.Tensor] = None) -> dict:
     """Global average pool -> fc1 + LeakyReLU -> fcn -> argmax and, with ``labels`` (N,) int64, the softmax cross-entropy
     (kg_cls_head_fwd; no host synchronisation).  Returns dict(pooled (N, C), feat (N, F), logits (N, L), pred (N,) int32) and
-    with labels loss_per_sample (N,), loss (0-d), correct (0-d int32); else those three are None."""
+    with labels loss_per_sample (N,), loss (0-d), correct (0-d int32); else those three are None.  ``feat_out`` (N, F) fp32 /
+    ``pred_out`` (N,) int32: contiguous row slices of larger (N_total, F) / (N_total,) buffers that the launch writes - and
+    the dict returns - instead of fresh tensors: the chunks of a large set land in one feature matrix."""
     lib = load_library()
-    _need_cuda(h, w1, b1, w2, b2, labels)
+    _need_cuda(h, w1, b1, w2, b2, labels, feat_out, pred_out)
     f, l = w1.shape[0], w2.shape[0]
     a = _cls_head_args(*h.shape, f, l, slope)
     h = _bind(a, "h", "h", h, True)
@@ -1987,10 +2003,16 @@ def cls_head_fwd(h: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.
     a.w1, a.b1 = _cls_flat(w1, f * c, torch.float32, "w1").data_ptr(), _cls_flat(b1, f, torch.float32, "b1").data_ptr()
     a.w2, a.b2 = _cls_flat(w2, l * f, torch.float32, "w2").data_ptr(), _cls_flat(b2, l, torch.float32, "b2").data_ptr()
     dev = h.device
+    if feat_out is not None and tuple(feat_out.shape) != (n, f):
+        raise ValueError(f"kg_cls_head: feat_out must be ({n}, {f}), got {tuple(feat_out.shape)}")
+    if pred_out is not None and tuple(pred_out.shape) != (n,):
+        raise ValueError(f"kg_cls_head: pred_out must be ({n},), got {tuple(pred_out.shape)}")
     out = dict(pooled=torch.empty((n, c), dtype=torch.float32, device=dev),
-               feat=torch.empty((n, f), dtype=torch.float32, device=dev),
+               feat=torch.empty((n, f), dtype=torch.float32, device=dev) if feat_out is None
+               else _cls_flat(feat_out, n * f, torch.float32, "feat_out"),
                logits=torch.empty((n, l), dtype=torch.float32, device=dev),
-               pred=torch.empty(n, dtype=torch.int32, device=dev),
+               pred=torch.empty(n, dtype=torch.int32, device=dev) if pred_out is None
+               else _cls_flat(pred_out, n, torch.int32, "pred_out"),
                loss_per_sample=None, loss=None, correct=None)
     a.pooled, a.feat, a.logits, a.pred = (out[k].data_ptr() for k in ("pooled", "feat", "logits", "pred"))
     if labels is not None:
@@ -2040,6 +2062,54 @@ def cls_head_wgrad(ws: torch.Tensor, pooled: torch.Tensor, feat: torch.Tensor, n
         raise ValueError("kg_cls_head_wgrad: the workspace of cls_head_bwd expected")
     a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
     _check(lib.kg_cls_head_wgrad(C.byref(a), _stream()), "kg_cls_head_wgrad")
+
+
+def cls_scores(feats: Sequence[torch.Tensor], preds: Sequence[torch.Tensor], labels: torch.Tensor, div_pairs: torch.Tensor,
+               mm_pairs: torch.Tensor, n_classes: int) -> dict:
+    """Accuracy, per-class counts, diversity and multimodality of 1..CLS_MAX_SETS sets in ONE kg_cls_scores call (two
+    launches, no host synchronisation, the same bits on every call).  ``feats``: (N, F) fp32 with unit column
+    stride and one shared row stride (row slices of a wider matrix are read in place); ``preds``: (N,) int32; shared by the
+    sets: ``labels`` (N,) int64, ``div_pairs`` (Sd, 2) and ``mm_pairs`` (n_classes * Sl, 2) int32 row indices
+    (metrics.cls_pair_tables).  Returns device tensors: scores (S, 3) fp32 and scores64 (S, 3) fp64 = [accuracy, diversity,
+    multimodality], correct (S,) int32, correct_per_class (S, K) int32, count_per_class (K,) int32, dist (S, Sd + K Sl) fp64."""
+    lib = load_library()
+    feats, preds, k = list(feats), list(preds), int(n_classes)
+    s = len(feats)
+    if len(preds) != s:
+        raise ValueError(f"kg_cls_scores: {s} feature sets, {len(preds)} prediction vectors")
+    if not 1 <= s <= CLS_MAX_SETS:       # (the library says so too; feats[0] below needs one set)
+        raise ValueError(f"kg_cls_scores: nsets={s} outside [1, {CLS_MAX_SETS}]")
+    _need_cuda(labels, div_pairs, mm_pairs, *feats, *preds)
+    n, f = feats[0].shape
+    ld = feats[0].stride(0) if n > 1 else max(f, feats[0].stride(0))
+    for t in feats:
+        if t.dtype != torch.float32 or tuple(t.shape) != (n, f) or (f > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) != ld):
+            raise ValueError(f"kg_cls_scores: every feature set must be fp32 ({n}, {f}) with unit column stride and row stride {ld}")
+    preds = [_cls_flat(t, n, torch.int32, "pred") for t in preds]
+    labels = _cls_flat(labels, n, torch.int64, "labels")
+    if div_pairs.dim() != 2 or div_pairs.shape[1] != 2 or mm_pairs.dim() != 2 or mm_pairs.shape[1] != 2 \
+            or mm_pairs.shape[0] % max(k, 1):
+        raise ValueError("kg_cls_scores: div_pairs (Sd, 2) and mm_pairs (n_classes * Sl, 2) expected")
+    sd, sl = div_pairs.shape[0], mm_pairs.shape[0] // max(k, 1)
+    div_pairs = _cls_flat(div_pairs, 2 * sd, torch.int32, "div_pairs")
+    mm_pairs = _cls_flat(mm_pairs, 2 * k * sl, torch.int32, "mm_pairs")
+    dev = feats[0].device
+    out = dict(scores=torch.empty((s, 3), dtype=torch.float32, device=dev),
+               scores64=torch.empty((s, 3), dtype=torch.float64, device=dev),
+               correct=torch.empty(s, dtype=torch.int32, device=dev),
+               correct_per_class=torch.empty((s, max(k, 1)), dtype=torch.int32, device=dev),
+               count_per_class=torch.empty(max(k, 1), dtype=torch.int32, device=dev),
+               dist=torch.empty((s, max(1, sd + k * sl)), dtype=torch.float64, device=dev))
+    a = _ClsScoresArgs()
+    a.nsets, a.N, a.F, a.K, a.Sd, a.Sl, a.feat_ld = s, n, f, k, sd, sl, ld
+    for g in range(s):
+        a.feat[g], a.pred[g] = feats[g].data_ptr(), preds[g].data_ptr()
+    a.labels, a.div_pairs, a.mm_pairs = labels.data_ptr(), div_pairs.data_ptr(), mm_pairs.data_ptr()
+    for key in ("dist", "scores64", "scores", "correct", "correct_per_class", "count_per_class"):
+        setattr(a, key, out[key].data_ptr())
+    _count("kg_cls_scores", 3.0 * s * (sd + k * sl) * f)
+    _check(lib.kg_cls_scores(C.byref(a), _stream()), "kg_cls_scores")
+    return out
 
 
 def _label_bias_args(labels, emb, wg, K, C_out, cin, J, ak):

@@ -160,3 +160,25 @@ class Classifier(_GraphModule):
 
     def features(self, x):
         return self.classify(x)["features"]
+
+
+def load_classifier(path, device):
+    """(Classifier on ``device``, meta) from a ``classifier_<n>.pth`` of tools/train_classifier.py: the state dict plus
+    ``meta`` - in_channels, n_classes, t_size, latent, feat_dim, dataset and the training set's normalisation (scale, shift)"""
+    sd = torch.load(path, weights_only=False)
+    meta = sd.pop("meta")
+    clf = Classifier(meta["in_channels"], meta["n_classes"], meta["t_size"], latent=meta["latent"], feat_dim=meta["feat_dim"],
+                     dataset=meta["dataset"])
+    clf.load_state_dict(sd)
+    return clf.to(device), meta
+
+
+META_MUST_AGREE = ("dataset", "n_classes", "in_channels", "t_size", "scale", "shift")
+
+
+def check_classifier_meta(meta: dict, run: dict) -> None:
+    """ValueError unless the checkpoint's ``meta`` agrees with the run's ``dataset``, ``n_classes``, ``in_channels``, ``t_size``
+    and the Feeder's ``scale`` / ``shift``: a classifier trained on another normalisation scores garbage silently"""
+    bad = {k: (meta.get(k), run[k]) for k in META_MUST_AGREE if k not in meta or meta[k] != run[k]}
+    if bad:
+        raise ValueError("the classifier checkpoint disagrees with the run (checkpoint, run): %s" % bad)

@@ -4,6 +4,9 @@
 //                       per KG_CLS_TILE samples, then ONE workgroup for the batch mean of the loss and the correct count
 //   kg_cls_head_bwd     softmax cross-entropy, fcn^T, LeakyReLU', fc1^T and the trunk's top gradient, same tiles
 //   kg_cls_head_wgrad   the four parameter gradients: one thread per output element, summed over the samples in index order
+//   kg_cls_scores       accuracy, per-class counts, diversity and multimodality of up to KG_CLS_MAX_SETS sets:
+//                       a wave per (set, pair) for the fp64 feature distances, then ONE workgroup per set for the tallies
+//                       (integer adds in LDS) and the two means (one thread, index order)
 //
 // Latency bound (fc1.weight, 128 KB at the default sizes, is the largest operand).  Deterministic: every output element has
 // one owner, workgroups exchange nothing inside a launch - no tickets, no atomics, no polled words.
@@ -280,6 +283,94 @@ __global__ __launch_bounds__(NT) void kg_cls_head_wgrad_kernel(const KgClsHeadAr
     *out = (a.accumulate ? *out : 0.f) + s;
 }
 
+// dist[s, p] of the pair p (the diversity table, then the multimodality table): one wave, the lanes strided over the features
+__global__ __launch_bounds__(NT) void kg_cls_dist_kernel(const KgClsScoresArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int npairs = a.Sd + a.K * a.Sl;
+    const long wp = (long)blockIdx.x * NW + (threadIdx.x >> 6);       // (wave-uniform)
+    if (wp >= (long)a.nsets * npairs) return;
+    const int s = (int)(wp / npairs), p = (int)(wp - (long)s * npairs);
+    const int32_t* pr = p < a.Sd ? a.div_pairs + 2 * (long)p : a.mm_pairs + 2 * (long)(p - a.Sd);
+    const int i = pr[0], j = pr[1];
+    double d = NAN;
+    if (i >= 0 && i < a.N && j >= 0 && j < a.N) {
+        const float* fs = a.feat[0];
+#pragma unroll
+        for (int q = 1; q < KG_CLS_MAX_SETS; ++q)
+            if (s == q) fs = a.feat[q];
+        const float* x = fs + (long)i * a.feat_ld;
+        const float* y = fs + (long)j * a.feat_ld;
+        double acc = 0.0;
+        for (int f = lane; f < a.F; f += 64) {
+            const double t = (double)x[f] - (double)y[f];
+            acc = fma(t, t, acc);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        d = sqrt(acc);
+    }
+    if (lane == 0) a.dist[wp] = d;
+}
+
+// set s = blockIdx.x: the integer tallies (LDS counters: integer addition does not depend on the order), then thread 0 adds
+// the set's distances in index order - staged through LDS a tile at a time - and divides once per mean
+__global__ __launch_bounds__(NT) void kg_cls_scores_finish_kernel(const KgClsScoresArgs a) {
+    constexpr int DT = 1024;
+    __shared__ int cor_s[MAXL];
+    __shared__ int cnt_s[MAXL];
+    __shared__ int tot_s[NW];
+    __shared__ double tile_s[DT];
+    const int tid = threadIdx.x, s = blockIdx.x, K = a.K, N = a.N;
+    const int32_t* pred = a.pred[0];
+#pragma unroll
+    for (int q = 1; q < KG_CLS_MAX_SETS; ++q)
+        if (s == q) pred = a.pred[q];
+    for (int c = tid; c < K; c += NT) { cor_s[c] = 0; cnt_s[c] = 0; }
+    __syncthreads();
+    int cnt = 0;
+    for (int n = tid; n < N; n += NT) {
+        const long y = a.labels[n];
+        if (y >= 0 && y < (long)K) {
+            atomicAdd(&cnt_s[y], 1);
+            if ((long)pred[n] == y) { atomicAdd(&cor_s[y], 1); ++cnt; }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    if ((tid & 63) == 0) tot_s[tid >> 6] = cnt;
+    __syncthreads();
+    for (int c = tid; c < K; c += NT) {
+        a.correct_per_class[(long)s * K + c] = cor_s[c];
+        if (s == 0) a.count_per_class[c] = cnt_s[c];
+    }
+    const int npairs = a.Sd + K * a.Sl;
+    const double* dist = a.dist + (long)s * npairs;
+    double sd = 0.0, sm = 0.0;
+    for (int p0 = 0; p0 < npairs; p0 += DT) {
+        const int np = min(DT, npairs - p0);
+        __syncthreads();
+        for (int p = tid; p < np; p += NT) tile_s[p] = dist[p0 + p];
+        __syncthreads();
+        if (tid == 0) {
+            const int nd = max(0, min(np, a.Sd - p0));       // the tile's diversity pairs come first
+#pragma unroll 8
+            for (int p = 0; p < nd; ++p) sd += tile_s[p];
+#pragma unroll 8
+            for (int p = nd; p < np; ++p) sm += tile_s[p];
+        }
+    }
+    if (tid != 0) return;
+    int total = 0;
+    for (int w = 0; w < NW; ++w) total += tot_s[w];
+    a.correct[s] = total;
+    const double sc[3] = {(double)total / (double)N, sd / (double)a.Sd, sm / (double)(K * a.Sl)};
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        a.scores64[s * 3 + q] = sc[q];
+        a.scores[s * 3 + q] = (float)sc[q];
+    }
+}
+
 int validate_cls(const KgClsHeadArgs* a, const char* who) {
     KG_REQUIRE(a != nullptr, "%s: null args", who);
     KG_REQUIRE(a->N >= 1, "%s: N=%d < 1", who, a->N);
@@ -333,4 +424,26 @@ extern "C" int kg_cls_head_wgrad(const KgClsHeadArgs* a, void* stream) {
     const long total = (long)a->F * a->C + a->F + (long)a->L * a->F + a->L;
     hipLaunchKernelGGL(kg_cls_head_wgrad_kernel, dim3(kg_cdiv(total, NT)), dim3(NT), 0, (hipStream_t)stream, *a);
     return kg_launch_status("kg_cls_head_wgrad");
+}
+
+extern "C" int kg_cls_scores(const KgClsScoresArgs* a, void* stream) {
+    const char* who = "kg_cls_scores";
+    KG_REQUIRE(a != nullptr, "%s: null args", who);
+    KG_REQUIRE(a->nsets >= 1 && a->nsets <= KG_CLS_MAX_SETS, "%s: nsets=%d outside [1, %d]", who, a->nsets, KG_CLS_MAX_SETS);
+    KG_REQUIRE(a->N >= 1, "%s: N=%d < 1", who, a->N);
+    KG_REQUIRE(a->F >= 1 && a->F <= MAXF, "%s: F=%d outside [1, %d]", who, a->F, MAXF);
+    KG_REQUIRE(a->K >= 1 && a->K <= MAXL, "%s: K=%d outside [1, %d]", who, a->K, MAXL);
+    KG_REQUIRE(a->Sd >= 1 && a->Sl >= 1, "%s: Sd=%d / Sl=%d < 1", who, a->Sd, a->Sl);
+    KG_REQUIRE(a->feat_ld >= a->F, "%s: feat_ld=%lld < F=%d", who, (long long)a->feat_ld, a->F);
+    const long npairs = (long)a->Sd + (long)a->K * a->Sl;
+    KG_REQUIRE((long)a->K * a->Sl < (1L << 31) && (long)a->nsets * npairs < (1L << 31), "%s: too many pairs", who);
+    for (int s = 0; s < a->nsets; ++s) KG_REQUIRE(a->feat[s] && a->pred[s], "%s: null operand (set %d)", who, s);
+    KG_REQUIRE(a->labels && a->div_pairs && a->mm_pairs, "%s: null operand", who);
+    KG_REQUIRE(a->dist && a->scores64 && a->scores && a->correct && a->correct_per_class && a->count_per_class,
+               "%s: null output", who);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(kg_cls_dist_kernel, dim3(kg_cdiv((long)a->nsets * npairs, NW)), dim3(NT), 0, st, *a);
+    if (int rc = kg_launch_status("kg_cls_scores (dist)")) return rc;
+    hipLaunchKernelGGL(kg_cls_scores_finish_kernel, dim3(a->nsets), dim3(NT), 0, st, *a);
+    return kg_launch_status("kg_cls_scores");
 }

@@ -30,6 +30,15 @@ count, else a round of its own -, read in place by ONE kg_frechet_sets call per 
 against the real side's cache, which kg_frechet_real computed once per mode at construction.  The record then ends with
 ``"<g>/pose_fd"`` / ``"<g>/motion_fd"`` per generator (smaller is better) and goes through kg_eval_record2.
 
+With ``classifier`` and ``classifier_per_class > 0`` it also scores the Action2Motion / ACTOR protocol in
+the feature space of a trained ``classifier.Classifier``: a round of ``classifier_per_class`` samples per class from every
+generator - the PRDC or Frechet round when one has the same count, else a round of its own - goes through the
+classifier's trunk and head in chunks of ``classifier_batch`` (plane slices read in place, features and predictions
+written into static matrices), then ONE kg_frechet_sets call against the real features' cache and ONE kg_cls_scores call
+for all generators.  The record then ends with ``"<g>/accuracy"`` (larger is better), ``"<g>/feature_fd"`` (smaller is
+better), ``"<g>/diversity"`` and ``"<g>/multimodality"`` (closer to the real set's value - ``classifier_real`` - is
+better: recorded, never selected by) per generator.
+
 Nothing synchronises the host; everything is read through pointers when the launches run, so the captured evaluation
 follows the training replays in between.  ``records()``, ``best()`` and ``state_dict()`` read the device; the Evaluator
 never writes to a generator.  Definitions the tests pin this against: tests/eval_def.py.
@@ -69,19 +78,30 @@ def default_select(names: Sequence[str], modes: Sequence[str]) -> str:
     return "%s/%s" % (gen, mode)
 
 
+NO_SENSE = ("diversity", "multimodality")      # closer to the real set's value is better: neither direction is
+
+
 def score_sense(name: str) -> str:
-    """``"max"`` for precision / recall / density / coverage (larger is better), ``"min"`` for the MMD modes"""
-    return "max" if str(name).rsplit("/", 1)[-1] in metrics.PRDC_NAMES else "min"
+    """``"max"`` for precision / recall / density / coverage and accuracy (larger is better), ``"min"`` for the MMD modes and
+    every Frechet distance; ValueError for diversity / multimodality, which have no better direction"""
+    last = str(name).rsplit("/", 1)[-1]
+    if last in NO_SENSE:
+        raise ValueError("score_sense: %r is better the closer it is to the real set's value: it cannot decide a selection" % (name,))
+    return "max" if last in metrics.PRDC_NAMES or last == "accuracy" else "min"
 
 
-def score_names(generators: Sequence[str], modes: Sequence[str], prdc: bool = False, frechet: Sequence[str] = ()) -> list:
+def score_names(generators: Sequence[str], modes: Sequence[str], prdc: bool = False, frechet: Sequence[str] = (),
+                classifier: bool = False) -> list:
     """The record's columns: ``"<g>/<mode>"`` generator by generator, then - with precision / recall / density / coverage
     on - ``"<g>/<name>"`` generator by generator in the order of ``metrics.PRDC_NAMES``, then - with the Frechet modes
-    ``frechet`` (of ``metrics.FRECHET_MODES``) - ``"<g>/pose_fd"`` and / or ``"<g>/motion_fd"`` generator by generator"""
+    ``frechet`` (of ``metrics.FRECHET_MODES``) - ``"<g>/pose_fd"`` and / or ``"<g>/motion_fd"`` generator by generator, then -
+    with ``classifier`` - ``"<g>/<name>"`` generator by generator in the order of ``metrics.CLS_NAMES``"""
     names = ["%s/%s" % (g, m) for g in generators for m in modes]
     if prdc:
         names += ["%s/%s" % (g, q) for g in generators for q in metrics.PRDC_NAMES]
     names += ["%s/%s_fd" % (g, f) for g in generators for f in frechet]
+    if classifier:
+        names += ["%s/%s" % (g, q) for g in generators for q in metrics.CLS_NAMES]
     return names
 
 
@@ -129,15 +149,22 @@ class Evaluator:
     ``prdc_per_class`` (0: off): also score precision / recall / density / coverage with ``prdc_k`` neighbours on that many
     fake and real samples per class (``"<generator>/precision"`` ...; ``select`` may name one of them: larger is better).
     ``frechet_per_class`` (0: off): also score the Frechet distance of the ``frechet_modes`` (``"pose"``, ``"motion"``) on
-    that many fake and real samples per class (``"<generator>/pose_fd"``, ``"<generator>/motion_fd"``; smaller is better)."""
+    that many fake and real samples per class (``"<generator>/pose_fd"``, ``"<generator>/motion_fd"``; smaller is better).
+    ``classifier`` (a trained ``classifier.Classifier``; None or ``classifier_per_class`` 0: off): also score accuracy, feature
+    Frechet distance, diversity (``diversity_pairs`` pairs) and multimodality (``multimodality_pairs`` pairs per class) on that
+    many fake and real samples per class, features computed in chunks of ``classifier_batch``; ``classifier_real`` then holds
+    the real set's own values.  The Evaluator never writes to the classifier and never changes its mode."""
 
     def __init__(self, generators: Dict[str, torch.nn.Module], real, real_labels=None, pairs: int = 10,
                  modes: Sequence[str] = ("avg", "joint"), select: Optional[str] = None, seed: int = 0,
                  trunc: Optional[float] = None, trunc_mode: str = "-", iteration: Optional[torch.Tensor] = None,
                  ring_len: int = 1024, use_graph: bool = True, t_size: Optional[int] = None, prdc_per_class: int = 0,
-                 prdc_k: int = 5, frechet_per_class: int = 0, frechet_modes: Sequence[str] = ("pose", "motion")):
+                 prdc_k: int = 5, frechet_per_class: int = 0, frechet_modes: Sequence[str] = ("pose", "motion"),
+                 classifier=None, classifier_per_class: int = 0, classifier_batch: int = 512, diversity_pairs: int = 200,
+                 multimodality_pairs: int = 20):
         if not generators:
             raise ValueError("Evaluator: at least one generator")
+        self._check_classifier_options(classifier, classifier_per_class, classifier_batch, diversity_pairs, multimodality_pairs)
         self._check_frechet_options(frechet_per_class, frechet_modes)
         self._check_prdc_options(prdc_per_class, prdc_k)
         self.modes = tuple(modes)
@@ -146,8 +173,10 @@ class Evaluator:
         if not self.modes:
             raise ValueError("Evaluator: at least one mode")
         self.gens = dict(generators)
-        self.names = score_names(list(self.gens), self.modes, bool(self.prdc_per_class), self.frechet_modes)
-        most = nv.EVAL2_MAX_SCORES if self.prdc_per_class or self.frechet_per_class else nv.EVAL_MAX_SCORES
+        self.names = score_names(list(self.gens), self.modes, bool(self.prdc_per_class), self.frechet_modes,
+                                 bool(self.classifier_per_class))
+        self._record2 = bool(self.prdc_per_class or self.frechet_per_class or self.classifier_per_class)
+        most = nv.EVAL2_MAX_SCORES if self._record2 else nv.EVAL_MAX_SCORES
         if len(self.names) > most:
             raise ValueError("Evaluator: %d scores, at most %d fit one record" % (len(self.names), most))
         self.select = default_select(list(self.gens), self.modes) if select is None else str(select)
@@ -179,6 +208,10 @@ class Evaluator:
             self._frechet_setup(real, real_labels, t_size, trunc, trunc_mode)
         else:
             self.frechet_samplers, self.frechet_real, self.frechet_cache = {}, None, {}
+        if self.classifier_per_class:
+            self._classifier_setup(real, real_labels, t_size, trunc, trunc_mode)
+        else:
+            self.cls_samplers, self.classifier_real = {}, None
         # the real side, once: row j*K + c = the j-th selected real sample of class c (the Sampler's label order)
         self.real = torch.as_tensor(self._select_real(real, real_labels, self.pairs, "pairs", t_size)).to(dev)
         self._pair_labels = np.arange(self.n)                  # every (fake, real) pair is a "class" of the kg_mmd call
@@ -223,6 +256,17 @@ class Evaluator:
         self.frechet_modes = tuple(f for f in metrics.FRECHET_MODES if f in tuple(frechet_modes)) if self.frechet_per_class else ()
         if self.frechet_per_class and (not self.frechet_modes or set(frechet_modes) - set(metrics.FRECHET_MODES)):
             raise ValueError("Evaluator: frechet_modes %r: one or more of %s" % (tuple(frechet_modes), metrics.FRECHET_MODES))
+
+    def _check_classifier_options(self, classifier, per_class, batch, diversity_pairs, multimodality_pairs):
+        self.classifier_per_class = int(per_class) if classifier is not None else 0
+        if int(per_class) < 0:
+            raise ValueError("Evaluator: classifier_per_class=%d < 0" % int(per_class))
+        self.classifier = classifier if self.classifier_per_class else None
+        self.classifier_batch = int(batch)
+        self.diversity_pairs, self.multimodality_pairs = int(diversity_pairs), int(multimodality_pairs)
+        if self.classifier_per_class and (self.classifier_batch < 1 or self.diversity_pairs < 1 or self.multimodality_pairs < 1):
+            raise ValueError("Evaluator: classifier_batch=%d, diversity_pairs=%d, multimodality_pairs=%d must be >= 1" % (
+                self.classifier_batch, self.diversity_pairs, self.multimodality_pairs))
 
     def _check_prdc_options(self, prdc_per_class, prdc_k):
         self.prdc_per_class, self.prdc_k = int(prdc_per_class), int(prdc_k)
@@ -343,6 +387,99 @@ class Evaluator:
             per_mode[f] = words
         return [per_mode[f][g] for g in range(len(outs)) for f in self.frechet_modes]
 
+    # ---- accuracy / feature FD / diversity / multimodality of a trained classifier ------------------------
+    def _classifier_features(self, x, feat, pred):
+        """the rows of x (n, C, T, V) through the classifier's trunk and head in chunks of ``classifier_batch``: plane slices
+        read in place, features and predictions written into their rows of feat (n, F) / pred (n,); no autograd, no tape"""
+        clf = self.classifier
+        w = [p.detach() for p in (clf.fc1.weight, clf.fc1.bias, clf.fcn.weight, clf.fcn.bias)]
+        with torch.no_grad():
+            for lo in range(0, x.shape[0], self.classifier_batch):
+                hi = min(x.shape[0], lo + self.classifier_batch)
+                nv.cls_head_fwd(clf._trunk(x[lo:hi]), *w, None, feat_out=feat[lo:hi], pred_out=pred[lo:hi])
+
+    def _classifier_setup(self, real, real_labels, t_size, trunc, trunc_mode):
+        """the checks; the real side, once: ``classifier_per_class`` samples of every class, class by class, their features
+        as ONE set through kg_frechet_real (the unconditional feature FD of ``metrics.classifier_scores``) and their own
+        accuracy / diversity / multimodality (``classifier_real``; deterministic, so not part of the state); the generators'
+        pair tables from the Sampler's label vector; per generator a Sampler - unless a PRDC or Frechet round of the same
+        count exists and is read instead - and static feature / prediction buffers"""
+        clf, dev, K, P = self.classifier, self.device, self.n_classes, self.classifier_per_class
+        F = int(clf.feat_dim)
+        if int(clf.n_classes) != K:
+            raise ValueError("Evaluator: the classifier has %d classes, the generators %d" % (int(clf.n_classes), K))
+        if next(clf.parameters()).device != dev:
+            raise ValueError("Evaluator: the classifier is on %s, the generators on %s" % (next(clf.parameters()).device, dev))
+        if not 1 <= F <= nv.FRECHET_MAX_DIM:
+            raise ValueError("Evaluator: the classifier's feat_dim=%d outside [1, %d]" % (F, nv.FRECHET_MAX_DIM))
+        if self.diversity_pairs > K * P or self.multimodality_pairs > P:
+            raise ValueError("Evaluator: diversity_pairs=%d above K*P=%d or multimodality_pairs=%d above P=%d" % (
+                self.diversity_pairs, K * P, self.multimodality_pairs, P))
+        real_x = torch.as_tensor(self._select_real(real, real_labels, P, "classes", t_size)).to(dev)       # (K*P, C, t, V)
+        _, C, T, V = real_x.shape
+        c_in = int(clf.st_gcn_networks[0].in_channels)
+        if c_in != C or int(clf.t_size) != T:
+            raise ValueError("Evaluator: the classifier takes (%d channels, %d frames), the samples have (%d, %d)" % (
+                c_in, int(clf.t_size), C, T))
+        self._cls_shape = tuple(real_x.shape)
+        if self.prdc_per_class == P:
+            self._cls_shared, self.cls_samplers = "prdc", {}
+        elif self.frechet_per_class == P:        # (not shared with PRDC, else the branch above: Samplers of its own)
+            self._cls_shared, self.cls_samplers = "frechet", {}
+        else:
+            self._cls_shared = None
+            self.cls_samplers = {k: Sampler(G, qtd=P, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False)
+                                 for k, G in self.gens.items()}
+        n = K * P
+        lab_gen = np.tile(np.arange(K), P)               # the Sampler's label vector: row j*K + c has class c
+        lab_real = np.repeat(np.arange(K), P)
+        self._cls_labels = torch.as_tensor(lab_gen, dtype=torch.int64).to(dev)
+        self._cls_tables = tuple(torch.as_tensor(t).to(dev) for t in metrics.cls_pair_tables(
+            lab_gen, K, self.diversity_pairs, self.multimodality_pairs, self.seed))
+        self._cls_feat = {k: torch.zeros((n, F), dtype=torch.float32, device=dev) for k in self.gens}
+        self._cls_pred = {k: torch.zeros(n, dtype=torch.int32, device=dev) for k in self.gens}
+        with torch.cuda.device(dev):
+            feat_r = torch.zeros((n, F), dtype=torch.float32, device=dev)
+            pred_r = torch.zeros(n, dtype=torch.int32, device=dev)
+            self._classifier_features(real_x, feat_r, pred_r)
+            self._cls_cache = nv.frechet_real(nv.FrechetView(feat_r, 0, F, 0, 0), n, 1, False, 1, F, 1)
+            tabs = [torch.as_tensor(t).to(dev) for t in metrics.cls_pair_tables(
+                lab_real, K, self.diversity_pairs, self.multimodality_pairs, self.seed)]
+            res = nv.cls_scores([feat_r], [pred_r], torch.as_tensor(lab_real, dtype=torch.int64).to(dev), *tabs, K)
+            self.classifier_real = {"accuracy": res["scores64"][0, 0], "diversity": res["scores64"][0, 1],
+                                    "multimodality": res["scores64"][0, 2], "correct_per_class": res["correct_per_class"][0],
+                                    "features": feat_r}
+            sets = min(len(self.gens), nv.FRECHET_MAX_SETS)
+            self._cls_ws = torch.empty(nv.frechet_sets_workspace_bytes(sets, n, 1, False, 1, F, 1) // 8, dtype=torch.float64,
+                                       device=dev)
+
+    def _classifier_scores(self):
+        """the classifier rounds of all generators (a PRDC / Frechet round of the same count when one exists), their features;
+        then per group of generators ONE kg_frechet_sets and ONE kg_cls_scores: the score words are one-element views of
+        mean32 and scores - per generator in the order of metrics.CLS_NAMES"""
+        K, P = self.n_classes, self.classifier_per_class
+        n, F = K * P, int(self.classifier.feat_dim)
+        if self._cls_shared == "prdc":
+            rounds = [s._out for s in self.prdc_samplers.values()]
+        elif self._cls_shared == "frechet":
+            rounds = [s._out for s in self.frechet_samplers.values()]
+        else:
+            rounds = self.cls_samplers.values()
+        outs, _, _ = self._checked_rounds(rounds, self._cls_shape)
+        keys = list(self.gens)
+        for k, out in zip(keys, outs):
+            self._classifier_features(out, self._cls_feat[k], self._cls_pred[k])
+        most = min(nv.FRECHET_MAX_SETS, nv.CLS_MAX_SETS)
+        words = []
+        for q in range(0, len(keys), most):
+            feats = [self._cls_feat[k] for k in keys[q:q + most]]
+            preds = [self._cls_pred[k] for k in keys[q:q + most]]
+            fd = nv.frechet_sets(self._cls_cache, feats, 0, F, 0, 0, n, 1, False, 1, F, 1, ws=self._cls_ws)
+            sc = nv.cls_scores(feats, preds, self._cls_labels, *self._cls_tables, K)
+            for g in range(len(feats)):
+                words += [sc["scores"][g, 0:1], fd["mean32"][g:g + 1], sc["scores"][g, 1:2], sc["scores"][g, 2:3]]
+        return words
+
     # ---- the launch sequence -------------------------------------------------------------------------------------------
     def _round(self):
         """what a graph holds: per generator a Sampler round, the re-layout, kg_mmd per mode; then the record, then the
@@ -360,7 +497,9 @@ class Evaluator:
             scores += self._prdc_scores()
         if self.frechet_per_class:
             scores += self._frechet_scores()
-        if self.prdc_per_class or self.frechet_per_class:
+        if self.classifier_per_class:
+            scores += self._classifier_scores()
+        if self._record2:
             nv.eval_record2(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
                             self.best_iter, self.flag, maximise=self.maximise)
         else:
@@ -375,7 +514,8 @@ class Evaluator:
         return ts + list(self.snap_buffers.values())
 
     def _all_samplers(self):
-        return list(self.samplers.values()) + list(self.prdc_samplers.values()) + list(self.frechet_samplers.values())
+        return list(self.samplers.values()) + list(self.prdc_samplers.values()) + list(self.frechet_samplers.values()) \
+            + list(self.cls_samplers.values())
 
     def _capture(self):
         """Single-stream capture, no parallel branches.  The warm-up rounds in front of it are real evaluations:
@@ -465,6 +605,9 @@ class Evaluator:
             sd["prdc"] = {"per_class": self.prdc_per_class, "k": self.prdc_k}
         if self.frechet_per_class:           # (the real side's cache is recomputed from the data: not part of the state)
             sd["frechet"] = {"per_class": self.frechet_per_class, "modes": list(self.frechet_modes)}
+        if self.classifier_per_class:        # (the classifier's weights are the caller's, the real side is recomputed)
+            sd["classifier"] = {"per_class": self.classifier_per_class, "diversity_pairs": self.diversity_pairs,
+                                "multimodality_pairs": self.multimodality_pairs}
         return sd
 
     def check_compatible(self, sd: dict) -> None:
@@ -476,6 +619,14 @@ class Evaluator:
         theirs = sd.get("frechet")
         if (None if theirs is None else {"per_class": int(dict(theirs)["per_class"]), "modes": list(dict(theirs)["modes"])}) != mine:
             raise ValueError("Evaluator.load_state_dict: frechet is %r in the state, %r here" % (theirs, mine))
+        # (an Evaluator-like object of before the classifier columns has none of these attributes: the option is off)
+        mine = None
+        if getattr(self, "classifier_per_class", 0):
+            mine = {"per_class": self.classifier_per_class, "diversity_pairs": self.diversity_pairs,
+                    "multimodality_pairs": self.multimodality_pairs}
+        theirs = sd.get("classifier")
+        if (None if theirs is None else {k: int(v) for k, v in dict(theirs).items()}) != mine:
+            raise ValueError("Evaluator.load_state_dict: classifier is %r in the state, %r here" % (theirs, mine))
         for k, mine in (("pairs", self.pairs), ("select", self.select), ("modes", list(self.modes)), ("names", list(self.names))):
             if (list(sd[k]) if isinstance(mine, list) else sd[k]) != mine:
                 raise ValueError("Evaluator.load_state_dict: %s is %r in the state, %r here" % (k, sd[k], mine))

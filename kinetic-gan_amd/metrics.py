@@ -364,10 +364,62 @@ def frechet_features(feat_gen, feat_real, labels_gen=None, labels_real=None, per
     return frechet(feat_gen[:, None, None, :], feat_real[:, None, None, :], labels_gen, labels_real, "pose", per_class, moments)
 
 
-def _classifier_pass(clf, x, ids: Optional[np.ndarray], batch: int):
-    """features (N, d) and the correct count (0-d int64 on the device, None without labels) of x in chunks of ``batch``"""
+CLS_NAMES = ("accuracy", "feature_fd", "diversity", "multimodality")
+
+
+def cls_pair_tables(label_ids, n_classes: int, diversity_pairs: int, multimodality_pairs: int, seed: int = 0):
+    """The two pair tables of kg_cls_scores for N samples with class ids ``label_ids`` - Action2Motion's sampling, on the
+    host with numpy only: (div_pairs (Sd, 2), mm_pairs (n_classes * Sl, 2)) int32 row indices.  ONE
+    ``np.random.RandomState(seed)``, drawn in this order:
+
+      1. ``first = choice(N, Sd, replace=False)``, then ``second = choice(N, Sd, replace=False)``: diversity pair p is
+         (first[p], second[p]);
+      2. for every class c = 0 .. n_classes - 1 with its n_c members in index order: ``choice(n_c, Sl, replace=False)``
+         twice, mapped to row indices: multimodality pair c * Sl + q is (first_c[q], second_c[q]).
+
+    The two draws of a pair are independent: a pair may hold the same row twice.  ValueError when Sd > N, when a class has
+    fewer than Sl members or when a label is outside [0, n_classes)."""
+    lab = np.asarray(label_ids).astype(np.int64).reshape(-1)
+    n, k, sd, sl = lab.size, int(n_classes), int(diversity_pairs), int(multimodality_pairs)
+    if k < 1 or sd < 1 or sl < 1:
+        raise ValueError("cls_pair_tables: n_classes=%d, diversity_pairs=%d, multimodality_pairs=%d must be >= 1" % (k, sd, sl))
+    if lab.size and (lab.min() < 0 or lab.max() >= k):
+        raise ValueError("cls_pair_tables: a label outside [0, %d)" % k)
+    if sd > n:
+        raise ValueError("cls_pair_tables: diversity_pairs=%d above the %d samples" % (sd, n))
+    members = [np.flatnonzero(lab == c) for c in range(k)]
+    for c, m in enumerate(members):
+        if m.size < sl:
+            raise ValueError("cls_pair_tables: class %d has %d samples, multimodality_pairs=%d needed" % (c, m.size, sl))
+    rng = np.random.RandomState(int(seed))
+    first = rng.choice(n, sd, replace=False)
+    second = rng.choice(n, sd, replace=False)
+    div = np.stack([first, second], 1).astype(np.int32)
+    mm = np.empty((k * sl, 2), dtype=np.int32)
+    for c, m in enumerate(members):
+        a = rng.choice(m.size, sl, replace=False)
+        b = rng.choice(m.size, sl, replace=False)
+        mm[c * sl:(c + 1) * sl, 0], mm[c * sl:(c + 1) * sl, 1] = m[a], m[b]
+    return div, mm
+
+
+def _classifier_pass(clf, x, ids: Optional[np.ndarray], batch: int, want_pred: bool = False):
+    """features (N, d) and the correct count (0-d int64 on the device, None without labels) of x in chunks of ``batch``;
+    ``want_pred``: (features, pred (N,) int32) instead, every chunk written into its rows of ONE matrix / vector
+    (``cls_head_fwd(feat_out=, pred_out=)``: no cat, no host read, no stock add)"""
     dev = next(clf.parameters()).device
     x = torch.as_tensor(x) if not torch.is_tensor(x) else x
+    if want_pred:
+        n = int(x.shape[0])
+        feat = torch.empty((n, clf.feat_dim), dtype=torch.float32, device=dev)
+        pred = torch.empty(n, dtype=torch.int32, device=dev)
+        with torch.no_grad():
+            for lo in range(0, n, batch):
+                hi = min(n, lo + batch)
+                h = clf._trunk(x[lo:hi].to(dev, dtype=torch.float32))
+                _native.cls_head_fwd(h, clf.fc1.weight.detach(), clf.fc1.bias.detach(), clf.fcn.weight.detach(),
+                                     clf.fcn.bias.detach(), None, feat_out=feat[lo:hi], pred_out=pred[lo:hi])
+        return feat, pred
     feats, correct = [], None
     with torch.no_grad():
         for lo in range(0, x.shape[0], batch):
@@ -382,7 +434,7 @@ def _classifier_pass(clf, x, ids: Optional[np.ndarray], batch: int):
 
 
 def classifier_scores(clf, gen, labels_gen, real, labels_real=None, per_class: Optional[int] = None, batch: int = 512,
-                      class_fd: bool = True) -> dict:
+                      class_fd: bool = True, diversity_pairs: int = 0, multimodality_pairs: int = 0, pair_seed: int = 0) -> dict:
     """The protocol of Action2Motion / ACTOR with a ``classifier.Classifier`` trained on the user's own data:
     ``accuracy`` (and the integer ``correct``) - the recognition accuracy of the generated samples ``gen`` (N, C, T, V)
     against their conditioning labels; ``accuracy_real`` when ``labels_real`` is given; ``feature_fd`` - the Frechet distance
@@ -390,10 +442,21 @@ def classifier_scores(clf, gen, labels_gen, real, labels_real=None, per_class: O
     also ``feature_fd_class_mean`` / ``feature_fd_per_class`` (``frechet_features`` with both label vectors and
     ``per_class``; ``class_fd=False`` leaves these two out).  Labels are one-hot rows or class ids.  Features are computed in chunks of ``batch`` without autograd;
     the Frechet values stay fp64 device tensors, the accuracies are host numbers (one read); ``features_gen`` /
-    ``features_real`` (N, d) are handed back as well."""
+    ``features_real`` (N, d) are handed back as well.
+
+    ``diversity_pairs`` and ``multimodality_pairs`` both above 0: one kg_cls_scores call on the generated set
+    with the tables ``cls_pair_tables(labels_gen, clf.n_classes, ..., pair_seed)`` also gives ``diversity``,
+    ``multimodality`` (0-d fp64), ``correct_per_class`` and ``count_per_class`` (K,) int32, ``pred_gen`` (N,) int32 and
+    ``pair_tables``; with ``labels_real`` a second call with the real set's own tables gives ``diversity_real`` /
+    ``multimodality_real`` - all device tensors, no extra host read."""
     n_g, n_r = int(gen.shape[0]), int(real.shape[0])
     ids_g, _ = _label_ids(labels_gen, n_g, "labels_gen")
     ids_r = None if labels_real is None else _label_ids(labels_real, n_r, "labels_real")[0]
+    sd, sl = int(diversity_pairs), int(multimodality_pairs)
+    if (sd > 0) != (sl > 0) or sd < 0 or sl < 0:
+        raise ValueError("classifier_scores: diversity_pairs=%d and multimodality_pairs=%d: both 0 or both above 0" % (sd, sl))
+    if sd:
+        return _classifier_scores_pairs(clf, gen, ids_g, real, ids_r, per_class, batch, class_fd, sd, sl, int(pair_seed))
     feat_g, cor_g = _classifier_pass(clf, gen, ids_g, batch)
     feat_r, cor_r = _classifier_pass(clf, real, ids_r, batch)
     out = {"correct": int(cor_g), "features_gen": feat_g, "features_real": feat_r}
@@ -405,6 +468,42 @@ def classifier_scores(clf, gen, labels_gen, real, labels_real=None, per_class: O
     if ids_r is not None and class_fd:
         res = frechet_features(feat_g, feat_r, ids_g, ids_r, per_class)
         out["feature_fd_class_mean"], out["feature_fd_per_class"] = res["mean"], res["values"]
+    return out
+
+
+def _classifier_scores_pairs(clf, gen, ids_g, real, ids_r, per_class, batch, class_fd, sd, sl, seed) -> dict:
+    """``classifier_scores`` with the pair counts on: every set goes through the trunk once, its chunks land in one feature
+    matrix and one prediction vector, and ONE kg_cls_scores call per labelled set gives the integer counts and the means"""
+    K = int(clf.n_classes)
+    feat_g, pred_g = _classifier_pass(clf, gen, None, batch, want_pred=True)
+    feat_r, pred_r = _classifier_pass(clf, real, None, batch, want_pred=True)
+    dev = feat_g.device
+
+    def scores(feat, pred, ids):
+        div, mm = cls_pair_tables(ids, K, sd, sl, seed)
+        res = _native.cls_scores([feat], [pred], torch.as_tensor(ids, dtype=torch.int64).to(dev), torch.as_tensor(div).to(dev),
+                                 torch.as_tensor(mm).to(dev), K)
+        return res, (div, mm)
+
+    res_g, tables_g = scores(feat_g, pred_g, ids_g)
+    res_r, tables_r = scores(feat_r, pred_r, ids_r) if ids_r is not None else (None, None)
+    # (the ONE host read: the counts of both sets)
+    counts = torch.cat([res_g["correct"]] + ([] if res_r is None else [res_r["correct"]])).tolist()
+    out = {"correct": int(counts[0]), "features_gen": feat_g, "features_real": feat_r}
+    out["accuracy"] = out["correct"] / float(feat_g.shape[0])
+    if res_r is not None:
+        out["correct_real"] = int(counts[1])
+        out["accuracy_real"] = out["correct_real"] / float(feat_r.shape[0])
+    out["feature_fd"] = frechet_features(feat_g, feat_r)["mean"]
+    if ids_r is not None and class_fd:
+        res = frechet_features(feat_g, feat_r, ids_g, ids_r, per_class)
+        out["feature_fd_class_mean"], out["feature_fd_per_class"] = res["mean"], res["values"]
+    out.update(diversity=res_g["scores64"][0, 1], multimodality=res_g["scores64"][0, 2],
+               correct_per_class=res_g["correct_per_class"][0], count_per_class=res_g["count_per_class"],
+               pred_gen=pred_g, pair_tables=tables_g)
+    if res_r is not None:
+        out.update(diversity_real=res_r["scores64"][0, 1], multimodality_real=res_r["scores64"][0, 2], pred_real=pred_r,
+                   pair_tables_real=tables_r)
     return out
 
 

@@ -122,7 +122,9 @@ class TrainLoop:
                  eval_interval: Optional[int] = None, eval_pairs: int = 10, eval_select: Optional[str] = None,
                  eval_modes=("avg", "joint"), eval_trunc: Optional[float] = None, eval_trunc_mode: str = "-",
                  eval_data: Optional[Feeder] = None, eval_prdc: int = 0, eval_prdc_k: int = 5,
-                 eval_frechet: int = 0, eval_frechet_modes=("pose", "motion")):
+                 eval_frechet: int = 0, eval_frechet_modes=("pose", "motion"), eval_classifier=None,
+                 eval_classifier_samples: int = 0, eval_classifier_batch: int = 512, eval_diversity_pairs: int = 200,
+                 eval_multimodality_pairs: int = 20):
         self.G, self.D = G, D
         self.device = next(G.parameters()).device
         if self.device.type != "cuda":
@@ -194,6 +196,8 @@ class TrainLoop:
         # best-scoring weights there.  Off: no launch, no file, no state key is added.  eval_prdc (0: off):
         # the evaluation also scores precision / recall / density / coverage on that many samples per class.
         # eval_frechet (0: off): and the Frechet distance of eval_frechet_modes on that many samples per class.
+        # eval_classifier (a trained classifier.Classifier) with eval_classifier_samples > 0: and accuracy, feature Frechet
+        # distance, diversity and multimodality on that many samples per class.
         self.eval_interval = int(eval_interval) if eval_interval else None
         self.evaluator = None
         if self.eval_interval:
@@ -205,7 +209,9 @@ class TrainLoop:
                                        select=eval_select, seed=self.seed, trunc=eval_trunc, trunc_mode=eval_trunc_mode,
                                        iteration=self.step_dev, use_graph=self.use_graph, t_size=self.t,
                                        prdc_per_class=eval_prdc, prdc_k=eval_prdc_k, frechet_per_class=eval_frechet,
-                                       frechet_modes=eval_frechet_modes)
+                                       frechet_modes=eval_frechet_modes, classifier=eval_classifier,
+                                       classifier_per_class=eval_classifier_samples, classifier_batch=eval_classifier_batch,
+                                       diversity_pairs=eval_diversity_pairs, multimodality_pairs=eval_multimodality_pairs)
 
     # ---- schedule ------------------------------------------------------------------------------------------------
     @property

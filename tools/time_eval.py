@@ -28,7 +28,13 @@ evaluation replay three ways - with Frechet through kg_frechet_sets (the real si
 from one kg_frechet call per generator and mode (the real moments and the Jacobi solve of S_R repeated every time), and
 without Frechet - alternating in one process: ``--rounds`` rounds, each the median of ``--eval-replays`` event-timed replays
 per variant; spread = max - min of the medians; "faster" only if the gap exceeds the larger spread.
-    python tools/time_eval.py [--rounds 3] [--prdc 100 | --frechet 100] [--log FILE]"""
+``--classifier P`` (record: profiles/eval_classifier_time.log): instead of the above, the cost of scoring accuracy,
+feature Frechet distance, diversity and multimodality under an action classifier (untrained weights: the cost does not depend
+on them) on P samples per class inside an evaluation, at the NTU and the H36M shapes, live + ema.  ONE evaluation replay
+three ways - with the classifier columns (one kg_frechet_sets + one kg_cls_scores for both generators, the real side cached),
+with the same columns composed from one ``metrics.classifier_scores`` call per generator (eager: it reads the host), and
+without them - alternating in one process as under ``--frechet``; then kg_cls_scores alone as a graph of its own.
+    python tools/time_eval.py [--rounds 3] [--prdc 100 | --frechet 100 | --classifier 100] [--log FILE]"""
 import argparse
 import os
 import statistics
@@ -218,6 +224,91 @@ def frechet_part(args, say, dev):
         torch.cuda.empty_cache()
 
 
+def time_calls(fn, n):
+    """ms of each of n eager calls of fn, host synchronisations of its own included (wall clock around a device sync)"""
+    import time
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return ts
+
+
+def classifier_part(args, say, dev):
+    """``--classifier P``: see the module docstring"""
+    from kinetic_gan_amd.classifier import Classifier
+    P = args.classifier
+    for name, c in PRDC_SHAPES:
+        K = c["n_classes"]
+        gens = {}
+        for g, seed in (("live", 1234), ("ema", 4321)):      # two generators of different weights (no training needed here)
+            torch.manual_seed(seed)
+            gens[g] = Generator(c["latent"], c["channels"], K, c["t_size"], c["mlp"], dataset=c["dataset"]).to(dev)
+        torch.manual_seed(99)
+        clf = Classifier(c["channels"], K, c["t_size"], dataset=c["dataset"]).to(dev)
+        rng = np.random.RandomState(0)
+        real = torch.as_tensor((rng.rand(K * P, c["channels"], c["t_size"], c["v"]) * 2 - 1).astype(np.float32))
+        labels = np.tile(np.arange(K), P)
+        sd, sl = min(200, K * P), min(20, P)
+        say("%s shapes: %d classes x %d samples per class of %d frames, feat_dim %d, %d diversity pairs, %d multimodality pairs "
+            "per class, live + ema" % (name, K, P, c["t_size"], clf.feat_dim, sd, sl))
+        on = Evaluator(gens, real, labels, pairs=PAIRS, seed=0, classifier=clf, classifier_per_class=P, diversity_pairs=sd,
+                       multimodality_pairs=sl)
+        off = Evaluator(gens, real, labels, pairs=PAIRS, seed=0)
+        ev = {"with the classifier columns": on, "without them": off}
+        for x in ev.values():
+            x.evaluate()                     # (captures)
+        torch.cuda.synchronize()
+        # the same columns from one metrics.classifier_scores call per generator, on rounds already drawn
+        smp = {g: Sampler(G, qtd=P, seed=0) for g, G in gens.items()}
+        outs = {g: s.next()[0] for g, s in smp.items()}
+        lab_real = np.repeat(np.arange(K), P)
+        real_dev = torch.as_tensor(on._select_real(real, labels, P, "classes", c["t_size"])).to(dev)
+
+        def composed():
+            return [metrics.classifier_scores(clf, o, labels, real_dev, lab_real, class_fd=False, diversity_pairs=sd,
+                                              multimodality_pairs=sl) for o in outs.values()]
+
+        t_round = statistics.median(time_replays(smp["live"]._graph, args.eval_replays))
+        em = {k: [] for k in list(ev) + ["composed"]}
+        for r in range(args.rounds):
+            for k, x in ev.items():
+                ts = time_replays(x._graph, args.eval_replays)
+                x.n_evals += args.eval_replays + 1
+                for s in x._all_samplers():
+                    s.step_count += args.eval_replays + 1
+                em[k].append(statistics.median(ts))
+                say("%s evaluation replay, %-30s round %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
+                    name, k + ",", r, em[k][-1], args.eval_replays, min(ts), max(ts)))
+            ts = time_calls(composed, max(3, args.eval_replays // 3))
+            em["composed"].append(statistics.median(ts))
+            say("%s metrics.classifier_scores per generator (2 calls, eager, real side recomputed), round %d: median %.4f ms over %d "
+                "calls (min %.4f, max %.4f)" % (name, r, em["composed"][-1], len(ts), min(ts), max(ts)))
+        m = {k: statistics.median(v) for k, v in em.items()}
+        sp = {k: max(v) - min(v) for k, v in em.items()}
+        a, b = list(ev)
+        say("%s evaluation replay: %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f): the classifier columns cost %+.4f ms; "
+            "two Sampler rounds of %d samples are %.4f ms of that" % (name, a, m[a], sp[a], b, m[b], sp[b], m[a] - m[b], K * P,
+                                                                     2 * t_round))
+        say("%s the same columns from metrics.classifier_scores, one call per generator, without the rounds: %.4f ms (spread %.4f)" % (
+            name, m["composed"], sp["composed"]))
+        # kg_cls_scores alone
+        feats, preds = list(on._cls_feat.values()), list(on._cls_pred.values())
+        g = _capture(lambda: nv.cls_scores(feats, preds, on._cls_labels, *on._cls_tables, K))
+        meds = [statistics.median(time_replays(g, args.replays)) for _ in range(args.reps)]
+        say("%s kg_cls_scores alone (2 sets, N = %d, F = %d, %d pairs; two launches): %.4f ms (median of %d repetitions of %d replays, "
+            "spread %.4f)" % (name, K * P, clf.feat_dim, sd + K * sl, statistics.median(meds), args.reps, args.replays,
+                              max(meds) - min(meds)))
+        rec = on.records()
+        say("%s last recorded scores: %s" % (name, ", ".join("%s %.6g" % (n, v) for n, v in zip(rec["names"], rec["scores"][-1]))))
+        del ev, on, off, gens, smp, outs, clf, g, composed, real_dev
+        torch.cuda.empty_cache()
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
@@ -227,6 +318,8 @@ def parse_args(argv=None):
     ap.add_argument("--prdc", type=int, default=0, help="samples per class: time the PRDC part of an evaluation instead (DESIGN.md 17)")
     ap.add_argument("--frechet", type=int, default=0,
                     help="samples per class: time the Frechet part of an evaluation instead (DESIGN.md 19)")
+    ap.add_argument("--classifier", type=int, default=0,
+                    help="samples per class: time the classifier columns of an evaluation instead (DESIGN.md 21)")
     ap.add_argument("--eval-replays", type=int, default=30,
                     help="replays of a whole evaluation / a Sampler round under --prdc and --frechet")
     ap.add_argument("--log", default=None, help="also write the lines to this file")
@@ -244,10 +337,12 @@ def main(argv=None):
         print(s, flush=True)
         lines.append(s)
 
-    if args.prdc or args.frechet:
+    if args.prdc or args.frechet or args.classifier:
         say("device %s" % torch.cuda.get_device_name(0))
         if args.prdc:
             prdc_part(args, say, dev)
+        elif args.classifier:
+            classifier_part(args, say, dev)
         else:
             frechet_part(args, say, dev)
         if args.log:

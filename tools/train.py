@@ -12,7 +12,11 @@ inside the loop: writes ``metrics.csv`` and ``models/generator_best.pth``, the w
 ``--eval_prdc N`` also scores precision / recall / density / coverage on N samples per class with ``--eval_prdc_k`` neighbours:
 eight more ``metrics.csv`` columns, and ``--eval_select`` may name one, e.g. ``ema/coverage``; ``--eval_frechet N`` also scores
 the Frechet pose / motion distance on N samples per class, ``--eval_frechet_modes`` choosing between them: up to four more
-columns, and ``--eval_select`` may name one, e.g. ``ema/motion_fd``)."""
+columns, and ``--eval_select`` may name one, e.g. ``ema/motion_fd``; ``--eval_classifier classifier_<n>.pth`` with
+``--eval_classifier_samples N`` also scores accuracy, feature Frechet distance, diversity and multimodality under a classifier
+trained by tools/train_classifier.py on N samples per class - ``--eval_classifier_batch``, ``--eval_diversity_pairs``,
+``--eval_multimodality_pairs``: eight more columns, and ``--eval_select`` may name ``<live|ema>/accuracy`` or
+``<live|ema>/feature_fd``; a checkpoint trained on another dataset, shape or normalisation is refused)."""
 import argparse
 import os
 import sys
@@ -22,10 +26,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import kinetic_gan_amd  # noqa: E402,F401
+from kinetic_gan_amd.classifier import check_classifier_meta, load_classifier  # noqa: E402
 from kinetic_gan_amd.discriminator import Discriminator  # noqa: E402
 from kinetic_gan_amd.feeder import Feeder  # noqa: E402
 from kinetic_gan_amd.generator import Generator  # noqa: E402
-from kinetic_gan_amd.train import TrainLoop  # noqa: E402
+from kinetic_gan_amd.train import TrainLoop, norm_constants  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -64,7 +69,9 @@ def parse_args(argv=None):
     p.add_argument("--eval_select", type=str, default=None,
                    help="the score that picks the best weights, '<live|ema>/<avg|joint>' (default: ema/avg with --ema_decay, else live/avg); "
                         "with --eval_prdc also '<live|ema>/<precision|recall|density|coverage>' (larger is better); "
-                        "with --eval_frechet also '<live|ema>/<pose_fd|motion_fd>' (smaller is better)")
+                        "with --eval_frechet also '<live|ema>/<pose_fd|motion_fd>' (smaller is better); "
+                        "with --eval_classifier also '<live|ema>/accuracy' (larger is better) and '<live|ema>/feature_fd' "
+                        "(smaller is better)")
     p.add_argument("--eval_prdc", type=int, default=0,
                    help="samples per class on which an evaluation also scores precision / recall / density / coverage (0 = off)")
     p.add_argument("--eval_prdc_k", type=int, default=5, help="neighbours of --eval_prdc")
@@ -72,6 +79,14 @@ def parse_args(argv=None):
                    help="samples per class on which an evaluation also scores the Frechet pose / motion distance (0 = off)")
     p.add_argument("--eval_frechet_modes", type=str, nargs="+", default=["pose", "motion"], choices=["pose", "motion"],
                    help="the Frechet distances of --eval_frechet")
+    p.add_argument("--eval_classifier", type=str, default=None,
+                   help="classifier_<n>.pth of tools/train_classifier.py: an evaluation also scores accuracy, feature Frechet "
+                        "distance, diversity and multimodality (needs --eval_classifier_samples)")
+    p.add_argument("--eval_classifier_samples", type=int, default=0,
+                   help="samples per class of the --eval_classifier scores (0 = off; e.g. 100)")
+    p.add_argument("--eval_classifier_batch", type=int, default=512, help="samples per classifier pass of an evaluation")
+    p.add_argument("--eval_diversity_pairs", type=int, default=200, help="pairs of the diversity score")
+    p.add_argument("--eval_multimodality_pairs", type=int, default=20, help="pairs per class of the multimodality score")
     p.add_argument("--eval_trunc", type=float, default=None, help="truncation factor of the evaluation's samples")
     p.add_argument("--eval_trunc_mode", type=str, default="-", help="'-' none, 'z' or 'w' truncation of the evaluation's samples")
     p.add_argument("--eval_data_path", type=str, default=None, help="real samples of the evaluation (default: the training data)")
@@ -100,13 +115,25 @@ def main(argv=None):
         if not opt.eval_label_path:
             raise SystemExit("--eval_data_path needs --eval_label_path")
         eval_data = Feeder(opt.eval_data_path, opt.eval_label_path, dataset=opt.dataset)
+    clf = None
+    if opt.eval_interval and opt.eval_classifier and opt.eval_classifier_samples:
+        clf, meta = load_classifier(opt.eval_classifier, dev)
+        try:
+            for f in [feeder] + ([] if eval_data is None else [eval_data]):
+                scale, shift = norm_constants(f)
+                check_classifier_meta(meta, dict(dataset=opt.dataset, n_classes=opt.n_classes, in_channels=opt.channels,
+                                                 t_size=min(opt.t_size, f.T), scale=scale, shift=shift))
+        except ValueError as e:
+            raise SystemExit("--eval_classifier %s: %s" % (opt.eval_classifier, e))
     loop = TrainLoop(G, D, feeder, opt.batch_size, opt.t_size, n_critic=opt.n_critic, seed=opt.seed, lr=opt.lr, b1=opt.b1,
                      b2=opt.b2, lambda_gp=float(opt.lambda_gp), use_graph=not opt.no_graph,
                      ring_len=max(4096, opt.log_interval), ema_decay=opt.ema_decay or None, ema_warmup=opt.ema_warmup,
                      eval_interval=opt.eval_interval or None, eval_pairs=opt.eval_pairs, eval_select=opt.eval_select,
                      eval_trunc=opt.eval_trunc, eval_trunc_mode=opt.eval_trunc_mode, eval_data=eval_data,
                      eval_prdc=opt.eval_prdc, eval_prdc_k=opt.eval_prdc_k, eval_frechet=opt.eval_frechet,
-                     eval_frechet_modes=tuple(opt.eval_frechet_modes))
+                     eval_frechet_modes=tuple(opt.eval_frechet_modes), eval_classifier=clf,
+                     eval_classifier_samples=opt.eval_classifier_samples, eval_classifier_batch=opt.eval_classifier_batch,
+                     eval_diversity_pairs=opt.eval_diversity_pairs, eval_multimodality_pairs=opt.eval_multimodality_pairs)
     print("dataset: %d samples, %d batches per epoch, %s (%.1f MB cropped)" % (
         len(feeder), loop.bpe, "streamed" if loop.streaming else "resident on the device", loop.resident.nbytes / 1e6))
     if opt.resume:
