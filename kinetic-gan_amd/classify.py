@@ -10,14 +10,14 @@ is captured once and replayed; the host only uploads the next epoch's permutatio
 """
 from __future__ import annotations
 
-import collections
 from typing import List, Tuple
 
 import numpy as np
 import torch
 
 from . import _native as nv
-from .train import ResidentDataset, _capture, epoch_permutation
+from .replay import LossRecord, Pacer, PermutationFeed, capture_keeping
+from .train import ResidentDataset
 from .wgan_gp import FlatParams, _const_like
 
 
@@ -56,23 +56,15 @@ class ClassifierLoop:
         self.labels = torch.zeros(B, dtype=torch.int64, device=dev)
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ring_len = int(ring_len)
-        self.ring = torch.full((self.ring_len, 2), float("nan"), dtype=torch.float32, device=dev)
+        self._record = LossRecord(ring_len, dev)         # (loss, batch accuracy) of every iteration
+        self.ring, self.ring_len = self._record.ring, self._record.ring_len
         self.step_count = 0                              # host mirror of step_dev
-        self.run_ahead = max(2, int(run_ahead))
-        self._marks = collections.deque()
-        self._flushed = 0
-        self._hist: List[np.ndarray] = []
+        self._pacer = Pacer(run_ahead)
+        self.run_ahead = self._pacer.run_ahead
         self._graph_obj = None
         r = self.resident
-        plen = self.bpe * B
-        self._perm = torch.zeros((2, plen), dtype=torch.int64, device=dev)
-        self._perm_host = [torch.empty(plen, dtype=torch.int64, pin_memory=True) for _ in range(2)]
-        self._perm_done = [None, None]
-        self._perm_wait = [False, False]
-        self._perm_epochs = [None, None]                 # epoch held by each slot of the device permutation
-        self._copy_stream = torch.cuda.Stream(device=dev)
-        self._gather = nv.StepData(r.data, r.labels, self._perm, self.bpe, r.scale, r.shift, self.real, self.labels)
+        self._perm = PermutationFeed(self.n, self.bpe * B, self.seed, dev)
+        self._gather = nv.StepData(r.data, r.labels, self._perm.perm, self.bpe, r.scale, r.shift, self.real, self.labels)
 
     @property
     def epoch(self) -> int:
@@ -97,59 +89,20 @@ class ClassifierLoop:
 
     def _graph(self):
         """The captured iteration.  The warm-up calls in front of the capture are real iterations: everything they move
-        (parameters, optimiser state, the counter, the ring) is put back afterwards, as ``TrainLoop._graph`` does."""
+        (parameters, optimiser state, the counter, the ring; on the host, whether the gradient bucket is known to be zero)
+        is put back afterwards."""
         if self._graph_obj is None:
-            torch.cuda.synchronize(self.device)
-            ts = self._state_tensors()
-            keep = [t.clone() for t in ts]
             clean = self.flat._clean
-            g = _capture(self._iteration)
-            for t, k in zip(ts, keep):
-                t.copy_(k)
-            self.flat._clean = clean
-            torch.cuda.synchronize(self.device)
-            self._graph_obj = g
+            self._graph_obj = capture_keeping(self._iteration, self._state_tensors(), self.device,
+                                              restore_host=lambda: setattr(self.flat, "_clean", clean))
         return self._graph_obj
-
-    def _upload_perm(self, epoch: int):
-        """permutation of `epoch` into slot epoch & 1 on the copy stream, behind the work enqueued so far; the training
-        stream waits for it when it first needs the slot (``TrainLoop._upload_perm``)"""
-        slot = epoch & 1
-        if self._perm_done[slot] is not None:
-            self._perm_done[slot].synchronize()
-        idx = epoch_permutation(self.n, self.seed, epoch)
-        self._perm_host[slot].numpy()[:] = idx[:self._perm.shape[1]]
-        self._copy_stream.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self._copy_stream):
-            self._perm[slot].copy_(self._perm_host[slot], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self._copy_stream)
-        self._perm_done[slot] = ev
-        self._perm_epochs[slot] = epoch
-        self._perm_wait[slot] = True
-
-    def _feed(self):
-        epoch = self.step_count // self.bpe
-        if self._perm_epochs[epoch & 1] != epoch:
-            self._upload_perm(epoch)
-        if self._perm_epochs[(epoch + 1) & 1] != epoch + 1:
-            self._upload_perm(epoch + 1)
-        if self._perm_wait[epoch & 1]:
-            torch.cuda.current_stream(self.device).wait_event(self._perm_done[epoch & 1])
-            self._perm_wait[epoch & 1] = False
 
     def step(self) -> None:
         """One iteration; no host synchronisation (loss and accuracy stay in the device ring until ``losses()``); the host
         runs at most ~run_ahead iterations ahead of the device, as ``TrainLoop.step``."""
-        if self.step_count - self._flushed >= self.ring_len:
-            self._flush()
-        if self.step_count % (self.run_ahead // 2) == 0:
-            if len(self._marks) >= 2:
-                self._marks.popleft().synchronize()
-            ev = torch.cuda.Event()
-            ev.record()
-            self._marks.append(ev)
-        self._feed()
+        self._record.before_step(self.step_count)
+        self._pacer.tick(self.step_count)
+        self._perm.feed(self.step_count, self.bpe)
         if self.use_graph:
             self._graph().replay()
         else:
@@ -157,46 +110,24 @@ class ClassifierLoop:
         self.step_count += 1
 
     # ---- record ----------------------------------------------------------------------------------------------------
-    def _flush(self):
-        n = self.step_count - self._flushed
-        if n <= 0:
-            return
-        ring = self.ring.cpu().numpy()
-        slots = np.arange(self._flushed, self.step_count) % self.ring_len
-        self._hist.append(ring[slots].copy())
-        self._flushed = self.step_count
-
     def losses(self) -> Tuple[np.ndarray, np.ndarray]:
         """(loss, batch accuracy) of every iteration since the run (or its resumption) began.  Synchronises."""
-        self._flush()
-        h = np.concatenate(self._hist) if self._hist else np.zeros((0, 2), dtype=np.float32)
-        return h[:, 0], h[:, 1]
+        return self._record.history(self.step_count)
 
     # ---- resume ----------------------------------------------------------------------------------------------------
     def state_dict(self) -> dict:
-        self._flush()
-        f = self.flat
+        self._record.flush(self.step_count)
         return {"step": self.step_count, "seed": self.seed, "batch_size": self.B, "batches_per_epoch": self.bpe,
-                "flat": f.flat.cpu(), "exp_avg": f.exp_avg.cpu(), "exp_avg_sq": f.exp_avg_sq.cpu(), "adam_step": f.step.cpu(),
-                "last_losses": self.ring[(self.step_count - 1) % self.ring_len].cpu() if self.step_count else None}
+                **self.flat.state_dict(), "last_losses": self._record.last_row(self.step_count)}
 
     def load_state_dict(self, sd: dict) -> None:
         for k, mine in (("seed", self.seed), ("batch_size", self.B), ("batches_per_epoch", self.bpe)):
             if sd[k] != mine:
                 raise ValueError("ClassifierLoop.load_state_dict: %s is %r in the checkpoint, %r here" % (k, sd[k], mine))
-        f = self.flat
-        if sd["flat"].numel() != f.flat.numel():
-            raise ValueError("ClassifierLoop.load_state_dict: the checkpoint's parameters do not fit this classifier")
-        f.flat.copy_(sd["flat"])
-        f.exp_avg.copy_(sd["exp_avg"])
-        f.exp_avg_sq.copy_(sd["exp_avg_sq"])
-        f.step.copy_(sd["adam_step"])
-        f.grad.zero_()
-        self.step_count = self._flushed = int(sd["step"])
-        self._hist = []
+        self.flat.load_state_dict(sd)
+        self.step_count = int(sd["step"])
         self.step_dev.fill_(self.step_count)
-        if sd.get("last_losses") is not None:
-            self.ring[(self.step_count - 1) % self.ring_len].copy_(sd["last_losses"])
+        self._record.load(self.step_count, sd.get("last_losses"))
         torch.cuda.synchronize(self.device)
 
     # ---- held-out accuracy -------------------------------------------------------------------------------------------

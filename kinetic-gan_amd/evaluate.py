@@ -54,6 +54,7 @@ import torch
 
 from . import _native as nv
 from . import metrics
+from .replay import capture_keeping
 from .sample import Sampler
 
 
@@ -520,15 +521,7 @@ class Evaluator:
     def _capture(self):
         """Single-stream capture, no parallel branches.  The warm-up rounds in front of it are real evaluations:
         everything they move is put back."""
-        from .train import _capture
-        torch.cuda.synchronize(self.device)
-        ts = self._state_tensors()
-        keep = [t.clone() for t in ts]
-        g = _capture(self._round)
-        for t, k in zip(ts, keep):
-            t.copy_(k)
-        torch.cuda.synchronize(self.device)
-        return g
+        return capture_keeping(self._round, self._state_tensors(), self.device)
 
     @torch.no_grad()
     def evaluate(self) -> None:

@@ -24,6 +24,7 @@ import torch
 from . import _native as nv
 from . import gen_trunk as gt
 from .generator import truncate_z
+from .replay import capture_keeping
 
 
 @torch.no_grad()
@@ -213,13 +214,7 @@ class Sampler:
 
     def _capture(self):
         """Single-stream capture.  The warm-up rounds in front of it are real draws: the counter is put back."""
-        from .train import _capture
-        torch.cuda.synchronize(self.device)
-        keep = self.step_dev.clone()
-        g = _capture(self._round)
-        self.step_dev.copy_(keep)
-        torch.cuda.synchronize(self.device)
-        return g
+        return capture_keeping(self._round, [self.step_dev], self.device)
 
     @torch.no_grad()
     def next(self):

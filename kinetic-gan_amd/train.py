@@ -18,7 +18,6 @@ Definitions the tests pin this against: tests/train_def.py (numpy).  DESIGN.md 1
 """
 from __future__ import annotations
 
-import collections
 import os
 import warnings
 from typing import Dict, List, Optional, Tuple
@@ -30,6 +29,8 @@ from . import _native as nv
 from .checkpoint import AsyncCheckpointWriter
 from .evaluate import write_metrics_csv
 from .feeder import DeviceBatches, Feeder
+from .replay import LossRecord, Pacer, PermutationFeed, capture_keeping
+from .replay import epoch_permutation  # noqa: F401  (re-exported)
 from .sample import sample_actions
 from .wgan_gp import Trainer
 
@@ -38,14 +39,6 @@ def update_pattern(batches_per_epoch: int, n_critic: int, n_steps: int, start: i
     """with_g of iterations start .. start + n_steps - 1: the generator is updated when the batch index INSIDE the epoch
     is a multiple of n_critic (kinetic-gan.py:160), so the pattern restarts with every epoch."""
     return [((s % batches_per_epoch) % n_critic) == 0 for s in range(start, start + n_steps)]
-
-
-def epoch_permutation(n: int, seed: int, epoch: int, shuffle: bool = True) -> np.ndarray:
-    """The sample order of one epoch, exactly ``DeviceBatches._order``'s."""
-    idx = np.arange(n)
-    if shuffle:
-        np.random.RandomState(seed + epoch).shuffle(idx)
-    return idx
 
 
 def norm_constants(feeder: Feeder) -> Tuple[float, float]:
@@ -89,25 +82,6 @@ class ResidentDataset:
             done[slot].record()
         self.labels = torch.as_tensor(np.asarray(feeder.label, dtype=np.int64)).to(self.device)
         torch.cuda.synchronize(self.device)
-
-
-def _capture(fn, before_capture=None, warmup: int = 3):
-    """fn() as a hipGraph: allocator warm-up on a side stream, then a thread-local capture (other threads of the process
-    - a checkpoint writer, a collective's watchdog - cannot invalidate it).  ``before_capture`` runs between the two."""
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for _ in range(warmup):
-            fn()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    if before_capture is not None:
-        before_capture()
-    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-        fn()
-    torch.cuda.synchronize()
-    return graph
 
 
 class TrainLoop:
@@ -165,32 +139,20 @@ class TrainLoop:
         self.noise_d, self.noise_g = nv.noise_views(self.noise, self.plane_shapes)
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ring_len = int(ring_len)
-        self.ring = torch.full((self.ring_len, 2), float("nan"), dtype=torch.float32, device=dev)
+        self._record = LossRecord(ring_len, dev)             # (d_loss, g_loss) of every iteration
+        self.ring, self.ring_len = self._record.ring, self._record.ring_len
         self.step_count = 0                  # host mirror of step_dev
-        # the host enqueues at most ~run_ahead iterations ahead of the device (an event every run_ahead / 2 iterations,
-        # the host waits for the one before last): a queue filled to its limit replays measurably slower
-        self.run_ahead = max(2, int(run_ahead))
-        self._marks = collections.deque()
-        self._flushed = 0                    # iterations whose losses have been read from the ring
-        self._first = 0                      # iteration the loss record starts at (a resumed run: where it resumed)
-        self._d_hist: List[np.ndarray] = []
-        self._g_hist: List[np.ndarray] = []
+        self._pacer = Pacer(run_ahead)
+        self.run_ahead = self._pacer.run_ahead
         self._graphs: Dict[bool, object] = {}
-        self._perm_epochs = [None, None]     # epoch held by each slot of the device permutation
-        self._gather = None
+        self._gather = self._perm = None
         self._batches = self._batch_iter = None
         if self.streaming:
             self._batches = DeviceBatches(feeder, B, self.t, dev, seed=self.seed, rank=self.rank, world=self.world)
         else:
             r = self.resident
-            plen = self.bpe * self.world * B
-            self._perm = torch.zeros((2, plen), dtype=torch.int64, device=dev)
-            self._perm_host = [torch.empty(plen, dtype=torch.int64, pin_memory=True) for _ in range(2)]
-            self._perm_done = [None, None]
-            self._perm_wait = [False, False]
-            self._copy_stream = torch.cuda.Stream(device=dev)
-            self._gather = nv.StepData(r.data, r.labels, self._perm, self.bpe, r.scale, r.shift, self.real, self.labels)
+            self._perm = PermutationFeed(self.n, self.bpe * self.world * B, self.seed, dev)
+            self._gather = nv.StepData(r.data, r.labels, self._perm.perm, self.bpe, r.scale, r.shift, self.real, self.labels)
         # eval_interval (None or 0: off): every eval_interval finished iterations one Evaluator replay is enqueued behind the
         # iteration - it scores the live (and the averaged) generator, appends to a record on the device and snapshots the
         # best-scoring weights there.  Off: no launch, no file, no state key is added.  eval_prdc (0: off):
@@ -253,37 +215,14 @@ class TrainLoop:
         g = self._graphs.get(with_g)
         if g is not None:
             return g
-        torch.cuda.synchronize(self.device)          # (a permutation upload in flight included)
-        ts = self._state_tensors()
-        keep = [t.clone() for t in ts]
         tr = self.trainer
 
         def drop_warmup_graph():
             # a sample the last warm-up call left behind would keep its autograd graph (created on the warm-up stream)
             tr._w = tr._fake_g = None
-        g = _capture(lambda: self._iteration(with_g), before_capture=drop_warmup_graph)
-        for t, k in zip(ts, keep):
-            t.copy_(k)
-        torch.cuda.synchronize(self.device)
+        g = capture_keeping(lambda: self._iteration(with_g), self._state_tensors(), self.device, before_capture=drop_warmup_graph)
         self._graphs[with_g] = g
         return g
-
-    def _upload_perm(self, epoch: int):
-        """permutation of `epoch` into slot epoch & 1 on the copy stream, behind the work enqueued so far (replays that
-        still read the slot's previous epoch); the training stream waits for it when it first needs the slot"""
-        slot = epoch & 1
-        if self._perm_done[slot] is not None:
-            self._perm_done[slot].synchronize()              # the pinned buffer's last copy (an epoch ago)
-        idx = epoch_permutation(self.n, self.seed, epoch)
-        self._perm_host[slot].numpy()[:] = idx[:self._perm.shape[1]]
-        self._copy_stream.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self._copy_stream):
-            self._perm[slot].copy_(self._perm_host[slot], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self._copy_stream)
-        self._perm_done[slot] = ev
-        self._perm_epochs[slot] = epoch
-        self._perm_wait[slot] = True
 
     def _feed(self):
         """host work in front of an iteration: none inside an epoch on the resident path"""
@@ -300,25 +239,12 @@ class TrainLoop:
             if i == self.bpe - 1:
                 self._batch_iter = None
             return
-        if self._perm_epochs[epoch & 1] != epoch:            # first iteration of a (resumed) run
-            self._upload_perm(epoch)
-        if self._perm_epochs[(epoch + 1) & 1] != epoch + 1:
-            # one epoch ahead (normally at i == 0): every replay of the epoch this slot held has been enqueued
-            self._upload_perm(epoch + 1)
-        if self._perm_wait[epoch & 1]:
-            torch.cuda.current_stream(self.device).wait_event(self._perm_done[epoch & 1])
-            self._perm_wait[epoch & 1] = False
+        self._perm.feed(self.step_count, self.bpe)
 
     def step(self) -> None:
         """One iteration; no host synchronisation (the losses stay in the device ring until ``losses()``)."""
-        if self.step_count - self._flushed >= self.ring_len:
-            self._flush()                    # the ring is full: one bulk read per ring_len iterations at the most
-        if self.step_count % (self.run_ahead // 2) == 0:
-            if len(self._marks) >= 2:
-                self._marks.popleft().synchronize()      # long complete unless the host is run_ahead iterations ahead
-            ev = torch.cuda.Event()
-            ev.record()
-            self._marks.append(ev)
+        self._record.before_step(self.step_count)
+        self._pacer.tick(self.step_count)
         self._feed()
         wg = self.with_g()
         if self.use_graph:
@@ -330,34 +256,20 @@ class TrainLoop:
             self.evaluator.evaluate()        # enqueued behind the iteration; reads step_dev = the finished count
 
     # ---- losses ----------------------------------------------------------------------------------------------------
-    def _flush(self):
-        n = self.step_count - self._flushed
-        if n <= 0:
-            return
-        ring = self.ring.cpu().numpy()       # ONE device -> host read
-        slots = (np.arange(self._flushed, self.step_count)) % self.ring_len
-        self._d_hist.append(ring[slots, 0].copy())
-        self._g_hist.append(ring[slots, 1].copy())
-        self._flushed = self.step_count
-
     def losses(self) -> Tuple[np.ndarray, np.ndarray]:
         """(d_loss, g_loss) of every iteration since the run (or its resumption) began; an iteration without generator
         step repeats the last g_loss, as the reference's record does.  Synchronises."""
-        self._flush()
-        cat = lambda h: np.concatenate(h) if h else np.zeros(0, dtype=np.float32)      # noqa: E731
-        return cat(self._d_hist), cat(self._g_hist)
+        return self._record.history(self.step_count)
 
     # ---- resume ----------------------------------------------------------------------------------------------------
     def state_dict(self) -> dict:
         """Everything a bit-exact continuation needs, on the host."""
-        self._flush()
+        self._record.flush(self.step_count)
         tr = self.trainer
         out = {"step": self.step_count, "epoch": self.epoch, "seed": self.seed, "n_critic": self.n_critic,
-               "batch_size": self.B, "batches_per_epoch": self.bpe,
-               "last_losses": self.ring[(self.step_count - 1) % self.ring_len].cpu() if self.step_count else None}
+               "batch_size": self.B, "batches_per_epoch": self.bpe, "last_losses": self._record.last_row(self.step_count)}
         for name, f, m in (("G", tr.fG, self.G), ("D", tr.fD, self.D)):
-            out[name] = {"flat": f.flat.cpu(), "exp_avg": f.exp_avg.cpu(), "exp_avg_sq": f.exp_avg_sq.cpu(),
-                         "adam_step": f.step.cpu(), "buffers": {k: b.cpu() for k, b in m.named_buffers()}}
+            out[name] = dict(f.state_dict(), buffers={k: b.cpu() for k, b in m.named_buffers()})
         if tr.fG.ema is not None:
             out["G"]["ema"] = tr.fG.ema.cpu()
             out["ema"] = {"decay": self.ema_decay, "warmup": self.ema_warmup}
@@ -379,11 +291,7 @@ class TrainLoop:
                     raise ValueError("TrainLoop.load_state_dict: ema %s is %r in the checkpoint, %r here" % (k, sd["ema"][k], mine))
         for name, f, m in (("G", tr.fG, self.G), ("D", tr.fD, self.D)):
             s = sd[name]
-            f.flat.copy_(s["flat"])
-            f.exp_avg.copy_(s["exp_avg"])
-            f.exp_avg_sq.copy_(s["exp_avg_sq"])
-            f.step.copy_(s["adam_step"])
-            f.grad.zero_()
+            f.load_state_dict(s)
             bufs = dict(m.named_buffers())
             if set(bufs) != set(s["buffers"]):
                 raise ValueError("TrainLoop.load_state_dict: buffers of %s do not match" % name)
@@ -396,11 +304,9 @@ class TrainLoop:
                 warnings.warn("TrainLoop.load_state_dict: the checkpoint holds no weight average; it starts from the loaded "
                               "generator weights")
                 tr.fG.ema.copy_(tr.fG.flat)
-        self.step_count = self._flushed = self._first = int(sd["step"])
-        self._d_hist, self._g_hist = [], []
+        self.step_count = int(sd["step"])
         self.step_dev.fill_(self.step_count)
-        if sd.get("last_losses") is not None:
-            self.ring[(self.step_count - 1) % self.ring_len].copy_(sd["last_losses"])
+        self._record.load(self.step_count, sd.get("last_losses"))
         self._batch_iter = None
         if self.evaluator is not None:           # (a record in the state is ignored by a loop without evaluation)
             if sd.get("eval") is not None:

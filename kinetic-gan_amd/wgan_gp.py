@@ -177,6 +177,21 @@ class FlatParams:
                              1.0 / world, self.fused_step, self.ema_decay, self.ema_warmup)
         self._clean = self.fused_step
 
+    def state_dict(self) -> dict:
+        """Parameters and optimiser state on the host (the weight average is its owner's to save)."""
+        return {"flat": self.flat.cpu(), "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(),
+                "adam_step": self.step.cpu()}
+
+    def load_state_dict(self, sd: dict) -> None:
+        if sd["flat"].numel() != self.flat.numel():
+            raise ValueError("FlatParams.load_state_dict: the state holds %d parameters, this module %d" % (
+                sd["flat"].numel(), self.flat.numel()))
+        self.flat.copy_(sd["flat"])
+        self.exp_avg.copy_(sd["exp_avg"])
+        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        self.step.copy_(sd["adam_step"])
+        self.grad.zero_()
+
 
 def penalty_of(d_inter, inter, keep: Optional[dict] = None):
     """kinetic-gan.py:103-113: ((|d D(inter) / d inter|_2 - 1)^2).mean() for an already evaluated D(inter).

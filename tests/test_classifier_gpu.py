@@ -125,10 +125,10 @@ def _fixture_feeder():
     return Feeder(os.path.join(GOLDEN, "feeder_h36m_data.npy"), os.path.join(GOLDEN, "feeder_h36m_label.pkl"), dataset="h36m")
 
 
-def _loop(feeder, use_graph, seed_model=9):
+def _loop(feeder, use_graph, seed_model=9, **kw):
     clf = Classifier(2, 4, 16, dataset="h36m")
     fill_module(clf, seed=seed_model)
-    return ClassifierLoop(clf.to(DEV), feeder, 4, 16, seed=2, lr=1e-3, use_graph=use_graph)
+    return ClassifierLoop(clf.to(DEV), feeder, 4, 16, seed=2, lr=1e-3, use_graph=use_graph, **kw)
 
 
 def _state_bits(loop):
@@ -169,12 +169,24 @@ def test_classifier_loop():
         replay.step()
     for a, b in zip(_state_bits(replay), want):
         assert np.array_equal(a, b)
+    # (b') a ring of four rows (it wraps, and is read in mid-run) and a host that waits at every iteration: the same record,
+    # parameters and moments
+    short = _loop(feeder, True, ring_len=4, run_ahead=2)
+    assert short.ring_len == 4 and short.run_ahead == 2
+    for _ in range(6):
+        short.step()
+    for a, b in zip(short.losses(), replay.losses()):
+        assert len(a) == 6 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    for a, b in zip(_state_bits(short)[:4], want[:4]):
+        assert np.array_equal(a, b)
+    assert np.array_equal(_state_bits(short)[5], want[5])
     # (c) resume: state after three iterations into a fresh loop, three more
     first = _loop(feeder, False)
     for _ in range(3):
         first.step()
     sd = first.state_dict()
-    assert sd["step"] == 3 and set(sd) >= {"flat", "exp_avg", "exp_avg_sq", "adam_step", "step", "seed"}
+    assert sd["step"] == 3 and set(sd) == {"step", "seed", "batch_size", "batches_per_epoch", "flat", "exp_avg", "exp_avg_sq",
+                                           "adam_step", "last_losses"}
     second = _loop(feeder, True, seed_model=10)          # other initial weights: everything comes from the state
     second.load_state_dict(sd)
     for _ in range(3):

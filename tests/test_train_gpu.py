@@ -301,13 +301,33 @@ def test_eager_loop_matches_graph_loop(six_steps, tmp_path):
     assert np.array_equal(d, six_steps[1]) and np.array_equal(g, six_steps[2])
 
 
-def test_resume_is_bit_exact(six_steps, tmp_path):
-    """3 iterations + state_dict through a file + 3 iterations in a fresh loop == 6 iterations"""
+@pytest.mark.parametrize("use_graph", [True, False])
+def test_short_ring_wraps_and_flushes(six_steps, tmp_path, use_graph):
+    """a ring of four rows under six iterations: the fifth - critic only, so kg_loss_append repeats the g_loss of the row
+    before it, which lies across the wrap - is enqueued behind a flush in mid-run; run_ahead=2: the host waits at every
+    iteration.  State and both loss arrays bit for bit those of the default loop"""
+    loop, G, D = make_loop(tmp_path, ring_len=4, run_ahead=2, use_graph=use_graph)
+    assert loop.ring_len == 4 and tuple(loop.ring.shape) == (4, 2) and loop.run_ahead == 2
+    assert not loop.with_g(4)
+    for _ in range(6):
+        loop.step()
+    d, g = loop.losses()
+    assert_same_state(six_steps[0], loop_state(loop, G, D), "ring_len=4, run_ahead=2, use_graph=%s vs the default loop" % use_graph)
+    assert np.array_equal(bits(d), bits(six_steps[1])) and np.array_equal(bits(g), bits(six_steps[2]))
+
+
+@pytest.mark.parametrize("at", [3, 4])
+def test_resume_is_bit_exact(six_steps, tmp_path, at):
+    """``at`` iterations + state_dict through a file + the rest in a fresh loop == 6 iterations; at = 3 is an epoch boundary,
+    4 lies inside an epoch: the first iteration uploads the current epoch's permutation and the next one's"""
     loop, G, D = make_loop(tmp_path / "a")
-    for _ in range(3):
+    for _ in range(at):
         loop.step()
     path = str(tmp_path / "loop_state.pth")
-    torch.save(loop.state_dict(), path)
+    sd = loop.state_dict()
+    assert set(sd) == {"step", "epoch", "seed", "n_critic", "batch_size", "batches_per_epoch", "last_losses", "G", "D"}
+    assert set(sd["G"]) == set(sd["D"]) == {"flat", "exp_avg", "exp_avg_sq", "adam_step", "buffers"}
+    torch.save(sd, path)
     d0, g0 = loop.losses()
     del loop
     loop2, G2, D2 = make_loop(tmp_path / "b")
@@ -315,11 +335,13 @@ def test_resume_is_bit_exact(six_steps, tmp_path):
         loop2.trainer.fG.flat.add_(0.25)
         loop2.trainer.fD.flat.mul_(0.5)
     loop2.load_state_dict(torch.load(path, weights_only=False))
-    assert loop2.step_count == 3 and loop2.epoch == 1
-    for _ in range(3):
+    assert loop2.step_count == at and loop2.epoch == 1
+    for k in range(6 - at):
         loop2.step()
+        if k == 0:
+            assert sorted(loop2._perm._epochs) == [1, 2]
     d1, g1 = loop2.losses()
-    assert_same_state(six_steps[0], loop_state(loop2, G2, D2), "3 + resume + 3 vs 6")
+    assert_same_state(six_steps[0], loop_state(loop2, G2, D2), "%d + resume + %d vs 6" % (at, 6 - at))
     assert np.array_equal(np.concatenate((d0, d1)), six_steps[1])
     assert np.array_equal(np.concatenate((g0, g1)), six_steps[2])
 

@@ -51,8 +51,9 @@ from kinetic_gan_amd import _native as nv  # noqa: E402
 from kinetic_gan_amd import metrics  # noqa: E402
 from kinetic_gan_amd.evaluate import Evaluator  # noqa: E402
 from kinetic_gan_amd.generator import Generator  # noqa: E402
+from kinetic_gan_amd.replay import capture  # noqa: E402
 from kinetic_gan_amd.sample import Sampler  # noqa: E402
-from kinetic_gan_amd.train import ResidentDataset, TrainLoop, _capture  # noqa: E402
+from kinetic_gan_amd.train import ResidentDataset, TrainLoop  # noqa: E402
 from time_train_loop import BATCH, CFG, SyntheticFeeder, models, time_loop  # noqa: E402
 
 DECAY, PAIRS, INTERVAL = 0.999, 10, 100
@@ -111,9 +112,9 @@ def prdc_part(args, say, dev):
         rv = e._prdc_rv._replace(so=T * V)
         fv = {g: nv.PrdcView(t, sn, K * sn, sc) for g, t in outs.items()}
         ws1 = torch.empty(nv.prdc_workspace_bytes(N, N, C, T * V, K, K5) // 4, dtype=torch.int32, device=dev)
-        graphs = {"kg_prdc_sets, cached real radii": _capture(lambda: nv.prdc_sets(
+        graphs = {"kg_prdc_sets, cached real radii": capture(lambda: nv.prdc_sets(
                       rv, list(outs.values()), sn, K * sn, sc, e.prdc_radii, N, N, C, T * V, K, K5, ws=e._prdc_ws)),
-                  "kg_prdc per generator": _capture(lambda: [nv.prdc(rv, v, N, N, C, T * V, K, K5, ws=ws1) for v in fv.values()])}
+                  "kg_prdc per generator": capture(lambda: [nv.prdc(rv, v, N, N, C, T * V, K, K5, ws=ws1) for v in fv.values()])}
         meds = {k: [] for k in graphs}
         for r in range(args.reps):
             for k, g in graphs.items():
@@ -298,7 +299,7 @@ def classifier_part(args, say, dev):
             name, m["composed"], sp["composed"]))
         # kg_cls_scores alone
         feats, preds = list(on._cls_feat.values()), list(on._cls_pred.values())
-        g = _capture(lambda: nv.cls_scores(feats, preds, on._cls_labels, *on._cls_tables, K))
+        g = capture(lambda: nv.cls_scores(feats, preds, on._cls_labels, *on._cls_tables, K))
         meds = [statistics.median(time_replays(g, args.replays)) for _ in range(args.reps)]
         say("%s kg_cls_scores alone (2 sets, N = %d, F = %d, %d pairs; two launches): %.4f ms (median of %d repetitions of %d replays, "
             "spread %.4f)" % (name, K * P, clf.feat_dim, sd + K * sl, statistics.median(meds), args.reps, args.replays,
@@ -389,9 +390,9 @@ def main(argv=None):
     nchw = out.contiguous()
     parts = {}
     for mode in ev.modes:
-        g = _capture(lambda: metrics.calculate_mmd(nchw, ev.real, ev._pair_labels, mode))
+        g = capture(lambda: metrics.calculate_mmd(nchw, ev.real, ev._pair_labels, mode))
         parts[mode] = statistics.median(time_replays(g, args.replays))
-    g = _capture(lambda: nchw.copy_(out))
+    g = capture(lambda: nchw.copy_(out))
     t_copy = statistics.median(time_replays(g, args.replays))
     total = 2 * t_round + 2 * sum(parts.values())
     say("parts, each a graph of its own: Sampler round of %d samples %.4f ms; kg_mmd %s; re-layout copy_ %.4f ms" % (
