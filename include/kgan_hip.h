@@ -87,9 +87,10 @@ typedef struct KgConvArgs {
     int32_t* sync;  int32_t sync_len;         /* optional: sync_len zeroed ticket counters.  A K-split launch with at most
                                                  sync_len output tiles then completes them itself - the last workgroup of
                                                  a tile to arrive sums the partial slabs in split order and runs the
-                                                 epilogue - instead of a second launch; the counters are
-                                                 zero again when the launch ends.  NULL: the separate epilogue launch.
-                                                 Launches that share the counters must not overlap.                   */
+                                                 epilogue - instead of a second launch; a tile's counter
+                                                 is zero again from the moment its last ticket is drawn.
+                                                 NULL: the separate epilogue launch.  Launches that share the counters
+                                                 must not overlap.                                                     */
     int32_t o_tstride;                        /* 0 / 1: output frames follow each other; s > 1: output frame `to` is
                                                  written at frame to * s of `out` (a transposed stride-2 temporal conv
                                                  runs as two launches, one per output-frame parity, each with only
@@ -326,7 +327,8 @@ int kg_gen_adj_prepare(const KgGenPrepJob* jobs, int32_t njobs, void* stream);
  *                       (C) buffers (NULL: skipped) - e.g. their slices of the flat gradient bucket
  *   kg_gen_tail_apply : du (and dr) from g, out, u, r and coef in one pass
  * u == NULL: no BatchNorm on the tcn branch; mean_r == NULL: none on the residual branch (r may still be given: an
- * identity residual, dr = gp).  `counters`: >= C zeroed int32, left zeroed.                                          */
+ * identity residual, dr = gp).  `counters`: >= C zeroed int32, left zeroed (each is zero
+ * again from the moment its last ticket is drawn).                                                     */
 typedef struct KgGenTailArgs {
     int32_t N, C, T, V;  int32_t act;  float slope;
     const float* g;  int64_t g_sN, g_sC;
@@ -365,7 +367,8 @@ int     kg_gen_tail_apply(const KgGenTailArgs* a, void* stream);
  *         buffers), merged by the last workgroup to arrive.
  * Every tensor the deferred parameter-gradient launches read (x, yc, z, u, r / du, dr, gyc, zf) is written exactly as
  * the staged form writes it.  kg_genblock_lds_bytes: dynamic LDS the launch needs, or -1 when the block does not fit
- * (then the staged entry points apply).  `counters`: >= 1 zeroed int32, left zeroed.                                */
+ * (then the staged entry points apply).  `counters`: >= 1 zeroed int32, left zeroed (forward: zero again from the
+ * moment the launch's last ticket is drawn; backward: when its last workgroup has finished - DESIGN.md 5.6).          */
 typedef struct KgPlane { float* p;  int64_t sN, sC; } KgPlane;             /* (N, C, T, V) plane tensor, NULL p = absent */
 typedef struct KgGenBnLayer {                                             /* one training-mode BatchNorm2d of the block */
     const float* gamma;  const float* beta;  float* running_mean;  float* running_var;  int64_t* num_batches_tracked;
@@ -494,7 +497,8 @@ int kg_bn_bwd(const KgBnArgs* a, void* stream);
  * along N (a.N = samples PER batch; batch q = samples [q N, (q+1) N) of a.x): a.coef is (groups, 4, C), the running
  * statistics take the batches' updates in order, num_batches_tracked += groups - the same results as `groups`
  * kg_bn_fwd calls per layer (generator.py:142,160 on the two syntheses of a WGAN-GP iteration, kinetic-gan.py:143,167).
- * `counters`: >= sum of C zeroed int32, left zeroed.                                                                 */
+ * `counters`: >= sum of C zeroed int32, left zeroed (a channel's counter is zero again from the moment its last ticket
+ * is drawn).                                                                                          */
 typedef struct KgBnJob {
     KgBnArgs a;
     int32_t groups;
@@ -928,7 +932,7 @@ int     kg_frechet_sets(const KgFrechetSetsArgs* a, void* stream);
 #define KG_STREAM_NOISE_G 3
 typedef struct KgStepInputsArgs {
     int64_t* step;                  /* device: iteration counter                                                     */
-    int32_t* ticket;                /* device: one zeroed int32, left at zero                                        */
+    int32_t* ticket;                /* device: one zeroed int32, left at zero (from the last ticket's draw on)       */
     uint64_t seed;
     int32_t rank, world;
     int32_t B;
@@ -996,7 +1000,7 @@ int     kg_genblock_infer(const KgGenBlockInferArgs* a, void* stream);
 #define KG_STREAM_SAMPLE 0x100
 typedef struct KgSampleInputsArgs {
     int64_t* step;                  /* device: replay counter                                                        */
-    int32_t* ticket;                /* device: one zeroed int32, left at zero                                        */
+    int32_t* ticket;                /* device: one zeroed int32, left at zero (from the last ticket's draw on)       */
     uint64_t seed;
     int32_t B, latent;
     float* z;                       /* (B, latent) or NULL                                                           */

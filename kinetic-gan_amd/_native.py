@@ -653,7 +653,8 @@ _sync_bufs = {}
 
 
 def _sync_buffer(device) -> torch.Tensor:
-    """Zeroed ticket counters of the last-arriver kernels (kg_bn_*_many, kg_agg_outer_many, ...): one buffer per (device, stream) -
+    """Zeroed ticket counters of the last-arriver kernels (kg_bn_fwd_many, kg_bn_bwd_many, kg_gen_tail_stats, kg_genblock_fwd,
+    kg_genblock_bwd, in-kernel K-split completion of kg_conv / kg_conv_many; csrc/kg_handoff.h): one buffer per (device, stream) -
     launches of one stream run one after the other, and every launch leaves its counters at zero again."""
     key = (device.index, torch.cuda.current_stream(device).cuda_stream)
     buf = _sync_bufs.get(key)

@@ -201,6 +201,15 @@ __device__ __forceinline__ void* kg_uniform_ptr(const void* p) {
     return (void*)(((unsigned long long)hi << 32) | lo);
 }
 
+// the job of a many-job launch that owns item i: job j has the items [beg[j], beg[j + 1]) - workgroups as a rule (uniform)
+__device__ __forceinline__ int kg_job_of(const int* beg, int njobs, int i) {
+    int ji = 0;
+#pragma unroll 1
+    while (ji + 1 < njobs && i >= beg[ji + 1]) ++ji;
+    return ji;
+}
+__device__ __forceinline__ int kg_job_of_block(const int* beg, int njobs) { return kg_job_of(beg, njobs, (int)blockIdx.x); }
+
 // Deterministic sum over S partial slabs: ws[k*per + i], k < S.  Block = 256 threads = 64 outputs x 4
 // slab lanes (one wave per lane: every load is one coalesced 256-byte row); returns the total in the
 // threads of wave 0 (others return 0 and must not store).

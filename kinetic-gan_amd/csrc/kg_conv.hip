@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "kg_common.h"
+#include "kg_handoff.h"
 
 // Optional instrumentation build (-DKG_CONV_TIMING, tools/time_conv.py): lane 0 of every workgroup records the
 // constant-rate (100 MHz) s_memrealtime at kernel entry, before and after the K-slice loop and after its stores,
@@ -195,7 +196,7 @@ __device__ __forceinline__ void store_tile(const KgConvArgs& a, const Split& sp,
                 for (int r = 0; r < 16; ++r) {
                     const int row = i * 32 + (r & 3) + 8 * (r >> 2);
                     if (KG_REG_ON(r) && row < mrem)
-                        __hip_atomic_store(slab + (long)row * ncols, acc[i][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        kg_pub_store(slab + (long)row * ncols, acc[i][r]);
                 }
             return;
         }
@@ -280,16 +281,7 @@ template <int TM, bool PART, bool PLAIN>
 __device__ __forceinline__ void finish_split(const KgConvArgs& a, const Split& sp, kg_f32x16 (&acc)[TM], const ColInfo& xc,
                                              int col0, int m0, int kh, int ncols, const float* bias_lds, unsigned regmask,
                                              int tile_id, int* flag_lds) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int tk = __hip_atomic_fetch_add(a.sync + tile_id, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = tk == sp.nsplit - 1;
-        if (last) __hip_atomic_store(a.sync + tile_id, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *flag_lds = last;
-    }
-    __syncthreads();
-    if (!*flag_lds) return;
+    if (!kg_arrive_last(a.sync + tile_id, sp.nsplit, flag_lds)) return;
     if (xc.valid) {
         const int mrem = PLAIN ? (1 << 20) : a.M - m0 - 4 * kh;
         const long per = (long)a.M * ncols;
@@ -315,8 +307,7 @@ __device__ __forceinline__ void finish_split(const KgConvArgs& a, const Split& s
                         const int kk = k0 + k < sp.nsplit ? k0 + k : sp.nsplit - 1;
                         v[k][r] = 0.f;
                         if (!PART || ((regmask >> r) & 1u))          // (uniform per wave)
-                            v[k][r] = __hip_atomic_load(slab + (long)kk * per + (long)(row < mrem ? row : -4 * kh) * ncols,
-                                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            v[k][r] = kg_pub_load(slab + (long)kk * per + (long)(row < mrem ? row : -4 * kh) * ncols);
                     }
 #pragma unroll
                 for (int k = 0; k < KB; ++k)

@@ -16,7 +16,9 @@
 //
 // These are HBM / latency bound streaming kernels (the generator is 5 % of the iteration's flops); the adjacency
 // product U A_k is formed in LDS by every workgroup (<= 3 * 11 * 25 * 25 multiply-adds).
+#include "kg_bn_math.h"
 #include "kg_common.h"
+#include "kg_handoff.h"
 
 namespace {
 
@@ -182,8 +184,7 @@ struct AdjJobs { int njobs; int beg[KG_GEN_ADJ_MAX_JOBS + 1]; KgGenAdjJob job[KG
 __global__ __launch_bounds__(NT) void kg_gen_adj_finish_kernel(const AdjJobs js) {
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= js.beg[js.njobs]) return;
-    int ji = 0;
-    while (ji + 1 < js.njobs && i >= js.beg[ji + 1]) ++ji;
+    const int ji = kg_job_of(js.beg, js.njobs, i);       // (an element's job, not a workgroup's)
     const KgGenAdjJob& j = js.job[ji];
     const int e = i - js.beg[ji];
     const int V = j.V, Vc = j.Vc;
@@ -269,11 +270,9 @@ __global__ __launch_bounds__(NT) void kg_gen_tail_stats_kernel(const KgGenTailAr
             for (int q = 0; q < 4; ++q) {
                 float tq = 0.f;
                 for (int w = 0; w < NT / 64; ++w) tq += red[q][w];
-                __hip_atomic_store(part + p * 4 + q, tq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                kg_pub_store(part + p * 4 + q, tq);
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const int tk = __hip_atomic_fetch_add(a.counters + c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last = (tk == P - 1);
+            last = kg_ticket_draw(a.counters + c, P);
         }
         __syncthreads();
         if (!last) return;
@@ -281,7 +280,7 @@ __global__ __launch_bounds__(NT) void kg_gen_tail_stats_kernel(const KgGenTailAr
         // them - deterministic, and not a chain of P dependent loads in one lane (50 chunks: ~12 us)
         for (int k = tid; k < P; k += NT)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) t[q] += __hip_atomic_load(part + k * 4 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int q = 0; q < 4; ++q) t[q] += kg_pub_load(part + k * 4 + q);
         __syncthreads();                    // red is read by thread 0 above
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -302,26 +301,11 @@ __global__ __launch_bounds__(NT) void kg_gen_tail_stats_kernel(const KgGenTailAr
     }
     const float inv_n = 1.f / (float)ncols;
     float at = 1.f, bt = 0.f, ct = 0.f, ar = 1.f, br = 0.f, cr = 0.f;
-    if (bn_t) {
-        const float rstd = a.rstd_t[c], q = t[1] * rstd;
-        at = (a.gamma_t ? a.gamma_t[c] : 1.f) * rstd;
-        bt = -at * rstd * q * inv_n;
-        ct = -at * t[0] * inv_n - bt * mt;
-        if (a.dgamma_t) a.dgamma_t[c] += q;
-        if (a.dbeta_t) a.dbeta_t[c] += t[0];
-    }
-    if (bn_r) {
-        const float rstd = a.rstd_r[c], q = t[2] * rstd;
-        ar = (a.gamma_r ? a.gamma_r[c] : 1.f) * rstd;
-        br = -ar * rstd * q * inv_n;
-        cr = -ar * t[0] * inv_n - br * mr;
-        if (a.dgamma_r) a.dgamma_r[c] += q;
-        if (a.dbeta_r) a.dbeta_r[c] += t[0];
-    }
+    if (bn_t) kg_tail_bwd_branch(at, bt, ct, c, t[0], t[1], inv_n, a.rstd_t, a.mean_t, a.gamma_t, a.dgamma_t, a.dbeta_t);
+    if (bn_r) kg_tail_bwd_branch(ar, br, cr, c, t[0], t[2], inv_n, a.rstd_r, a.mean_r, a.gamma_r, a.dgamma_r, a.dbeta_r);
     if (a.noise && a.dnw) a.dnw[c] += t[3];
     a.coef[0 * a.C + c] = at; a.coef[1 * a.C + c] = bt; a.coef[2 * a.C + c] = ct;
     a.coef[3 * a.C + c] = ar; a.coef[4 * a.C + c] = br; a.coef[5 * a.C + c] = cr;
-    if (P > 1) a.counters[c] = 0;
 }
 
 __global__ __launch_bounds__(NT) void kg_gen_tail_apply_kernel(const KgGenTailArgs a, const FastDiv ld) {

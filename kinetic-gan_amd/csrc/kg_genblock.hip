@@ -26,7 +26,9 @@
 //
 // Inference (kg_genblock_infer): in eval mode the BatchNorm coefficients are inputs, so the same stages end in
 // the block's own normalise + noise + activation - no statistics, no tape, no workspace, no ticket, no pending tail.
+#include "kg_bn_math.h"
 #include "kg_common.h"
+#include "kg_handoff.h"
 
 namespace {
 
@@ -541,20 +543,14 @@ __global__ __launch_bounds__(NT) void kg_genblock_fwd_kernel(const KgGenBlockArg
         q = gb_seg_sum(q, P);
         if (live && slot == 0) {
             float* part = a.ws + ((long)(br * a.N + n) * C + c) * 2;
-            __hip_atomic_store(part + 0, mean, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(part + 1, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            kg_pub_store(part + 0, mean);
+            kg_pub_store(part + 1, q);
         }
     }
     GB_STAMP(0, 6);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const int tk = __hip_atomic_fetch_add(a.counters, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (tk == (int)gridDim.x - 1);
-    }
-    __syncthreads();
+    const bool is_last = kg_arrive_last(a.counters, (int)gridDim.x, &last);
     GB_STAMP(0, 7);
-    if (!last) { GB_STORE_TAPE(); return; }
+    if (!is_last) { GB_STORE_TAPE(); return; }
     // The last workgroup to arrive merges the samples: thread (branch, batch, channel) takes the samples of its batch 32 at
     // a time - 64 loads in flight, consecutive channels in consecutive lanes - forms the chunk's pooled (mean, M2) from the
     // equal-sized samples (mean = average of the means, M2 = sum [M2_s + L (mean_s - mean)^2]) and merges chunks in order
@@ -584,8 +580,8 @@ __global__ __launch_bounds__(NT) void kg_genblock_fwd_kernel(const KgGenBlockArg
 #pragma unroll
                 for (int i = 0; i < SB; ++i) {
                     const int sidx = s0 + i < h ? s0 + i : h - 1;
-                    mk[i] = __hip_atomic_load(part + (long)sidx * C * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    qk[i] = __hip_atomic_load(part + (long)sidx * C * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    mk[i] = kg_pub_load(part + (long)sidx * C * 2);
+                    qk[i] = kg_pub_load(part + (long)sidx * C * 2 + 1);
                 }
                 const int cnt = h - s0 < SB ? h - s0 : SB;
                 float sm = 0.f;
@@ -598,10 +594,7 @@ __global__ __launch_bounds__(NT) void kg_genblock_fwd_kernel(const KgGenBlockArg
                     const float dd = mk[i] - cm;
                     cq += i < cnt ? fmaf((float)Nf * dd, dd, qk[i]) : 0.f;
                 }
-                const float nb = (float)cnt * (float)Nf, n_new = n_tot + nb, delta = cm - mean;
-                mean += delta * (nb / n_new);
-                M2 += cq + delta * delta * (n_tot * nb / n_new);
-                n_tot = n_new;
+                kg_chan_merge(n_tot, mean, M2, (float)cnt * (float)Nf, cm, cq);
             }
             MV_[((br * a.groups + g) * C + c) * 2 + 0] = mean;
             MV_[((br * a.groups + g) * C + c) * 2 + 1] = M2 / n_tot;
@@ -617,22 +610,12 @@ __global__ __launch_bounds__(NT) void kg_genblock_fwd_kernel(const KgGenBlockArg
         const float n_tot = (float)h * (float)Nf;
         for (int g = 0; g < a.groups; ++g) {
             const float mean = MV_[((br * a.groups + g) * C + c) * 2 + 0], var = MV_[((br * a.groups + g) * C + c) * 2 + 1];
-            const float rstd = 1.f / sqrtf(var + bl.eps);
-            const float scale = gam * rstd;
-            const float shift = bet - mean * scale;
-            float* coef = bl.coef + (long)g * 4 * C;
-            coef[0 * C + c] = scale;
-            coef[1 * C + c] = shift;
-            coef[2 * C + c] = mean;
-            coef[3 * C + c] = rstd;
-            const float unb = var * (n_tot / (n_tot > 1.f ? n_tot - 1.f : 1.f));
-            rm = (1.f - bl.momentum) * rm + bl.momentum * mean;
-            rv = (1.f - bl.momentum) * rv + bl.momentum * unb;
+            kg_bn_fwd_coef(bl.coef + (long)g * 4 * C, C, c, mean, var, gam, bet, bl.eps);
+            kg_bn_running_update(rm, rv, bl.momentum, mean, var, n_tot);
         }
         if (bl.running_mean) { bl.running_mean[c] = rm; bl.running_var[c] = rv; }
         if (bl.num_batches_tracked && c == 0) *bl.num_batches_tracked += a.groups;
     }
-    if (tid == 0) __hip_atomic_store(a.counters, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     GB_STORE_TAPE();
 }
 
@@ -833,17 +816,21 @@ __global__ __launch_bounds__(NT) void kg_genblock_bwd_kernel(const KgGenBlockBwd
             }
             s0 = gb_seg_sum(s0, P); s1 = gb_seg_sum(s1, P); s2 = gb_seg_sum(s2, P); s3 = gb_seg_sum(s3, P);
             if (live && slot == 0) {
-                __hip_atomic_store(part + c * 4 + 0, s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(part + c * 4 + 1, s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(part + c * 4 + 2, s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(part + c * 4 + 3, s3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                kg_pub_store(part + c * 4 + 0, s0);
+                kg_pub_store(part + c * 4 + 1, s1);
+                kg_pub_store(part + c * 4 + 2, s2);
+                kg_pub_store(part + c * 4 + 3, s3);
             }
         }
         GB_STAMP(1, 6);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // kg_arrive_last, spelled out from its pieces, with the reset at the END of the last arriver's work: this kernel has no
+        // scalar register to spare, and with the helper call, or with the reset at the draw, the compiler fetched the tail's
+        // argument lines in the prologue of EVERY workgroup and parked 8-38 more SGPRs in VGPR lanes (G3 / G4: +0.3-0.5 us
+        // per launch, profiles/lastarriver_refactor_resources.log).  In this form the kernel's code is the earlier one's.
+        kg_pub_drain();
         __syncthreads();
         if (tid == 0) {
-            const int tk = __hip_atomic_fetch_add(a.counters, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int tk = kg_ticket_number_(a.counters);
             last = (tk == (int)gridDim.x - 1);
         }
         __syncthreads();
@@ -867,7 +854,7 @@ __global__ __launch_bounds__(NT) void kg_genblock_bwd_kernel(const KgGenBlockBwd
                     const int sidx = s0 + i * P < a.N ? s0 + i * P : 0;
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-                        v[i][q] = __hip_atomic_load(a.ws + ((long)sidx * Cin + c) * 4 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        v[i][q] = kg_pub_load(a.ws + ((long)sidx * Cin + c) * 4 + q);
                 }
 #pragma unroll
                 for (int i = 0; i < SB; ++i)
@@ -878,28 +865,14 @@ __global__ __launch_bounds__(NT) void kg_genblock_bwd_kernel(const KgGenBlockBwd
             for (int q = 0; q < 4; ++q) t[q] = gb_seg_sum(t[q], P);
             if (live && slot == 0) {
                 float at = 1.f, bt = 0.f, ct = 0.f, ar = 1.f, br = 0.f, cr = 0.f;
-                if (pbn_t) {
-                    const float rstd = a.prstd_t[c], q = t[1] * rstd, mt = a.pmean_t[c];
-                    at = (a.pgamma_t ? a.pgamma_t[c] : 1.f) * rstd;
-                    bt = -at * rstd * q * inv_n;
-                    ct = -at * t[0] * inv_n - bt * mt;
-                    if (a.dgamma_t) a.dgamma_t[c] += q;
-                    if (a.dbeta_t) a.dbeta_t[c] += t[0];
-                }
-                if (pbn_r) {
-                    const float rstd = a.prstd_r[c], q = t[2] * rstd, mr = a.pmean_r[c];
-                    ar = (a.pgamma_r ? a.pgamma_r[c] : 1.f) * rstd;
-                    br = -ar * rstd * q * inv_n;
-                    cr = -ar * t[0] * inv_n - br * mr;
-                    if (a.dgamma_r) a.dgamma_r[c] += q;
-                    if (a.dbeta_r) a.dbeta_r[c] += t[0];
-                }
+                if (pbn_t) kg_tail_bwd_branch(at, bt, ct, c, t[0], t[1], inv_n, a.prstd_t, a.pmean_t, a.pgamma_t, a.dgamma_t, a.dbeta_t);
+                if (pbn_r) kg_tail_bwd_branch(ar, br, cr, c, t[0], t[2], inv_n, a.prstd_r, a.pmean_r, a.pgamma_r, a.dgamma_r, a.dbeta_r);
                 if (a.pnoise && a.dnw) a.dnw[c] += t[3];
                 a.pcoef[0 * Cin + c] = at; a.pcoef[1 * Cin + c] = bt; a.pcoef[2 * Cin + c] = ct;
                 a.pcoef[3 * Cin + c] = ar; a.pcoef[4 * Cin + c] = br; a.pcoef[5 * Cin + c] = cr;
             }
         }
-        if (tid == 0) __hip_atomic_store(a.counters, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) kg_ticket_reset_(a.counters);
         GB_STORE_GX();
     }
 }

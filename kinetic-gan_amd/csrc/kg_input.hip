@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "kg_common.h"
+#include "kg_handoff.h"
 
 namespace {
 
@@ -98,7 +99,7 @@ __device__ __forceinline__ void store4(float* dst, long e0, long len, const floa
 }
 
 __global__ __launch_bounds__(SI_NT) void kg_step_inputs_kernel(StepDev a) {
-    const long long s = __hip_atomic_load(a.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const long long s = kg_pub_load(a.step);
     const unsigned blk = blockIdx.x;
     const unsigned s_lo = (unsigned)((unsigned long long)s), s_hi = (unsigned)((unsigned long long)s >> 32);
 
@@ -192,13 +193,7 @@ __global__ __launch_bounds__(SI_NT) void kg_step_inputs_kernel(StepDev a) {
 
     // last arriver advances the counter (every workgroup has read it before it draws its ticket)
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const int t = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (t == (int)gridDim.x - 1) {
-            __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.step, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    if (threadIdx.x == 0 && kg_ticket_draw(a.ticket, (int)gridDim.x)) kg_pub_store(a.step, s + 1);
 }
 
 __global__ __launch_bounds__(64) void kg_loss_append_kernel(float* ring, long ring_len, const long long* step, const float* d_loss,
@@ -222,7 +217,7 @@ struct SampleDev {
 };
 
 __global__ __launch_bounds__(SI_NT) void kg_sample_inputs_kernel(SampleDev a) {
-    const long long s = __hip_atomic_load(a.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const long long s = kg_pub_load(a.step);
     const unsigned blk = blockIdx.x;
     const unsigned s_lo = (unsigned)((unsigned long long)s), s_hi = (unsigned)((unsigned long long)s >> 32);
     const int k = blk < a.b[0] ? 0 : (blk < a.b[1] ? 1 : 2);
@@ -238,13 +233,7 @@ __global__ __launch_bounds__(SI_NT) void kg_sample_inputs_kernel(SampleDev a) {
     }
     // last arriver advances the counter (every workgroup has read it before it draws its ticket): nobody waits
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const int t = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (t == (int)gridDim.x - 1) {
-            __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.step, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    if (threadIdx.x == 0 && kg_ticket_draw(a.ticket, (int)gridDim.x)) kg_pub_store(a.step, s + 1);
 }
 
 }  // namespace

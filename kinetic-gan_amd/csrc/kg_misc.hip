@@ -3,7 +3,9 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include "kg_bn_math.h"
 #include "kg_common.h"
+#include "kg_handoff.h"
 
 // ---- error string ---------------------------------------------------------------------------
 static thread_local char kg_err_buf[512] = "";
@@ -181,18 +183,14 @@ constexpr int RS_MANY_MAX = 24;
 struct RowsumMany { int njobs; int beg[RS_MANY_MAX + 1]; int P[RS_MANY_MAX]; KgRowsumArgs job[RS_MANY_MAX]; };
 
 __global__ __launch_bounds__(NT) void kg_rowsum_many_kernel(const RowsumMany m) {
-    int ji = 0;
-#pragma unroll 1
-    while (ji + 1 < m.njobs && (int)blockIdx.x >= m.beg[ji + 1]) ++ji;      // (uniform)
+    const int ji = kg_job_of_block(m.beg, m.njobs);
     const int local = blockIdx.x - m.beg[ji];
     const int P = m.P[ji];
     rowsum_part(m.job[ji], P, local % P, local / P);
 }
 
 __global__ __launch_bounds__(64) void kg_rowsum_many_finish(const RowsumMany m) {
-    int ji = 0;
-#pragma unroll 1
-    while (ji + 1 < m.njobs && (int)blockIdx.x >= m.beg[ji + 1]) ++ji;      // (uniform); beg: finish rows here
+    const int ji = kg_job_of_block(m.beg, m.njobs);      // beg: finish rows here
     rowsum_finish_row(m.job[ji], m.P[ji], blockIdx.x - m.beg[ji]);
 }
 
@@ -231,22 +229,14 @@ __global__ __launch_bounds__(BT) void kg_bn_fwd_kernel(const KgBnArgs a) {
         var = a.running_var[c];
     }
     if (tid == 0) {
-        const float rstd = 1.f / sqrtf(var + a.eps);
-        const float scale = a.gamma ? a.gamma[c] * rstd : rstd;
-        const float shift = (a.beta ? a.beta[c] : 0.f) - mean * scale;
-        a.coef[0 * a.C + c] = scale;
-        a.coef[1 * a.C + c] = shift;
-        a.coef[2 * a.C + c] = mean;
-        a.coef[3 * a.C + c] = rstd;
+        kg_bn_fwd_coef(a.coef, a.C, c, mean, var, a.gamma ? a.gamma[c] : 1.f, a.beta ? a.beta[c] : 0.f, a.eps);
         if (a.training && a.running_mean) {
             // momentum < 0: torch's momentum=None, the cumulative moving average with factor 1 / (batches seen so far,
             // this one included) - formed from the LIVE counter, which a trailing one-thread launch increments (all
             // channels' workgroups read the same, not yet incremented, value)
             const float m = a.momentum >= 0.f ? a.momentum
                                               : 1.f / (float)((a.num_batches_tracked ? *a.num_batches_tracked : 0) + 1);
-            const float unb = var * ((float)ncols / (float)(ncols > 1 ? ncols - 1 : 1));
-            a.running_mean[c] = (1.f - m) * a.running_mean[c] + m * mean;
-            a.running_var[c] = (1.f - m) * a.running_var[c] + m * unb;
+            kg_bn_running_update(a.running_mean[c], a.running_var[c], m, mean, var, ncols);
         }
         if (a.training && a.num_batches_tracked && c == 0 && a.momentum >= 0.f) *a.num_batches_tracked += 1;
     }
@@ -270,9 +260,7 @@ struct BnMany { int njobs; int beg[BN_MANY_MAX + 1]; int P[BN_MANY_MAX]; int cbe
 __global__ __launch_bounds__(NT) void kg_bn_fwd_many_kernel(const BnMany m) {
     __shared__ float red[2][NT / 64];
     __shared__ int last;
-    int ji = 0;
-#pragma unroll 1
-    while (ji + 1 < m.njobs && (int)blockIdx.x >= m.beg[ji + 1]) ++ji;      // (uniform)
+    const int ji = kg_job_of_block(m.beg, m.njobs);
     const KgBnArgs& a = m.job[ji].a;
     const int G = m.job[ji].groups, P = m.P[ji];
     int local = blockIdx.x - m.beg[ji];
@@ -310,14 +298,11 @@ __global__ __launch_bounds__(NT) void kg_bn_fwd_many_kernel(const BnMany m) {
     block_sum2<NT>(q2, dummy, red);
     float* const part = m.ws + m.wbeg[ji] + ((long)c * G * P) * 2;     // [G][P][2] of this channel
     if (tid == 0) {
-        // agent-scope (write-through) stores, acknowledged before the ticket is drawn; the merging workgroup reads
-        // them with agent-scope loads.  (A __threadfence() here writes back / invalidates the whole L2 per workgroup:
-        // measured 32 us for a 1024-workgroup launch.)
-        __hip_atomic_store(part + ((long)q * P + p) * 2 + 0, mloc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(part + ((long)q * P + p) * 2 + 1, q2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = __hip_atomic_fetch_add(m.counters + m.cbeg[ji] + c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (t == G * P - 1);
+        // kg_handoff.h.  (A __threadfence() here writes back / invalidates the whole L2 per workgroup: measured 32 us for
+        // a 1024-workgroup launch.)
+        kg_pub_store(part + ((long)q * P + p) * 2 + 0, mloc);
+        kg_pub_store(part + ((long)q * P + p) * 2 + 1, q2);
+        last = kg_ticket_draw(m.counters + m.cbeg[ji] + c, G * P);
     }
     __syncthreads();
     if (!last) return;
@@ -327,7 +312,7 @@ __global__ __launch_bounds__(NT) void kg_bn_fwd_many_kernel(const BnMany m) {
     const int npart = G * P * 2;
     const bool staged = npart <= BN_PART_LDS;
     if (staged) {
-        for (int i = tid; i < npart; i += NT) pl[i] = __hip_atomic_load(part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = tid; i < npart; i += NT) pl[i] = kg_pub_load(part + i);
         __syncthreads();
     }
     if (tid != 0) return;
@@ -336,34 +321,15 @@ __global__ __launch_bounds__(NT) void kg_bn_fwd_many_kernel(const BnMany m) {
         for (int k = 0; k < P; ++k) {
             const long kb = (long)k * BN_CHUNK;
             const float nb = (float)((kb + BN_CHUNK < ncols ? kb + BN_CHUNK : ncols) - kb);
-            const float mk = staged ? pl[(g * P + k) * 2 + 0]
-                                    : __hip_atomic_load(part + ((long)g * P + k) * 2 + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const float qk = staged ? pl[(g * P + k) * 2 + 1]
-                                    : __hip_atomic_load(part + ((long)g * P + k) * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const float n_new = n_tot + nb;
-            const float delta = mk - mean;
-            mean += delta * (nb / n_new);
-            M2 += qk + delta * delta * (n_tot * nb / n_new);
-            n_tot = n_new;
+            const float mk = staged ? pl[(g * P + k) * 2 + 0] : kg_pub_load(part + ((long)g * P + k) * 2 + 0);
+            const float qk = staged ? pl[(g * P + k) * 2 + 1] : kg_pub_load(part + ((long)g * P + k) * 2 + 1);
+            kg_chan_merge(n_tot, mean, M2, nb, mk, qk);
         }
         const float var = M2 / n_tot;
-        const float rstd = 1.f / sqrtf(var + a.eps);
-        const float scale = a.gamma ? a.gamma[c] * rstd : rstd;
-        const float shift = (a.beta ? a.beta[c] : 0.f) - mean * scale;
-        float* coef = a.coef + (long)g * 4 * a.C;
-        coef[0 * a.C + c] = scale;
-        coef[1 * a.C + c] = shift;
-        coef[2 * a.C + c] = mean;
-        coef[3 * a.C + c] = rstd;
-        if (a.running_mean) {
-            const float mo = a.momentum;
-            const float unb = var * (n_tot / (n_tot > 1.f ? n_tot - 1.f : 1.f));
-            a.running_mean[c] = (1.f - mo) * a.running_mean[c] + mo * mean;
-            a.running_var[c] = (1.f - mo) * a.running_var[c] + mo * unb;
-        }
+        kg_bn_fwd_coef(a.coef + (long)g * 4 * a.C, a.C, c, mean, var, a.gamma ? a.gamma[c] : 1.f, a.beta ? a.beta[c] : 0.f, a.eps);
+        if (a.running_mean) kg_bn_running_update(a.running_mean[c], a.running_var[c], a.momentum, mean, var, n_tot);
     }
     if (a.num_batches_tracked && c == 0) *a.num_batches_tracked += G;
-    m.counters[m.cbeg[ji] + c] = 0;
 }
 
 template <int BT>
@@ -384,20 +350,7 @@ __global__ __launch_bounds__(BT) void kg_bn_bwd_kernel(const KgBnArgs a) {
         s1 = fmaf(gv, xp[(long)w.n * a.x_sN + w.r] - mean, s1);
     }
     block_sum2<NT>(s0, s1, red);
-    if (tid == 0) {
-        const float q = s1 * rstd;                                   // sum g * xhat
-        const float ga = (a.gamma ? a.gamma[c] : 1.f) * rstd;
-        float b = 0.f, cc = 0.f;
-        if (a.training) {
-            b = -ga * rstd * q / (float)ncols;
-            cc = -ga * s0 / (float)ncols - b * mean;
-        }
-        a.coef[0 * a.C + c] = ga;
-        a.coef[1 * a.C + c] = b;
-        a.coef[2 * a.C + c] = cc;
-        a.coef[3 * a.C + c] = q;
-        a.coef[4 * a.C + c] = s0;
-    }
+    if (tid == 0) kg_bn_bwd_coef(a.coef, a.C, c, s0, s1, mean, rstd, a.gamma ? a.gamma[c] : 1.f, a.training, (float)ncols);
 }
 
 // The backward sums of several BatchNorm layers (the two of a generator block share the incoming gradient) in one
@@ -409,9 +362,7 @@ struct BnBwdMany { int njobs; int beg[BN_MANY_MAX + 1]; int P[BN_MANY_MAX]; int 
 __global__ __launch_bounds__(NT) void kg_bn_bwd_many_kernel(const BnBwdMany m) {
     __shared__ float red[2][NT / 64];
     __shared__ int last;
-    int ji = 0;
-#pragma unroll 1
-    while (ji + 1 < m.njobs && (int)blockIdx.x >= m.beg[ji + 1]) ++ji;      // (uniform)
+    const int ji = kg_job_of_block(m.beg, m.njobs);
     const KgBnArgs& a = m.job[ji];
     const int P = m.P[ji];
     const int local = blockIdx.x - m.beg[ji];
@@ -445,32 +396,18 @@ __global__ __launch_bounds__(NT) void kg_bn_bwd_many_kernel(const BnBwdMany m) {
     block_sum2<NT>(s0, s1, red);
     float* const part = m.ws + m.wbeg[ji] + (long)c * P * 2;
     if (tid == 0) {
-        __hip_atomic_store(part + p * 2 + 0, s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(part + p * 2 + 1, s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = __hip_atomic_fetch_add(m.counters + m.cbeg[ji] + c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (t == P - 1);
+        kg_pub_store(part + p * 2 + 0, s0);
+        kg_pub_store(part + p * 2 + 1, s1);
+        last = kg_ticket_draw(m.counters + m.cbeg[ji] + c, P);
     }
     __syncthreads();
     if (!last || tid != 0) return;
     float t0 = 0.f, t1 = 0.f;
     for (int k = 0; k < P; ++k) {
-        t0 += __hip_atomic_load(part + k * 2 + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t1 += __hip_atomic_load(part + k * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        t0 += kg_pub_load(part + k * 2 + 0);
+        t1 += kg_pub_load(part + k * 2 + 1);
     }
-    const float q = t1 * rstd;                                   // sum g * xhat
-    const float ga = (a.gamma ? a.gamma[c] : 1.f) * rstd;
-    float b = 0.f, cc = 0.f;
-    if (a.training) {
-        b = -ga * rstd * q / (float)ncols;
-        cc = -ga * t0 / (float)ncols - b * mean;
-    }
-    a.coef[0 * a.C + c] = ga;
-    a.coef[1 * a.C + c] = b;
-    a.coef[2 * a.C + c] = cc;
-    a.coef[3 * a.C + c] = q;
-    a.coef[4 * a.C + c] = t0;
-    m.counters[m.cbeg[ji] + c] = 0;
+    kg_bn_bwd_coef(a.coef, a.C, c, t0, t1, mean, rstd, a.gamma ? a.gamma[c] : 1.f, a.training, (float)ncols);
 }
 
 // ---- pointwise -------------------------------------------------------------------------------
@@ -772,40 +709,46 @@ extern "C" int kg_bn_bwd(const KgBnArgs* a, void* stream) {
     return kg_launch_status("kg_bn_bwd");
 }
 
-extern "C" int64_t kg_bn_bwd_many_workspace_bytes(const KgBnArgs* jobs, int32_t njobs) {
-    if (jobs == nullptr || njobs < 1 || njobs > BN_MANY_MAX) { kg_set_error("kg_bn_bwd_many: 1..%d jobs", BN_MANY_MAX); return -1; }
-    int64_t f = 0;
-    for (int i = 0; i < njobs; ++i) {
-        if (validate_bn(&jobs[i], "kg_bn_bwd_many")) return -1;
-        f += (int64_t)jobs[i].C * kg_cdiv((long)jobs[i].N * jobs[i].T * jobs[i].V, BN_CHUNK) * 2;
-    }
-    return f * (int64_t)sizeof(float);
-}
-
-extern "C" int kg_bn_bwd_many(const KgBnArgs* jobs, int32_t njobs, float* ws, int64_t ws_bytes, int32_t* counters,
-                              int32_t counters_len, void* stream) {
+// (the launcher's checks of g / mean / rstd apply with m: sizing a workspace needs the shapes alone)
+static int bn_bwd_many_layout(const KgBnArgs* jobs, int32_t njobs, BnBwdMany* m, int64_t* ws_floats, int* ncounters) {
     KG_REQUIRE(jobs != nullptr && njobs >= 1 && njobs <= BN_MANY_MAX, "kg_bn_bwd_many: 1..%d jobs", BN_MANY_MAX);
-    BnBwdMany m;
     long wg = 0, wsf = 0;
     int cb = 0;
     for (int i = 0; i < njobs; ++i) {
         const KgBnArgs* a = &jobs[i];
         if (int rc = validate_bn(a, "kg_bn_bwd_many")) return rc;
-        KG_REQUIRE(a->g && a->mean && a->rstd, "kg_bn_bwd_many: job %d null pointer", i);
+        KG_REQUIRE(!m || (a->g && a->mean && a->rstd), "kg_bn_bwd_many: job %d null pointer", i);
         const int P = kg_cdiv((long)a->N * a->T * a->V, BN_CHUNK);
-        m.beg[i] = (int)wg; m.P[i] = P; m.cbeg[i] = cb; m.wbeg[i] = wsf; m.job[i] = *a;
+        if (m) { m->beg[i] = (int)wg; m->P[i] = P; m->cbeg[i] = cb; m->wbeg[i] = wsf; m->job[i] = *a; }
         wg += (long)a->C * P;
         wsf += (long)a->C * P * 2;
         cb += a->C;
     }
-    KG_REQUIRE(wg < (1L << 31), "kg_bn_bwd_many: grid too large");
+    KG_REQUIRE(!m || wg < (1L << 31), "kg_bn_bwd_many: grid too large");
+    if (m) { m->beg[njobs] = (int)wg; m->njobs = njobs; }
+    *ws_floats = wsf;
+    *ncounters = cb;
+    return 0;
+}
+
+extern "C" int64_t kg_bn_bwd_many_workspace_bytes(const KgBnArgs* jobs, int32_t njobs) {
+    int64_t wsf = 0;
+    int nc = 0;
+    if (bn_bwd_many_layout(jobs, njobs, nullptr, &wsf, &nc)) return -1;
+    return wsf * (int64_t)sizeof(float);
+}
+
+extern "C" int kg_bn_bwd_many(const KgBnArgs* jobs, int32_t njobs, float* ws, int64_t ws_bytes, int32_t* counters,
+                              int32_t counters_len, void* stream) {
+    BnBwdMany m;
+    int64_t wsf = 0;
+    int nc = 0;
+    if (int rc = bn_bwd_many_layout(jobs, njobs, &m, &wsf, &nc)) return rc;
     KG_REQUIRE(ws != nullptr && ws_bytes >= wsf * (int64_t)sizeof(float), "kg_bn_bwd_many: workspace too small");
-    KG_REQUIRE(counters != nullptr && counters_len >= cb, "kg_bn_bwd_many: %d zeroed counters needed", cb);
-    m.beg[njobs] = (int)wg;
-    m.njobs = njobs;
+    KG_REQUIRE(counters != nullptr && counters_len >= nc, "kg_bn_bwd_many: %d zeroed counters needed", nc);
     m.ws = ws;
     m.counters = counters;
-    hipLaunchKernelGGL(kg_bn_bwd_many_kernel, dim3((int)wg), dim3(NT), 0, (hipStream_t)stream, m);
+    hipLaunchKernelGGL(kg_bn_bwd_many_kernel, dim3(m.beg[njobs]), dim3(NT), 0, (hipStream_t)stream, m);
     return kg_launch_status("kg_bn_bwd_many");
 }
 

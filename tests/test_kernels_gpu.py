@@ -842,7 +842,10 @@ def test_rowsum_product_row_alone():
 
 
 @pytest.mark.parametrize("shapes", [[(4, 3, 32, 25), (4, 3, 32, 25)], [(6, 256, 4, 5)], [(64, 32, 16, 11), (64, 32, 16, 11)],
-                                    [(2, 3, 64, 25), (2, 70, 9, 7), (8, 5, 300, 3), (4, 1, 1, 1)]])
+                                    [(2, 3, 64, 25), (2, 70, 9, 7), (8, 5, 300, 3), (4, 1, 1, 1)],
+                                    # 514 chunks per stacked batch: 2 * 514 * 2 = 2056 partials > BN_PART_LDS = 2048, the smallest
+                                    # shape whose last arriver merges straight from memory instead of staging the partials in LDS
+                                    [(2, 1, 8192, 257)]])
 def test_bn_fwd_many_equals_per_group_launches(shapes):
     """kg_bn_fwd_many (chunked partials + last-arriver merge, several layers and two stacked batches per launch)
     against torch.nn.BatchNorm2d applied to the stacked batches one after the other: coefficients per batch, running
