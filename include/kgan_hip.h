@@ -809,6 +809,46 @@ int     kg_prdc_radii(const KgPrdcRadiiArgs* a, void* stream);
 int64_t kg_prdc_sets_workspace_bytes(const KgPrdcSetsArgs* a);   /* < 0 for invalid shapes                           */
 int     kg_prdc_sets(const KgPrdcSetsArgs* a, void* stream);
 
+/* ---- exact k nearest neighbours between two point sets (additive, ABI v9; DESIGN.md 22, csrc/kg_nn.hip) -------------------
+ * For every class c: Q query points and N base points of dimension D = d_outer*d_inner, read through strides (elements) as
+ * kg_prdc reads its sets:
+ *   q_i[(o, e)] = f_q(query + c*q_sc + i*q_sp + o*q_so + e)     (o < d_outer, e < d_inner: the inner run is contiguous)
+ * and likewise b_j with f_b.  f is the identity, or with q_affine / b_affine != 0 the affine (x * scale) + shift in two
+ * separately rounded fp32 operations (no FMA: the arithmetic of kg_step_inputs) - an unnormalised array searched in place
+ * gives the bits of the normalised one.  With d2(a, b) = sum_d (a_d - b_d)^2 (direct differences in fp32, one fmaf per
+ * dimension, d ascending: the chain of kg_prdc, never |a|^2 + |b|^2 - 2ab, so near-copies do not cancel):
+ *   (d2[c, i, r], idx[c, i, r]), r < k = the k smallest of { (d2(q_i, b_j), j) : j < N, j != i if exclude_self } in the
+ *   total order (d2, j) ascending: ties go to the lower base index, a duplicate is a neighbour at distance 0.
+ * exclude_self leaves pair i == j out by INDEX (one set searched against itself: query and base name the same points).
+ * Two launches: search (a workgroup = one class x a row tile of `tile` queries x one of `split` chunks of base points; the
+ * k best (d2, j) of every row are kept in LDS and written to ws), merge (a wave per query ranks its split * k candidates).
+ * No atomics, no tickets, no Q x N matrix.  tile (0 automatic, 32, 64) and split (0 automatic, else that many chunks of
+ * ceil(N / split) points, at most KG_NN_MAX_SPLIT and N) only choose the plan: every plan gives the same bits.
+ * ws is kg_nn_workspace_bytes(a) = classes * Q * split * k * 8 bytes (split: the plan's) and may hold anything.
+ * Every pointer is read when the launches run; nothing is synchronised; capturable on one stream.
+ * Rejected (< 0, kg_last_error() names the field): null query / base / idx / d2 / ws; Q, N, classes, d_outer or d_inner < 1;
+ * Q or N above KG_NN_MAX_POINTS; k < 1, k > KG_NN_MAX_K or k > N - (exclude_self ? 1 : 0); tile not 0 / 32 / 64; split
+ * outside [0, min(KG_NN_MAX_SPLIT, N)]; 2^24 workgroups or more in one launch; ws_bytes too small.                         */
+#define KG_NN_MAX_K 32
+#define KG_NN_MAX_POINTS 16777216   /* per class and side (2^24); no count is formed, so there is no n*m bound as in PRDC    */
+#define KG_NN_MAX_SPLIT 32
+typedef struct KgNnArgs {
+    const float* query;  int64_t q_sc, q_sp, q_so;  /* class, point, outer-dimension strides (elements)                   */
+    const float* base;   int64_t b_sc, b_sp, b_so;
+    int32_t Q, N;                   /* query / base points per class                                                   */
+    int32_t d_outer, d_inner;       /* D = d_outer*d_inner; element (o, e) at + o*so + e                                */
+    int32_t classes, k;
+    int32_t exclude_self;           /* != 0: pair i == j is left out by index                                          */
+    int32_t q_affine, b_affine;     /* != 0: that side is read as (x * scale) + shift                                  */
+    float q_scale, q_shift, b_scale, b_shift;
+    int32_t tile, split;            /* 0 = automatic, or a forced plan (tests)                                         */
+    int32_t* idx;                   /* (classes, Q, k): base index inside the class                                    */
+    float* d2;                      /* (classes, Q, k): squared distances, non-decreasing along k                      */
+    void* ws;  int64_t ws_bytes;
+} KgNnArgs;
+int64_t kg_nn_workspace_bytes(const KgNnArgs* a);   /* < 0 for invalid shapes                                          */
+int     kg_nn(const KgNnArgs* a, void* stream);
+
 /* ---- Frechet distance of pose / motion / caller features in fp64 (additive, ABI v9; DESIGN.md 18, csrc/kg_frechet.hip) -----
  * For every class c: a real set of n and a fake set of m samples of `frames` frames, a frame being d = d_outer*d_inner <= 96
  * floats read through strides (elements):

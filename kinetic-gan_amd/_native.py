@@ -352,6 +352,22 @@ class _PrdcSetsArgs(C.Structure):
                 ("counts", C.c_void_p), ("values", c_f32p), ("mean", c_f32p),
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
+NN_MAX_K = 32
+NN_MAX_POINTS = 1 << 24
+NN_MAX_SPLIT = 32
+
+
+class _NnArgs(C.Structure):
+    _fields_ = [("query", c_f32p), ("q_sc", C.c_int64), ("q_sp", C.c_int64), ("q_so", C.c_int64),
+                ("base", c_f32p), ("b_sc", C.c_int64), ("b_sp", C.c_int64), ("b_so", C.c_int64),
+                ("Q", C.c_int32), ("N", C.c_int32), ("d_outer", C.c_int32), ("d_inner", C.c_int32),
+                ("classes", C.c_int32), ("k", C.c_int32), ("exclude_self", C.c_int32),
+                ("q_affine", C.c_int32), ("b_affine", C.c_int32),
+                ("q_scale", C.c_float), ("q_shift", C.c_float), ("b_scale", C.c_float), ("b_shift", C.c_float),
+                ("tile", C.c_int32), ("split", C.c_int32),
+                ("idx", C.c_void_p), ("d2", c_f32p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
 FRECHET_MAX_DIM = 96
 
 
@@ -568,6 +584,8 @@ EXPORTS = {
     "kg_prdc_radii": (C.c_int, [C.POINTER(_PrdcRadiiArgs), C.c_void_p]),
     "kg_prdc_sets_workspace_bytes": (C.c_int64, [C.POINTER(_PrdcSetsArgs)]),
     "kg_prdc_sets": (C.c_int, [C.POINTER(_PrdcSetsArgs), C.c_void_p]),
+    "kg_nn_workspace_bytes": (C.c_int64, [C.POINTER(_NnArgs)]),
+    "kg_nn": (C.c_int, [C.POINTER(_NnArgs), C.c_void_p]),
     "kg_frechet_workspace_bytes": (C.c_int64, [C.POINTER(_FrechetArgs)]),
     "kg_frechet": (C.c_int, [C.POINTER(_FrechetArgs), C.c_void_p]),
     "kg_frechet_real_workspace_bytes": (C.c_int64, [C.POINTER(_FrechetRealArgs)]),
@@ -2486,6 +2504,64 @@ def prdc_sets(real: PrdcView, fakes: Sequence[torch.Tensor], f_sc: int, f_sp: in
     _count("kg_prdc_sets", 3.0 * nsets * (float(m) * m + float(n) * m) * d_outer * d_inner * classes)
     _check(lib.kg_prdc_sets(C.byref(a), _stream()), "kg_prdc_sets")
     return out
+
+
+# ---- exact k nearest neighbours between two point sets (kg_nn.hip) --------------------------------------------------------
+
+def _nn_shape(a: "_NnArgs", Q, N, d_outer, d_inner, classes, k, exclude_self, q_affine, b_affine, tile, split):
+    a.Q, a.N, a.d_outer, a.d_inner, a.classes, a.k = int(Q), int(N), int(d_outer), int(d_inner), int(classes), int(k)
+    a.exclude_self, a.tile, a.split = int(bool(exclude_self)), int(tile), int(split)
+    for pre, aff in (("q", q_affine), ("b", b_affine)):
+        if aff is not None:
+            setattr(a, pre + "_affine", 1)
+            setattr(a, pre + "_scale", float(aff[0]))
+            setattr(a, pre + "_shift", float(aff[1]))
+
+
+def nn_workspace_bytes(Q: int, N: int, d_outer: int, d_inner: int, classes: int, k: int, exclude_self: bool = False,
+                       tile: int = 0, split: int = 0) -> int:
+    """kg_nn_workspace_bytes of a shape = classes * Q * split * k * 8 with the plan's split (RuntimeError naming the field for
+    a shape kg_nn rejects); no GPU call"""
+    a = _NnArgs()
+    _nn_shape(a, Q, N, d_outer, d_inner, classes, k, exclude_self, None, None, tile, split)
+    return _query("kg_nn_workspace_bytes", a)
+
+
+def nn(query: PrdcView, base: PrdcView, Q: int, N: int, d_outer: int, d_inner: int, classes: int, k: int,
+       exclude_self: bool = False, q_affine: Optional[Tuple[float, float]] = None,
+       b_affine: Optional[Tuple[float, float]] = None, tile: int = 0, split: int = 0,
+       ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Enqueue kg_nn (search and merge launch) on the current stream; no host synchronisation.  For every class and query
+    the k base points with the smallest (squared distance, index): returns (idx (classes, Q, k) int32 - the base index
+    inside the class -, d2 (classes, Q, k) fp32) on the device.  ``query`` / ``base``: how each side is walked (the views of
+    ``prdc``); ``exclude_self``: pair i == j is left out by index; ``q_affine`` / ``b_affine``: (scale, shift), that side
+    is read as (x * scale) + shift in two roundings; ``tile`` / ``split``: 0 or a forced plan (same bits under every plan);
+    ``ws`` as in ``prdc``."""
+    for v in (query, base):
+        if v.t.dtype != torch.float32:
+            raise TypeError(f"kg_nn: fp32 only, got {v.t.dtype}")
+    a = _NnArgs()
+    _nn_shape(a, Q, N, d_outer, d_inner, classes, k, exclude_self, q_affine, b_affine, tile, split)
+    nbytes = _query("kg_nn_workspace_bytes", a)
+    _need_cuda(query.t, base.t, ws)
+    for name, v, p in (("query", query, Q), ("base", base, N)):
+        if not _prdc_extent_ok(v, p, d_outer, d_inner, classes):
+            raise ValueError(f"kg_nn: the strides of {name} reach outside its tensor")
+    dev = query.t.device
+    if ws is None:
+        ws = _workspace("kg_nn_workspace_bytes", a, dev)
+    elif not ws.is_contiguous() or ws.element_size() != 4 or ws.numel() * 4 < nbytes:
+        raise ValueError("kg_nn: ws must be a contiguous tensor of 4-byte elements, at least %d bytes" % nbytes)
+    else:
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    idx = torch.empty((classes, Q, k), dtype=torch.int32, device=dev)
+    d2 = torch.empty((classes, Q, k), dtype=torch.float32, device=dev)
+    a.query, a.q_sc, a.q_sp, a.q_so = query.t.data_ptr(), query.sc, query.sp, query.so
+    a.base, a.b_sc, a.b_sp, a.b_so = base.t.data_ptr(), base.sc, base.sp, base.so
+    a.idx, a.d2 = idx.data_ptr(), d2.data_ptr()
+    _count("kg_nn", 3.0 * float(Q) * N * d_outer * d_inner * classes)
+    _check(load_library().kg_nn(C.byref(a), _stream()), "kg_nn")
+    return idx, d2
 
 
 # ---- Frechet distance of pose / motion / caller features (kg_frechet.hip) -------------------------------------------------

@@ -27,20 +27,17 @@
 #include <math.h>
 
 #include "kg_common.h"
+#include "kg_dist_tile.h"
 
 namespace {
 
-constexpr int PR_NT = 256;      // threads of a tile workgroup: 16 x 16 micro-tiles
-constexpr int PR_KC = 32;       // dimensions staged per chunk
-constexpr int PR_PAD = 4;       // floats of padding per staged row: rows stay 16-byte aligned, row stride = 4 banks mod 32
+constexpr int PR_NT = DT_NT;    // threads of a tile workgroup, dimensions staged per chunk and row padding: the shared
+constexpr int PR_KC = DT_KC;    // tile's (kg_dist_tile.h)
+constexpr int PR_PAD = DT_PAD;
 constexpr int PR_FIN = 1024;    // threads of the finishing workgroup
 constexpr long PR_MAX_GRID = 1L << 24;  // workgroups of a tile launch (exclusive): grid x PR_NT threads stays below 2^32
 
-struct PrdcSet {
-    const float* p;
-    long sc, sp, so;
-    int n;
-};
+using PrdcSet = DistSet;
 
 struct PrdcDev {
     PrdcSet set[2];             // 0 = real, 1 = fake (its p: fake set 0)
@@ -62,69 +59,12 @@ struct PrdcFin {
     int n, m, classes, k, nsets;
 };
 
-// Stage PR_KC dimensions of TI points (points p0.. of base) into s[k][p]; zeros outside the set / dimension.
-// Lane bits of the element index e: [0,3) -> k low, [3,5) -> p low, [5,7) -> k high, [7,..) -> p high: a wave reads 64
-// contiguous bytes of each of 4 points, and the 32 lanes of a half wave write 32 different LDS banks
-// (bank = 4 k + p mod 32 with the padded row).
-template <int TI>
-__device__ __forceinline__ void prdc_stage(float (*s)[TI + PR_PAD], const float* base, long sp, long so, const FastDiv& inner,
-                                           int p0, int n, int k0, int kn) {
-    static_assert(PR_NT == 256, "the k bits of the element index must lie below the loop stride");
-    // e advances by PR_NT = 2^8 and k is made of bits [0,3) and [5,7) of e: a thread stages ONE dimension of several points
-    const int k = (threadIdx.x & 7) | ((threadIdx.x >> 2) & 24);
-    const bool kin = k < kn;
-    unsigned o = 0, r = 0;
-    if (kin) inner.divmod((unsigned)(k0 + k), o, r);
-    const float* col = base + ((long)o * so + r);
-    for (int e = threadIdx.x; e < PR_KC * TI; e += PR_NT) {
-        const int p = ((e >> 3) & 3) | ((e >> 5) & ~3);
-        const int pi = p0 + p;
-        s[k][p] = (kin && pi < n) ? col[(long)pi * sp] : 0.f;
-    }
-}
-
-// acc[r][s] += (x_{i0 + ri MI + r}[d] - y_{j0 + rj MI + s}[d])^2 over all D dimensions, d ascending
+// the tile body (kg_dist_tile.h) on two sets of this launch, the values as stored
 template <int TI, int MI>
 __device__ __forceinline__ void prdc_tile(float (&acc)[MI][MI], float (*si)[TI + PR_PAD], float (*sj)[TI + PR_PAD],
                                           const PrdcDev& a, const PrdcSet& X, const float* xb, int i0, const PrdcSet& Y,
                                           const float* yb, int j0, bool live) {
-    const int ri = threadIdx.x >> 4, rj = threadIdx.x & 15;
-#pragma unroll
-    for (int r = 0; r < MI; ++r)
-#pragma unroll
-        for (int s = 0; s < MI; ++s) acc[r][s] = 0.f;
-
-    auto step = [&](int k) {
-        float xi[MI], yj[MI];
-#pragma unroll
-        for (int r = 0; r < MI; ++r) {
-            xi[r] = si[k][ri * MI + r];
-            yj[r] = sj[k][rj * MI + r];
-        }
-#pragma unroll
-        for (int r = 0; r < MI; ++r)
-#pragma unroll
-            for (int s = 0; s < MI; ++s) {
-                const float d = xi[r] - yj[s];
-                acc[r][s] = fmaf(d, d, acc[r][s]);
-            }
-    };
-
-    for (int k0 = 0; k0 < a.D; k0 += PR_KC) {
-        const int kn = min(PR_KC, a.D - k0);
-        prdc_stage<TI>(si, xb, X.sp, X.so, a.inner, i0, X.n, k0, kn);
-        prdc_stage<TI>(sj, yb, Y.sp, Y.so, a.inner, j0, Y.n, k0, kn);
-        __syncthreads();
-        if (live) {     // (wave-uniform: a wave whose rows all lie outside the set only helps staging)
-            if (kn == PR_KC) {
-#pragma unroll
-                for (int k = 0; k < PR_KC; ++k) step(k);
-            } else {
-                for (int k = 0; k < kn; ++k) step(k);
-            }
-        }
-        __syncthreads();
-    }
+    dist_tile<TI, MI>(acc, si, sj, a.D, a.inner, X, xb, i0, Y, yb, j0, live, DistIdentity(), DistIdentity());
 }
 
 template <int TI, int MI>

@@ -1,6 +1,8 @@
 """MMD evaluation of generated actions (evaluation/mmd-actions.py of the reference) on the kg_mmd HIP kernels, and
 precision / recall / density / coverage of sample sets on the kg_prdc kernels (``prdc``) and the Frechet distance of
-pose / motion / caller features in fp64 on the kg_frechet kernels (``frechet``, ``frechet_features``), at the end.
+pose / motion / caller features in fp64 on the kg_frechet kernels (``frechet``, ``frechet_features``), and nearest training
+samples with the memorisation scores built on them on the kg_nn kernels (``nearest``, ``memorisation``, ``nn_two_sample``),
+at the end.
 
 The reference scores samples with a kernel two-sample statistic (MMD) under 14 RBF bandwidths 10^-4 .. 10^9: per class
 the first selected fake and real sample, each a set of V points (joints) per frame (``avg``: the mean over frames of
@@ -182,7 +184,7 @@ def calculate_mmd(gen, real, labels, mode: str = "avg", bandwidths: Sequence[flo
 PRDC_NAMES = ("precision", "recall", "density", "coverage")
 
 
-def _label_ids(labels, n: int, what: str) -> Tuple[np.ndarray, int]:
+def _label_ids(labels, n: int, what: str, who: str = "prdc") -> Tuple[np.ndarray, int]:
     """labels -> (class id per sample, classes the labels can name); None = one class"""
     if labels is None:
         return np.zeros(n, dtype=np.int64), 1
@@ -196,11 +198,11 @@ def _label_ids(labels, n: int, what: str) -> Tuple[np.ndarray, int]:
         lab = lab.astype(np.int64)
         k = int(lab.max()) + 1 if lab.size else 0
     if lab.shape[0] != n:
-        raise ValueError("prdc: %d %s for %d samples" % (lab.shape[0], what, n))
+        raise ValueError("%s: %d %s for %d samples" % (who, lab.shape[0], what, n))
     return lab, k
 
 
-def _class_rows(lab: np.ndarray, classes: int, per_class: Optional[int], what: str) -> np.ndarray:
+def _class_rows(lab: np.ndarray, classes: int, per_class: Optional[int], what: str, who: str = "prdc") -> np.ndarray:
     """(classes, count) sample indices: the first ``per_class`` samples of every class in index order (default: all of
     them; the classes must then hold the same number)"""
     rows = [np.flatnonzero(lab == c) for c in range(classes)]
@@ -208,15 +210,15 @@ def _class_rows(lab: np.ndarray, classes: int, per_class: Optional[int], what: s
         count = rows[0].size
         for c, r in enumerate(rows):
             if r.size != count:
-                raise ValueError("prdc: class %d has %d %s samples, class 0 has %d (ragged classes: pass per_class)"
-                                 % (c, r.size, what, count))
+                raise ValueError("%s: class %d has %d %s samples, class 0 has %d (ragged classes: pass per_class)"
+                                 % (who, c, r.size, what, count))
     else:
         count = int(per_class)
         for c, r in enumerate(rows):
             if r.size < count:
-                raise ValueError("prdc: class %d has %d %s samples, per_class=%d needed" % (c, r.size, what, count))
+                raise ValueError("%s: class %d has %d %s samples, per_class=%d needed" % (who, c, r.size, what, count))
     if count < 1:
-        raise ValueError("prdc: class 0 has no %s sample" % what)
+        raise ValueError("%s: class 0 has no %s sample" % (who, what))
     return np.stack([r[:count] for r in rows])
 
 
@@ -241,6 +243,17 @@ def _prdc_view(t: torch.Tensor, idx: np.ndarray):
     else:
         d_outer, d_inner, so = C, T * V, t.stride(1)
     return _native.PrdcView(t[base], cs * t.stride(0), ps * t.stride(0), so), d_outer, d_inner
+
+
+def _view_pair(a: torch.Tensor, idx_a: np.ndarray, b: torch.Tensor, idx_b: np.ndarray):
+    """(view of a, view of b, d_outer, d_inner): _prdc_view of both sets with ONE split of the dimension"""
+    av, d_outer, d_inner = _prdc_view(a, idx_a)
+    bv, bo, bi = _prdc_view(b, idx_b)
+    if (bo, bi) != (d_outer, d_inner):          # one side is a crop, the other is not: both as channel rows
+        C, T, V = a.shape[1:]
+        av, bv = (v if v.so or C == 1 else v._replace(so=T * V) for v in (av, bv))
+        d_outer, d_inner = C, T * V
+    return av, bv, d_outer, d_inner
 
 
 def prdc(gen, real, labels_gen=None, labels_real=None, k: int = 5, per_class: Optional[int] = None,
@@ -274,12 +287,7 @@ def prdc(gen, real, labels_gen=None, labels_real=None, k: int = 5, per_class: Op
     if not 1 <= k <= min(_native.PRDC_MAX_K, min(n, m) - 1):
         raise ValueError("prdc: k=%d outside [1, min(%d, min(n=%d, m=%d) - 1)]" % (k, _native.PRDC_MAX_K, n, m))
     gen, real = _as_cuda(gen), _as_cuda(real)
-    rv, d_outer, d_inner = _prdc_view(real, idx_r)
-    gv, go, gi = _prdc_view(gen, idx_g)
-    if (go, gi) != (d_outer, d_inner):          # one side is a crop, the other is not: both as channel rows
-        C, T, V = real.shape[1:]
-        rv, gv = (v if v.so or C == 1 else v._replace(so=T * V) for v in (rv, gv))
-        d_outer, d_inner = C, T * V
+    rv, gv, d_outer, d_inner = _view_pair(real, idx_r, gen, idx_g)
     return _native.prdc(rv, gv, n, m, d_outer, d_inner, classes, k, want_mean=True, per_point=per_point)
 
 
@@ -505,6 +513,178 @@ def _classifier_scores_pairs(clf, gen, ids_g, real, ids_r, per_class, batch, cla
         out.update(diversity_real=res_r["scores64"][0, 1], multimodality_real=res_r["scores64"][0, 2], pred_real=pred_r,
                    pair_tables_real=tables_r)
     return out
+
+
+# ---- nearest training samples, memorisation scores, the 1-NN two-sample test (kg_nn.hip) --------------------
+
+NN_TWO_SAMPLE_NAMES = ("acc_real", "acc_fake", "acc")
+
+
+def _nn_side(x, who: str, what: str):
+    """(samples (n, C, T, V) where they lie, (scale, shift) or None, the labels the object carries or None) of one side of a
+    search: a batch, or a ``train.ResidentDataset`` - its ``data`` is on the device, cropped, NOT normalised, and is searched
+    in place through the dataset's affine"""
+    if all(hasattr(x, f) for f in ("fits", "data", "scale", "shift")):
+        if not x.fits or x.data is None:
+            raise ValueError("%s: the ResidentDataset given as %s does not fit the device (fits=False): pass the samples"
+                             % (who, what))
+        affine = (float(x.scale), float(x.shift))
+        return x.data, None if affine == (1.0, 0.0) else affine, getattr(x, "labels", None)
+    return _as_f32(x), None, None
+
+
+def _nn_check_pair(q: torch.Tensor, b: torch.Tensor, who: str, names=("query", "base")):
+    if q.dim() != 4 or b.dim() != 4:
+        raise ValueError("%s: samples are (N, C, T, V), got %s and %s" % (who, tuple(q.shape), tuple(b.shape)))
+    if q.shape[1:] != b.shape[1:]:
+        raise ValueError("%s: %s samples %s and %s samples %s differ in shape"
+                         % (who, names[0], tuple(q.shape[1:]), names[1], tuple(b.shape[1:])))
+
+
+def _nn_check_k(k: int, N: int, exclude_self: bool, who: str):
+    most = min(_native.NN_MAX_K, N - (1 if exclude_self else 0))
+    if not 1 <= k <= most:
+        raise ValueError("%s: k=%d outside [1, min(%d, N=%d%s)]" % (who, k, _native.NN_MAX_K, N, " - 1" if exclude_self else ""))
+
+
+def _nn_rows(q, idx_q: np.ndarray, qa, b, idx_b: np.ndarray, ba, k: int, exclude_self: bool):
+    """one kg_nn call on the samples idx_q (classes, Q) of q and idx_b (classes, N) of b -> (idx, d2) (classes, Q, k)"""
+    q, b = _as_cuda(q), _as_cuda(b)
+    qv, bv, d_outer, d_inner = _view_pair(q, idx_q, b, idx_b)
+    return _native.nn(qv, bv, idx_q.shape[1], idx_b.shape[1], d_outer, d_inner, idx_q.shape[0], k,
+                      exclude_self=exclude_self, q_affine=qa, b_affine=ba)
+
+
+def nearest(query, base, k: int = 1, exclude_self: bool = False, labels_query=None, labels_base=None,
+            per_class: Optional[int] = None) -> dict:
+    """The k nearest ``base`` samples of every ``query`` sample (a sample = one point of dimension C*T*V) in one kg_nn call:
+    exact, ties to the lower index, a duplicate is a neighbour at distance 0.
+
+    query (Nq, C, T, V), base (Nb, C, T, V): CUDA tensors, CPU tensors or numpy, read in place where the samples lie evenly
+    spaced (a crop in T included); either may be a ``train.ResidentDataset``, whose unnormalised ``data`` is searched in
+    place with the dataset's (scale, shift) - nothing is copied - and whose labels stand in for missing ``labels_base``.
+    Without labels it is ONE global search.  With labels (one-hot or ids) the search runs class by class on the selection of
+    ``prdc``: the first ``per_class`` samples of every class on each side (default: all; a side's classes must then hold the
+    same number).  ``exclude_self`` leaves pair i == j out by index: a set searched against itself.
+    Returns device tensors ``idx`` (K, Q, k) int32 - the neighbour's position inside its class's selection -, ``d2``
+    (K, Q, k) squared distances, non-decreasing along k, ``index`` (K, Q, k) int64 - the neighbour's index in ``base`` -, and
+    the selections ``rows_query`` (K, Q), ``rows_base`` (K, N) as numpy indices.  No host sync (labels that live on the
+    device are read once)."""
+    who = "nearest"
+    q, qa, _ = _nn_side(query, who, "query")
+    b, ba, own = _nn_side(base, who, "base")
+    _nn_check_pair(q, b, who)
+    if labels_base is None and labels_query is not None:
+        labels_base = own
+    lab_q, kq = _label_ids(labels_query, q.shape[0], "labels_query", who)
+    lab_b, kb = _label_ids(labels_base, b.shape[0], "labels_base", who)
+    classes = max(kq, kb)
+    if classes < 1:
+        raise ValueError("%s: no samples" % who)
+    idx_q = _class_rows(lab_q, classes, per_class, "query", who)
+    idx_b = _class_rows(lab_b, classes, per_class, "base", who)
+    _nn_check_k(k, idx_b.shape[1], exclude_self, who)
+    idx, d2 = _nn_rows(q, idx_q, qa, b, idx_b, ba, k, exclude_self)
+    rows = torch.as_tensor(idx_b, device=idx.device)
+    index = torch.gather(rows, 1, idx.reshape(classes, -1).long()).reshape(idx.shape)
+    return dict(idx=idx, d2=d2, index=index, rows_query=idx_q, rows_base=idx_b)
+
+
+def _share(count: torch.Tensor, of: int) -> torch.Tensor:
+    """an integer tally over its denominator: evaluated in float64, rounded once"""
+    return (count.double() / float(of)).float()
+
+
+def memorisation(gen, labels_gen, train, labels_train=None, heldout=None, labels_heldout=None, train_loo=None) -> dict:
+    """Does the generator replay its training set?  One global search gen -> train (k = 1) and one train -> train (k = 1,
+    leave-one-out); a generated sample that lies closer to its nearest training sample than that sample lies to any OTHER
+    training sample counts as a copy (authenticity, Alaa et al. 2022).
+
+    gen (Ng, C, T, V) with its conditioning labels; ``train``: a batch with ``labels_train``, or a ``train.ResidentDataset``
+    (searched in place, its own labels by default).  ``train_loo``: the (Nt,) leave-one-out distances of an earlier call
+    (``train_loo_d2`` of its result) - the train -> train pass depends on the training set alone and is then not repeated.
+    Returns device tensors: ``nn_index`` (Ng,) int64 and ``nn_d2`` (Ng,) - the nearest training sample i* of every generated
+    sample and its squared distance -, ``authentic`` (Ng,) bool = [d2(f_j, r_i*) >= d2_loo(r_i*)], ``authenticity`` = their
+    share, ``label_agreement`` = the share whose nearest training sample carries the conditioning label, ``counts`` (2,)
+    int64 (authentic, agreeing), ``train_loo_d2`` (Nt,).  With ``heldout`` (real samples the generator never saw, with
+    ``labels_heldout``) the same for it as queries under ``heldout_*``: what a perfect generator scores.  Tallies are
+    integers on the device; the shares are evaluated in float64 and rounded once."""
+    who = "memorisation"
+    t, ta, own = _nn_side(train, who, "train")
+    if labels_train is None:
+        labels_train = own
+    if labels_train is None:
+        raise ValueError("%s: labels_train is needed (the training set carries none)" % who)
+    sets = [("", "gen", _as_f32(gen), labels_gen, "labels_gen")]
+    if heldout is not None:
+        sets.append(("heldout_", "heldout", _as_f32(heldout), labels_heldout, "labels_heldout"))
+    nt = t.shape[0] if t.dim() == 4 else 0
+    labs = []
+    for _, what, x, lab, name in sets:
+        _nn_check_pair(x, t, who, (what, "train"))
+        if lab is None:
+            raise ValueError("%s: %s is needed" % (who, name))
+        labs.append(_label_ids(lab, x.shape[0], name, who)[0])
+    lab_t = _label_ids(labels_train, nt, "labels_train", who)[0]
+    if nt < 2:
+        raise ValueError("%s: the leave-one-out pass needs at least 2 training samples, got %d" % (who, nt))
+    if train_loo is not None and (train_loo.dim() != 1 or train_loo.shape[0] != nt or train_loo.dtype != torch.float32):
+        raise ValueError("%s: train_loo must be the (%d,) fp32 leave-one-out distances of this training set" % (who, nt))
+    t = _as_cuda(t)                             # (once: up to three searches read it)
+    rows_t = np.arange(nt)[None, :]
+    if train_loo is None:
+        train_loo = _nn_rows(t, rows_t, ta, t, rows_t, ta, 1, True)[1].reshape(-1)
+    out = dict(train_loo_d2=train_loo)
+    lab_t = torch.as_tensor(lab_t, device=train_loo.device)
+    for (pre, _, x, _, _), lab in zip(sets, labs):
+        idx, d2 = _nn_rows(x, np.arange(x.shape[0])[None, :], None, t, rows_t, ta, 1, False)
+        idx, d2 = idx.reshape(-1).long(), d2.reshape(-1)
+        authentic = d2 >= train_loo[idx]
+        agree = lab_t[idx] == torch.as_tensor(lab, device=idx.device)
+        counts = torch.stack([authentic.sum(), agree.sum()])
+        out.update({pre + "nn_index": idx, pre + "nn_d2": d2, pre + "authentic": authentic, pre + "counts": counts,
+                    pre + "authenticity": _share(counts[0], x.shape[0]),
+                    pre + "label_agreement": _share(counts[1], x.shape[0])})
+    return out
+
+
+def nn_two_sample(gen, real, labels_gen=None, labels_real=None, per_class: Optional[int] = None) -> dict:
+    """The leave-one-out 1-NN two-sample test (Lopez-Paz & Oquab 2017; Xu et al. 2018) per class: every sample of R u F, with
+    |R| = |F| = n per class, is classified by its nearest OTHER sample of the union; the accuracy of an indistinguishable
+    generator is 0.5, ``acc_fake`` -> 0 means copies of real samples, -> 1 a separable (or collapsed) fake set.
+
+    Built from four k = 1 searches (R -> R and F -> F leave-one-out, R -> F, F -> R); a tie between a real and a fake
+    neighbour goes to the real one: real i is correct iff d2_RR(i) <= d2_RF(i), fake j iff d2_FF(j) < d2_FR(j).  Arguments
+    and selection as ``prdc``.  Returns device tensors ``acc_real``, ``acc_fake``, ``acc`` (K,), ``counts`` (K, 2) int64
+    (correct reals, correct fakes) and ``mean`` (3,) - the class means in the order NN_TWO_SAMPLE_NAMES.  Tallies are
+    integers on the device; every quotient is evaluated in float64 and rounded once."""
+    who = "nn_two_sample"
+    gen, real = _as_f32(gen), _as_f32(real)
+    _nn_check_pair(gen, real, who, ("gen", "real"))
+    lab_g, kg = _label_ids(labels_gen, gen.shape[0], "labels_gen", who)
+    lab_r, kr = _label_ids(labels_real, real.shape[0], "labels_real", who)
+    classes = max(kg, kr)
+    if classes < 1:
+        raise ValueError("%s: no samples" % who)
+    idx_r = _class_rows(lab_r, classes, per_class, "real", who)
+    idx_g = _class_rows(lab_g, classes, per_class, "fake", who)
+    n = idx_r.shape[1]
+    if idx_g.shape[1] != n:
+        raise ValueError("%s: %d real and %d fake samples per class (the test needs |R| = |F|: pass per_class)"
+                         % (who, n, idx_g.shape[1]))
+    if n < 2:
+        raise ValueError("%s: %d samples per class and set, the leave-one-out search needs 2" % (who, n))
+    gen, real = _as_cuda(gen), _as_cuda(real)
+    d = {}
+    for key, (a, ia), (b, ib) in (("rr", (real, idx_r), (real, idx_r)), ("rf", (real, idx_r), (gen, idx_g)),
+                                  ("ff", (gen, idx_g), (gen, idx_g)), ("fr", (gen, idx_g), (real, idx_r))):
+        d[key] = _nn_rows(a, ia, None, b, ib, None, 1, key in ("rr", "ff"))[1].reshape(classes, n)
+    counts = torch.stack([(d["rr"] <= d["rf"]).sum(1), (d["ff"] < d["fr"]).sum(1)], dim=1)
+    total = counts.sum(0)
+    return dict(acc_real=_share(counts[:, 0], n), acc_fake=_share(counts[:, 1], n), acc=_share(counts.sum(1), 2 * n),
+                counts=counts,
+                mean=torch.stack([_share(total[0], classes * n), _share(total[1], classes * n),
+                                  _share(total.sum(), 2 * classes * n)]))
 
 
 def select_reference_samples(feeder, classes: Optional[Sequence[int]] = None, t_size: int = 64, per_class: int = 100):
