@@ -849,6 +849,69 @@ typedef struct KgNnArgs {
 int64_t kg_nn_workspace_bytes(const KgNnArgs* a);   /* < 0 for invalid shapes                                          */
 int     kg_nn(const KgNnArgs* a, void* stream);
 
+/* ---- several query sets against ONE base; memorisation score words (additive, ABI v9; DESIGN.md 23, csrc/kg_nn.hip) --------
+ * The Evaluator's case: the training set is the base for a whole run and every named generator's round is a query set.
+ * kg_nn_sets: nsets (1..KG_NN_MAX_SETS) query sets query[g] with shared strides, Q and affine against one base.  For every
+ * set g, idx[g] and d2[g] equal, bit for bit, what kg_nn(query[g], base) writes on the same data, under every (tile, split)
+ * plan of either call: a set only chooses the query pointer and the output rows - neither the plan nor the grouping into
+ * sets shows in any bit.  There is no exclude_self: a group of sets searched against one base has no "self".
+ * Two launches whatever nsets is - the kernels of kg_nn, of which kg_nn is the one-set case: a search workgroup is one
+ * (set, class, row tile, chunk), a merge wave one (set, class, query).  The automatic plan counts the sets as row tiles: the
+ * tile is 64 once nsets * classes * ceil(Q / 64) * min(32, ceil(N / 64)) >= 512, and the chunks make up what
+ * nsets * classes * row tiles lack of 512 workgroups - fewer, longer chunks than one set gets.
+ * ws = kg_nn_sets_workspace_bytes(a) = nsets * classes * Q * split * k * 8 bytes (split: the plan's) and may hold anything.
+ * Every pointer is read when the launches run; nothing is synchronised; capturable on one stream.
+ * Rejected (< 0, kg_last_error() names the field): nsets outside [1, KG_NN_MAX_SETS]; null query[g] (g < nsets) / base /
+ * idx / d2 / ws; every rule of kg_nn but the exclude_self ones (k > N); nsets * classes * row tiles * split or
+ * ceil(nsets * classes * Q / 4) of 2^24 workgroups or more; ws_bytes too small.
+ *
+ * kg_nn_scores: from the nearest neighbour (idx, d2) of every query of nsets sets to the memorisation tallies of
+ * metrics.memorisation.  idx / d2 are (nsets, Q) with the element stride ld (set g, query j at g*Q*ld + j*ld: column 0 of a
+ * (nsets, 1, Q, k) result of kg_nn_sets is ld = k, read in place).  Per set g and query j, with i = idx[g][j]:
+ *   authentic_j = d2[g][j] >= base_loo[i]          (>=: equality is authentic; base_loo (N): the leave-one-out nearest
+ *                                                   squared distance of every base point - d2 of kg_nn(base, base,
+ *                                                   k = 1, exclude_self))
+ *   agree_j     = base_labels[i] == query_labels[j]
+ *   counts (nsets, 2) int64 = #authentic, #agreeing;   counts_per_class (nsets, n_classes, 2) int32 (or NULL) the same by
+ *   the QUERY's label;   scores64 (nsets, 2) = counts / Q evaluated in fp64;   scores (nsets, 2) = its one fp32 rounding.
+ * ONE launch, one workgroup per set: integer tallies in LDS, no atomics on global memory, one owner per output word, every
+ * word written on every call - the same bits on every call.  Nothing is synchronised; capturable.
+ * Outside the definition, and never out of bounds: a query whose idx is outside [0, N) is SKIPPED (nothing is read for it,
+ * it counts nowhere); a query label outside [0, n_classes) counts in `counts` and in no class.
+ * Rejected (< 0, kg_last_error() names the field): null idx / d2 / query_labels / base_labels / base_loo / counts /
+ * scores64 / scores; Q, N, n_classes or ld < 1; nsets outside [1, KG_NN_MAX_SETS]; Q or N above KG_NN_MAX_POINTS; n_classes
+ * above KG_NN_SCORES_MAX_CLASSES (the LDS tallies: 2 words per class).                                                   */
+#define KG_NN_MAX_SETS 4
+#define KG_NN_SCORES_MAX_CLASSES 1024
+typedef struct KgNnSetsArgs {
+    const float* query[KG_NN_MAX_SETS];  int64_t q_sc, q_sp, q_so;    /* query[0 .. nsets): strides, Q and affine are shared */
+    int32_t nsets;
+    const float* base;   int64_t b_sc, b_sp, b_so;
+    int32_t Q, N;
+    int32_t d_outer, d_inner;
+    int32_t classes, k;
+    int32_t q_affine, b_affine;
+    float q_scale, q_shift, b_scale, b_shift;
+    int32_t tile, split;            /* 0 = automatic, or a forced plan (tests)                                         */
+    int32_t* idx;                   /* (nsets, classes, Q, k)                                                          */
+    float* d2;                      /* (nsets, classes, Q, k)                                                          */
+    void* ws;  int64_t ws_bytes;
+} KgNnSetsArgs;
+typedef struct KgNnScoresArgs {
+    int32_t nsets, Q, N, n_classes;
+    int64_t ld;                     /* elements between two queries of idx / d2                                        */
+    const int32_t* idx;  const float* d2;           /* (nsets, Q) x ld                                                   */
+    const int32_t* query_labels;    /* (Q), shared by the sets                                                         */
+    const int32_t* base_labels;     /* (N)                                                                             */
+    const float* base_loo;          /* (N)                                                                             */
+    int64_t* counts;                /* out: (nsets, 2)                                                                 */
+    int32_t* counts_per_class;      /* out: (nsets, n_classes, 2) or NULL                                              */
+    double* scores64;  float* scores;               /* out: (nsets, 2), (nsets, 2)                                       */
+} KgNnScoresArgs;
+int64_t kg_nn_sets_workspace_bytes(const KgNnSetsArgs* a);   /* < 0 for invalid shapes                                 */
+int     kg_nn_sets(const KgNnSetsArgs* a, void* stream);
+int     kg_nn_scores(const KgNnScoresArgs* a, void* stream);
+
 /* ---- Frechet distance of pose / motion / caller features in fp64 (additive, ABI v9; DESIGN.md 18, csrc/kg_frechet.hip) -----
  * For every class c: a real set of n and a fake set of m samples of `frames` frames, a frame being d = d_outer*d_inner <= 96
  * floats read through strides (elements):

@@ -368,6 +368,31 @@ class _NnArgs(C.Structure):
                 ("idx", C.c_void_p), ("d2", c_f32p),
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
+NN_MAX_SETS = 4
+NN_SCORES_MAX_CLASSES = 1024
+
+
+class _NnSetsArgs(C.Structure):
+    _fields_ = [("query", c_f32p * NN_MAX_SETS), ("q_sc", C.c_int64), ("q_sp", C.c_int64), ("q_so", C.c_int64),
+                ("nsets", C.c_int32),
+                ("base", c_f32p), ("b_sc", C.c_int64), ("b_sp", C.c_int64), ("b_so", C.c_int64),
+                ("Q", C.c_int32), ("N", C.c_int32), ("d_outer", C.c_int32), ("d_inner", C.c_int32),
+                ("classes", C.c_int32), ("k", C.c_int32),
+                ("q_affine", C.c_int32), ("b_affine", C.c_int32),
+                ("q_scale", C.c_float), ("q_shift", C.c_float), ("b_scale", C.c_float), ("b_shift", C.c_float),
+                ("tile", C.c_int32), ("split", C.c_int32),
+                ("idx", C.c_void_p), ("d2", c_f32p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
+class _NnScoresArgs(C.Structure):
+    _fields_ = [("nsets", C.c_int32), ("Q", C.c_int32), ("N", C.c_int32), ("n_classes", C.c_int32),
+                ("ld", C.c_int64),
+                ("idx", C.c_void_p), ("d2", c_f32p),
+                ("query_labels", C.c_void_p), ("base_labels", C.c_void_p), ("base_loo", c_f32p),
+                ("counts", C.c_void_p), ("counts_per_class", C.c_void_p),
+                ("scores64", C.c_void_p), ("scores", c_f32p)]
+
 FRECHET_MAX_DIM = 96
 
 
@@ -586,6 +611,9 @@ EXPORTS = {
     "kg_prdc_sets": (C.c_int, [C.POINTER(_PrdcSetsArgs), C.c_void_p]),
     "kg_nn_workspace_bytes": (C.c_int64, [C.POINTER(_NnArgs)]),
     "kg_nn": (C.c_int, [C.POINTER(_NnArgs), C.c_void_p]),
+    "kg_nn_sets_workspace_bytes": (C.c_int64, [C.POINTER(_NnSetsArgs)]),
+    "kg_nn_sets": (C.c_int, [C.POINTER(_NnSetsArgs), C.c_void_p]),
+    "kg_nn_scores": (C.c_int, [C.POINTER(_NnScoresArgs), C.c_void_p]),
     "kg_frechet_workspace_bytes": (C.c_int64, [C.POINTER(_FrechetArgs)]),
     "kg_frechet": (C.c_int, [C.POINTER(_FrechetArgs), C.c_void_p]),
     "kg_frechet_real_workspace_bytes": (C.c_int64, [C.POINTER(_FrechetRealArgs)]),
@@ -2510,7 +2538,9 @@ def prdc_sets(real: PrdcView, fakes: Sequence[torch.Tensor], f_sc: int, f_sp: in
 
 def _nn_shape(a: "_NnArgs", Q, N, d_outer, d_inner, classes, k, exclude_self, q_affine, b_affine, tile, split):
     a.Q, a.N, a.d_outer, a.d_inner, a.classes, a.k = int(Q), int(N), int(d_outer), int(d_inner), int(classes), int(k)
-    a.exclude_self, a.tile, a.split = int(bool(exclude_self)), int(tile), int(split)
+    a.tile, a.split = int(tile), int(split)
+    if exclude_self is not None:                # (None: a struct without the field - the sets)
+        a.exclude_self = int(bool(exclude_self))
     for pre, aff in (("q", q_affine), ("b", b_affine)):
         if aff is not None:
             setattr(a, pre + "_affine", 1)
@@ -2562,6 +2592,103 @@ def nn(query: PrdcView, base: PrdcView, Q: int, N: int, d_outer: int, d_inner: i
     _count("kg_nn", 3.0 * float(Q) * N * d_outer * d_inner * classes)
     _check(load_library().kg_nn(C.byref(a), _stream()), "kg_nn")
     return idx, d2
+
+
+def nn_sets_workspace_bytes(nsets: int, Q: int, N: int, d_outer: int, d_inner: int, classes: int, k: int, tile: int = 0,
+                            split: int = 0) -> int:
+    """kg_nn_sets_workspace_bytes of a shape = nsets * classes * Q * split * k * 8 with the plan's split (RuntimeError naming
+    the field for a shape kg_nn_sets rejects); no GPU call"""
+    a = _NnSetsArgs()
+    a.nsets = int(nsets)
+    _nn_shape(a, Q, N, d_outer, d_inner, classes, k, None, None, None, tile, split)
+    return _query("kg_nn_sets_workspace_bytes", a)
+
+
+def nn_sets(queries: Sequence[torch.Tensor], q_sc: int, q_sp: int, q_so: int, base: PrdcView, Q: int, N: int, d_outer: int,
+            d_inner: int, classes: int, k: int, q_affine: Optional[Tuple[float, float]] = None,
+            b_affine: Optional[Tuple[float, float]] = None, tile: int = 0, split: int = 0,
+            ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Enqueue kg_nn_sets: the ``queries`` (1..NN_MAX_SETS fp32 tensors walked with the shared strides q_sc / q_sp / q_so and
+    the shared ``q_affine``) against ONE base in two launches whatever the number of sets; no host synchronisation.  Returns
+    (idx (nsets, classes, Q, k) int32, d2 (nsets, classes, Q, k) fp32) on the device; set g equals, bit for bit,
+    ``nn(PrdcView(queries[g], ...), base)``.  The other arguments as in ``nn`` (there is no ``exclude_self``)."""
+    queries = list(queries)
+    for t in queries + [base.t]:
+        if t.dtype != torch.float32:
+            raise TypeError(f"kg_nn_sets: fp32 only, got {t.dtype}")
+    nsets = len(queries)
+    a = _NnSetsArgs()
+    a.nsets = nsets
+    _nn_shape(a, Q, N, d_outer, d_inner, classes, k, None, q_affine, b_affine, tile, split)
+    nbytes = _query("kg_nn_sets_workspace_bytes", a)
+    _need_cuda(base.t, ws, *queries)
+    for g, t in enumerate(queries):
+        if not _prdc_extent_ok(PrdcView(t, q_sc, q_sp, q_so), Q, d_outer, d_inner, classes):
+            raise ValueError(f"kg_nn_sets: the strides of query set {g} reach outside its tensor")
+    if not _prdc_extent_ok(base, N, d_outer, d_inner, classes):
+        raise ValueError("kg_nn_sets: the strides of base reach outside its tensor")
+    dev = base.t.device
+    if ws is None:
+        ws = _workspace("kg_nn_sets_workspace_bytes", a, dev)
+    elif not ws.is_contiguous() or ws.element_size() != 4 or ws.numel() * 4 < nbytes:
+        raise ValueError("kg_nn_sets: ws must be a contiguous tensor of 4-byte elements, at least %d bytes" % nbytes)
+    else:
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    idx = torch.empty((nsets, classes, Q, k), dtype=torch.int32, device=dev)
+    d2 = torch.empty((nsets, classes, Q, k), dtype=torch.float32, device=dev)
+    for g, t in enumerate(queries):
+        a.query[g] = t.data_ptr()
+    a.q_sc, a.q_sp, a.q_so = int(q_sc), int(q_sp), int(q_so)
+    a.base, a.b_sc, a.b_sp, a.b_so = base.t.data_ptr(), base.sc, base.sp, base.so
+    a.idx, a.d2 = idx.data_ptr(), d2.data_ptr()
+    _count("kg_nn_sets", 3.0 * nsets * float(Q) * N * d_outer * d_inner * classes)
+    _check(load_library().kg_nn_sets(C.byref(a), _stream()), "kg_nn_sets")
+    return idx, d2
+
+
+def nn_scores(idx: torch.Tensor, d2: torch.Tensor, query_labels: torch.Tensor, base_labels: torch.Tensor,
+              base_loo: torch.Tensor, n_classes: int, per_class: bool = False) -> dict:
+    """Enqueue kg_nn_scores (ONE launch): the memorisation tallies of 1..NN_MAX_SETS sets from their nearest neighbours.
+    ``idx`` int32 / ``d2`` fp32: (nsets, Q), or (nsets, Q, k) / (nsets, 1, Q, k) results of ``nn_sets`` whose column 0 is
+    read in place; ``query_labels`` (Q,) int32 shared by the sets, ``base_labels`` (N,) int32, ``base_loo`` (N,) fp32 - the
+    leave-one-out nearest squared distance of every base point.  Returns device tensors counts (nsets, 2) int64 (authentic,
+    agreeing), scores64 (nsets, 2), scores (nsets, 2) fp32 = the one rounding of counts / Q, and with ``per_class``
+    counts_per_class (nsets, n_classes, 2) int32 by the query's label.  No host synchronisation."""
+    who = "kg_nn_scores"
+    if idx.dim() == 4 and idx.shape[1] == 1:
+        idx, d2 = idx[:, 0], d2[:, 0]
+    if idx.dim() == 3:
+        idx, d2 = idx[:, :, 0], d2[:, :, 0]
+    if idx.dim() != 2 or idx.shape != d2.shape or idx.dtype != torch.int32 or d2.dtype != torch.float32:
+        raise ValueError(f"{who}: idx int32 and d2 fp32 of one shape (nsets, Q[, k]) expected")
+    nsets, Q = idx.shape
+    ld = idx.stride(1) if Q > 1 else 1
+    for t in (idx, d2):
+        if (Q > 1 and t.stride(1) != ld) or (nsets > 1 and t.stride(0) != Q * ld) or ld < 1:
+            raise ValueError(f"{who}: idx / d2 must be (nsets, Q) views with strides (Q * ld, ld)")
+    for name, t, dt in (("query_labels", query_labels, torch.int32), ("base_labels", base_labels, torch.int32),
+                        ("base_loo", base_loo, torch.float32)):
+        if t.dim() != 1 or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous 1-D {dt} tensor")
+    if query_labels.shape[0] != Q or base_labels.shape[0] != base_loo.shape[0]:
+        raise ValueError(f"{who}: {query_labels.shape[0]} query_labels for Q={Q}, {base_labels.shape[0]} base_labels for "
+                         f"{base_loo.shape[0]} base_loo")
+    _need_cuda(idx, d2, query_labels, base_labels, base_loo)
+    dev = idx.device
+    out = dict(counts=torch.empty((nsets, 2), dtype=torch.int64, device=dev),
+               scores64=torch.empty((nsets, 2), dtype=torch.float64, device=dev),
+               scores=torch.empty((nsets, 2), dtype=torch.float32, device=dev))
+    if per_class:
+        out["counts_per_class"] = torch.empty((nsets, max(int(n_classes), 0), 2), dtype=torch.int32, device=dev)
+    a = _NnScoresArgs()
+    a.nsets, a.Q, a.N, a.n_classes, a.ld = nsets, Q, base_loo.shape[0], int(n_classes), ld
+    a.idx, a.d2 = idx.data_ptr(), d2.data_ptr()
+    a.query_labels, a.base_labels, a.base_loo = query_labels.data_ptr(), base_labels.data_ptr(), base_loo.data_ptr()
+    a.counts, a.counts_per_class = out["counts"].data_ptr(), _ptr(out.get("counts_per_class"))
+    a.scores64, a.scores = out["scores64"].data_ptr(), out["scores"].data_ptr()
+    _count(who, 0.0)
+    _check(load_library().kg_nn_scores(C.byref(a), _stream()), who)
+    return out
 
 
 # ---- Frechet distance of pose / motion / caller features (kg_frechet.hip) -------------------------------------------------

@@ -39,6 +39,16 @@ for all generators.  The record then ends with ``"<g>/accuracy"`` (larger is bet
 better), ``"<g>/diversity"`` and ``"<g>/multimodality"`` (closer to the real set's value - ``classifier_real`` - is
 better: recorded, never selected by) per generator.
 
+With ``memorisation`` (``"features"`` or ``"raw"``) it also scores whether the generators replay the training
+set ``memorisation_train``: every generator's round - the classifier round's feature matrices in feature space, a round of
+``memorisation_per_class`` samples per class in raw space (a PRDC, Frechet or classifier round of that count when one
+exists) - is a query set of ONE kg_nn_sets call (k = 1, two launches for all generators) against the training set, whose
+features (feature space), leave-one-out distances and labels were computed once, at construction; ONE kg_nn_scores launch
+then writes the score words.  The record ends with ``"<g>/authenticity"`` (the share of samples that lie no closer to their
+nearest training sample than that sample lies to another training sample: noise scores 1, a copier 0, the value to be near
+is ``memorisation_real["authenticity"]`` - recorded, never selected by) and ``"<g>/label_agreement"`` (the share whose
+nearest training sample carries the conditioning label; larger is better) per generator.
+
 Nothing synchronises the host; everything is read through pointers when the launches run, so the captured evaluation
 follows the training replays in between.  ``records()``, ``best()`` and ``state_dict()`` read the device; the Evaluator
 never writes to a generator.  Definitions the tests pin this against: tests/eval_def.py.
@@ -79,30 +89,35 @@ def default_select(names: Sequence[str], modes: Sequence[str]) -> str:
     return "%s/%s" % (gen, mode)
 
 
-NO_SENSE = ("diversity", "multimodality")      # closer to the real set's value is better: neither direction is
+NO_SENSE = ("diversity", "multimodality", "authenticity")      # closer to the real set's value is better: neither direction is
+MEMORISATION_MODES = ("features", "raw")
 
 
 def score_sense(name: str) -> str:
-    """``"max"`` for precision / recall / density / coverage and accuracy (larger is better), ``"min"`` for the MMD modes and
-    every Frechet distance; ValueError for diversity / multimodality, which have no better direction"""
+    """``"max"`` for precision / recall / density / coverage, accuracy and label_agreement (larger is better), ``"min"`` for the
+    MMD modes and every Frechet distance; ValueError for diversity / multimodality / authenticity, which have no better
+    direction"""
     last = str(name).rsplit("/", 1)[-1]
     if last in NO_SENSE:
         raise ValueError("score_sense: %r is better the closer it is to the real set's value: it cannot decide a selection" % (name,))
-    return "max" if last in metrics.PRDC_NAMES or last == "accuracy" else "min"
+    return "max" if last in metrics.PRDC_NAMES or last in ("accuracy", "label_agreement") else "min"
 
 
 def score_names(generators: Sequence[str], modes: Sequence[str], prdc: bool = False, frechet: Sequence[str] = (),
-                classifier: bool = False) -> list:
+                classifier: bool = False, memorisation: bool = False) -> list:
     """The record's columns: ``"<g>/<mode>"`` generator by generator, then - with precision / recall / density / coverage
     on - ``"<g>/<name>"`` generator by generator in the order of ``metrics.PRDC_NAMES``, then - with the Frechet modes
     ``frechet`` (of ``metrics.FRECHET_MODES``) - ``"<g>/pose_fd"`` and / or ``"<g>/motion_fd"`` generator by generator, then -
-    with ``classifier`` - ``"<g>/<name>"`` generator by generator in the order of ``metrics.CLS_NAMES``"""
+    with ``classifier`` - ``"<g>/<name>"`` generator by generator in the order of ``metrics.CLS_NAMES``, then - with
+    ``memorisation`` - ``"<g>/<name>"`` generator by generator in the order of ``metrics.MEMORISATION_NAMES``"""
     names = ["%s/%s" % (g, m) for g in generators for m in modes]
     if prdc:
         names += ["%s/%s" % (g, q) for g in generators for q in metrics.PRDC_NAMES]
     names += ["%s/%s_fd" % (g, f) for g in generators for f in frechet]
     if classifier:
         names += ["%s/%s" % (g, q) for g in generators for q in metrics.CLS_NAMES]
+    if memorisation:
+        names += ["%s/%s" % (g, q) for g in generators for q in metrics.MEMORISATION_NAMES]
     return names
 
 
@@ -154,7 +169,15 @@ class Evaluator:
     ``classifier`` (a trained ``classifier.Classifier``; None or ``classifier_per_class`` 0: off): also score accuracy, feature
     Frechet distance, diversity (``diversity_pairs`` pairs) and multimodality (``multimodality_pairs`` pairs per class) on that
     many fake and real samples per class, features computed in chunks of ``classifier_batch``; ``classifier_real`` then holds
-    the real set's own values.  The Evaluator never writes to the classifier and never changes its mode."""
+    the real set's own values.  The Evaluator never writes to the classifier and never changes its mode.
+    ``memorisation`` (None: off; ``"features"``: in the classifier's feature space, which needs ``classifier`` and
+    ``classifier_per_class`` and scores that round; ``"raw"``: on ``memorisation_per_class`` samples per class): also score
+    authenticity and label agreement against the training set ``memorisation_train`` - a ``train.ResidentDataset`` (raw space
+    searches it in place through its (scale, shift)) or (N, C, T, V) samples with ``memorisation_train_labels`` -, whose
+    leave-one-out distances (and features) are computed once here.  ``memorisation_real`` holds the two scores of the selected
+    real samples as queries: what a perfect generator scores - but only when ``real`` is held out from the training set
+    (real samples that ARE training samples lie at distance 0 from themselves and score authenticity 0).  The Evaluator never
+    writes to the training set."""
 
     def __init__(self, generators: Dict[str, torch.nn.Module], real, real_labels=None, pairs: int = 10,
                  modes: Sequence[str] = ("avg", "joint"), select: Optional[str] = None, seed: int = 0,
@@ -162,10 +185,12 @@ class Evaluator:
                  ring_len: int = 1024, use_graph: bool = True, t_size: Optional[int] = None, prdc_per_class: int = 0,
                  prdc_k: int = 5, frechet_per_class: int = 0, frechet_modes: Sequence[str] = ("pose", "motion"),
                  classifier=None, classifier_per_class: int = 0, classifier_batch: int = 512, diversity_pairs: int = 200,
-                 multimodality_pairs: int = 20):
+                 multimodality_pairs: int = 20, memorisation: Optional[str] = None, memorisation_train=None,
+                 memorisation_train_labels=None, memorisation_per_class: int = 0):
         if not generators:
             raise ValueError("Evaluator: at least one generator")
         self._check_classifier_options(classifier, classifier_per_class, classifier_batch, diversity_pairs, multimodality_pairs)
+        self._check_memorisation_options(memorisation, memorisation_train, memorisation_per_class)
         self._check_frechet_options(frechet_per_class, frechet_modes)
         self._check_prdc_options(prdc_per_class, prdc_k)
         self.modes = tuple(modes)
@@ -175,8 +200,8 @@ class Evaluator:
             raise ValueError("Evaluator: at least one mode")
         self.gens = dict(generators)
         self.names = score_names(list(self.gens), self.modes, bool(self.prdc_per_class), self.frechet_modes,
-                                 bool(self.classifier_per_class))
-        self._record2 = bool(self.prdc_per_class or self.frechet_per_class or self.classifier_per_class)
+                                 bool(self.classifier_per_class), bool(self.memorisation))
+        self._record2 = bool(self.prdc_per_class or self.frechet_per_class or self.classifier_per_class or self.memorisation)
         most = nv.EVAL2_MAX_SCORES if self._record2 else nv.EVAL_MAX_SCORES
         if len(self.names) > most:
             raise ValueError("Evaluator: %d scores, at most %d fit one record" % (len(self.names), most))
@@ -213,6 +238,10 @@ class Evaluator:
             self._classifier_setup(real, real_labels, t_size, trunc, trunc_mode)
         else:
             self.cls_samplers, self.classifier_real = {}, None
+        if self.memorisation:
+            self._memorisation_setup(real, real_labels, t_size, trunc, trunc_mode, memorisation_train, memorisation_train_labels)
+        else:
+            self.mem_samplers, self.memorisation_real = {}, None
         # the real side, once: row j*K + c = the j-th selected real sample of class c (the Sampler's label order)
         self.real = torch.as_tensor(self._select_real(real, real_labels, self.pairs, "pairs", t_size)).to(dev)
         self._pair_labels = np.arange(self.n)                  # every (fake, real) pair is a "class" of the kg_mmd call
@@ -268,6 +297,28 @@ class Evaluator:
         if self.classifier_per_class and (self.classifier_batch < 1 or self.diversity_pairs < 1 or self.multimodality_pairs < 1):
             raise ValueError("Evaluator: classifier_batch=%d, diversity_pairs=%d, multimodality_pairs=%d must be >= 1" % (
                 self.classifier_batch, self.diversity_pairs, self.multimodality_pairs))
+
+    def _check_memorisation_options(self, mode, train, per_class):
+        """(after the classifier's options) ``memorisation_per_class`` becomes the number of samples per class that are scored"""
+        self.memorisation = None if mode is None else str(mode)
+        self.memorisation_per_class = int(per_class)
+        if self.memorisation is None:
+            return
+        if self.memorisation not in MEMORISATION_MODES:
+            raise ValueError("Evaluator: memorisation=%r is none of %s" % (mode, MEMORISATION_MODES))
+        if train is None:
+            raise ValueError("Evaluator: memorisation=%r needs the training set (memorisation_train)" % self.memorisation)
+        if self.memorisation == "features":
+            if not self.classifier_per_class:
+                raise ValueError("Evaluator: memorisation='features' scores the classifier round's features: it needs "
+                                 "classifier= and classifier_per_class > 0")
+            if self.memorisation_per_class:
+                raise ValueError("Evaluator: memorisation='features' scores the classifier round (classifier_per_class=%d "
+                                 "samples per class); memorisation_per_class=%d is for memorisation='raw'" % (
+                                     self.classifier_per_class, self.memorisation_per_class))
+            self.memorisation_per_class = self.classifier_per_class
+        elif self.memorisation_per_class < 1:
+            raise ValueError("Evaluator: memorisation='raw' needs memorisation_per_class >= 1, got %d" % self.memorisation_per_class)
 
     def _check_prdc_options(self, prdc_per_class, prdc_k):
         self.prdc_per_class, self.prdc_k = int(prdc_per_class), int(prdc_k)
@@ -481,6 +532,108 @@ class Evaluator:
                 words += [sc["scores"][g, 0:1], fd["mean32"][g:g + 1], sc["scores"][g, 1:2], sc["scores"][g, 2:3]]
         return words
 
+    # ---- authenticity / label agreement against the training set -------------------------------------------
+    def _memorisation_setup(self, real, real_labels, t_size, trunc, trunc_mode, train, train_labels):
+        """the checks; the training side, once: its int32 labels, in feature space its features (through the classifier in
+        chunks of ``classifier_batch``, a ResidentDataset normalised chunk by chunk with the arithmetic of its gather), the
+        train -> train leave-one-out distances (one kg_nn with exclude_self) and the real side's own two scores
+        (``memorisation_real``) - all deterministic, so not part of the state; the workspace; in raw space per generator a
+        Sampler, unless a PRDC, Frechet or classifier round of the same count exists and is read instead"""
+        who = "Evaluator"
+        dev, K, P = self.device, self.n_classes, self.memorisation_per_class
+        t, ta, own = metrics._nn_side(train, who, "memorisation_train")
+        if train_labels is None:
+            train_labels = own
+        if train_labels is None:
+            raise ValueError("Evaluator: memorisation_train_labels is needed (the training set carries none)")
+        if t.dim() != 4:
+            raise ValueError("Evaluator: memorisation_train holds (N, C, T, V) samples, got %s" % (tuple(t.shape),))
+        N = int(t.shape[0])
+        if N > nv.NN_MAX_POINTS:
+            raise ValueError("Evaluator: %d training samples, kg_nn takes at most %d" % (N, nv.NN_MAX_POINTS))
+        if N < 2:
+            raise ValueError("Evaluator: the leave-one-out pass needs at least 2 training samples, got %d" % N)
+        if K > nv.NN_SCORES_MAX_CLASSES:
+            raise ValueError("Evaluator: %d classes, kg_nn_scores takes at most %d" % (K, nv.NN_SCORES_MAX_CLASSES))
+        lab_t = metrics._label_ids(train_labels, N, "memorisation_train_labels", who)[0]
+        real_x = torch.as_tensor(self._select_real(real, real_labels, P, "classes", t_size)).to(dev)       # (K*P, C, t, V)
+        if tuple(t.shape[1:]) != tuple(real_x.shape[1:]):
+            raise ValueError("Evaluator: the training samples are (channels, frames, joints) = %s, the generators' %s" % (
+                tuple(t.shape[1:]), tuple(real_x.shape[1:])))
+        if t.device != dev:
+            t = t.to(dev)
+        t = t.contiguous()                      # (a ResidentDataset's array is: nothing is copied)
+        _, C, T, V = real_x.shape
+        n = K * P
+        self._mem_shape, self._mem_train, self._mem_N = tuple(real_x.shape), t, N
+        lab_real = np.repeat(np.arange(K), P)
+        self._mem_qlab = torch.as_tensor(np.tile(np.arange(K), P).astype(np.int32)).to(dev)    # the Sampler's label vector
+        self._mem_blab = torch.as_tensor(lab_t.astype(np.int32)).to(dev)
+        self.mem_samplers, self._mem_shared = {}, None
+        with torch.cuda.device(dev):
+            if self.memorisation == "features":
+                F = int(self.classifier.feat_dim)
+                feat = torch.zeros((N, F), dtype=torch.float32, device=dev)
+                pred = torch.zeros(N, dtype=torch.int32, device=dev)
+                for lo in range(0, N, self.classifier_batch):
+                    x = t[lo:lo + self.classifier_batch]
+                    if ta is not None:          # (x * scale) + shift in two roundings: the normalised sample's bits
+                        x = x * ta[0] + ta[1]
+                    self._classifier_features(x, feat[lo:lo + self.classifier_batch], pred[lo:lo + self.classifier_batch])
+                self.memorisation_train_features = feat
+                self._mem_dims, self._mem_q = (1, F), (0, F, 0)
+                self._mem_bv, self._mem_ba = nv.PrdcView(feat, 0, F, 0), None
+                real_q, train_q = self.classifier_real["features"], feat
+            else:
+                D = C * T * V
+                for kind, per, group in (("prdc", self.prdc_per_class, self.prdc_samplers),
+                                         ("frechet", self.frechet_per_class, self.frechet_samplers),
+                                         ("classifier", self.classifier_per_class, self.cls_samplers)):
+                    if per == P and group:      # (a round that is itself shared has no Samplers: its owner came first)
+                        self._mem_shared = kind
+                        break
+                else:
+                    self.mem_samplers = {k: Sampler(G, qtd=P, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False)
+                                         for k, G in self.gens.items()}
+                self._mem_dims = (1, D) if C == 1 else (C, T * V)
+                self._mem_q = None              # (the rounds' strides, read when they exist)
+                self._mem_bv, self._mem_ba = nv.PrdcView(t, 0, D, 0 if C == 1 else T * V), ta
+                real_q, train_q = real_x, (train if ta is not None else t)     # (a ResidentDataset: through its affine)
+            d_outer, d_inner = self._mem_dims
+            bv = self._mem_bv
+            self._mem_loo = nv.nn(bv, bv, N, N, d_outer, d_inner, 1, 1, exclude_self=True, q_affine=self._mem_ba,
+                                  b_affine=self._mem_ba)[1].reshape(-1)
+            res = metrics.memorisation_sets([real_q], lab_real, train_q, lab_t, train_loo=self._mem_loo)
+            self.memorisation_real = {"authenticity": res["authenticity"][0], "label_agreement": res["label_agreement"][0],
+                                      "counts": res["counts"][0]}
+            sizes = {min(nv.NN_MAX_SETS, len(self.gens) - q) for q in range(0, len(self.gens), nv.NN_MAX_SETS)}
+            nbytes = max(nv.nn_sets_workspace_bytes(g, n, N, d_outer, d_inner, 1, 1) for g in sizes)
+            self._mem_ws = torch.empty(max(1, nbytes // 4), dtype=torch.int32, device=dev)
+
+    def _memorisation_scores(self):
+        """the query sets of all generators - the classifier round's feature matrices, or the raw rounds (a PRDC, Frechet or
+        classifier round of the same count when one exists) read in place -, then per group of generators ONE kg_nn_sets
+        (k = 1) and ONE kg_nn_scores: the score words are one-element views of scores, per generator in the order of
+        metrics.MEMORISATION_NAMES"""
+        K, P, N = self.n_classes, self.memorisation_per_class, self._mem_N
+        d_outer, d_inner = self._mem_dims
+        if self.memorisation == "features":
+            qs, (q_sc, q_sp, q_so) = [self._cls_feat[k] for k in self.gens], self._mem_q
+        else:
+            shared = {"prdc": self.prdc_samplers, "frechet": self.frechet_samplers, "classifier": self.cls_samplers}
+            rounds = [s._out for s in shared[self._mem_shared].values()] if self._mem_shared else self.mem_samplers.values()
+            qs, sn, sc = self._checked_rounds(rounds, self._mem_shape)
+            q_sc, q_sp, q_so = 0, sn, (0 if d_outer == 1 else sc)
+        words = []
+        for q in range(0, len(qs), nv.NN_MAX_SETS):
+            part = qs[q:q + nv.NN_MAX_SETS]
+            idx, d2 = nv.nn_sets(part, q_sc, q_sp, q_so, self._mem_bv, K * P, N, d_outer, d_inner, 1, 1, b_affine=self._mem_ba,
+                                 ws=self._mem_ws)
+            sc_ = nv.nn_scores(idx, d2, self._mem_qlab, self._mem_blab, self._mem_loo, K)
+            for g in range(len(part)):
+                words += [sc_["scores"][g, 0:1], sc_["scores"][g, 1:2]]
+        return words
+
     # ---- the launch sequence -------------------------------------------------------------------------------------------
     def _round(self):
         """what a graph holds: per generator a Sampler round, the re-layout, kg_mmd per mode; then the record, then the
@@ -500,6 +653,8 @@ class Evaluator:
             scores += self._frechet_scores()
         if self.classifier_per_class:
             scores += self._classifier_scores()
+        if self.memorisation:
+            scores += self._memorisation_scores()
         if self._record2:
             nv.eval_record2(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
                             self.best_iter, self.flag, maximise=self.maximise)
@@ -516,7 +671,7 @@ class Evaluator:
 
     def _all_samplers(self):
         return list(self.samplers.values()) + list(self.prdc_samplers.values()) + list(self.frechet_samplers.values()) \
-            + list(self.cls_samplers.values())
+            + list(self.cls_samplers.values()) + list(self.mem_samplers.values())
 
     def _capture(self):
         """Single-stream capture, no parallel branches.  The warm-up rounds in front of it are real evaluations:
@@ -601,6 +756,8 @@ class Evaluator:
         if self.classifier_per_class:        # (the classifier's weights are the caller's, the real side is recomputed)
             sd["classifier"] = {"per_class": self.classifier_per_class, "diversity_pairs": self.diversity_pairs,
                                 "multimodality_pairs": self.multimodality_pairs}
+        if self.memorisation:                # (the training side is recomputed from the data: not part of the state)
+            sd["memorisation"] = {"mode": self.memorisation, "per_class": self.memorisation_per_class}
         return sd
 
     def check_compatible(self, sd: dict) -> None:
@@ -620,6 +777,10 @@ class Evaluator:
         theirs = sd.get("classifier")
         if (None if theirs is None else {k: int(v) for k, v in dict(theirs).items()}) != mine:
             raise ValueError("Evaluator.load_state_dict: classifier is %r in the state, %r here" % (theirs, mine))
+        mine = {"mode": self.memorisation, "per_class": self.memorisation_per_class} if getattr(self, "memorisation", None) else None
+        theirs = sd.get("memorisation")
+        if (None if theirs is None else {"mode": str(dict(theirs)["mode"]), "per_class": int(dict(theirs)["per_class"])}) != mine:
+            raise ValueError("Evaluator.load_state_dict: memorisation is %r in the state, %r here" % (theirs, mine))
         for k, mine in (("pairs", self.pairs), ("select", self.select), ("modes", list(self.modes)), ("names", list(self.names))):
             if (list(sd[k]) if isinstance(mine, list) else sd[k]) != mine:
                 raise ValueError("Evaluator.load_state_dict: %s is %r in the state, %r here" % (k, sd[k], mine))

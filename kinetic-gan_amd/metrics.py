@@ -648,6 +648,99 @@ def memorisation(gen, labels_gen, train, labels_train=None, heldout=None, labels
     return out
 
 
+MEMORISATION_NAMES = ("authenticity", "label_agreement")
+
+
+def _as_points(x, who: str, what: str):
+    """a (n, d) feature matrix as (n, 1, 1, d) samples - one point of dimension d each, searched with d_outer = 1 -, its rows
+    read in place (a column slice of a wider matrix keeps its row stride)"""
+    x = _as_f32(x)
+    if x.dim() != 2:
+        raise ValueError("%s: %s is a (n, d) feature matrix, got %s" % (who, what, tuple(x.shape)))
+    if x.shape[1] > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    return x.unsqueeze(1).unsqueeze(1)
+
+
+def memorisation_features(feat_gen, labels_gen, feat_train, labels_train, feat_heldout=None, labels_heldout=None,
+                          train_loo=None) -> dict:
+    """``memorisation`` in a feature space: (n, d) fp32 matrices - a classifier's features of the generated, the training and
+    (optionally) the held-out samples - searched as points of dimension d (kg_nn with d_outer = 1).  Arguments, result keys
+    and their meaning are those of ``memorisation``; a copy is now a generated sample whose FEATURES lie closer to a training
+    sample's than that sample's lie to any other training sample's.  ValueError for argument errors, before the GPU is
+    touched."""
+    who = "memorisation_features"
+    gen = _as_points(feat_gen, who, "feat_gen")
+    train = _as_points(feat_train, who, "feat_train")
+    held = None if feat_heldout is None else _as_points(feat_heldout, who, "feat_heldout")
+    if labels_train is None:
+        raise ValueError("%s: labels_train is needed" % who)
+    return memorisation(gen, labels_gen, train, labels_train, held, labels_heldout, train_loo)
+
+
+def memorisation_sets(sets, labels, train, labels_train=None, train_loo=None) -> dict:
+    """``memorisation`` of 1 to 4 generated sets that share one label vector against ONE training set, in ONE kg_nn_sets call
+    (two launches whatever the number of sets) plus ONE kg_nn_scores launch: the Evaluator's form.
+
+    ``sets``: a list of (n, C, T, V) batches or of (n, d) feature matrices, all of one shape; ``labels`` (n,) their shared
+    conditioning labels; ``train``: a batch, a ``train.ResidentDataset`` (searched in place, its own labels by default) or a
+    (N, d) feature matrix, with ``labels_train``; ``train_loo`` as in ``memorisation``.  Returns device tensors ``nn_index``
+    (nsets, n) int64, ``nn_d2`` (nsets, n), ``counts`` (nsets, 2) int64 (authentic, agreeing), ``authenticity`` and
+    ``label_agreement`` (nsets,) fp32, ``counts_per_class`` (nsets, classes, 2) int32 by the conditioning label, and
+    ``train_loo_d2`` (N,).  Entry g of each equals, bit for bit, the same key of ``memorisation(sets[g], labels, train, ...)``
+    (``memorisation_features`` for matrices).  No host synchronisation (labels that live on the device are read once)."""
+    who = "memorisation_sets"
+    sets = list(sets) if isinstance(sets, (list, tuple)) else None
+    if not sets or len(sets) > _native.NN_MAX_SETS:
+        raise ValueError("%s: sets is a list of 1 to %d batches or feature matrices" % (who, _native.NN_MAX_SETS))
+    xs = [_as_f32(x) for x in sets]
+    if any(x.shape != xs[0].shape for x in xs):
+        raise ValueError("%s: the sets differ in shape: %s" % (who, [tuple(x.shape) for x in xs]))
+    flat = xs[0].dim() == 2
+    if flat:
+        xs = [_as_points(x, who, "set %d" % g) for g, x in enumerate(xs)]
+        if not all(hasattr(train, f) for f in ("fits", "data", "scale", "shift")):
+            train = _as_points(train, who, "train")
+    t, ta, own = _nn_side(train, who, "train")
+    if labels_train is None:
+        labels_train = own
+    if labels_train is None:
+        raise ValueError("%s: labels_train is needed (the training set carries none)" % who)
+    for g, x in enumerate(xs):
+        _nn_check_pair(x, t, who, ("set %d" % g, "train"))
+    if labels is None:
+        raise ValueError("%s: labels is needed" % who)
+    n, nt = xs[0].shape[0], t.shape[0]
+    lab, kq = _label_ids(labels, n, "labels", who)
+    lab_t, kt = _label_ids(labels_train, nt, "labels_train", who)
+    if nt < 2:
+        raise ValueError("%s: the leave-one-out pass needs at least 2 training samples, got %d" % (who, nt))
+    if n < 1:
+        raise ValueError("%s: the sets hold no sample" % who)
+    if train_loo is not None and (train_loo.dim() != 1 or train_loo.shape[0] != nt or train_loo.dtype != torch.float32):
+        raise ValueError("%s: train_loo must be the (%d,) fp32 leave-one-out distances of this training set" % (who, nt))
+    classes = max(kq, kt, 1)
+    if classes > _native.NN_SCORES_MAX_CLASSES:
+        raise ValueError("%s: %d classes, at most %d" % (who, classes, _native.NN_SCORES_MAX_CLASSES))
+    t = _as_cuda(t)
+    xs = [_as_cuda(x) for x in xs]
+    rows, rows_t = np.arange(n)[None, :], np.arange(nt)[None, :]
+    if train_loo is None:
+        train_loo = _nn_rows(t, rows_t, ta, t, rows_t, ta, 1, True)[1].reshape(-1)
+    views = [_view_pair(x, rows, t, rows_t) for x in xs]
+    if any((v[0].sc, v[0].sp, v[0].so, v[2], v[3]) != (views[0][0].sc, views[0][0].sp, views[0][0].so, views[0][2], views[0][3])
+           for v in views):                     # the sets are walked with shared strides
+        views = [_view_pair(x.contiguous(), rows, t, rows_t) for x in xs]
+    qv, bv, d_outer, d_inner = views[0]
+    idx, d2 = _native.nn_sets([v[0].t for v in views], qv.sc, qv.sp, qv.so, bv, n, nt, d_outer, d_inner, 1, 1, b_affine=ta)
+    dev = idx.device
+    res = _native.nn_scores(idx, d2, torch.as_tensor(lab.astype(np.int32), device=dev),
+                            torch.as_tensor(lab_t.astype(np.int32), device=dev), train_loo, classes, per_class=True)
+    return dict(nn_index=idx.reshape(len(xs), n).long(), nn_d2=d2.reshape(len(xs), n), counts=res["counts"],
+                authenticity=res["scores"][:, 0], label_agreement=res["scores"][:, 1],
+                counts_per_class=res["counts_per_class"], train_loo_d2=train_loo)
+
+
 def nn_two_sample(gen, real, labels_gen=None, labels_real=None, per_class: Optional[int] = None) -> dict:
     """The leave-one-out 1-NN two-sample test (Lopez-Paz & Oquab 2017; Xu et al. 2018) per class: every sample of R u F, with
     |R| = |F| = n per class, is classified by its nearest OTHER sample of the union; the accuracy of an indistinguishable

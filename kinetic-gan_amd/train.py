@@ -98,7 +98,8 @@ class TrainLoop:
                  eval_data: Optional[Feeder] = None, eval_prdc: int = 0, eval_prdc_k: int = 5,
                  eval_frechet: int = 0, eval_frechet_modes=("pose", "motion"), eval_classifier=None,
                  eval_classifier_samples: int = 0, eval_classifier_batch: int = 512, eval_diversity_pairs: int = 200,
-                 eval_multimodality_pairs: int = 20):
+                 eval_multimodality_pairs: int = 20, eval_memorisation: Optional[str] = None,
+                 eval_memorisation_samples: int = 0):
         self.G, self.D = G, D
         self.device = next(G.parameters()).device
         if self.device.type != "cuda":
@@ -114,6 +115,10 @@ class TrainLoop:
             self.resident = ResidentDataset(feeder, t_size, self.device, max_resident_bytes)
         self.feeder = feeder
         self.streaming = not self.resident.fits
+        if eval_interval and eval_memorisation and self.streaming:
+            raise ValueError("TrainLoop: eval_memorisation=%r searches the training set on the device, but this dataset is "
+                             "streamed (%.1f MB cropped do not fit max_resident_bytes): pass a ResidentDataset that fits, or "
+                             "score memorisation offline with tools/nearest_actions.py" % (eval_memorisation, self.resident.nbytes / 1e6))
         self.t = self.resident.t
         self.n = len(feeder)
         self.bpe = (self.n // self.B) // self.world          # batches of one epoch per rank, tail dropped
@@ -159,7 +164,9 @@ class TrainLoop:
         # the evaluation also scores precision / recall / density / coverage on that many samples per class.
         # eval_frechet (0: off): and the Frechet distance of eval_frechet_modes on that many samples per class.
         # eval_classifier (a trained classifier.Classifier) with eval_classifier_samples > 0: and accuracy, feature Frechet
-        # distance, diversity and multimodality on that many samples per class.
+        # distance, diversity and multimodality on that many samples per class.  eval_memorisation ("features":
+        # the classifier round's features; "raw": eval_memorisation_samples samples per class): and authenticity / label
+        # agreement against the loop's own ResidentDataset, searched where it lies; a streamed dataset is refused.
         self.eval_interval = int(eval_interval) if eval_interval else None
         self.evaluator = None
         if self.eval_interval:
@@ -173,7 +180,10 @@ class TrainLoop:
                                        prdc_per_class=eval_prdc, prdc_k=eval_prdc_k, frechet_per_class=eval_frechet,
                                        frechet_modes=eval_frechet_modes, classifier=eval_classifier,
                                        classifier_per_class=eval_classifier_samples, classifier_batch=eval_classifier_batch,
-                                       diversity_pairs=eval_diversity_pairs, multimodality_pairs=eval_multimodality_pairs)
+                                       diversity_pairs=eval_diversity_pairs, multimodality_pairs=eval_multimodality_pairs,
+                                       memorisation=eval_memorisation or None,
+                                       memorisation_train=self.resident if eval_memorisation else None,
+                                       memorisation_per_class=eval_memorisation_samples)
 
     # ---- schedule ------------------------------------------------------------------------------------------------
     @property

@@ -10,6 +10,10 @@ the same two numbers for the selected real samples as queries (pass a set the ge
 generator scores) and the class means of the leave-one-out 1-NN two-sample test between the selected fake and real samples
 (ideal 0.5; acc_fake -> 0 means copies).  --pairs_out writes one row (generated index, train index, d2) per generated
 sample and each of its --k nearest training samples as a float64 .npy, for the visualisation scripts.
+--classifier classifier_<n>.pth (tools/train_classifier.py; --classifier_batch samples per pass) also prints
+feature_authenticity / feature_label_agreement and their real_ twins: the same scores in the classifier's feature space
+(metrics.memorisation_features), all three sets going through Classifier.features in chunks; a checkpoint
+trained on another dataset, shape or normalisation is refused.
 
     python tools/nearest_actions.py --data_real val_data.npy --labels_real val_label.pkl \\
         --data_fake gen_data.npy --labels_fake gen_label.pkl --data_train train_data.npy --labels_train train_label.pkl \\
@@ -23,10 +27,24 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import kinetic_gan_amd  # noqa: F401,E402
+from kinetic_gan_amd.classifier import check_classifier_meta, load_classifier  # noqa: E402
 from kinetic_gan_amd.feeder import Feeder  # noqa: E402
-from kinetic_gan_amd.metrics import (NN_TWO_SAMPLE_NAMES, memorisation, nearest, nn_two_sample,  # noqa: E402
-                                     select_reference_samples)
-from kinetic_gan_amd.train import ResidentDataset  # noqa: E402
+from kinetic_gan_amd.metrics import (NN_TWO_SAMPLE_NAMES, memorisation, memorisation_features, nearest,  # noqa: E402
+                                     nn_two_sample, select_reference_samples)
+from kinetic_gan_amd.train import ResidentDataset, norm_constants  # noqa: E402
+
+
+def features(clf, x, batch, affine=None):
+    """(n, F) features of the samples x (n, C, T, V) on the device, ``batch`` at a time; ``affine``: (scale, shift) of samples
+    that are not normalised yet"""
+    out = []
+    with torch.no_grad():
+        for lo in range(0, x.shape[0], batch):
+            chunk = x[lo:lo + batch]
+            if affine is not None:
+                chunk = chunk * affine[0] + affine[1]
+            out.append(clf.features(chunk))
+    return torch.cat(out)
 
 
 def main(argv=None):
@@ -42,6 +60,9 @@ def main(argv=None):
     ap.add_argument("--k", type=int, default=1, help="nearest training samples written to --pairs_out")
     ap.add_argument("--per_class", type=int, default=100, help="samples of every class, of each set")
     ap.add_argument("--pairs_out", type=str, default=None, help=".npy of (generated index, train index, d2) rows")
+    ap.add_argument("--classifier", type=str, default=None,
+                    help="classifier_<n>.pth of tools/train_classifier.py: also score in its feature space")
+    ap.add_argument("--classifier_batch", type=int, default=512, help="samples per classifier pass")
     opt = ap.parse_args(argv)
     print(opt)
 
@@ -63,6 +84,22 @@ def main(argv=None):
     scores = dict(authenticity=mem["authenticity"], label_agreement=mem["label_agreement"],
                   real_authenticity=mem["heldout_authenticity"], real_label_agreement=mem["heldout_label_agreement"])
     scores.update(zip(("nn_" + n for n in NN_TWO_SAMPLE_NAMES), two["mean"]))
+    if opt.classifier:
+        clf, meta = load_classifier(opt.classifier, dev)
+        try:
+            scale, shift = norm_constants(train_f)
+            check_classifier_meta(meta, dict(dataset=opt.dataset, n_classes=len(classes), in_channels=train_f.C,
+                                             t_size=train.t, scale=scale, shift=shift))
+        except ValueError as e:
+            raise SystemExit("--classifier %s: %s" % (opt.classifier, e))
+        clf.eval()
+        affine = None if (train.scale, train.shift) == (1.0, 0.0) else (train.scale, train.shift)
+        feat = memorisation_features(features(clf, fake, opt.classifier_batch), fake_lab,
+                                     features(clf, train.data, opt.classifier_batch, affine), train.labels,
+                                     features(clf, real, opt.classifier_batch), real_lab)
+        scores.update(feature_authenticity=feat["authenticity"], feature_label_agreement=feat["label_agreement"],
+                      real_feature_authenticity=feat["heldout_authenticity"],
+                      real_feature_label_agreement=feat["heldout_label_agreement"])
     scores = {n: float(v) for n, v in scores.items()}
     if opt.pairs_out:
         near = nearest(fake, train, k=opt.k)

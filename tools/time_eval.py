@@ -34,7 +34,15 @@ on them) on P samples per class inside an evaluation, at the NTU and the H36M sh
 three ways - with the classifier columns (one kg_frechet_sets + one kg_cls_scores for both generators, the real side cached),
 with the same columns composed from one ``metrics.classifier_scores`` call per generator (eager: it reads the host), and
 without them - alternating in one process as under ``--frechet``; then kg_cls_scores alone as a graph of its own.
-    python tools/time_eval.py [--rounds 3] [--prdc 100 | --frechet 100 | --classifier 100] [--log FILE]"""
+``--memorisation {features,raw}`` (record: profiles/eval_memorisation_time.log): instead of the above, the cost of
+the authenticity / label agreement columns on ``--memorisation-samples`` samples per class inside an evaluation, at the NTU
+shapes (a synthetic training set of 40000 samples) and the H36M shapes (4000), live + ema.  The evaluation replay with and
+without the two columns per generator (feature space: both with the classifier columns, whose round is scored; raw space: a
+round of its own) alternating in one process as under ``--frechet``; the same columns composed from one
+``metrics.memorisation_features`` / ``memorisation`` call per generator on rounds already drawn (eager: it reads the host; the
+leave-one-out distances given); then, each a graph of its own, kg_nn_sets over both generators against two kg_nn calls -
+"faster" only if the gap exceeds the larger spread - and kg_nn_scores alone.
+    python tools/time_eval.py [--rounds 3] [--prdc 100 | --frechet 100 | --classifier 100 | --memorisation features] [--log FILE]"""
 import argparse
 import os
 import statistics
@@ -310,6 +318,121 @@ def classifier_part(args, say, dev):
         torch.cuda.empty_cache()
 
 
+MEM_TRAIN = {"NTU": 40000, "H36M": 4000}       # synthetic training-set sizes (tools/time_nn.py)
+
+
+def memorisation_part(args, say, dev):
+    """``--memorisation {features,raw}``: see the module docstring"""
+    from kinetic_gan_amd.classifier import Classifier
+    mode, P = args.memorisation, args.memorisation_samples
+    for name, c in PRDC_SHAPES:
+        K, Nt = c["n_classes"], MEM_TRAIN[name]
+        gens = {}
+        for g, seed in (("live", 1234), ("ema", 4321)):      # two generators of different weights (no training needed here)
+            torch.manual_seed(seed)
+            gens[g] = Generator(c["latent"], c["channels"], K, c["t_size"], c["mlp"], dataset=c["dataset"]).to(dev)
+        rng = np.random.RandomState(0)
+        real = torch.as_tensor((rng.rand(K * P, c["channels"], c["t_size"], c["v"]) * 2 - 1).astype(np.float32))
+        labels = np.tile(np.arange(K), P)
+        g_ = torch.Generator(device=dev).manual_seed(7)
+        train = torch.rand((Nt, c["channels"], c["t_size"], c["v"]), device=dev, generator=g_) * 2 - 1
+        lab_t = np.arange(Nt) % K
+        base = {}
+        if mode == "features":
+            torch.manual_seed(99)
+            clf = Classifier(c["channels"], K, c["t_size"], dataset=c["dataset"]).to(dev)
+            base = dict(classifier=clf, classifier_per_class=P, diversity_pairs=min(200, K * P), multimodality_pairs=min(20, P))
+            mem = dict(memorisation="features")
+        else:
+            mem = dict(memorisation="raw", memorisation_per_class=P)
+        on = Evaluator(gens, real, labels, pairs=PAIRS, seed=0, memorisation_train=train, memorisation_train_labels=lab_t, **base, **mem)
+        off = Evaluator(gens, real, labels, pairs=PAIRS, seed=0, **base)
+        d_outer, d_inner = on._mem_dims
+        say("%s shapes, %s space: %d classes x %d samples per class against %d training samples, D = %d, live + ema%s" % (
+            name, mode, K, P, Nt, d_outer * d_inner, "; both replays hold the classifier columns" if base else ""))
+        ev = {"with the memorisation columns": on, "without them": off}
+        for x in ev.values():
+            x.evaluate()                     # (captures)
+        torch.cuda.synchronize()
+        # the same columns from one metrics call per generator, on rounds already drawn
+        smp = {g: Sampler(G, qtd=P, seed=0) for g, G in gens.items()}
+        outs = {g: s.next()[0] for g, s in smp.items()}
+        if mode == "features":
+            feats = list(on._cls_feat.values())
+            tf = on.memorisation_train_features
+
+            def composed():
+                return [metrics.memorisation_features(f, labels, tf, lab_t, train_loo=on._mem_loo) for f in feats]
+        else:
+            def composed():
+                return [metrics.memorisation(o, labels, train, lab_t, train_loo=on._mem_loo) for o in outs.values()]
+
+        em = {k: [] for k in list(ev) + ["composed"]}
+        for r in range(args.rounds):
+            for k, x in ev.items():
+                ts = time_replays(x._graph, args.eval_replays)
+                x.n_evals += args.eval_replays + 1
+                for s in x._all_samplers():
+                    s.step_count += args.eval_replays + 1
+                em[k].append(statistics.median(ts))
+                say("%s evaluation replay, %-32s round %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
+                    name, k + ",", r, em[k][-1], args.eval_replays, min(ts), max(ts)))
+            ts = time_calls(composed, max(3, args.eval_replays // 3))
+            em["composed"].append(statistics.median(ts))
+            say("%s metrics.memorisation%s per generator (2 calls, eager, train_loo given), round %d: median %.4f ms over %d calls "
+                "(min %.4f, max %.4f)" % (name, "_features" if mode == "features" else "", r, em["composed"][-1], len(ts), min(ts), max(ts)))
+        m = {k: statistics.median(v) for k, v in em.items()}
+        sp = {k: max(v) - min(v) for k, v in em.items()}
+        a, b = list(ev)
+        say("%s evaluation replay: %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f): the memorisation columns cost %+.4f ms" % (
+            name, a, m[a], sp[a], b, m[b], sp[b], m[a] - m[b]))
+        say("%s the same columns composed from one metrics call per generator, without the rounds: %.4f ms (spread %.4f)" % (
+            name, m["composed"], sp["composed"]))
+        # kg_nn_sets over both generators against two kg_nn calls, then kg_nn_scores alone: graphs of their own
+        n = K * P
+        if mode == "features":
+            qs, (q_sc, q_sp, q_so) = feats, on._mem_q
+        else:
+            qs = list(outs.values())
+            sn, sc = nv._sn_sc(qs[0])
+            q_sc, q_sp, q_so = 0, sn, (0 if d_outer == 1 else sc)
+        bv, ba = on._mem_bv, on._mem_ba
+        ws1 = torch.empty(nv.nn_workspace_bytes(n, Nt, d_outer, d_inner, 1, 1) // 4, dtype=torch.int32, device=dev)
+        graphs = {"kg_nn_sets, both generators": capture(lambda: nv.nn_sets(qs, q_sc, q_sp, q_so, bv, n, Nt, d_outer, d_inner, 1, 1,
+                                                                            b_affine=ba, ws=on._mem_ws)),
+                  "kg_nn per generator": capture(lambda: [nv.nn(nv.PrdcView(q, q_sc, q_sp, q_so), bv, n, Nt, d_outer, d_inner, 1, 1,
+                                                                b_affine=ba, ws=ws1) for q in qs])}
+        replays = args.replays if mode == "features" else args.eval_replays
+        meds = {k: [] for k in graphs}
+        for r in range(args.reps):
+            for k, g in graphs.items():
+                ts = time_replays(g, replays)
+                meds[k].append(statistics.median(ts))
+                say("%s search, %-30s repetition %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
+                    name, k + ",", r, meds[k][-1], replays, min(ts), max(ts)))
+        gm = {k: statistics.median(v) for k, v in meds.items()}
+        gs = {k: max(v) - min(v) for k, v in meds.items()}
+        a, b = list(graphs)
+        gap, wide = gm[b] - gm[a], max(gs.values())
+        verdict = "not separated" if abs(gap) <= wide else ("kg_nn_sets is faster" if gap > 0 else "kg_nn_sets is slower")
+        split = lambda f, *x: f(*x) // (x[0] * 8) if f is nv.nn_workspace_bytes else f(*x) // (x[0] * x[1] * 8)      # noqa: E731
+        say("%s search: %s %.4f ms (spread %.4f; %d chunks), %s %.4f ms (spread %.4f; %d chunks each); gap %+.4f ms against the larger "
+            "spread %.4f ms: %s (two launches instead of four either way)" % (
+                name, a, gm[a], gs[a], split(nv.nn_sets_workspace_bytes, 2, n, Nt, d_outer, d_inner, 1, 1), b, gm[b], gs[b],
+                split(nv.nn_workspace_bytes, n, Nt, d_outer, d_inner, 1, 1), gap, wide, verdict))
+        idx, d2 = nv.nn_sets(qs, q_sc, q_sp, q_so, bv, n, Nt, d_outer, d_inner, 1, 1, b_affine=ba, ws=on._mem_ws)
+        g = capture(lambda: nv.nn_scores(idx, d2, on._mem_qlab, on._mem_blab, on._mem_loo, K))
+        sm = [statistics.median(time_replays(g, args.replays)) for _ in range(args.reps)]
+        say("%s kg_nn_scores alone (2 sets, Q = %d, N = %d; one launch): %.4f ms (median of %d repetitions of %d replays, spread %.4f)" % (
+            name, n, Nt, statistics.median(sm), args.reps, args.replays, max(sm) - min(sm)))
+        rec = on.records()
+        say("%s last recorded scores: %s; the real side's own: authenticity %.4f, label_agreement %.4f" % (
+            name, ", ".join("%s %.6g" % (n_, v) for n_, v in zip(rec["names"][-4:], rec["scores"][-1][-4:])),
+            float(on.memorisation_real["authenticity"]), float(on.memorisation_real["label_agreement"])))
+        del ev, on, off, gens, smp, outs, graphs, g, composed, train, qs, bv, idx, d2, ws1
+        torch.cuda.empty_cache()
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
@@ -321,6 +444,9 @@ def parse_args(argv=None):
                     help="samples per class: time the Frechet part of an evaluation instead (DESIGN.md 19)")
     ap.add_argument("--classifier", type=int, default=0,
                     help="samples per class: time the classifier columns of an evaluation instead (DESIGN.md 21)")
+    ap.add_argument("--memorisation", type=str, default=None, choices=["features", "raw"],
+                    help="time the memorisation columns of an evaluation in that space instead (DESIGN.md 23)")
+    ap.add_argument("--memorisation-samples", type=int, default=100, help="samples per class of --memorisation")
     ap.add_argument("--eval-replays", type=int, default=30,
                     help="replays of a whole evaluation / a Sampler round under --prdc and --frechet")
     ap.add_argument("--log", default=None, help="also write the lines to this file")
@@ -338,9 +464,11 @@ def main(argv=None):
         print(s, flush=True)
         lines.append(s)
 
-    if args.prdc or args.frechet or args.classifier:
+    if args.prdc or args.frechet or args.classifier or args.memorisation:
         say("device %s" % torch.cuda.get_device_name(0))
-        if args.prdc:
+        if args.memorisation:
+            memorisation_part(args, say, dev)
+        elif args.prdc:
             prdc_part(args, say, dev)
         elif args.classifier:
             classifier_part(args, say, dev)

@@ -16,7 +16,11 @@ columns, and ``--eval_select`` may name one, e.g. ``ema/motion_fd``; ``--eval_cl
 ``--eval_classifier_samples N`` also scores accuracy, feature Frechet distance, diversity and multimodality under a classifier
 trained by tools/train_classifier.py on N samples per class - ``--eval_classifier_batch``, ``--eval_diversity_pairs``,
 ``--eval_multimodality_pairs``: eight more columns, and ``--eval_select`` may name ``<live|ema>/accuracy`` or
-``<live|ema>/feature_fd``; a checkpoint trained on another dataset, shape or normalisation is refused)."""
+``<live|ema>/feature_fd``; a checkpoint trained on another dataset, shape or normalisation is refused;
+``--eval_memorisation features`` (the --eval_classifier round's features) or ``--eval_memorisation raw`` with
+``--eval_memorisation_samples P`` also scores authenticity and label agreement against the training set on the device: four
+more columns, ``--eval_select`` may name ``<live|ema>/label_agreement``; a dataset that is streamed - ``--max_resident_bytes``
+or half the free device memory is too small for it - is refused at start-up)."""
 import argparse
 import os
 import sys
@@ -87,6 +91,15 @@ def parse_args(argv=None):
     p.add_argument("--eval_classifier_batch", type=int, default=512, help="samples per classifier pass of an evaluation")
     p.add_argument("--eval_diversity_pairs", type=int, default=200, help="pairs of the diversity score")
     p.add_argument("--eval_multimodality_pairs", type=int, default=20, help="pairs per class of the multimodality score")
+    p.add_argument("--eval_memorisation", type=str, default=None, choices=["features", "raw"],
+                   help="an evaluation also scores authenticity and label agreement against the training set: 'features' in the "
+                        "--eval_classifier round's feature space (the per-interval form), 'raw' on the samples themselves "
+                        "(needs --eval_memorisation_samples; at NTU one search of the whole training set per generator)")
+    p.add_argument("--eval_memorisation_samples", type=int, default=0,
+                   help="samples per class of --eval_memorisation raw")
+    p.add_argument("--max_resident_bytes", type=int, default=None,
+                   help="device memory the cropped dataset may take to stay resident (default: half of what is free); a larger "
+                        "dataset is streamed")
     p.add_argument("--eval_trunc", type=float, default=None, help="truncation factor of the evaluation's samples")
     p.add_argument("--eval_trunc_mode", type=str, default="-", help="'-' none, 'z' or 'w' truncation of the evaluation's samples")
     p.add_argument("--eval_data_path", type=str, default=None, help="real samples of the evaluation (default: the training data)")
@@ -125,15 +138,12 @@ def main(argv=None):
                                                  t_size=min(opt.t_size, f.T), scale=scale, shift=shift))
         except ValueError as e:
             raise SystemExit("--eval_classifier %s: %s" % (opt.eval_classifier, e))
-    loop = TrainLoop(G, D, feeder, opt.batch_size, opt.t_size, n_critic=opt.n_critic, seed=opt.seed, lr=opt.lr, b1=opt.b1,
-                     b2=opt.b2, lambda_gp=float(opt.lambda_gp), use_graph=not opt.no_graph,
-                     ring_len=max(4096, opt.log_interval), ema_decay=opt.ema_decay or None, ema_warmup=opt.ema_warmup,
-                     eval_interval=opt.eval_interval or None, eval_pairs=opt.eval_pairs, eval_select=opt.eval_select,
-                     eval_trunc=opt.eval_trunc, eval_trunc_mode=opt.eval_trunc_mode, eval_data=eval_data,
-                     eval_prdc=opt.eval_prdc, eval_prdc_k=opt.eval_prdc_k, eval_frechet=opt.eval_frechet,
-                     eval_frechet_modes=tuple(opt.eval_frechet_modes), eval_classifier=clf,
-                     eval_classifier_samples=opt.eval_classifier_samples, eval_classifier_batch=opt.eval_classifier_batch,
-                     eval_diversity_pairs=opt.eval_diversity_pairs, eval_multimodality_pairs=opt.eval_multimodality_pairs)
+    try:
+        loop = _make_loop(opt, G, D, feeder, eval_data, clf)
+    except ValueError as e:
+        if opt.eval_memorisation and "eval_memorisation" in str(e):
+            raise SystemExit("--eval_memorisation %s: %s" % (opt.eval_memorisation, e))
+        raise
     print("dataset: %d samples, %d batches per epoch, %s (%.1f MB cropped)" % (
         len(feeder), loop.bpe, "streamed" if loop.streaming else "resident on the device", loop.resident.nbytes / 1e6))
     if opt.resume:
@@ -141,6 +151,20 @@ def main(argv=None):
         print("resumed at iteration %d (epoch %d)" % (loop.step_count, loop.epoch))
     loop.run(opt.n_epochs, opt.sample_interval, opt.checkpoint_interval, opt.out, log_interval=opt.log_interval,
              state_path=os.path.join(opt.out, "loop_state.pth"))
+
+
+def _make_loop(opt, G, D, feeder, eval_data, clf):
+    return TrainLoop(G, D, feeder, opt.batch_size, opt.t_size, n_critic=opt.n_critic, seed=opt.seed, lr=opt.lr, b1=opt.b1,
+                     b2=opt.b2, lambda_gp=float(opt.lambda_gp), use_graph=not opt.no_graph,
+                     ring_len=max(4096, opt.log_interval), ema_decay=opt.ema_decay or None, ema_warmup=opt.ema_warmup,
+                     eval_interval=opt.eval_interval or None, eval_pairs=opt.eval_pairs, eval_select=opt.eval_select,
+                     eval_trunc=opt.eval_trunc, eval_trunc_mode=opt.eval_trunc_mode, eval_data=eval_data,
+                     eval_prdc=opt.eval_prdc, eval_prdc_k=opt.eval_prdc_k, eval_frechet=opt.eval_frechet,
+                     eval_frechet_modes=tuple(opt.eval_frechet_modes), eval_classifier=clf,
+                     eval_classifier_samples=opt.eval_classifier_samples, eval_classifier_batch=opt.eval_classifier_batch,
+                     eval_diversity_pairs=opt.eval_diversity_pairs, eval_multimodality_pairs=opt.eval_multimodality_pairs,
+                     eval_memorisation=opt.eval_memorisation, eval_memorisation_samples=opt.eval_memorisation_samples,
+                     max_resident_bytes=opt.max_resident_bytes)
 
 
 if __name__ == "__main__":
