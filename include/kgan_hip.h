@@ -912,6 +912,65 @@ int64_t kg_nn_sets_workspace_bytes(const KgNnSetsArgs* a);   /* < 0 for invalid 
 int     kg_nn_sets(const KgNnSetsArgs* a, void* stream);
 int     kg_nn_scores(const KgNnScoresArgs* a, void* stream);
 
+/* ---- matrix-core pre-filter with exact re-score for kg_nn (additive, ABI v9; DESIGN.md 24, csrc/kg_nn_gram.hip) ---------------
+ * kg_nn_gram: the arguments of kg_nn_sets (plus exclude_self, which needs nsets == 1).  For every set g, idx[g] and d2[g]
+ * equal, bit for bit, what kg_nn(query[g], base) writes on the same data: the k smallest under (d2, j), d2 the fp32
+ * direct-difference fmaf chain in ascending dimension, the affine two roundings, exclude_self by index - for EVERY input of
+ * that definition, data on which the Gram form |q|^2 + |b|^2 - 2 q.b loses all its digits included.  The Gram value is only a
+ * filter:
+ *   1 search   a workgroup = (set, class, row tile, chunk) as in kg_nn.  The tile of q.b comes from the fp32 matrix cores
+ *              (v_mfma_f32_32x32x2f32 on LDS-staged operands; the accumulator restarts every 256 dimensions and the blocks
+ *              are summed in order, so a pair's value depends on the two points alone).  key(i, j) = fma(-2, q_i.b_j, nb_j)
+ *              with nb_j = b_norms[c, j]; each row keeps its `cand` smallest (key, j).
+ *   2 merge    the merge of kg_nn with k = cand: the row's cand smallest (key, j) over all chunks.
+ *   3 re-score every candidate's d2 from the chain of kg_nn (a wave per row, a lane per candidate); the candidates ordered by
+ *              (d2, j), the first k are written.  With t the k-th of them and a the cand-th smallest key the row is
+ *              CERTIFIED when   (1 - tau) * (a + nq * (1 - e_n) - E) - E_abs  >  t   (evaluated in fp64; nq the row's fp32
+ *              squared norm, E = (e_n + 2 e_g + 4 u) * max(nq, max_j nb_j) * (1 + 2 e_n), u = 2^-24, tau = (D + 4) u,
+ *              e_n = 1.01 (ceil(D / 64) + 8) u, e_g = 1.01 (min(D, 256) + ceil(D / 256) + 4) u, E_abs = (D + 16) 2^-120:
+ *              DESIGN.md 24 derives it): no base point outside the candidates can enter the list or tie with it.  A row all
+ *              of whose admissible base points are candidates (N - excluded <= cand) is certified as well.
+ *   4 compact  the rows that are not certified, per (set, class) in row order, by a scan; stats.
+ *   5, 6       the search and merge of kg_nn over the listed rows only (a grid sized for all rows, workgroups past the end
+ *              of a list leave at once); their results overwrite those rows.
+ * Six launches whatever the data; no host synchronisation, no atomics on global memory, capturable on one stream, the same
+ * bits on every call; ws may hold anything.  stats (nsets, classes, 2) int32 is always written: certified rows, fallback
+ * rows - the same under every (tile, split) plan (they depend on cand).
+ * cand: 0 = automatic, min(32, max(k + 8, 2 k)); else k < cand <= KG_NN_MAX_K (tests).  k = KG_NN_MAX_K has no cand.
+ * b_norms (classes, N) and b_norm_parts (classes, KG_NN_NORM_PARTS) are kg_nn_norms of the base, computed once for a base that
+ * does not change.  ws = kg_nn_gram_workspace_bytes(a) = nsets * classes * (Q * (8 * cand * (split + 1) + 8) + 4) bytes.
+ * Rejected (< 0, kg_last_error() names the field; all before any GPU call): every rule of kg_nn_sets; exclude_self with
+ * nsets != 1 (and then k > N - 1); cand outside {0} u (k, KG_NN_MAX_K]; k = KG_NN_MAX_K; null b_norms / b_norm_parts / stats.
+ *
+ * kg_nn_norms: ONE launch - the fp32 squared norm of every BASE point of `a` (base, b_s*, N, d_outer, d_inner, classes, the
+ * b_affine: no other field is read) into norms (classes, N), and the largest of them in KG_NN_NORM_PARTS parts per class into
+ * parts (classes, KG_NN_NORM_PARTS): parts[c, p] = max over the points j = p mod KG_NN_NORM_PARTS (0 where there is none); the
+ * class's largest norm is the largest of its parts (a workgroup owns one part: no atomics, no second launch).  A norm is one
+ * fmaf chain per lane over the dimensions lane, lane + 64, .. and a butterfly sum of the 64 lanes.                         */
+#define KG_NN_NORM_PARTS 64
+typedef struct KgNnGramArgs {
+    const float* query[KG_NN_MAX_SETS];  int64_t q_sc, q_sp, q_so;    /* query[0 .. nsets): strides, Q and affine are shared */
+    int32_t nsets;
+    const float* base;   int64_t b_sc, b_sp, b_so;
+    int32_t Q, N;
+    int32_t d_outer, d_inner;
+    int32_t classes, k;
+    int32_t exclude_self;           /* != 0: pair i == j is left out by index (nsets == 1)                               */
+    int32_t q_affine, b_affine;
+    float q_scale, q_shift, b_scale, b_shift;
+    int32_t cand;                   /* 0 = automatic, or a forced number of candidates per row (tests)                   */
+    int32_t tile, split;            /* 0 = automatic, or a forced plan (tests)                                           */
+    const float* b_norms;           /* (classes, N): kg_nn_norms of the base                                            */
+    const float* b_norm_parts;      /* (classes, KG_NN_NORM_PARTS)                                                      */
+    int32_t* idx;                   /* (nsets, classes, Q, k)                                                           */
+    float* d2;                      /* (nsets, classes, Q, k)                                                           */
+    int32_t* stats;                 /* (nsets, classes, 2): certified rows, fallback rows                               */
+    void* ws;  int64_t ws_bytes;
+} KgNnGramArgs;
+int     kg_nn_norms(const KgNnGramArgs* a, float* norms, float* parts, void* stream);
+int64_t kg_nn_gram_workspace_bytes(const KgNnGramArgs* a);   /* < 0 for invalid shapes                                 */
+int     kg_nn_gram(const KgNnGramArgs* a, void* stream);
+
 /* ---- Frechet distance of pose / motion / caller features in fp64 (additive, ABI v9; DESIGN.md 18, csrc/kg_frechet.hip) -----
  * For every class c: a real set of n and a fake set of m samples of `frames` frames, a frame being d = d_outer*d_inner <= 96
  * floats read through strides (elements):

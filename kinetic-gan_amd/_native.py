@@ -385,6 +385,23 @@ class _NnSetsArgs(C.Structure):
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
+NN_NORM_PARTS = 64
+
+
+class _NnGramArgs(C.Structure):
+    _fields_ = [("query", c_f32p * NN_MAX_SETS), ("q_sc", C.c_int64), ("q_sp", C.c_int64), ("q_so", C.c_int64),
+                ("nsets", C.c_int32),
+                ("base", c_f32p), ("b_sc", C.c_int64), ("b_sp", C.c_int64), ("b_so", C.c_int64),
+                ("Q", C.c_int32), ("N", C.c_int32), ("d_outer", C.c_int32), ("d_inner", C.c_int32),
+                ("classes", C.c_int32), ("k", C.c_int32), ("exclude_self", C.c_int32),
+                ("q_affine", C.c_int32), ("b_affine", C.c_int32),
+                ("q_scale", C.c_float), ("q_shift", C.c_float), ("b_scale", C.c_float), ("b_shift", C.c_float),
+                ("cand", C.c_int32), ("tile", C.c_int32), ("split", C.c_int32),
+                ("b_norms", c_f32p), ("b_norm_parts", c_f32p),
+                ("idx", C.c_void_p), ("d2", c_f32p), ("stats", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
 class _NnScoresArgs(C.Structure):
     _fields_ = [("nsets", C.c_int32), ("Q", C.c_int32), ("N", C.c_int32), ("n_classes", C.c_int32),
                 ("ld", C.c_int64),
@@ -614,6 +631,9 @@ EXPORTS = {
     "kg_nn_sets_workspace_bytes": (C.c_int64, [C.POINTER(_NnSetsArgs)]),
     "kg_nn_sets": (C.c_int, [C.POINTER(_NnSetsArgs), C.c_void_p]),
     "kg_nn_scores": (C.c_int, [C.POINTER(_NnScoresArgs), C.c_void_p]),
+    "kg_nn_norms": (C.c_int, [C.POINTER(_NnGramArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kg_nn_gram_workspace_bytes": (C.c_int64, [C.POINTER(_NnGramArgs)]),
+    "kg_nn_gram": (C.c_int, [C.POINTER(_NnGramArgs), C.c_void_p]),
     "kg_frechet_workspace_bytes": (C.c_int64, [C.POINTER(_FrechetArgs)]),
     "kg_frechet": (C.c_int, [C.POINTER(_FrechetArgs), C.c_void_p]),
     "kg_frechet_real_workspace_bytes": (C.c_int64, [C.POINTER(_FrechetRealArgs)]),
@@ -2689,6 +2709,92 @@ def nn_scores(idx: torch.Tensor, d2: torch.Tensor, query_labels: torch.Tensor, b
     _count(who, 0.0)
     _check(load_library().kg_nn_scores(C.byref(a), _stream()), who)
     return out
+
+
+# ---- matrix-core pre-filter with exact re-score (kg_nn_gram.hip) ---------------------------------------------
+
+def nn_norms(x: PrdcView, n: int, d_outer: int, d_inner: int, classes: int,
+             affine: Optional[Tuple[float, float]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Enqueue kg_nn_norms (ONE launch): (norms (classes, n), parts (classes, NN_NORM_PARTS)) fp32 - the squared norm of every
+    point of the set as ``nn_gram`` reads it (strides, ``affine``) and the largest of them in NN_NORM_PARTS parts per class
+    (``parts.amax(1)`` is the class's largest norm).  Computed once for a base that does not change."""
+    if x.t.dtype != torch.float32:
+        raise TypeError(f"kg_nn_norms: fp32 only, got {x.t.dtype}")
+    _need_cuda(x.t)
+    if min(n, d_outer, d_inner, classes) >= 1 and not _prdc_extent_ok(x, n, d_outer, d_inner, classes):
+        raise ValueError("kg_nn_norms: the strides of x reach outside its tensor")
+    a = _NnGramArgs()
+    a.base, a.b_sc, a.b_sp, a.b_so = x.t.data_ptr(), x.sc, x.sp, x.so
+    a.N, a.d_outer, a.d_inner, a.classes = int(n), int(d_outer), int(d_inner), int(classes)
+    if affine is not None:
+        a.b_affine, a.b_scale, a.b_shift = 1, float(affine[0]), float(affine[1])
+    norms = torch.empty((max(classes, 0), max(n, 0)), dtype=torch.float32, device=x.t.device)
+    parts = torch.empty((max(classes, 0), NN_NORM_PARTS), dtype=torch.float32, device=x.t.device)
+    _count("kg_nn_norms", 2.0 * float(n) * d_outer * d_inner * classes)
+    _check(load_library().kg_nn_norms(C.byref(a), norms.data_ptr(), parts.data_ptr(), _stream()), "kg_nn_norms")
+    return norms, parts
+
+
+def nn_gram_workspace_bytes(nsets: int, Q: int, N: int, d_outer: int, d_inner: int, classes: int, k: int,
+                            exclude_self: bool = False, cand: int = 0, tile: int = 0, split: int = 0) -> int:
+    """kg_nn_gram_workspace_bytes of a shape = nsets * classes * (Q * (8 * cand * (split + 1) + 8) + 4) with the plan's split
+    and cand (RuntimeError naming the field for a shape kg_nn_gram rejects); no GPU call"""
+    a = _NnGramArgs()
+    a.nsets, a.cand = int(nsets), int(cand)
+    _nn_shape(a, Q, N, d_outer, d_inner, classes, k, exclude_self, None, None, tile, split)
+    return _query("kg_nn_gram_workspace_bytes", a)
+
+
+def nn_gram(queries: Sequence[torch.Tensor], q_sc: int, q_sp: int, q_so: int, base: PrdcView, Q: int, N: int, d_outer: int,
+            d_inner: int, classes: int, k: int, exclude_self: bool = False, q_affine: Optional[Tuple[float, float]] = None,
+            b_affine: Optional[Tuple[float, float]] = None, cand: int = 0, tile: int = 0, split: int = 0,
+            base_norms: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+            ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Enqueue kg_nn_gram: the results of ``nn_sets`` (of ``nn`` with ``exclude_self``, one set), bit for bit, through the
+    matrix-core pre-filter with exact re-score and fallback - six launches, no host synchronisation.  Returns (idx (nsets,
+    classes, Q, k) int32, d2 (nsets, classes, Q, k) fp32, stats (nsets, classes, 2) int32: certified rows, fallback rows) on
+    the device.  ``base_norms``: ``nn_norms`` of the base (same view and affine) - without it that launch is made here;
+    ``cand``: 0 or a forced number of candidates per row (k < cand <= NN_MAX_K).  The other arguments as in ``nn_sets``."""
+    queries = list(queries)
+    for t in queries + [base.t]:
+        if t.dtype != torch.float32:
+            raise TypeError(f"kg_nn_gram: fp32 only, got {t.dtype}")
+    nsets = len(queries)
+    a = _NnGramArgs()
+    a.nsets, a.cand = nsets, int(cand)
+    _nn_shape(a, Q, N, d_outer, d_inner, classes, k, exclude_self, q_affine, b_affine, tile, split)
+    nbytes = _query("kg_nn_gram_workspace_bytes", a)
+    _need_cuda(base.t, ws, *queries)
+    for g, t in enumerate(queries):
+        if not _prdc_extent_ok(PrdcView(t, q_sc, q_sp, q_so), Q, d_outer, d_inner, classes):
+            raise ValueError(f"kg_nn_gram: the strides of query set {g} reach outside its tensor")
+    if not _prdc_extent_ok(base, N, d_outer, d_inner, classes):
+        raise ValueError("kg_nn_gram: the strides of base reach outside its tensor")
+    dev = base.t.device
+    if base_norms is None:
+        base_norms = nn_norms(base, N, d_outer, d_inner, classes, b_affine)
+    norms, parts = base_norms
+    for t, n, name in ((norms, classes * N, "norms (classes, N)"), (parts, classes * NN_NORM_PARTS, "parts (classes, %d)" % NN_NORM_PARTS)):
+        _need_cuda(t)
+        _dest(t, n, "kg_nn_gram: base_norms[...] %s must be a contiguous fp32 tensor" % name)
+    if ws is None:
+        ws = _workspace("kg_nn_gram_workspace_bytes", a, dev)
+    elif not ws.is_contiguous() or ws.element_size() != 4 or ws.numel() * 4 < nbytes:
+        raise ValueError("kg_nn_gram: ws must be a contiguous tensor of 4-byte elements, at least %d bytes" % nbytes)
+    else:
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    idx = torch.empty((nsets, classes, Q, k), dtype=torch.int32, device=dev)
+    d2 = torch.empty((nsets, classes, Q, k), dtype=torch.float32, device=dev)
+    stats = torch.empty((nsets, classes, 2), dtype=torch.int32, device=dev)
+    for g, t in enumerate(queries):
+        a.query[g] = t.data_ptr()
+    a.q_sc, a.q_sp, a.q_so = int(q_sc), int(q_sp), int(q_so)
+    a.base, a.b_sc, a.b_sp, a.b_so = base.t.data_ptr(), base.sc, base.sp, base.so
+    a.b_norms, a.b_norm_parts = norms.data_ptr(), parts.data_ptr()
+    a.idx, a.d2, a.stats = idx.data_ptr(), d2.data_ptr(), stats.data_ptr()
+    _count("kg_nn_gram", 2.0 * nsets * float(Q) * N * d_outer * d_inner * classes)
+    _check(load_library().kg_nn_gram(C.byref(a), _stream()), "kg_nn_gram")
+    return idx, d2, stats
 
 
 # ---- Frechet distance of pose / motion / caller features (kg_frechet.hip) -------------------------------------------------

@@ -177,7 +177,10 @@ class Evaluator:
     leave-one-out distances (and features) are computed once here.  ``memorisation_real`` holds the two scores of the selected
     real samples as queries: what a perfect generator scores - but only when ``real`` is held out from the training set
     (real samples that ARE training samples lie at distance 0 from themselves and score authenticity 0).  The Evaluator never
-    writes to the training set."""
+    writes to the training set.  ``memorisation_method`` (``"exact"``, ``"gram"``): with ``"gram"`` every search - the one-off
+    leave-one-out pass included - runs through kg_nn_gram, the matrix-core pre-filter with exact re-score: the
+    same bits in every column; the training side's norms are computed once here, the six launches are part of the captured
+    evaluation, and ``memorisation_stats`` holds the (sets, 1, 2) certified / fallback row counts of the last call."""
 
     def __init__(self, generators: Dict[str, torch.nn.Module], real, real_labels=None, pairs: int = 10,
                  modes: Sequence[str] = ("avg", "joint"), select: Optional[str] = None, seed: int = 0,
@@ -186,11 +189,14 @@ class Evaluator:
                  prdc_k: int = 5, frechet_per_class: int = 0, frechet_modes: Sequence[str] = ("pose", "motion"),
                  classifier=None, classifier_per_class: int = 0, classifier_batch: int = 512, diversity_pairs: int = 200,
                  multimodality_pairs: int = 20, memorisation: Optional[str] = None, memorisation_train=None,
-                 memorisation_train_labels=None, memorisation_per_class: int = 0):
+                 memorisation_train_labels=None, memorisation_per_class: int = 0, memorisation_method: str = "exact"):
         if not generators:
             raise ValueError("Evaluator: at least one generator")
         self._check_classifier_options(classifier, classifier_per_class, classifier_batch, diversity_pairs, multimodality_pairs)
         self._check_memorisation_options(memorisation, memorisation_train, memorisation_per_class)
+        self.memorisation_method = str(memorisation_method)
+        self._mem_gram = metrics._nn_method(memorisation_method, "Evaluator")
+        self.memorisation_stats = None
         self._check_frechet_options(frechet_per_class, frechet_modes)
         self._check_prdc_options(prdc_per_class, prdc_k)
         self.modes = tuple(modes)
@@ -601,13 +607,21 @@ class Evaluator:
                 real_q, train_q = real_x, (train if ta is not None else t)     # (a ResidentDataset: through its affine)
             d_outer, d_inner = self._mem_dims
             bv = self._mem_bv
-            self._mem_loo = nv.nn(bv, bv, N, N, d_outer, d_inner, 1, 1, exclude_self=True, q_affine=self._mem_ba,
-                                  b_affine=self._mem_ba)[1].reshape(-1)
-            res = metrics.memorisation_sets([real_q], lab_real, train_q, lab_t, train_loo=self._mem_loo)
+            if self._mem_gram:                  # the training side's norms, once; the one-off pass through the pre-filter too
+                self._mem_norms = nv.nn_norms(bv, N, d_outer, d_inner, 1, self._mem_ba)
+                self._mem_loo = nv.nn_gram([bv.t], bv.sc, bv.sp, bv.so, bv, N, N, d_outer, d_inner, 1, 1, exclude_self=True,
+                                           q_affine=self._mem_ba, b_affine=self._mem_ba,
+                                           base_norms=self._mem_norms)[1].reshape(-1)
+            else:
+                self._mem_loo = nv.nn(bv, bv, N, N, d_outer, d_inner, 1, 1, exclude_self=True, q_affine=self._mem_ba,
+                                      b_affine=self._mem_ba)[1].reshape(-1)
+            res = metrics.memorisation_sets([real_q], lab_real, train_q, lab_t, train_loo=self._mem_loo,
+                                            method=self.memorisation_method)
             self.memorisation_real = {"authenticity": res["authenticity"][0], "label_agreement": res["label_agreement"][0],
                                       "counts": res["counts"][0]}
             sizes = {min(nv.NN_MAX_SETS, len(self.gens) - q) for q in range(0, len(self.gens), nv.NN_MAX_SETS)}
-            nbytes = max(nv.nn_sets_workspace_bytes(g, n, N, d_outer, d_inner, 1, 1) for g in sizes)
+            ws_bytes = nv.nn_gram_workspace_bytes if self._mem_gram else nv.nn_sets_workspace_bytes
+            nbytes = max(ws_bytes(g, n, N, d_outer, d_inner, 1, 1) for g in sizes)
             self._mem_ws = torch.empty(max(1, nbytes // 4), dtype=torch.int32, device=dev)
 
     def _memorisation_scores(self):
@@ -627,8 +641,13 @@ class Evaluator:
         words = []
         for q in range(0, len(qs), nv.NN_MAX_SETS):
             part = qs[q:q + nv.NN_MAX_SETS]
-            idx, d2 = nv.nn_sets(part, q_sc, q_sp, q_so, self._mem_bv, K * P, N, d_outer, d_inner, 1, 1, b_affine=self._mem_ba,
-                                 ws=self._mem_ws)
+            if self._mem_gram:
+                idx, d2, self.memorisation_stats = nv.nn_gram(part, q_sc, q_sp, q_so, self._mem_bv, K * P, N, d_outer, d_inner, 1,
+                                                              1, b_affine=self._mem_ba, base_norms=self._mem_norms,
+                                                              ws=self._mem_ws)
+            else:
+                idx, d2 = nv.nn_sets(part, q_sc, q_sp, q_so, self._mem_bv, K * P, N, d_outer, d_inner, 1, 1,
+                                     b_affine=self._mem_ba, ws=self._mem_ws)
             sc_ = nv.nn_scores(idx, d2, self._mem_qlab, self._mem_blab, self._mem_loo, K)
             for g in range(len(part)):
                 words += [sc_["scores"][g, 0:1], sc_["scores"][g, 1:2]]

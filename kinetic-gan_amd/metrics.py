@@ -547,16 +547,39 @@ def _nn_check_k(k: int, N: int, exclude_self: bool, who: str):
         raise ValueError("%s: k=%d outside [1, min(%d, N=%d%s)]" % (who, k, _native.NN_MAX_K, N, " - 1" if exclude_self else ""))
 
 
-def _nn_rows(q, idx_q: np.ndarray, qa, b, idx_b: np.ndarray, ba, k: int, exclude_self: bool):
-    """one kg_nn call on the samples idx_q (classes, Q) of q and idx_b (classes, N) of b -> (idx, d2) (classes, Q, k)"""
+NN_METHODS = ("exact", "gram")
+
+
+def _nn_method(method, who: str) -> bool:
+    """True for the matrix-core pre-filter (kg_nn_gram: the same bits), False for the exact search"""
+    if method not in NN_METHODS:
+        raise ValueError("%s: method=%r is none of %s" % (who, method, ", ".join(repr(m) for m in NN_METHODS)))
+    return method == "gram"
+
+
+def _nn_rows(q, idx_q: np.ndarray, qa, b, idx_b: np.ndarray, ba, k: int, exclude_self: bool, gram: bool = False,
+             stats: Optional[list] = None):
+    """one kg_nn call on the samples idx_q (classes, Q) of q and idx_b (classes, N) of b -> (idx, d2) (classes, Q, k);
+    ``gram``: one kg_nn_gram call (and one kg_nn_norms of the base) instead, its (classes, 2) stats appended to ``stats``"""
     q, b = _as_cuda(q), _as_cuda(b)
     qv, bv, d_outer, d_inner = _view_pair(q, idx_q, b, idx_b)
+    if gram:
+        idx, d2, st = _native.nn_gram([qv.t], qv.sc, qv.sp, qv.so, bv, idx_q.shape[1], idx_b.shape[1], d_outer, d_inner,
+                                      idx_q.shape[0], k, exclude_self=exclude_self, q_affine=qa, b_affine=ba)
+        if stats is not None:
+            stats.append(st[0])
+        return idx[0], d2[0]
     return _native.nn(qv, bv, idx_q.shape[1], idx_b.shape[1], d_outer, d_inner, idx_q.shape[0], k,
                       exclude_self=exclude_self, q_affine=qa, b_affine=ba)
 
 
+def _nn_gram_k(k: int, who: str):
+    if k >= _native.NN_MAX_K:
+        raise ValueError("%s: method='gram' keeps more than k candidates per row: k=%d must be below %d" % (who, k, _native.NN_MAX_K))
+
+
 def nearest(query, base, k: int = 1, exclude_self: bool = False, labels_query=None, labels_base=None,
-            per_class: Optional[int] = None) -> dict:
+            per_class: Optional[int] = None, method: str = "exact") -> dict:
     """The k nearest ``base`` samples of every ``query`` sample (a sample = one point of dimension C*T*V) in one kg_nn call:
     exact, ties to the lower index, a duplicate is a neighbour at distance 0.
 
@@ -569,8 +592,12 @@ def nearest(query, base, k: int = 1, exclude_self: bool = False, labels_query=No
     Returns device tensors ``idx`` (K, Q, k) int32 - the neighbour's position inside its class's selection -, ``d2``
     (K, Q, k) squared distances, non-decreasing along k, ``index`` (K, Q, k) int64 - the neighbour's index in ``base`` -, and
     the selections ``rows_query`` (K, Q), ``rows_base`` (K, N) as numpy indices.  No host sync (labels that live on the
-    device are read once)."""
+    device are read once).
+    ``method="gram"``: the same bits through kg_nn_gram - the matrix-core pre-filter with exact re-score (k below
+    32) -; the result then carries ``certified`` / ``fallback`` (K,) int32: the rows the filter's certificate settled and the
+    rows that went through the exact search."""
     who = "nearest"
+    gram = _nn_method(method, who)
     q, qa, _ = _nn_side(query, who, "query")
     b, ba, own = _nn_side(base, who, "base")
     _nn_check_pair(q, b, who)
@@ -584,10 +611,16 @@ def nearest(query, base, k: int = 1, exclude_self: bool = False, labels_query=No
     idx_q = _class_rows(lab_q, classes, per_class, "query", who)
     idx_b = _class_rows(lab_b, classes, per_class, "base", who)
     _nn_check_k(k, idx_b.shape[1], exclude_self, who)
-    idx, d2 = _nn_rows(q, idx_q, qa, b, idx_b, ba, k, exclude_self)
+    if gram:
+        _nn_gram_k(k, who)
+    stats = []
+    idx, d2 = _nn_rows(q, idx_q, qa, b, idx_b, ba, k, exclude_self, gram, stats)
     rows = torch.as_tensor(idx_b, device=idx.device)
     index = torch.gather(rows, 1, idx.reshape(classes, -1).long()).reshape(idx.shape)
-    return dict(idx=idx, d2=d2, index=index, rows_query=idx_q, rows_base=idx_b)
+    out = dict(idx=idx, d2=d2, index=index, rows_query=idx_q, rows_base=idx_b)
+    if gram:
+        out.update(certified=stats[0][:, 0], fallback=stats[0][:, 1])
+    return out
 
 
 def _share(count: torch.Tensor, of: int) -> torch.Tensor:
@@ -595,7 +628,8 @@ def _share(count: torch.Tensor, of: int) -> torch.Tensor:
     return (count.double() / float(of)).float()
 
 
-def memorisation(gen, labels_gen, train, labels_train=None, heldout=None, labels_heldout=None, train_loo=None) -> dict:
+def memorisation(gen, labels_gen, train, labels_train=None, heldout=None, labels_heldout=None, train_loo=None,
+                 method: str = "exact") -> dict:
     """Does the generator replay its training set?  One global search gen -> train (k = 1) and one train -> train (k = 1,
     leave-one-out); a generated sample that lies closer to its nearest training sample than that sample lies to any OTHER
     training sample counts as a copy (authenticity, Alaa et al. 2022).
@@ -608,8 +642,11 @@ def memorisation(gen, labels_gen, train, labels_train=None, heldout=None, labels
     share, ``label_agreement`` = the share whose nearest training sample carries the conditioning label, ``counts`` (2,)
     int64 (authentic, agreeing), ``train_loo_d2`` (Nt,).  With ``heldout`` (real samples the generator never saw, with
     ``labels_heldout``) the same for it as queries under ``heldout_*``: what a perfect generator scores.  Tallies are
-    integers on the device; the shares are evaluated in float64 and rounded once."""
+    integers on the device; the shares are evaluated in float64 and rounded once.
+    ``method="gram"``: every search through kg_nn_gram (the same bits; ``nearest``); ``certified`` / ``fallback`` (and
+    ``heldout_*``, ``train_loo_*`` when that pass ran) are then the 0-d int32 row counts of each search."""
     who = "memorisation"
+    gram = _nn_method(method, who)
     t, ta, own = _nn_side(train, who, "train")
     if labels_train is None:
         labels_train = own
@@ -632,12 +669,17 @@ def memorisation(gen, labels_gen, train, labels_train=None, heldout=None, labels
         raise ValueError("%s: train_loo must be the (%d,) fp32 leave-one-out distances of this training set" % (who, nt))
     t = _as_cuda(t)                             # (once: up to three searches read it)
     rows_t = np.arange(nt)[None, :]
+    out, stats = {}, []
     if train_loo is None:
-        train_loo = _nn_rows(t, rows_t, ta, t, rows_t, ta, 1, True)[1].reshape(-1)
-    out = dict(train_loo_d2=train_loo)
+        train_loo = _nn_rows(t, rows_t, ta, t, rows_t, ta, 1, True, gram, stats)[1].reshape(-1)
+        if gram:
+            out.update(train_loo_certified=stats[-1][0, 0], train_loo_fallback=stats[-1][0, 1])
+    out["train_loo_d2"] = train_loo
     lab_t = torch.as_tensor(lab_t, device=train_loo.device)
     for (pre, _, x, _, _), lab in zip(sets, labs):
-        idx, d2 = _nn_rows(x, np.arange(x.shape[0])[None, :], None, t, rows_t, ta, 1, False)
+        idx, d2 = _nn_rows(x, np.arange(x.shape[0])[None, :], None, t, rows_t, ta, 1, False, gram, stats)
+        if gram:
+            out.update({pre + "certified": stats[-1][0, 0], pre + "fallback": stats[-1][0, 1]})
         idx, d2 = idx.reshape(-1).long(), d2.reshape(-1)
         authentic = d2 >= train_loo[idx]
         agree = lab_t[idx] == torch.as_tensor(lab, device=idx.device)
@@ -663,7 +705,7 @@ def _as_points(x, who: str, what: str):
 
 
 def memorisation_features(feat_gen, labels_gen, feat_train, labels_train, feat_heldout=None, labels_heldout=None,
-                          train_loo=None) -> dict:
+                          train_loo=None, method: str = "exact") -> dict:
     """``memorisation`` in a feature space: (n, d) fp32 matrices - a classifier's features of the generated, the training and
     (optionally) the held-out samples - searched as points of dimension d (kg_nn with d_outer = 1).  Arguments, result keys
     and their meaning are those of ``memorisation``; a copy is now a generated sample whose FEATURES lie closer to a training
@@ -675,10 +717,10 @@ def memorisation_features(feat_gen, labels_gen, feat_train, labels_train, feat_h
     held = None if feat_heldout is None else _as_points(feat_heldout, who, "feat_heldout")
     if labels_train is None:
         raise ValueError("%s: labels_train is needed" % who)
-    return memorisation(gen, labels_gen, train, labels_train, held, labels_heldout, train_loo)
+    return memorisation(gen, labels_gen, train, labels_train, held, labels_heldout, train_loo, method)
 
 
-def memorisation_sets(sets, labels, train, labels_train=None, train_loo=None) -> dict:
+def memorisation_sets(sets, labels, train, labels_train=None, train_loo=None, method: str = "exact", train_norms=None) -> dict:
     """``memorisation`` of 1 to 4 generated sets that share one label vector against ONE training set, in ONE kg_nn_sets call
     (two launches whatever the number of sets) plus ONE kg_nn_scores launch: the Evaluator's form.
 
@@ -688,8 +730,12 @@ def memorisation_sets(sets, labels, train, labels_train=None, train_loo=None) ->
     (nsets, n) int64, ``nn_d2`` (nsets, n), ``counts`` (nsets, 2) int64 (authentic, agreeing), ``authenticity`` and
     ``label_agreement`` (nsets,) fp32, ``counts_per_class`` (nsets, classes, 2) int32 by the conditioning label, and
     ``train_loo_d2`` (N,).  Entry g of each equals, bit for bit, the same key of ``memorisation(sets[g], labels, train, ...)``
-    (``memorisation_features`` for matrices).  No host synchronisation (labels that live on the device are read once)."""
+    (``memorisation_features`` for matrices).  No host synchronisation (labels that live on the device are read once).
+    ``method="gram"``: ONE kg_nn_gram call instead of kg_nn_sets (the same bits); ``certified`` / ``fallback``
+    (nsets,) int32 are then its row counts; ``train_norms``: ``_native.nn_norms`` of the training set as it is searched here
+    (else that launch is made), handed back as ``train_norms``."""
     who = "memorisation_sets"
+    gram = _nn_method(method, who)
     sets = list(sets) if isinstance(sets, (list, tuple)) else None
     if not sets or len(sets) > _native.NN_MAX_SETS:
         raise ValueError("%s: sets is a list of 1 to %d batches or feature matrices" % (who, _native.NN_MAX_SETS))
@@ -726,22 +772,30 @@ def memorisation_sets(sets, labels, train, labels_train=None, train_loo=None) ->
     xs = [_as_cuda(x) for x in xs]
     rows, rows_t = np.arange(n)[None, :], np.arange(nt)[None, :]
     if train_loo is None:
-        train_loo = _nn_rows(t, rows_t, ta, t, rows_t, ta, 1, True)[1].reshape(-1)
+        train_loo = _nn_rows(t, rows_t, ta, t, rows_t, ta, 1, True, gram)[1].reshape(-1)
     views = [_view_pair(x, rows, t, rows_t) for x in xs]
     if any((v[0].sc, v[0].sp, v[0].so, v[2], v[3]) != (views[0][0].sc, views[0][0].sp, views[0][0].so, views[0][2], views[0][3])
            for v in views):                     # the sets are walked with shared strides
         views = [_view_pair(x.contiguous(), rows, t, rows_t) for x in xs]
     qv, bv, d_outer, d_inner = views[0]
-    idx, d2 = _native.nn_sets([v[0].t for v in views], qv.sc, qv.sp, qv.so, bv, n, nt, d_outer, d_inner, 1, 1, b_affine=ta)
+    extra = {}
+    if gram:
+        if train_norms is None:
+            train_norms = _native.nn_norms(bv, nt, d_outer, d_inner, 1, ta)
+        idx, d2, st = _native.nn_gram([v[0].t for v in views], qv.sc, qv.sp, qv.so, bv, n, nt, d_outer, d_inner, 1, 1, b_affine=ta,
+                                      base_norms=train_norms)
+        extra = dict(certified=st[:, 0, 0], fallback=st[:, 0, 1], train_norms=train_norms)
+    else:
+        idx, d2 = _native.nn_sets([v[0].t for v in views], qv.sc, qv.sp, qv.so, bv, n, nt, d_outer, d_inner, 1, 1, b_affine=ta)
     dev = idx.device
     res = _native.nn_scores(idx, d2, torch.as_tensor(lab.astype(np.int32), device=dev),
                             torch.as_tensor(lab_t.astype(np.int32), device=dev), train_loo, classes, per_class=True)
     return dict(nn_index=idx.reshape(len(xs), n).long(), nn_d2=d2.reshape(len(xs), n), counts=res["counts"],
                 authenticity=res["scores"][:, 0], label_agreement=res["scores"][:, 1],
-                counts_per_class=res["counts_per_class"], train_loo_d2=train_loo)
+                counts_per_class=res["counts_per_class"], train_loo_d2=train_loo, **extra)
 
 
-def nn_two_sample(gen, real, labels_gen=None, labels_real=None, per_class: Optional[int] = None) -> dict:
+def nn_two_sample(gen, real, labels_gen=None, labels_real=None, per_class: Optional[int] = None, method: str = "exact") -> dict:
     """The leave-one-out 1-NN two-sample test (Lopez-Paz & Oquab 2017; Xu et al. 2018) per class: every sample of R u F, with
     |R| = |F| = n per class, is classified by its nearest OTHER sample of the union; the accuracy of an indistinguishable
     generator is 0.5, ``acc_fake`` -> 0 means copies of real samples, -> 1 a separable (or collapsed) fake set.
@@ -750,8 +804,11 @@ def nn_two_sample(gen, real, labels_gen=None, labels_real=None, per_class: Optio
     neighbour goes to the real one: real i is correct iff d2_RR(i) <= d2_RF(i), fake j iff d2_FF(j) < d2_FR(j).  Arguments
     and selection as ``prdc``.  Returns device tensors ``acc_real``, ``acc_fake``, ``acc`` (K,), ``counts`` (K, 2) int64
     (correct reals, correct fakes) and ``mean`` (3,) - the class means in the order NN_TWO_SAMPLE_NAMES.  Tallies are
-    integers on the device; every quotient is evaluated in float64 and rounded once."""
+    integers on the device; every quotient is evaluated in float64 and rounded once.
+    ``method="gram"``: the four searches through kg_nn_gram (the same bits); ``certified`` / ``fallback`` (K,) int32 are then
+    the row counts summed over the four."""
     who = "nn_two_sample"
+    gram = _nn_method(method, who)
     gen, real = _as_f32(gen), _as_f32(real)
     _nn_check_pair(gen, real, who, ("gen", "real"))
     lab_g, kg = _label_ids(labels_gen, gen.shape[0], "labels_gen", who)
@@ -768,16 +825,20 @@ def nn_two_sample(gen, real, labels_gen=None, labels_real=None, per_class: Optio
     if n < 2:
         raise ValueError("%s: %d samples per class and set, the leave-one-out search needs 2" % (who, n))
     gen, real = _as_cuda(gen), _as_cuda(real)
-    d = {}
+    d, stats = {}, []
     for key, (a, ia), (b, ib) in (("rr", (real, idx_r), (real, idx_r)), ("rf", (real, idx_r), (gen, idx_g)),
                                   ("ff", (gen, idx_g), (gen, idx_g)), ("fr", (gen, idx_g), (real, idx_r))):
-        d[key] = _nn_rows(a, ia, None, b, ib, None, 1, key in ("rr", "ff"))[1].reshape(classes, n)
+        d[key] = _nn_rows(a, ia, None, b, ib, None, 1, key in ("rr", "ff"), gram, stats)[1].reshape(classes, n)
     counts = torch.stack([(d["rr"] <= d["rf"]).sum(1), (d["ff"] < d["fr"]).sum(1)], dim=1)
     total = counts.sum(0)
-    return dict(acc_real=_share(counts[:, 0], n), acc_fake=_share(counts[:, 1], n), acc=_share(counts.sum(1), 2 * n),
-                counts=counts,
-                mean=torch.stack([_share(total[0], classes * n), _share(total[1], classes * n),
-                                  _share(total.sum(), 2 * classes * n)]))
+    out = dict(acc_real=_share(counts[:, 0], n), acc_fake=_share(counts[:, 1], n), acc=_share(counts.sum(1), 2 * n),
+               counts=counts,
+               mean=torch.stack([_share(total[0], classes * n), _share(total[1], classes * n),
+                                 _share(total.sum(), 2 * classes * n)]))
+    if gram:
+        tot = torch.stack(stats).sum(0)
+        out.update(certified=tot[:, 0], fallback=tot[:, 1])
+    return out
 
 
 def select_reference_samples(feeder, classes: Optional[Sequence[int]] = None, t_size: int = 64, per_class: int = 100):

@@ -99,7 +99,7 @@ class TrainLoop:
                  eval_frechet: int = 0, eval_frechet_modes=("pose", "motion"), eval_classifier=None,
                  eval_classifier_samples: int = 0, eval_classifier_batch: int = 512, eval_diversity_pairs: int = 200,
                  eval_multimodality_pairs: int = 20, eval_memorisation: Optional[str] = None,
-                 eval_memorisation_samples: int = 0):
+                 eval_memorisation_samples: int = 0, eval_memorisation_method: str = "exact"):
         self.G, self.D = G, D
         self.device = next(G.parameters()).device
         if self.device.type != "cuda":
@@ -183,7 +183,8 @@ class TrainLoop:
                                        diversity_pairs=eval_diversity_pairs, multimodality_pairs=eval_multimodality_pairs,
                                        memorisation=eval_memorisation or None,
                                        memorisation_train=self.resident if eval_memorisation else None,
-                                       memorisation_per_class=eval_memorisation_samples)
+                                       memorisation_per_class=eval_memorisation_samples,
+                                       memorisation_method=eval_memorisation_method)
 
     # ---- schedule ------------------------------------------------------------------------------------------------
     @property

@@ -63,6 +63,9 @@ def main(argv=None):
     ap.add_argument("--classifier", type=str, default=None,
                     help="classifier_<n>.pth of tools/train_classifier.py: also score in its feature space")
     ap.add_argument("--classifier_batch", type=int, default=512, help="samples per classifier pass")
+    ap.add_argument("--method", type=str, default="exact", choices=["exact", "gram"],
+                    help="gram: every search through kg_nn_gram, the matrix-core pre-filter with exact re-score - the same "
+                         "scores and pairs (DESIGN.md 24); the certified / fallback row counts are printed")
     opt = ap.parse_args(argv)
     print(opt)
 
@@ -79,8 +82,12 @@ def main(argv=None):
     print(train.shape, "train")
     fake, real = torch.from_numpy(fake).to(dev), torch.from_numpy(real).to(dev)
 
-    mem = memorisation(fake, fake_lab, train, heldout=real, labels_heldout=real_lab)
-    two = nn_two_sample(fake, real, fake_lab, real_lab)
+    mem = memorisation(fake, fake_lab, train, heldout=real, labels_heldout=real_lab, method=opt.method)
+    two = nn_two_sample(fake, real, fake_lab, real_lab, method=opt.method)
+    if opt.method == "gram":
+        print("kg_nn_gram rows (certified, fallback): fake -> train %d %d, real -> train %d %d, train -> train %d %d, two-sample %d %d"
+              % (mem["certified"], mem["fallback"], mem["heldout_certified"], mem["heldout_fallback"], mem["train_loo_certified"],
+                 mem["train_loo_fallback"], two["certified"].sum(), two["fallback"].sum()))
     scores = dict(authenticity=mem["authenticity"], label_agreement=mem["label_agreement"],
                   real_authenticity=mem["heldout_authenticity"], real_label_agreement=mem["heldout_label_agreement"])
     scores.update(zip(("nn_" + n for n in NN_TWO_SAMPLE_NAMES), two["mean"]))
@@ -96,13 +103,13 @@ def main(argv=None):
         affine = None if (train.scale, train.shift) == (1.0, 0.0) else (train.scale, train.shift)
         feat = memorisation_features(features(clf, fake, opt.classifier_batch), fake_lab,
                                      features(clf, train.data, opt.classifier_batch, affine), train.labels,
-                                     features(clf, real, opt.classifier_batch), real_lab)
+                                     features(clf, real, opt.classifier_batch), real_lab, method=opt.method)
         scores.update(feature_authenticity=feat["authenticity"], feature_label_agreement=feat["label_agreement"],
                       real_feature_authenticity=feat["heldout_authenticity"],
                       real_feature_label_agreement=feat["heldout_label_agreement"])
     scores = {n: float(v) for n, v in scores.items()}
     if opt.pairs_out:
-        near = nearest(fake, train, k=opt.k)
+        near = nearest(fake, train, k=opt.k, method=opt.method)
         gen_index = np.repeat(fake_index, opt.k)            # the generated sample's index in its file
         pairs = np.stack([gen_index.astype(np.float64), near["index"].reshape(-1).double().cpu().numpy(),
                           near["d2"].reshape(-1).double().cpu().numpy()], axis=1)

@@ -351,9 +351,37 @@ def memorisation_part(args, say, dev):
         say("%s shapes, %s space: %d classes x %d samples per class against %d training samples, D = %d, live + ema%s" % (
             name, mode, K, P, Nt, d_outer * d_inner, "; both replays hold the classifier columns" if base else ""))
         ev = {"with the memorisation columns": on, "without them": off}
+        if args.memorisation_method == "gram":
+            # (record: profiles/eval_memorisation_gram_time.log) the same columns through kg_nn_gram: three
+            # replays alternate - exact search, pre-filter, no memorisation columns - and the recorded scores must agree
+            gram = Evaluator(gens, real, labels, pairs=PAIRS, seed=0, memorisation_train=train, memorisation_train_labels=lab_t,
+                             memorisation_method="gram", **base, **mem)
+            ev = {"with the memorisation columns": on, "with them through kg_nn_gram": gram, "without them": off}
         for x in ev.values():
             x.evaluate()                     # (captures)
         torch.cuda.synchronize()
+        if args.memorisation_method == "gram":
+            em = {k: [] for k in ev}
+            for r in range(args.rounds):
+                for k, x in ev.items():
+                    ts = time_replays(x._graph, args.eval_replays)
+                    em[k].append(statistics.median(ts))
+                    say("%s evaluation replay, %-32s round %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
+                        name, k + ",", r, em[k][-1], args.eval_replays, min(ts), max(ts)))
+            m = {k: statistics.median(v) for k, v in em.items()}
+            sp = {k: max(v) - min(v) for k, v in em.items()}
+            a, b, c_ = list(ev)
+            say("%s evaluation replay: exact %.4f ms (spread %.4f), kg_nn_gram %.4f ms (spread %.4f), without the columns %.4f ms "
+                "(spread %.4f): the columns cost %+.4f ms exact, %+.4f ms through the pre-filter" % (
+                    name, m[a], sp[a], m[b], sp[b], m[c_], sp[c_], m[a] - m[c_], m[b] - m[c_]))
+            ra, rb = on.records(), gram.records()
+            same = np.array_equal(np.asarray(ra["scores"][0]), np.asarray(rb["scores"][0]))
+            say("%s first recorded row equal in every column: %s; stats (certified, fallback) per generator of the last replay: %s; "
+                "leave-one-out distances equal: %s" % (name, same, gram.memorisation_stats[:, 0].tolist(),
+                                                        bool(torch.equal(on._mem_loo, gram._mem_loo))))
+            del ev, on, off, gram, gens, train
+            torch.cuda.empty_cache()
+            continue
         # the same columns from one metrics call per generator, on rounds already drawn
         smp = {g: Sampler(G, qtd=P, seed=0) for g, G in gens.items()}
         outs = {g: s.next()[0] for g, s in smp.items()}
@@ -447,6 +475,8 @@ def parse_args(argv=None):
     ap.add_argument("--memorisation", type=str, default=None, choices=["features", "raw"],
                     help="time the memorisation columns of an evaluation in that space instead (DESIGN.md 23)")
     ap.add_argument("--memorisation-samples", type=int, default=100, help="samples per class of --memorisation")
+    ap.add_argument("--memorisation_method", type=str, default="exact", choices=["exact", "gram"],
+                    help="gram: time the memorisation columns through kg_nn_gram against the exact search (DESIGN.md 24)")
     ap.add_argument("--eval-replays", type=int, default=30,
                     help="replays of a whole evaluation / a Sampler round under --prdc and --frechet")
     ap.add_argument("--log", default=None, help="also write the lines to this file")

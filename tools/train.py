@@ -18,7 +18,7 @@ trained by tools/train_classifier.py on N samples per class - ``--eval_classifie
 ``--eval_multimodality_pairs``: eight more columns, and ``--eval_select`` may name ``<live|ema>/accuracy`` or
 ``<live|ema>/feature_fd``; a checkpoint trained on another dataset, shape or normalisation is refused;
 ``--eval_memorisation features`` (the --eval_classifier round's features) or ``--eval_memorisation raw`` with
-``--eval_memorisation_samples P`` also scores authenticity and label agreement against the training set on the device: four
+``--eval_memorisation_samples P`` (and ``--eval_memorisation_method gram`` for the matrix-core pre-filter) also scores authenticity and label agreement against the training set on the device: four
 more columns, ``--eval_select`` may name ``<live|ema>/label_agreement``; a dataset that is streamed - ``--max_resident_bytes``
 or half the free device memory is too small for it - is refused at start-up)."""
 import argparse
@@ -97,6 +97,9 @@ def parse_args(argv=None):
                         "(needs --eval_memorisation_samples; at NTU one search of the whole training set per generator)")
     p.add_argument("--eval_memorisation_samples", type=int, default=0,
                    help="samples per class of --eval_memorisation raw")
+    p.add_argument("--eval_memorisation_method", type=str, default="exact", choices=["exact", "gram"],
+                   help="gram: the memorisation searches through kg_nn_gram, the matrix-core pre-filter with exact re-score "
+                        "(the same columns, DESIGN.md 24)")
     p.add_argument("--max_resident_bytes", type=int, default=None,
                    help="device memory the cropped dataset may take to stay resident (default: half of what is free); a larger "
                         "dataset is streamed")
@@ -164,6 +167,7 @@ def _make_loop(opt, G, D, feeder, eval_data, clf):
                      eval_classifier_samples=opt.eval_classifier_samples, eval_classifier_batch=opt.eval_classifier_batch,
                      eval_diversity_pairs=opt.eval_diversity_pairs, eval_multimodality_pairs=opt.eval_multimodality_pairs,
                      eval_memorisation=opt.eval_memorisation, eval_memorisation_samples=opt.eval_memorisation_samples,
+                     eval_memorisation_method=opt.eval_memorisation_method,
                      max_resident_bytes=opt.max_resident_bytes)
 
 
