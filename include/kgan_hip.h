@@ -1323,6 +1323,95 @@ typedef struct KgClsScoresArgs {
 } KgClsScoresArgs;
 int     kg_cls_scores(const KgClsScoresArgs* a, void* stream);
 
+/* ---- kinematic plausibility: bones, smoothness, W1 (additive, ABI v9; DESIGN.md 25, csrc/kg_kin.hip) ---------------------
+ * A sample is x[c, f, v], c < C (2 or 3), f < T, v < V, fp32, read in place:
+ *   x[c, f, v] of sample i of class k = x + k*sc + i*ss + f*sf + c*so + v            (the joint axis is contiguous)
+ * With bones (B, 2) joint pairs (u_b, v_b) and mirror (M, 2) pairs of bone indices, everything in fp64 from the fp32 inputs,
+ * |.| the Euclidean norm over c:
+ *   L[b, f] = |x[:, f, u_b] - x[:, f, v_b]|     mu_b = mean_f L[b, f]     sd_b = sqrt(mean_f (L[b, f] - mu_b)^2)  (two passes)
+ *   s = mean_{b, f} L[b, f]                     the sample's own length unit: every descriptor is dimensionless
+ *   D1 = x[f+1] - x[f],   D2 = (x[f+2] - 2 x[f+1]) + x[f],   D3 = ((x[f+3] - 3 x[f+2]) + 3 x[f+1]) - x[f]      per joint
+ * The KG_KIN_DESC = 6 descriptors of a sample:
+ *   0 bone_cv    mean over bones of sd_b / mu_b (a bone with mu_b == 0 contributes 0)
+ *   1 asymmetry  mean over mirror pairs (a, b) of abs(mu_a - mu_b) / (0.5 (mu_a + mu_b)) (a zero denominator contributes 0;
+ *                M == 0: the descriptor is 0)
+ *   2 speed      mean_{v, f < T-1} |D1| / s
+ *   3 accel      mean_{v, f < T-2} |D2| / s
+ *   4 jerk       mean_{v, f < T-3} |D3| / s
+ *   5 still      the share of (v, f < T-1) with |D1| < still_eps * s
+ * s == 0 (every bone collapsed): six zeros, and the sample counts in degenerate[class].  Non-finite inputs propagate.  The
+ * six fp64 values are rounded ONCE to fp32: desc (classes, n, 6).
+ * kg_kin_desc: ONE launch, a workgroup per sample.  The sample is staged into LDS through the strides (4 C T V bytes: it is
+ * read from memory once), then bone sums, the second pass about mu_b, and the joint differences, all in fp64; every sum has
+ * a fixed shape (a thread's items in index order, a shuffle tree, the waves in order), so two calls give the same bits.  No
+ * atomics on data.  degenerate: every workgroup hands its flag over (csrc/kg_handoff.h), the last one to arrive counts the
+ * flags of every class (integers).  ws = kg_kin_desc_workspace_bytes(a) = 4 classes n bytes, contents on entry do not matter;
+ * counters: >= 1 zeroed int32, left zeroed.  bones / mirror are HOST pointers: validated and copied into the launch's
+ * arguments.  kg_kin_desc_lds_bytes(a) = the LDS of a workgroup (4 C T V + a fixed part), < 0 for a shape it rejects.
+ * Rejected (< 0, kg_last_error() names the field) before any GPU call: null x / desc / degenerate / bones / ws / counters (a
+ * null mirror with M > 0); classes or n < 1; classes * n >= 2^24; C not 2 or 3; V outside [1, KG_KIN_MAX_JOINTS]; B outside
+ * [1, KG_KIN_MAX_BONES]; M outside [0, KG_KIN_MAX_MIRROR]; T < KG_KIN_MIN_FRAMES; C*T*V > KG_KIN_MAX_ELEMS; a negative stride;
+ * a bone endpoint outside [0, V); a mirror index outside [0, B); a non-finite or negative still_eps; ws_bytes too small;
+ * counters_len < 1.
+ *
+ * kg_kin_scores: nsets (1..KG_KIN_MAX_SETS) fake descriptor matrices fake[g] (classes, m, 6) against ONE real matrix
+ * (classes, n, 6), contiguous fp32; every score is a function of the stored fp32 values alone:
+ *   tree(t) = pad t with +0.0 to the next power of two P, then t[i] += t[i + h] for h = P/2, P/4, .., 1;  t[0]
+ *   mean_real (classes, 6), mean_fake (nsets, classes, 6) fp64 = tree(the column's values in sample order) / count
+ *   w1 (nsets, classes, 6) fp64, the Wasserstein-1 distance of the two empirical distributions of a descriptor: sort the
+ *     n + m values ascending to z; cr_i / cf_i = the real / fake values among the first i + 1;
+ *     term_i = (double)abs(cr_i * m - cf_i * n) * ((double)z_{i+1} - (double)z_i), i < n + m - 1 (64-bit integers);
+ *     w1 = tree(term) / (double)(n * m).  Ties have a gap of 0, so their order shows in no bit.  Any non-finite value among
+ *     the n + m: NaN.
+ *   w1_mean (nsets, 6) fp64 = (sum over classes in class order) / classes;   scores (nsets, 6) = its one fp32 rounding
+ *   nonfinite (nsets + 1, classes) int32 = the samples with a non-finite descriptor, the real side in row 0
+ * TWO launches whatever nsets is: a workgroup per (set, class, descriptor) - the means by trees in LDS (the real side's by the
+ * workgroups of set 0 only), then the n + m values as 64-bit keys in LDS (the order-preserving integer image of the fp32 value,
+ * a side bit, padding keys above everything), a bitonic sort, a prefix count, the terms written over the keys, the tree -; then
+ * one small launch for w1_mean, scores and nonfinite.  No atomics on global memory, no workspace, no host synchronisation;
+ * every output word has one owner and is written on every call; capturable on one stream.
+ * kg_kin_scores_lds_bytes(a) = the LDS of a workgroup of launch 1 (8 bytes per key of the padded power of two, at most
+ * 8 KG_KIN_MAX_POINTS = 128 KiB), < 0 for a shape it rejects.
+ * Rejected (< 0, kg_last_error() names the field) before any GPU call: a null real / output pointer; classes, n or m < 1;
+ * n + m > KG_KIN_MAX_POINTS; nsets outside [1, KG_KIN_MAX_SETS]; a null fake[g] with g < nsets; classes above 2^20.            */
+#define KG_KIN_DESC 6
+#define KG_KIN_MAX_JOINTS 32
+#define KG_KIN_MAX_BONES 32
+#define KG_KIN_MAX_MIRROR 16
+#define KG_KIN_MIN_FRAMES 4
+#define KG_KIN_MAX_ELEMS 32768
+#define KG_KIN_MAX_SETS 4
+#define KG_KIN_MAX_POINTS 16384
+typedef struct KgKinDescArgs {
+    const float* x;  int64_t sc, ss, sf, so;    /* class, sample, frame, channel strides (elements)                     */
+    int32_t n;                                  /* samples per class                                                   */
+    int32_t T, C, V;
+    int32_t classes;
+    int32_t B, M;
+    const int32_t* bones;                       /* HOST: (B, 2) joints                                                 */
+    const int32_t* mirror;                      /* HOST: (M, 2) bone indices; may be NULL when M == 0                  */
+    double still_eps;
+    float* desc;                                /* out: (classes, n, 6)                                                */
+    int32_t* degenerate;                        /* out: (classes)                                                      */
+    float* ws;  int64_t ws_bytes;  int32_t* counters;  int32_t counters_len;
+} KgKinDescArgs;
+typedef struct KgKinScoresArgs {
+    const float* real;                          /* (classes, n, 6)                                                     */
+    const float* fake[KG_KIN_MAX_SETS];         /* fake[0 .. nsets): (classes, m, 6)                                   */
+    int32_t nsets, n, m, classes;
+    double* mean_real;                          /* out: (classes, 6)                                                   */
+    double* mean_fake;                          /* out: (nsets, classes, 6)                                            */
+    double* w1;                                 /* out: (nsets, classes, 6)                                            */
+    double* w1_mean;                            /* out: (nsets, 6)                                                     */
+    float* scores;                              /* out: (nsets, 6) = (float)w1_mean                                    */
+    int32_t* nonfinite;                         /* out: (nsets + 1, classes)                                           */
+} KgKinScoresArgs;
+int64_t kg_kin_desc_workspace_bytes(const KgKinDescArgs* a);   /* < 0 for invalid arguments                            */
+int64_t kg_kin_desc_lds_bytes(const KgKinDescArgs* a);         /* < 0 for invalid arguments                            */
+int     kg_kin_desc(const KgKinDescArgs* a, void* stream);
+int64_t kg_kin_scores_lds_bytes(const KgKinScoresArgs* a);     /* < 0 for invalid arguments                            */
+int     kg_kin_scores(const KgKinScoresArgs* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

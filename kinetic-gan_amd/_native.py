@@ -443,6 +443,29 @@ class _FrechetSetsArgs(C.Structure):
                 ("mean32", c_f32p),
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
+KIN_DESC = 6
+KIN_MAX_JOINTS, KIN_MAX_BONES, KIN_MAX_MIRROR = 32, 32, 16
+KIN_MIN_FRAMES = 4
+KIN_MAX_ELEMS = 32768
+KIN_MAX_SETS = 4
+KIN_MAX_POINTS = 16384
+
+
+class _KinDescArgs(C.Structure):
+    _fields_ = [("x", c_f32p), ("sc", C.c_int64), ("ss", C.c_int64), ("sf", C.c_int64), ("so", C.c_int64),
+                ("n", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("V", C.c_int32), ("classes", C.c_int32),
+                ("B", C.c_int32), ("M", C.c_int32),
+                ("bones", C.c_void_p), ("mirror", C.c_void_p), ("still_eps", C.c_double),
+                ("desc", c_f32p), ("degenerate", C.c_void_p),
+                ("ws", c_f32p), ("ws_bytes", C.c_int64), ("counters", C.c_void_p), ("counters_len", C.c_int32)]
+
+
+class _KinScoresArgs(C.Structure):
+    _fields_ = [("real", c_f32p), ("fake", c_f32p * KIN_MAX_SETS),
+                ("nsets", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("classes", C.c_int32),
+                ("mean_real", C.c_void_p), ("mean_fake", C.c_void_p), ("w1", C.c_void_p), ("w1_mean", C.c_void_p),
+                ("scores", c_f32p), ("nonfinite", C.c_void_p)]
+
 STEP_MAX_PLANES = 8
 STREAM_Z, STREAM_ALPHA, STREAM_NOISE_D, STREAM_NOISE_G = 0, 1, 2, 3
 
@@ -660,6 +683,11 @@ EXPORTS = {
     "kg_cls_head_bwd": (C.c_int, [C.POINTER(_ClsHeadArgs), C.c_void_p]),
     "kg_cls_head_wgrad": (C.c_int, [C.POINTER(_ClsHeadArgs), C.c_void_p]),
     "kg_cls_scores": (C.c_int, [C.POINTER(_ClsScoresArgs), C.c_void_p]),
+    "kg_kin_desc_workspace_bytes": (C.c_int64, [C.POINTER(_KinDescArgs)]),
+    "kg_kin_desc_lds_bytes": (C.c_int64, [C.POINTER(_KinDescArgs)]),
+    "kg_kin_desc": (C.c_int, [C.POINTER(_KinDescArgs), C.c_void_p]),
+    "kg_kin_scores_lds_bytes": (C.c_int64, [C.POINTER(_KinScoresArgs)]),
+    "kg_kin_scores": (C.c_int, [C.POINTER(_KinScoresArgs), C.c_void_p]),
 }
 
 _lib = None
@@ -2976,6 +3004,113 @@ def frechet_sets(cache: dict, fakes: Sequence[torch.Tensor], f_sc: int, f_ss: in
     a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 8
     _count("kg_frechet_sets", 2.0 * nsets * float(m * (frames - int(bool(diff)))) * d * d * classes)
     _check(lib.kg_frechet_sets(C.byref(a), _stream()), "kg_frechet_sets")
+    return out
+
+
+# ---- kinematic plausibility: descriptors and their W1 scores (kg_kin.hip) -----------------------------------
+
+KinView = FrechetView       # element (class c, sample i, frame f, channel o, joint e): the same walk, so = the channel stride
+
+
+def _kin_table(pairs, what: str):
+    """(count, host int32 array or None) of a (count, 2) table of index pairs; the library checks the values"""
+    flat = [] if pairs is None else [int(v) for p in pairs for v in p]
+    if pairs is not None and any(len(p) != 2 for p in pairs):
+        raise ValueError(f"kg_kin_desc: {what} must be (count, 2) index pairs")
+    return len(flat) // 2, ((C.c_int32 * len(flat))(*flat) if flat else None)
+
+
+def _kin_desc_shape(n: int, T: int, Cc: int, V: int, classes: int, bones, mirror, still_eps: float):
+    """the struct with everything but the device pointers, and the host tables it points to (hold them until the call)"""
+    a = _KinDescArgs()
+    a.n, a.T, a.C, a.V, a.classes = int(n), int(T), int(Cc), int(V), int(classes)
+    a.B, tb = _kin_table(bones, "bones")
+    a.M, tm = _kin_table(mirror, "mirror")
+    a.bones = C.cast(tb, C.c_void_p) if tb is not None else None
+    a.mirror = C.cast(tm, C.c_void_p) if tm is not None else None
+    a.still_eps = float(still_eps)
+    return a, (tb, tm)
+
+
+def kin_desc_lds_bytes(n: int, T: int, Cc: int, V: int, classes: int, bones, mirror, still_eps: float = 1e-3) -> int:
+    """kg_kin_desc_lds_bytes of a shape (RuntimeError naming the field for arguments kg_kin_desc rejects); no GPU call"""
+    a, keep = _kin_desc_shape(n, T, Cc, V, classes, bones, mirror, still_eps)
+    return _query("kg_kin_desc_lds_bytes", a)
+
+
+def kin_desc(view: FrechetView, n: int, T: int, Cc: int, V: int, classes: int, bones, mirror, still_eps: float = 1e-3,
+             out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Enqueue kg_kin_desc (ONE launch, a workgroup per sample) on the current stream; no host synchronisation.
+    ``view`` walks the set as ``FrechetView`` does (so: the channel stride); ``bones`` (B, 2) joint pairs and ``mirror``
+    (M, 2) pairs of bone indices are host sequences.  Returns (desc (classes, n, 6) fp32 - ``out`` if given -, degenerate
+    (classes,) int32) on the device."""
+    who = "kg_kin_desc"
+    if view.t.dtype != torch.float32:
+        raise TypeError(f"{who}: fp32 only, got {view.t.dtype}")
+    a, keep = _kin_desc_shape(n, T, Cc, V, classes, bones, mirror, still_eps)
+    nbytes = _query("kg_kin_desc_workspace_bytes", a)
+    _need_cuda(view.t, out)
+    if not _frechet_extent_ok(view, n, T, Cc, V, classes):
+        raise ValueError(f"{who}: the strides of x reach outside its tensor")
+    dev = view.t.device
+    if out is None:
+        out = torch.empty((classes, n, KIN_DESC), dtype=torch.float32, device=dev)
+    else:
+        _dest(out, classes * n * KIN_DESC, f"{who}: out must be a contiguous fp32 tensor of classes * n * 6 elements")
+    degenerate = torch.empty(classes, dtype=torch.int32, device=dev)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    sync = _sync_buffer(dev)
+    a.x, a.sc, a.ss, a.sf, a.so = view.t.data_ptr(), view.sc, view.ss, view.sf, view.so
+    a.desc, a.degenerate = out.data_ptr(), degenerate.data_ptr()
+    a.ws, a.ws_bytes, a.counters, a.counters_len = ws.data_ptr(), nbytes, sync.data_ptr(), sync.numel()
+    _count(who, 0.0)
+    _check(load_library().kg_kin_desc(C.byref(a), _stream()), who)
+    return out, degenerate
+
+
+def _kin_scores_shape(nsets: int, n: int, m: int, classes: int) -> _KinScoresArgs:
+    a = _KinScoresArgs()
+    a.nsets, a.n, a.m, a.classes = int(nsets), int(n), int(m), int(classes)
+    return a
+
+
+def kin_scores_lds_bytes(nsets: int, n: int, m: int, classes: int) -> int:
+    """kg_kin_scores_lds_bytes of a shape (RuntimeError naming the field for a shape kg_kin_scores rejects); no GPU call"""
+    return _query("kg_kin_scores_lds_bytes", _kin_scores_shape(nsets, n, m, classes))
+
+
+def kin_scores(real_desc: torch.Tensor, fake_descs: Sequence[torch.Tensor]) -> dict:
+    """Enqueue kg_kin_scores (TWO launches whatever the number of sets): 1..KIN_MAX_SETS fake descriptor matrices (classes,
+    m, 6) with a shared m against the real one (classes, n, 6), all contiguous fp32.  Returns device tensors mean_real
+    (classes, 6), mean_fake (nsets, classes, 6), w1 (nsets, classes, 6), w1_mean (nsets, 6) fp64, scores (nsets, 6) fp32
+    and nonfinite (nsets + 1, classes) int32 (row 0: the real side).  No host synchronisation."""
+    who = "kg_kin_scores"
+    fake_descs = list(fake_descs)
+    nsets = len(fake_descs)
+    for name, t in [("real_desc", real_desc)] + [("fake_descs[%d]" % g, t) for g, t in enumerate(fake_descs)]:
+        if t.dim() != 3 or t.shape[2] != KIN_DESC or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous fp32 (classes, count, 6) tensor")
+        if t.shape[0] != real_desc.shape[0] or (name != "real_desc" and t.shape[1] != fake_descs[0].shape[1]):
+            raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}: the sets share classes and m")
+    classes, n = real_desc.shape[0], real_desc.shape[1]
+    m = fake_descs[0].shape[1] if nsets else 0
+    a = _kin_scores_shape(nsets, n, m, classes)
+    _query("kg_kin_scores_lds_bytes", a)
+    _need_cuda(real_desc, *fake_descs)
+    dev = real_desc.device
+    out = dict(mean_real=torch.empty((classes, KIN_DESC), dtype=torch.float64, device=dev),
+               mean_fake=torch.empty((nsets, classes, KIN_DESC), dtype=torch.float64, device=dev),
+               w1=torch.empty((nsets, classes, KIN_DESC), dtype=torch.float64, device=dev),
+               w1_mean=torch.empty((nsets, KIN_DESC), dtype=torch.float64, device=dev),
+               scores=torch.empty((nsets, KIN_DESC), dtype=torch.float32, device=dev),
+               nonfinite=torch.empty((nsets + 1, classes), dtype=torch.int32, device=dev))
+    a.real = real_desc.data_ptr()
+    for g, t in enumerate(fake_descs):
+        a.fake[g] = t.data_ptr()
+    a.mean_real, a.mean_fake, a.w1 = out["mean_real"].data_ptr(), out["mean_fake"].data_ptr(), out["w1"].data_ptr()
+    a.w1_mean, a.scores, a.nonfinite = out["w1_mean"].data_ptr(), out["scores"].data_ptr(), out["nonfinite"].data_ptr()
+    _count(who, 0.0)
+    _check(load_library().kg_kin_scores(C.byref(a), _stream()), who)
     return out
 
 

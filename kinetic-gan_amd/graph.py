@@ -151,6 +151,7 @@ class SkeletonGraph:
     lvls = 4
     # subclasses fill these
     bones: list = []
+    mirror_bones: list = []     # (left, right) pairs of indices into ``bones``: the limbs a body has twice
     joints: int = 0
     root_joint: int = 0
 
@@ -304,6 +305,8 @@ class graph_ntu(SkeletonGraph):
         (1, 2), (2, 21), (3, 21), (4, 3), (5, 21), (6, 5), (7, 6), (8, 7), (9, 21), (10, 9),
         (11, 10), (12, 11), (1, 13), (14, 13), (15, 14), (16, 15), (1, 17), (18, 17), (19, 18),
         (20, 19), (22, 8), (23, 8), (24, 12), (25, 12)]]
+    # arm, hand and leg chains, left against right (joints 5-8, 22, 23 / 9-12, 24, 25 and 13-16 / 17-20, one-based)
+    mirror_bones = [(4, 8), (5, 9), (6, 10), (7, 11), (12, 16), (13, 17), (14, 18), (15, 19), (20, 22), (21, 23)]
 
 
 class Graph_h36m(SkeletonGraph):
@@ -313,6 +316,8 @@ class Graph_h36m(SkeletonGraph):
     root_joint = 8
     bones = [(1, 2), (2, 3), (0, 1), (4, 5), (5, 6), (0, 4), (0, 7), (7, 8), (8, 9),
              (8, 10), (10, 11), (11, 12), (8, 13), (13, 14), (14, 15)]
+    # leg chains (joints 1-3 / 4-6), then arm chains (10-12 / 13-15)
+    mirror_bones = [(2, 5), (0, 3), (1, 4), (9, 12), (10, 13), (11, 14)]
 
     def _pinned(self, node, level):
         return node == 9 and level == 0   # graph_h36m.py:60

@@ -2,7 +2,8 @@
 precision / recall / density / coverage of sample sets on the kg_prdc kernels (``prdc``) and the Frechet distance of
 pose / motion / caller features in fp64 on the kg_frechet kernels (``frechet``, ``frechet_features``), and nearest training
 samples with the memorisation scores built on them on the kg_nn kernels (``nearest``, ``memorisation``, ``nn_two_sample``),
-at the end.
+at the end, and kinematic plausibility - bone lengths, symmetry, smoothness - on the kg_kin kernels (``kinematics``,
+``kinematics_real``, ``kinematics_sets``).
 
 The reference scores samples with a kernel two-sample statistic (MMD) under 14 RBF bandwidths 10^-4 .. 10^9: per class
 the first selected fake and real sample, each a set of V points (joints) per frame (``avg``: the mean over frames of
@@ -370,6 +371,159 @@ def frechet_features(feat_gen, feat_real, labels_gen=None, labels_real=None, per
         raise ValueError("frechet_features: gen features %s and real features %s differ in shape"
                          % (tuple(feat_gen.shape[1:]), tuple(feat_real.shape[1:])))
     return frechet(feat_gen[:, None, None, :], feat_real[:, None, None, :], labels_gen, labels_real, "pose", per_class, moments)
+
+
+KIN_NAMES = ("bone_cv", "asymmetry", "speed", "accel", "jerk", "still")
+
+
+def _kin_tables(dataset: str, bones, mirror, who: str):
+    """(bones, mirror) as lists of int pairs: the dataset's skeleton (graph.py) unless the caller brings a bone list - then
+    the mirror pairs are the caller's too (none given: no asymmetry term)"""
+    if bones is None:
+        from .graph import Graph_h36m, graph_ntu
+        if dataset not in ("ntu", "h36m"):
+            raise ValueError("%s: undefined dataset %r ('ntu' or 'h36m'; or pass bones)" % (who, dataset))
+        g = graph_ntu if dataset == "ntu" else Graph_h36m
+        bones, mirror = g.bones, (g.mirror_bones if mirror is None else mirror)
+    elif mirror is None:
+        mirror = ()
+    out = []
+    for name, tab in (("bones", bones), ("mirror", mirror)):
+        tab = np.asarray(tab, dtype=np.int64).reshape(-1, 2) if len(tab) else np.zeros((0, 2), dtype=np.int64)
+        out.append([(int(u), int(v)) for u, v in tab])
+    return out[0], out[1]
+
+
+def _kin_check(x: torch.Tensor, what: str, bones, mirror, still_eps: float, who: str):
+    """the limits of kg_kin_desc as ValueErrors naming the argument"""
+    if x.dim() != 4:
+        raise ValueError("%s: %s samples are (N, C, T, V), got %s" % (who, what, tuple(x.shape)))
+    _, C, T, V = x.shape
+    if C not in (2, 3):
+        raise ValueError("%s: %s has C=%d channels, 2 or 3 expected" % (who, what, C))
+    if not 1 <= V <= _native.KIN_MAX_JOINTS:
+        raise ValueError("%s: %s has V=%d joints, outside [1, %d]" % (who, what, V, _native.KIN_MAX_JOINTS))
+    if T < _native.KIN_MIN_FRAMES:
+        raise ValueError("%s: %s has T=%d frames, jerk needs %d" % (who, what, T, _native.KIN_MIN_FRAMES))
+    if C * T * V > _native.KIN_MAX_ELEMS:
+        raise ValueError("%s: %s has C*T*V = %d values per sample, above %d" % (who, what, C * T * V, _native.KIN_MAX_ELEMS))
+    if not 1 <= len(bones) <= _native.KIN_MAX_BONES:
+        raise ValueError("%s: %d bones, outside [1, %d]" % (who, len(bones), _native.KIN_MAX_BONES))
+    if len(mirror) > _native.KIN_MAX_MIRROR:
+        raise ValueError("%s: %d mirror pairs, above %d" % (who, len(mirror), _native.KIN_MAX_MIRROR))
+    if any(not 0 <= j < V for b in bones for j in b):
+        raise ValueError("%s: bones name a joint outside [0, V=%d) of %s (wrong dataset?)" % (who, V, what))
+    if any(not 0 <= j < len(bones) for p in mirror for j in p):
+        raise ValueError("%s: mirror names a bone outside [0, %d)" % (who, len(bones)))
+    if not (np.isfinite(still_eps) and still_eps >= 0):
+        raise ValueError("%s: still_eps=%r is not a finite number >= 0" % (who, still_eps))
+
+
+def _kin_side(x: torch.Tensor, idx: np.ndarray, bones, mirror, still_eps: float, out=None):
+    """(desc (K, count, 6), degenerate (K,)) of the samples idx (K, count) of x (N, C, T, V): one kg_kin_desc launch"""
+    _, C, T, V = x.shape
+    return _native.kin_desc(_frechet_view(x, idx), idx.shape[1], T, C, V, idx.shape[0], bones, mirror, still_eps, out=out)
+
+
+def kinematics_real(real, labels_real=None, dataset: str = "ntu", bones=None, mirror=None, per_class: Optional[int] = None,
+                    still_eps: float = 1e-3, classes: Optional[int] = None, with_degenerate: bool = False):
+    """The real side of ``kinematics`` once: the descriptor matrix (K, n, 6) fp32 on the device that ``kinematics_sets``
+    reads (one kg_kin_desc launch).  ``classes``: the number of classes when the labels do not name the last one.  With
+    ``with_degenerate`` returns (desc, degenerate (K,) int32)."""
+    who = "kinematics_real"
+    real = _as_f32(real)
+    bones, mirror = _kin_tables(dataset, bones, mirror, who)
+    _kin_check(real, "real", bones, mirror, still_eps, who)
+    lab_r, kr = _label_ids(labels_real, real.shape[0], "labels_real", who)
+    K = max(kr, int(classes or 0))
+    if K < 1:
+        raise ValueError("%s: no samples" % who)
+    idx_r = _class_rows(lab_r, K, per_class, "real", who)
+    desc, degenerate = _kin_side(_as_cuda(real), idx_r, bones, mirror, still_eps)
+    return (desc, degenerate) if with_degenerate else desc
+
+
+def kinematics_sets(sets, real_desc: torch.Tensor, labels=None, dataset: str = "ntu", bones=None, mirror=None,
+                    per_class: Optional[int] = None, still_eps: float = 1e-3) -> dict:
+    """Up to four generated sets (each (Nf, C, T, V), sharing ``labels`` and the shape) against the cached real descriptors
+    of ``kinematics_real``: one kg_kin_desc launch per set, then ONE kg_kin_scores call (two launches) for all of them.
+    Returns device tensors ``w1_mean`` (nsets, 6), ``scores`` (nsets, 6) fp32 (the one rounding of w1_mean: the word an
+    evaluation record carries), ``w1`` (nsets, K, 6), ``mean_real`` (K, 6), ``mean_fake`` (nsets, K, 6), ``nonfinite``
+    (nsets + 1, K) int32 (row 0: the real side), ``degenerate`` (nsets, K) int32 and ``desc`` (nsets, K, m, 6).  Every set's
+    slices are, bit for bit, the results of its own ``kinematics`` call."""
+    who = "kinematics_sets"
+    sets = [_as_f32(s) for s in sets]
+    if not 1 <= len(sets) <= _native.KIN_MAX_SETS:
+        raise ValueError("%s: %d sets, 1 to %d expected" % (who, len(sets), _native.KIN_MAX_SETS))
+    if real_desc.dim() != 3 or real_desc.shape[2] != _native.KIN_DESC or real_desc.dtype != torch.float32:
+        raise ValueError("%s: real_desc is the (K, n, 6) fp32 result of kinematics_real, got %s" % (who, tuple(real_desc.shape)))
+    bones, mirror = _kin_tables(dataset, bones, mirror, who)
+    for g, s in enumerate(sets):
+        _kin_check(s, "sets[%d]" % g, bones, mirror, still_eps, who)
+        if s.shape != sets[0].shape:
+            raise ValueError("%s: sets[%d] has shape %s, sets[0] %s" % (who, g, tuple(s.shape), tuple(sets[0].shape)))
+    lab, kg = _label_ids(labels, sets[0].shape[0], "labels", who)
+    K = real_desc.shape[0]
+    if kg > K:
+        raise ValueError("%s: labels name %d classes, real_desc has %d" % (who, kg, K))
+    idx = _class_rows(lab, K, per_class, "fake", who)
+    m, n = idx.shape[1], real_desc.shape[1]
+    if n + m > _native.KIN_MAX_POINTS:
+        raise ValueError("%s: n + m = %d + %d values per class, above %d" % (who, n, m, _native.KIN_MAX_POINTS))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    desc = torch.empty((len(sets), K, m, _native.KIN_DESC), dtype=torch.float32, device=dev)
+    degenerate = [_kin_side(_as_cuda(s), idx, bones, mirror, still_eps, out=desc[g])[1] for g, s in enumerate(sets)]
+    out = _native.kin_scores(real_desc.contiguous(), [desc[g] for g in range(len(sets))])
+    out.update(degenerate=torch.stack(degenerate), desc=desc)
+    return out
+
+
+def kinematics(gen, real, labels_gen=None, labels_real=None, dataset: str = "ntu", bones=None, mirror=None,
+               per_class: Optional[int] = None, still_eps: float = 1e-3, per_sample: bool = False) -> dict:
+    """Kinematic plausibility of generated skeleton sequences against real ones.  Every sample gets six
+    dimensionless descriptors, KIN_NAMES: the variation of its bone lengths over time, the left / right asymmetry of its
+    mean bone lengths, mean joint speed, acceleration and jerk in units of its own mean bone length, and the share of
+    (joint, frame) steps that do not move; per class and descriptor the score is the Wasserstein-1 distance between the
+    real and the generated samples' values (smaller is better).  fp64 throughout, in three launches of kg_kin_desc (one per
+    side) and kg_kin_scores.
+
+    gen (Nf, C, T, V), real (Nr, C, T, V): ``frechet``'s argument order and conventions - labels one-hot (N, K), class ids
+    (N,) or None for one class; the first ``per_class`` samples of every class (default: all; ragged classes raise
+    ValueError); evenly spaced samples and crops in T are read in place.  The two tensors may differ in value scale (raw
+    real data against normalised generated data): the descriptors are invariant under x * scale + shift, nothing is
+    normalised.  The skeleton is ``dataset``'s (graph.py: bones, mirror_bones) unless ``bones`` (B, 2) joint pairs - and
+    then ``mirror`` (M, 2) pairs of bone indices, default none - are given.  C in (2, 3), V <= 32, T >= 4, C*T*V <= 32768,
+    n + m <= 16384 per class.  Returns device tensors: ``w1_mean`` (6,) fp64 - the plain mean over classes -, ``scores``
+    (6,) its fp32 rounding, ``w1`` (K, 6), ``mean_real``, ``mean_fake`` (K, 6) the class means of the descriptors,
+    ``nonfinite`` (2, K) int32 samples with a non-finite descriptor (row 0: real) and ``degenerate``, ``degenerate_real``
+    (K,) int32 samples whose bones all have length zero (their descriptors are zero); with ``per_sample`` also ``desc_real``
+    (K, n, 6) and ``desc_fake`` (K, m, 6).  No host sync (labels that live on the device are read once)."""
+    who = "kinematics"
+    gen, real = _as_f32(gen), _as_f32(real)
+    bones, mirror = _kin_tables(dataset, bones, mirror, who)
+    _kin_check(gen, "gen", bones, mirror, still_eps, who)
+    _kin_check(real, "real", bones, mirror, still_eps, who)
+    if gen.shape[1:] != real.shape[1:]:
+        raise ValueError("%s: gen samples %s and real samples %s differ in shape" % (who, tuple(gen.shape[1:]),
+                                                                                    tuple(real.shape[1:])))
+    lab_g, kg = _label_ids(labels_gen, gen.shape[0], "labels_gen", who)
+    lab_r, kr = _label_ids(labels_real, real.shape[0], "labels_real", who)
+    classes = max(kg, kr)
+    if classes < 1:
+        raise ValueError("%s: no samples" % who)
+    idx_r = _class_rows(lab_r, classes, per_class, "real", who)
+    idx_g = _class_rows(lab_g, classes, per_class, "fake", who)
+    n, m = idx_r.shape[1], idx_g.shape[1]
+    if n + m > _native.KIN_MAX_POINTS:
+        raise ValueError("%s: n + m = %d + %d values per class, above %d (pass per_class)" % (who, n, m, _native.KIN_MAX_POINTS))
+    desc_r, deg_r = _kin_side(_as_cuda(real), idx_r, bones, mirror, still_eps)
+    desc_f, deg_f = _kin_side(_as_cuda(gen), idx_g, bones, mirror, still_eps)
+    res = _native.kin_scores(desc_r, [desc_f])
+    out = dict(w1_mean=res["w1_mean"][0], scores=res["scores"][0], w1=res["w1"][0], mean_real=res["mean_real"],
+               mean_fake=res["mean_fake"][0], nonfinite=res["nonfinite"], degenerate=deg_f, degenerate_real=deg_r)
+    if per_sample:
+        out.update(desc_real=desc_r, desc_fake=desc_f)
+    return out
 
 
 CLS_NAMES = ("accuracy", "feature_fd", "diversity", "multimodality")
