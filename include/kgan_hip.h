@@ -1225,6 +1225,27 @@ typedef struct KgEvalRecord2Args {
 } KgEvalRecord2Args;
 int kg_eval_record2(const KgEvalRecord2Args* a, void* stream);
 
+/* kg_eval_record3: kg_eval_record2 with room for KG_EVAL3_MAX_SCORES scores - the third instantiation of the
+ * same kernel template behind the same launcher; the definition, the sense and the host's initial values are those of
+ * kg_eval_record2, and with nscores <= KG_EVAL2_MAX_SCORES it leaves the same bits.  Rejected (< 0) before any GPU call:
+ * nscores outside [1, KG_EVAL3_MAX_SCORES], select outside [0, nscores), ring_len < 1, a null pointer (iter may be NULL).
+ * Call site: evaluate.Evaluator._round when the kinematic columns are recorded (live + ema with everything on = 40 > 32).  */
+#define KG_EVAL3_MAX_SCORES 64
+typedef struct KgEvalRecord3Args {
+    const float* scores[KG_EVAL3_MAX_SCORES];  /* device: one fp32 each                                               */
+    int32_t nscores, select;
+    const int64_t* iter;
+    int64_t* count;
+    float* ring_val;                /* (ring_len, nscores)                                                             */
+    int64_t* ring_iter;             /* (ring_len, 2): [iteration, improved]                                            */
+    int64_t ring_len;
+    float* best_val;
+    int64_t* best_iter;
+    int32_t* flag;
+    int32_t maximise;               /* 0: smaller is better, else larger is better                                     */
+} KgEvalRecord3Args;
+int kg_eval_record3(const KgEvalRecord3Args* a, void* stream);
+
 /* kg_copy_if: when *flag != 0 every job's run of `nwords` 4-byte words is copied src -> dst bit for bit; when *flag == 0
  * the launch writes nothing at all.  A job whose src and dst are both 16-byte aligned moves 128 bits per access with a
  * scalar tail, any other job word by word.  No ticket, no atomic, no LDS, no scratch: the grid only reads the decision a
@@ -1411,6 +1432,39 @@ int64_t kg_kin_desc_lds_bytes(const KgKinDescArgs* a);         /* < 0 for invali
 int     kg_kin_desc(const KgKinDescArgs* a, void* stream);
 int64_t kg_kin_scores_lds_bytes(const KgKinScoresArgs* a);     /* < 0 for invalid arguments                            */
 int     kg_kin_scores(const KgKinScoresArgs* a, void* stream);
+
+/* kg_kin_desc_sets: the descriptors of nsets (1..KG_KIN_MAX_SETS) sets x[g] in ONE launch.  The sets share
+ * the strides, n, T, C, V, classes, the two tables and still_eps; every set has outputs of its own.  The grid is
+ * nsets * classes * n workgroups, (set, class, sample) with the set as the slowest coordinate; a workgroup picks its set's two
+ * pointers and from there on runs the code of kg_kin_desc - one kernel body (a template: with one set the set coordinate is
+ * compiled away), one validation, one launcher; kg_kin_desc is the one-set case.  Per set g, bit for bit:
+ *     desc[g] (classes, n, 6) and degenerate[g*classes .. (g+1)*classes) = what kg_kin_desc(x[g]) writes
+ * (every sum keeps its shape, which depends on (T, V, B) alone).  ONE ticket over the whole grid (csrc/kg_handoff.h): the
+ * last workgroup to arrive counts the flags of every (set, class) with integer adds; no other atomics.
+ * ws = kg_kin_desc_sets_workspace_bytes(a) = 4 nsets classes n bytes, contents on entry do not matter; counters: >= 1 zeroed
+ * int32, left zeroed.  kg_kin_desc_sets_lds_bytes(a) = kg_kin_desc_lds_bytes of the shared shape.  No host synchronisation;
+ * capturable; launches that share ws or counters must not overlap.
+ * Rejected (< 0, kg_last_error() names the field) before any GPU call: every rule of kg_kin_desc; nsets outside
+ * [1, KG_KIN_MAX_SETS]; a null x[g] or desc[g] with g < nsets; nsets * classes * n >= 2^24.
+ * Call site: evaluate.Evaluator._kinematics_scores (the rounds of up to four generators through their shared strides).      */
+typedef struct KgKinDescSetsArgs {
+    const float* x[KG_KIN_MAX_SETS];            /* x[0 .. nsets)                                                        */
+    int64_t sc, ss, sf, so;                     /* class, sample, frame, channel strides (elements), shared            */
+    int32_t nsets;
+    int32_t n;                                  /* samples per class                                                   */
+    int32_t T, C, V;
+    int32_t classes;
+    int32_t B, M;
+    const int32_t* bones;                       /* HOST: (B, 2) joints                                                 */
+    const int32_t* mirror;                      /* HOST: (M, 2) bone indices; may be NULL when M == 0                  */
+    double still_eps;
+    float* desc[KG_KIN_MAX_SETS];               /* out: desc[0 .. nsets), each (classes, n, 6)                         */
+    int32_t* degenerate;                        /* out: (nsets, classes)                                               */
+    float* ws;  int64_t ws_bytes;  int32_t* counters;  int32_t counters_len;
+} KgKinDescSetsArgs;
+int64_t kg_kin_desc_sets_workspace_bytes(const KgKinDescSetsArgs* a);   /* < 0 for invalid arguments                   */
+int64_t kg_kin_desc_sets_lds_bytes(const KgKinDescSetsArgs* a);         /* < 0 for invalid arguments                   */
+int     kg_kin_desc_sets(const KgKinDescSetsArgs* a, void* stream);
 
 #ifdef __cplusplus
 }

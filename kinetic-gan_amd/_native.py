@@ -460,6 +460,16 @@ class _KinDescArgs(C.Structure):
                 ("ws", c_f32p), ("ws_bytes", C.c_int64), ("counters", C.c_void_p), ("counters_len", C.c_int32)]
 
 
+class _KinDescSetsArgs(C.Structure):
+    _fields_ = [("x", c_f32p * KIN_MAX_SETS), ("sc", C.c_int64), ("ss", C.c_int64), ("sf", C.c_int64), ("so", C.c_int64),
+                ("nsets", C.c_int32),
+                ("n", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("V", C.c_int32), ("classes", C.c_int32),
+                ("B", C.c_int32), ("M", C.c_int32),
+                ("bones", C.c_void_p), ("mirror", C.c_void_p), ("still_eps", C.c_double),
+                ("desc", c_f32p * KIN_MAX_SETS), ("degenerate", C.c_void_p),
+                ("ws", c_f32p), ("ws_bytes", C.c_int64), ("counters", C.c_void_p), ("counters_len", C.c_int32)]
+
+
 class _KinScoresArgs(C.Structure):
     _fields_ = [("real", c_f32p), ("fake", c_f32p * KIN_MAX_SETS),
                 ("nsets", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("classes", C.c_int32),
@@ -525,6 +535,16 @@ EVAL2_MAX_SCORES = 32
 
 class _EvalRecord2Args(C.Structure):
     _fields_ = [("scores", c_f32p * EVAL2_MAX_SCORES), ("nscores", C.c_int32), ("select", C.c_int32),
+                ("iter", C.c_void_p), ("count", C.c_void_p), ("ring_val", c_f32p), ("ring_iter", C.c_void_p),
+                ("ring_len", C.c_int64), ("best_val", c_f32p), ("best_iter", C.c_void_p), ("flag", C.c_void_p),
+                ("maximise", C.c_int32)]
+
+
+EVAL3_MAX_SCORES = 64
+
+
+class _EvalRecord3Args(C.Structure):
+    _fields_ = [("scores", c_f32p * EVAL3_MAX_SCORES), ("nscores", C.c_int32), ("select", C.c_int32),
                 ("iter", C.c_void_p), ("count", C.c_void_p), ("ring_val", c_f32p), ("ring_iter", C.c_void_p),
                 ("ring_len", C.c_int64), ("best_val", c_f32p), ("best_iter", C.c_void_p), ("flag", C.c_void_p),
                 ("maximise", C.c_int32)]
@@ -677,6 +697,7 @@ EXPORTS = {
                                 C.c_void_p]),
     "kg_eval_record": (C.c_int, [C.POINTER(_EvalRecordArgs), C.c_void_p]),
     "kg_eval_record2": (C.c_int, [C.POINTER(_EvalRecord2Args), C.c_void_p]),
+    "kg_eval_record3": (C.c_int, [C.POINTER(_EvalRecord3Args), C.c_void_p]),
     "kg_copy_if": (C.c_int, [C.c_void_p, C.POINTER(_CopyJob), C.c_int32, C.c_void_p]),
     "kg_cls_head_workspace_bytes": (C.c_int64, [C.POINTER(_ClsHeadArgs)]),
     "kg_cls_head_fwd": (C.c_int, [C.POINTER(_ClsHeadArgs), C.c_void_p]),
@@ -686,6 +707,9 @@ EXPORTS = {
     "kg_kin_desc_workspace_bytes": (C.c_int64, [C.POINTER(_KinDescArgs)]),
     "kg_kin_desc_lds_bytes": (C.c_int64, [C.POINTER(_KinDescArgs)]),
     "kg_kin_desc": (C.c_int, [C.POINTER(_KinDescArgs), C.c_void_p]),
+    "kg_kin_desc_sets_workspace_bytes": (C.c_int64, [C.POINTER(_KinDescSetsArgs)]),
+    "kg_kin_desc_sets_lds_bytes": (C.c_int64, [C.POINTER(_KinDescSetsArgs)]),
+    "kg_kin_desc_sets": (C.c_int, [C.POINTER(_KinDescSetsArgs), C.c_void_p]),
     "kg_kin_scores_lds_bytes": (C.c_int64, [C.POINTER(_KinScoresArgs)]),
     "kg_kin_scores": (C.c_int, [C.POINTER(_KinScoresArgs), C.c_void_p]),
 }
@@ -3020,9 +3044,10 @@ def _kin_table(pairs, what: str):
     return len(flat) // 2, ((C.c_int32 * len(flat))(*flat) if flat else None)
 
 
-def _kin_desc_shape(n: int, T: int, Cc: int, V: int, classes: int, bones, mirror, still_eps: float):
-    """the struct with everything but the device pointers, and the host tables it points to (hold them until the call)"""
-    a = _KinDescArgs()
+def _kin_desc_shape(n: int, T: int, Cc: int, V: int, classes: int, bones, mirror, still_eps: float, struct=None):
+    """the struct (``_KinDescArgs``, or ``struct``) with everything but the device pointers, and the host tables it points to
+    (hold them until the call)"""
+    a = (struct or _KinDescArgs)()
     a.n, a.T, a.C, a.V, a.classes = int(n), int(T), int(Cc), int(V), int(classes)
     a.B, tb = _kin_table(bones, "bones")
     a.M, tm = _kin_table(mirror, "mirror")
@@ -3066,6 +3091,77 @@ def kin_desc(view: FrechetView, n: int, T: int, Cc: int, V: int, classes: int, b
     _count(who, 0.0)
     _check(load_library().kg_kin_desc(C.byref(a), _stream()), who)
     return out, degenerate
+
+
+def _kin_desc_sets_shape(nsets: int, n: int, T: int, Cc: int, V: int, classes: int, bones, mirror, still_eps: float):
+    a, keep = _kin_desc_shape(n, T, Cc, V, classes, bones, mirror, still_eps, struct=_KinDescSetsArgs)
+    a.nsets = int(nsets)
+    return a, keep
+
+
+def kin_desc_sets_workspace_bytes(nsets: int, n: int, T: int, Cc: int, V: int, classes: int, bones, mirror,
+                                  still_eps: float = 1e-3) -> int:
+    """kg_kin_desc_sets_workspace_bytes of a shape (RuntimeError naming the field for arguments it rejects); no GPU call"""
+    a, keep = _kin_desc_sets_shape(nsets, n, T, Cc, V, classes, bones, mirror, still_eps)
+    return _query("kg_kin_desc_sets_workspace_bytes", a)
+
+
+def kin_desc_sets_lds_bytes(nsets: int, n: int, T: int, Cc: int, V: int, classes: int, bones, mirror,
+                            still_eps: float = 1e-3) -> int:
+    """kg_kin_desc_sets_lds_bytes of a shape (RuntimeError naming the field for arguments it rejects); no GPU call"""
+    a, keep = _kin_desc_sets_shape(nsets, n, T, Cc, V, classes, bones, mirror, still_eps)
+    return _query("kg_kin_desc_sets_lds_bytes", a)
+
+
+def kin_desc_sets(xs, sc: int, ss: int, sf: int, so: int, n: int, T: int, Cc: int, V: int, classes: int, bones, mirror,
+                  still_eps: float = 1e-3, out: Optional[torch.Tensor] = None,
+                  ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Enqueue kg_kin_desc_sets (ONE launch, a workgroup per (set, class, sample)) on the current stream; no host
+    synchronisation.  ``xs``: 1..KIN_MAX_SETS fp32 tensors - or ``FrechetView``s, whose strides must then agree and replace
+    the four given - each walked from its first element with the SHARED strides (sc, ss, sf, so: class, sample, frame,
+    channel; the joint axis is contiguous).  ``bones`` / ``mirror`` as in ``kin_desc``.  ``ws``: a contiguous fp32 tensor of
+    at least ``kin_desc_sets_workspace_bytes`` (default: allocated here).  Returns (desc (nsets, classes, n, 6) fp32 - ``out``
+    if given -, degenerate (nsets, classes) int32) on the device; desc[g] and degenerate[g] are bit for bit what ``kin_desc``
+    of set g gives."""
+    who = "kg_kin_desc_sets"
+    xs = list(xs)
+    if xs and isinstance(xs[0], FrechetView):
+        sc, ss, sf, so = xs[0].sc, xs[0].ss, xs[0].sf, xs[0].so
+        if any((v.sc, v.ss, v.sf, v.so) != (sc, ss, sf, so) for v in xs):
+            raise ValueError(f"{who}: the sets' views differ in their strides")
+        xs = [v.t for v in xs]
+    nsets = len(xs)
+    for t in xs:
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who}: fp32 only, got {t.dtype}")
+    a, keep = _kin_desc_sets_shape(nsets, n, T, Cc, V, classes, bones, mirror, still_eps)
+    nbytes = _query("kg_kin_desc_sets_workspace_bytes", a)
+    _need_cuda(*xs, out, ws)
+    for g, t in enumerate(xs):
+        if not _frechet_extent_ok(FrechetView(t, int(sc), int(ss), int(sf), int(so)), n, T, Cc, V, classes):
+            raise ValueError(f"{who}: the strides reach outside the tensor of x[{g}]")
+    dev = xs[0].device
+    if out is None:
+        out = torch.empty((nsets, classes, n, KIN_DESC), dtype=torch.float32, device=dev)
+    else:
+        _dest(out, nsets * classes * n * KIN_DESC, f"{who}: out must be a contiguous fp32 tensor of nsets * classes * n * 6 elements")
+    if ws is None:
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    elif ws.dtype != torch.float32 or not ws.is_contiguous():
+        raise ValueError(f"{who}: ws must be a contiguous fp32 tensor")
+    degenerate = torch.empty((nsets, classes), dtype=torch.int32, device=dev)
+    sync = _sync_buffer(dev)
+    per = classes * n * KIN_DESC
+    flat = out.view(-1)
+    for g, t in enumerate(xs):
+        a.x[g] = t.data_ptr()
+        a.desc[g] = flat[g * per:(g + 1) * per].data_ptr()
+    a.sc, a.ss, a.sf, a.so = int(sc), int(ss), int(sf), int(so)
+    a.degenerate = degenerate.data_ptr()
+    a.ws, a.ws_bytes, a.counters, a.counters_len = ws.data_ptr(), ws.numel() * 4, sync.data_ptr(), sync.numel()
+    _count(who, 0.0)
+    _check(load_library().kg_kin_desc_sets(C.byref(a), _stream()), who)
+    return out.view(nsets, classes, n, KIN_DESC), degenerate
 
 
 def _kin_scores_shape(nsets: int, n: int, m: int, classes: int) -> _KinScoresArgs:
@@ -3377,6 +3473,17 @@ def eval_record2(scores: Sequence[torch.Tensor], select: int, iteration: Optiona
                           ring_iter, best_val, best_iter, flag)
     a.maximise = 1 if maximise else 0
     _check(load_library().kg_eval_record2(C.byref(a), _stream()), "kg_eval_record2")
+
+
+def eval_record3(scores: Sequence[torch.Tensor], select: int, iteration: Optional[torch.Tensor], count: torch.Tensor,
+                 ring_val: torch.Tensor, ring_iter: torch.Tensor, best_val: torch.Tensor, best_iter: torch.Tensor,
+                 flag: torch.Tensor, maximise: bool = False) -> None:
+    """Enqueue kg_eval_record3: ``eval_record2`` for up to EVAL3_MAX_SCORES scores (the same kernel template; with 32 scores or
+    fewer it leaves the bits of ``eval_record2``)."""
+    a = _eval_record_args(_EvalRecord3Args, EVAL3_MAX_SCORES, "kg_eval_record3", scores, select, iteration, count, ring_val,
+                          ring_iter, best_val, best_iter, flag)
+    a.maximise = 1 if maximise else 0
+    _check(load_library().kg_eval_record3(C.byref(a), _stream()), "kg_eval_record3")
 
 
 def copy_if(flag: torch.Tensor, jobs: Sequence[Tuple[torch.Tensor, torch.Tensor]]) -> None:

@@ -3,6 +3,7 @@
 //                    to the device record and leaves the decision in `flag`
 //   kg_eval_record2: the same kernel template and the same launcher (eval_record_launch) with room for KG_EVAL2_MAX_SCORES
 //                    scores and a sense (larger or smaller is better)
+//   kg_eval_record3: the third instantiation, room for KG_EVAL3_MAX_SCORES scores (the kinematic columns)
 //   kg_copy_if     : a grid that only READS that decision and, when it is set, copies a table of word runs - the snapshot
 //                    of the best-scoring weights, taken by the device with no host synchronisation
 // Two launches on purpose: one writer of the decision, then readers of it, with a launch boundary in between - there is no
@@ -127,6 +128,13 @@ extern "C" int kg_eval_record(const KgEvalRecordArgs* a, void* stream) {
 extern "C" int kg_eval_record2(const KgEvalRecord2Args* a, void* stream) {
     KG_REQUIRE(a != nullptr, "kg_eval_record2: null arguments");
     return eval_record_launch<KG_EVAL2_MAX_SCORES>("kg_eval_record2", a->scores, a->nscores, a->select, a->maximise != 0 ? 1 : 0,
+                                                   a->iter, a->count, a->ring_val, a->ring_iter, a->ring_len, a->best_val,
+                                                   a->best_iter, a->flag, stream);
+}
+
+extern "C" int kg_eval_record3(const KgEvalRecord3Args* a, void* stream) {
+    KG_REQUIRE(a != nullptr, "kg_eval_record3: null arguments");
+    return eval_record_launch<KG_EVAL3_MAX_SCORES>("kg_eval_record3", a->scores, a->nscores, a->select, a->maximise != 0 ? 1 : 0,
                                                    a->iter, a->count, a->ring_val, a->ring_iter, a->ring_len, a->best_val,
                                                    a->best_iter, a->flag, stream);
 }

@@ -12,6 +12,11 @@
 // read of an argument array would put the whole struct into scratch).
 // degenerate: thread 0 stores the sample's flag (kg_handoff.h), the last workgroup to arrive counts every class's flags - a
 // wave per class, integer adds.
+// kg_kin_desc_sets: the same kernel body over nsets sets with shared strides - workgroup (g, class, sample), the set slowest;
+// the set's two pointers are picked with constant indices (the rule of the tables above), everything behind them is the
+// one-set code, so every set has the bits of its own kg_kin_desc call.  ONE ticket over the whole grid; the last arriver
+// counts the flags of every (set, class).  kg_kin_desc is the one-set case: one body (a template, whose one-set instantiation
+// has the set coordinate compiled away), one validation, one launcher.
 //
 // kg_kin_w1_kernel: one workgroup = one (set, class, descriptor) column.  ONE LDS array of P 8-byte words, P the power of two
 // >= n + m, serves in turn as: the real values as doubles (tree -> mean_real, set 0 only), the fake values (tree ->
@@ -48,10 +53,10 @@ struct KdFixed {
 static_assert(sizeof(KdFixed) % 16 == 0, "kg_kin_desc: the staged sample starts 16-byte aligned");
 
 struct KinDescDev {
-    const float* x;  long sc, ss, sf, so;
-    int n, T, C, V, classes, B, M;
+    const float* x[KG_KIN_MAX_SETS];  long sc, ss, sf, so;
+    int n, T, C, V, classes, B, M, nsets;
     double still_eps;
-    float* desc;  int* degenerate;  float* flags;  int* counter;
+    float* desc[KG_KIN_MAX_SETS];  int* degenerate;  float* flags;  int* counter;
     FastDiv divTV, divV;
     int bones[2 * KD_MAXB];
     int mirror[2 * KD_MAXM];
@@ -70,13 +75,21 @@ __device__ __forceinline__ double kd_len(const float* xs, int C, int TV, int pu,
 
 __device__ __forceinline__ double kd_norm(double d0, double d1, double d2) { return sqrt(d0 * d0 + d1 * d1 + d2 * d2); }
 
+// SETS = false: the one-set instantiation - g is the constant 0, so the set coordinate, its division and the pointer choice
+// compile away and kg_kin_desc (and a kg_kin_desc_sets call with one set) runs the code it ran before the sets existed
+template <bool SETS>
 __global__ __launch_bounds__(KD_NT) void kg_kin_desc_kernel(const KinDescDev a) {
     extern __shared__ __attribute__((aligned(16))) char kd_smem[];
     KdFixed& F = *(KdFixed*)kd_smem;
     float* xs = (float*)(kd_smem + sizeof(KdFixed));
     const int tid = threadIdx.x;
     const int T = a.T, C = a.C, V = a.V, B = a.B, M = a.M, TV = T * V;
-    const int cls = (int)blockIdx.x / a.n, smp = (int)blockIdx.x - cls * a.n;
+    // workgroup = (set g, class, sample), the set slowest; row = the sample's row in its set's (classes, n) outputs
+    const int per_set = a.classes * a.n, g = SETS ? (int)blockIdx.x / per_set : 0, row = (int)blockIdx.x - g * per_set;
+    const int cls = row / a.n, smp = row - cls * a.n;
+    // (the set's two pointers are picked with constant indices, each where it is used: picked up here, all eight are live
+    // across the table moves and cost the eighth wave per SIMD)
+    static_assert(KG_KIN_MAX_SETS == 4, "kg_kin_desc: the set's pointers are picked with constant indices");
 
     // tables -> LDS (constant indices into the arguments)
     {
@@ -89,7 +102,8 @@ __global__ __launch_bounds__(KD_NT) void kg_kin_desc_kernel(const KinDescDev a) 
     }
     // the sample -> LDS, [c][f][v]
     {
-        const float* src = a.x + (long)cls * a.sc + (long)smp * a.ss;
+        const float* xg = g == 0 ? a.x[0] : g == 1 ? a.x[1] : g == 2 ? a.x[2] : a.x[3];
+        const float* src = xg + (long)cls * a.sc + (long)smp * a.ss;
         const int tot = C * TV;
         for (int e = tid; e < tot; e += KD_NT) {
             unsigned c, r, f, v;
@@ -204,7 +218,8 @@ __global__ __launch_bounds__(KD_NT) void kg_kin_desc_kernel(const KinDescDev a) 
 #pragma unroll
         for (int k = 0; k < 4; ++k) r[k] = (F.red[0][k] + F.red[1][k]) + (F.red[2][k] + F.red[3][k]);
         const bool degen = s == 0.0;
-        float* o = a.desc + (long)blockIdx.x * KG_KIN_DESC;
+        float* dg = g == 0 ? a.desc[0] : g == 1 ? a.desc[1] : g == 2 ? a.desc[2] : a.desc[3];
+        float* o = dg + (long)row * KG_KIN_DESC;
         o[0] = degen ? 0.f : (float)F.bone_cv;
         o[1] = degen ? 0.f : (float)F.asym;
         o[2] = degen ? 0.f : (float)(r[0] / (double)n1 / s);
@@ -216,9 +231,10 @@ __global__ __launch_bounds__(KD_NT) void kg_kin_desc_kernel(const KinDescDev a) 
     }
     __syncthreads();
     if (!F.last) return;
-    // the last workgroup to arrive: a wave per class counts the flags (integers: any order gives the same count)
+    // the last workgroup to arrive: a wave per (set, class) counts the flags (integers: any order gives the same count);
+    // flags and degenerate are (nsets, classes, ..): c walks the sets' classes in one go
     const int lane = tid & 63;
-    for (int c = tid >> 6; c < a.classes; c += KD_NT / 64) {
+    for (int c = tid >> 6; c < (SETS ? a.nsets : 1) * a.classes; c += KD_NT / 64) {
         int k = 0;
         for (int i = lane; i < a.n; i += 64) k += kg_pub_load(a.flags + (long)c * a.n + i) != 0.f ? 1 : 0;
 #pragma unroll
@@ -388,12 +404,17 @@ int next_pow2(int x) {
     return p;
 }
 
-// everything but the device pointers: the shape, the strides, the two host tables, still_eps
-int kin_desc_validate(const KgKinDescArgs* a, const char* who) {
+// everything but the device pointers: the shape, the strides, the two host tables, still_eps.  A = KgKinDescArgs (nsets = 1)
+// or KgKinDescSetsArgs, which share every field name read here
+template <class A>
+int kin_desc_validate(const A* a, int nsets, const char* who) {
     KG_REQUIRE(a != nullptr, "%s: null args", who);
+    KG_REQUIRE(nsets >= 1 && nsets <= KG_KIN_MAX_SETS, "%s: nsets=%d outside [1, %d]", who, nsets, KG_KIN_MAX_SETS);
     KG_REQUIRE(a->classes >= 1, "%s: classes=%d < 1", who, a->classes);
     KG_REQUIRE(a->n >= 1, "%s: n=%d < 1", who, a->n);
     KG_REQUIRE((long)a->classes * a->n < (1L << 24), "%s: classes * n = %ld samples, at most 2^24 - 1", who, (long)a->classes * a->n);
+    KG_REQUIRE((long)nsets * a->classes * a->n < (1L << 24), "%s: nsets * classes * n = %ld workgroups, at most 2^24 - 1", who,
+               (long)nsets * a->classes * a->n);
     KG_REQUIRE(a->C == 2 || a->C == 3, "%s: C=%d is not 2 or 3", who, a->C);
     KG_REQUIRE(a->V >= 1 && a->V <= KG_KIN_MAX_JOINTS, "%s: V=%d outside [1, %d]", who, a->V, KG_KIN_MAX_JOINTS);
     KG_REQUIRE(a->B >= 1 && a->B <= KG_KIN_MAX_BONES, "%s: B=%d outside [1, %d]", who, a->B, KG_KIN_MAX_BONES);
@@ -413,7 +434,8 @@ int kin_desc_validate(const KgKinDescArgs* a, const char* who) {
     return 0;
 }
 
-int64_t kin_desc_lds(const KgKinDescArgs* a) { return (int64_t)sizeof(KdFixed) + 4 * (int64_t)a->C * a->T * a->V; }
+template <class A>
+int64_t kin_desc_lds(const A* a) { return (int64_t)sizeof(KdFixed) + 4 * (int64_t)a->C * a->T * a->V; }
 
 int kin_scores_validate(const KgKinScoresArgs* a, const char* who) {
     KG_REQUIRE(a != nullptr, "%s: null args", who);
@@ -443,40 +465,84 @@ static_assert(KW_MAX_LDS_1024 <= 160 * 1024 && KD_MAX_LDS <= 160 * 1024, "kg_kin
 }  // namespace
 
 extern "C" int64_t kg_kin_desc_workspace_bytes(const KgKinDescArgs* a) {
-    if (int rc = kin_desc_validate(a, "kg_kin_desc_workspace_bytes")) return rc;
+    if (int rc = kin_desc_validate(a, 1, "kg_kin_desc_workspace_bytes")) return rc;
     return 4 * (int64_t)a->classes * a->n;
 }
 
 extern "C" int64_t kg_kin_desc_lds_bytes(const KgKinDescArgs* a) {
-    if (int rc = kin_desc_validate(a, "kg_kin_desc_lds_bytes")) return rc;
+    if (int rc = kin_desc_validate(a, 1, "kg_kin_desc_lds_bytes")) return rc;
     return kin_desc_lds(a);
 }
 
-extern "C" int kg_kin_desc(const KgKinDescArgs* a, void* stream) {
-    const char* who = "kg_kin_desc";
-    if (int rc = kin_desc_validate(a, who)) return rc;
-    KG_REQUIRE(a->x != nullptr, "%s: null pointer x", who);
-    KG_REQUIRE(a->desc != nullptr, "%s: null pointer desc", who);
+extern "C" int64_t kg_kin_desc_sets_workspace_bytes(const KgKinDescSetsArgs* a) {
+    if (int rc = kin_desc_validate(a, a != nullptr ? a->nsets : 1, "kg_kin_desc_sets_workspace_bytes")) return rc;
+    return 4 * (int64_t)a->nsets * a->classes * a->n;
+}
+
+extern "C" int64_t kg_kin_desc_sets_lds_bytes(const KgKinDescSetsArgs* a) {
+    if (int rc = kin_desc_validate(a, a != nullptr ? a->nsets : 1, "kg_kin_desc_sets_lds_bytes")) return rc;
+    return kin_desc_lds(a);
+}
+
+namespace {
+
+unsigned long long kd_attr_mask = 0;     // (one for both instantiations of the launcher: they launch the same kernel)
+
+// Both descriptor entry points behind their validation: the pointer checks, the kernel's arguments and the ONE launch of
+// nsets * classes * n workgroups; x / desc: the nsets pointers of the call
+template <class A>
+int kin_desc_launch(const char* who, const A* a, int nsets, bool indexed, const float* const* x, float* const* desc, void* stream) {
+    for (int g = 0; g < nsets; ++g) {       // (the messages name the field of the caller's struct: x or x[g])
+        char at[16] = "";
+        if (indexed) snprintf(at, sizeof(at), "[%d]", g);
+        KG_REQUIRE(x[g] != nullptr, "%s: null pointer x%s", who, at);
+        KG_REQUIRE(desc[g] != nullptr, "%s: null pointer desc%s", who, at);
+    }
     KG_REQUIRE(a->degenerate != nullptr, "%s: null pointer degenerate", who);
     KG_REQUIRE(a->ws != nullptr, "%s: null pointer ws", who);
     KG_REQUIRE(a->counters != nullptr, "%s: null pointer counters", who);
     KG_REQUIRE(a->counters_len >= 1, "%s: counters_len=%d < 1", who, a->counters_len);
-    const int64_t need = 4 * (int64_t)a->classes * a->n;
-    KG_REQUIRE(a->ws_bytes >= need, "%s: ws_bytes=%lld < %lld (kg_kin_desc_workspace_bytes)", who, (long long)a->ws_bytes,
-               (long long)need);
+    const int64_t need = 4 * (int64_t)nsets * a->classes * a->n;
+    KG_REQUIRE(a->ws_bytes >= need, "%s: ws_bytes=%lld < %lld (%s_workspace_bytes)", who, (long long)a->ws_bytes, (long long)need, who);
     KinDescDev d = {};
-    d.x = a->x;  d.sc = a->sc;  d.ss = a->ss;  d.sf = a->sf;  d.so = a->so;
-    d.n = a->n;  d.T = a->T;  d.C = a->C;  d.V = a->V;  d.classes = a->classes;  d.B = a->B;  d.M = a->M;
+    for (int g = 0; g < nsets; ++g) {
+        d.x[g] = x[g];
+        d.desc[g] = desc[g];
+    }
+    d.sc = a->sc;  d.ss = a->ss;  d.sf = a->sf;  d.so = a->so;
+    d.n = a->n;  d.T = a->T;  d.C = a->C;  d.V = a->V;  d.classes = a->classes;  d.B = a->B;  d.M = a->M;  d.nsets = nsets;
     d.still_eps = a->still_eps;
-    d.desc = a->desc;  d.degenerate = a->degenerate;  d.flags = a->ws;  d.counter = a->counters;
+    d.degenerate = a->degenerate;  d.flags = a->ws;  d.counter = a->counters;
     d.divTV = FastDiv::make((unsigned)(a->T * a->V));
     d.divV = FastDiv::make((unsigned)a->V);
     for (int b = 0; b < 2 * a->B; ++b) d.bones[b] = a->bones[b];
     for (int p = 0; p < 2 * a->M; ++p) d.mirror[p] = a->mirror[p];
-    static unsigned long long attr_mask = 0;
-    if (kg_first_on_device(attr_mask)) KG_SET_DYN_LDS(kg_kin_desc_kernel, KD_MAX_LDS);
-    hipLaunchKernelGGL(kg_kin_desc_kernel, dim3(a->classes * a->n), dim3(KD_NT), (size_t)kin_desc_lds(a), (hipStream_t)stream, d);
+    if (kg_first_on_device(kd_attr_mask)) {
+        KG_SET_DYN_LDS(kg_kin_desc_kernel<false>, KD_MAX_LDS);
+        KG_SET_DYN_LDS(kg_kin_desc_kernel<true>, KD_MAX_LDS);
+    }
+    const dim3 grid(nsets * a->classes * a->n);
+    if (nsets == 1)
+        hipLaunchKernelGGL(kg_kin_desc_kernel<false>, grid, dim3(KD_NT), (size_t)kin_desc_lds(a), (hipStream_t)stream, d);
+    else
+        hipLaunchKernelGGL(kg_kin_desc_kernel<true>, grid, dim3(KD_NT), (size_t)kin_desc_lds(a), (hipStream_t)stream, d);
     return kg_launch_status(who);
+}
+
+}  // namespace
+
+extern "C" int kg_kin_desc(const KgKinDescArgs* a, void* stream) {
+    const char* who = "kg_kin_desc";
+    if (int rc = kin_desc_validate(a, 1, who)) return rc;
+    const float* x[1] = {a->x};
+    float* desc[1] = {a->desc};
+    return kin_desc_launch(who, a, 1, /*indexed=*/false, x, desc, stream);
+}
+
+extern "C" int kg_kin_desc_sets(const KgKinDescSetsArgs* a, void* stream) {
+    const char* who = "kg_kin_desc_sets";
+    if (int rc = kin_desc_validate(a, a != nullptr ? a->nsets : 1, who)) return rc;
+    return kin_desc_launch(who, a, a->nsets, /*indexed=*/true, a->x, a->desc, stream);
 }
 
 extern "C" int64_t kg_kin_scores_lds_bytes(const KgKinScoresArgs* a) {

@@ -49,6 +49,15 @@ nearest training sample than that sample lies to another training sample: noise 
 is ``memorisation_real["authenticity"]`` - recorded, never selected by) and ``"<g>/label_agreement"`` (the share whose
 nearest training sample carries the conditioning label; larger is better) per generator.
 
+With ``kinematics_per_class > 0`` it also scores kinematic plausibility - whether the samples are bodies at
+all: every generator's round of ``kinematics_per_class`` samples per class (a PRDC, Frechet, classifier or raw-memorisation
+round of that count when one exists) is a set of ONE kg_kin_desc_sets launch, read in place through the rounds' shared
+strides, and ONE kg_kin_scores call (two launches) then measures, per descriptor, the class-averaged Wasserstein-1 distance
+to the real samples' descriptors, which were computed once, at construction (``kinematics_real`` holds their means).  The
+record then ends with ``"<g>/bone_cv"``, ``"<g>/asymmetry"``, ``"<g>/speed"``, ``"<g>/accel"``, ``"<g>/jerk"`` and
+``"<g>/still"`` per generator (all smaller is better; a generator that emits non-finite values records NaN, which never
+wins) and goes through kg_eval_record3, which has room for 64 scores.
+
 Nothing synchronises the host; everything is read through pointers when the launches run, so the captured evaluation
 follows the training replays in between.  ``records()``, ``best()`` and ``state_dict()`` read the device; the Evaluator
 never writes to a generator.  Definitions the tests pin this against: tests/eval_def.py.
@@ -95,7 +104,7 @@ MEMORISATION_MODES = ("features", "raw")
 
 def score_sense(name: str) -> str:
     """``"max"`` for precision / recall / density / coverage, accuracy and label_agreement (larger is better), ``"min"`` for the
-    MMD modes and every Frechet distance; ValueError for diversity / multimodality / authenticity, which have no better
+    MMD modes, every Frechet distance and the six kinematic W1 distances; ValueError for diversity / multimodality / authenticity, which have no better
     direction"""
     last = str(name).rsplit("/", 1)[-1]
     if last in NO_SENSE:
@@ -104,12 +113,13 @@ def score_sense(name: str) -> str:
 
 
 def score_names(generators: Sequence[str], modes: Sequence[str], prdc: bool = False, frechet: Sequence[str] = (),
-                classifier: bool = False, memorisation: bool = False) -> list:
+                classifier: bool = False, memorisation: bool = False, kinematics: bool = False) -> list:
     """The record's columns: ``"<g>/<mode>"`` generator by generator, then - with precision / recall / density / coverage
     on - ``"<g>/<name>"`` generator by generator in the order of ``metrics.PRDC_NAMES``, then - with the Frechet modes
     ``frechet`` (of ``metrics.FRECHET_MODES``) - ``"<g>/pose_fd"`` and / or ``"<g>/motion_fd"`` generator by generator, then -
     with ``classifier`` - ``"<g>/<name>"`` generator by generator in the order of ``metrics.CLS_NAMES``, then - with
-    ``memorisation`` - ``"<g>/<name>"`` generator by generator in the order of ``metrics.MEMORISATION_NAMES``"""
+    ``memorisation`` - ``"<g>/<name>"`` generator by generator in the order of ``metrics.MEMORISATION_NAMES``, then - with
+    ``kinematics`` - ``"<g>/<name>"`` generator by generator in the order of ``metrics.KIN_NAMES``"""
     names = ["%s/%s" % (g, m) for g in generators for m in modes]
     if prdc:
         names += ["%s/%s" % (g, q) for g in generators for q in metrics.PRDC_NAMES]
@@ -118,6 +128,8 @@ def score_names(generators: Sequence[str], modes: Sequence[str], prdc: bool = Fa
         names += ["%s/%s" % (g, q) for g in generators for q in metrics.CLS_NAMES]
     if memorisation:
         names += ["%s/%s" % (g, q) for g in generators for q in metrics.MEMORISATION_NAMES]
+    if kinematics:
+        names += ["%s/%s" % (g, q) for g in generators for q in metrics.KIN_NAMES]
     return names
 
 
@@ -156,6 +168,13 @@ def _flat_storage(params):
     return flat, [p.storage_offset() - lo for p in params]
 
 
+def _kinematics_state(ev) -> dict:
+    """what a state keeps of the kinematic columns: the count, the threshold and the skeleton tables"""
+    return {"per_class": int(ev.kinematics_per_class), "still_eps": float(ev.kinematics_still_eps),
+            "bones": [[int(v) for v in b] for b in ev.kinematics_bones],
+            "mirror": [[int(v) for v in p] for p in ev.kinematics_mirror]}
+
+
 class Evaluator:
     """``generators``: {name: Generator} (one or more); the real side: a ``Feeder`` (``metrics.select_reference_samples``
     with ``per_class=pairs``, cropped to the generator's ``t_size``), or ``real`` (N, C, T, V) with class ids
@@ -180,7 +199,12 @@ class Evaluator:
     writes to the training set.  ``memorisation_method`` (``"exact"``, ``"gram"``): with ``"gram"`` every search - the one-off
     leave-one-out pass included - runs through kg_nn_gram, the matrix-core pre-filter with exact re-score: the
     same bits in every column; the training side's norms are computed once here, the six launches are part of the captured
-    evaluation, and ``memorisation_stats`` holds the (sets, 1, 2) certified / fallback row counts of the last call."""
+    evaluation, and ``memorisation_stats`` holds the (sets, 1, 2) certified / fallback row counts of the last call.
+    ``kinematics_per_class`` (0: off): also score the six kinematic W1 distances of ``metrics.kinematics`` on that many fake
+    and real samples per class, on the skeleton of ``kinematics_dataset`` (``"ntu"`` or ``"h36m"``) or the caller's
+    ``kinematics_bones`` (B, 2) joint pairs and ``kinematics_mirror`` (M, 2) pairs of bone indices; ``kinematics_still_eps``
+    is the threshold of the ``still`` descriptor.  ``kinematics_real`` then holds the real side's descriptor means (by
+    ``metrics.KIN_NAMES``), ``"class_means"`` (K, 6) and its ``"degenerate"`` / ``"nonfinite"`` sample counts."""
 
     def __init__(self, generators: Dict[str, torch.nn.Module], real, real_labels=None, pairs: int = 10,
                  modes: Sequence[str] = ("avg", "joint"), select: Optional[str] = None, seed: int = 0,
@@ -189,7 +213,9 @@ class Evaluator:
                  prdc_k: int = 5, frechet_per_class: int = 0, frechet_modes: Sequence[str] = ("pose", "motion"),
                  classifier=None, classifier_per_class: int = 0, classifier_batch: int = 512, diversity_pairs: int = 200,
                  multimodality_pairs: int = 20, memorisation: Optional[str] = None, memorisation_train=None,
-                 memorisation_train_labels=None, memorisation_per_class: int = 0, memorisation_method: str = "exact"):
+                 memorisation_train_labels=None, memorisation_per_class: int = 0, memorisation_method: str = "exact", *,
+                 kinematics_per_class: int = 0, kinematics_dataset: Optional[str] = None, kinematics_bones=None,
+                 kinematics_mirror=None, kinematics_still_eps: float = 1e-3):
         if not generators:
             raise ValueError("Evaluator: at least one generator")
         self._check_classifier_options(classifier, classifier_per_class, classifier_batch, diversity_pairs, multimodality_pairs)
@@ -199,6 +225,8 @@ class Evaluator:
         self.memorisation_stats = None
         self._check_frechet_options(frechet_per_class, frechet_modes)
         self._check_prdc_options(prdc_per_class, prdc_k)
+        self._check_kinematics_options(kinematics_per_class, kinematics_dataset, kinematics_bones, kinematics_mirror,
+                                       kinematics_still_eps)
         self.modes = tuple(modes)
         for m in self.modes:
             metrics._check_mode(m)
@@ -206,9 +234,10 @@ class Evaluator:
             raise ValueError("Evaluator: at least one mode")
         self.gens = dict(generators)
         self.names = score_names(list(self.gens), self.modes, bool(self.prdc_per_class), self.frechet_modes,
-                                 bool(self.classifier_per_class), bool(self.memorisation))
+                                 bool(self.classifier_per_class), bool(self.memorisation), kinematics=bool(self.kinematics_per_class))
         self._record2 = bool(self.prdc_per_class or self.frechet_per_class or self.classifier_per_class or self.memorisation)
-        most = nv.EVAL2_MAX_SCORES if self._record2 else nv.EVAL_MAX_SCORES
+        self._record3 = bool(self.kinematics_per_class)
+        most = nv.EVAL3_MAX_SCORES if self._record3 else (nv.EVAL2_MAX_SCORES if self._record2 else nv.EVAL_MAX_SCORES)
         if len(self.names) > most:
             raise ValueError("Evaluator: %d scores, at most %d fit one record" % (len(self.names), most))
         self.select = default_select(list(self.gens), self.modes) if select is None else str(select)
@@ -248,6 +277,10 @@ class Evaluator:
             self._memorisation_setup(real, real_labels, t_size, trunc, trunc_mode, memorisation_train, memorisation_train_labels)
         else:
             self.mem_samplers, self.memorisation_real = {}, None
+        if self.kinematics_per_class:
+            self._kinematics_setup(real, real_labels, t_size, trunc, trunc_mode)
+        else:
+            self.kin_samplers, self.kinematics_real = {}, None
         # the real side, once: row j*K + c = the j-th selected real sample of class c (the Sampler's label order)
         self.real = torch.as_tensor(self._select_real(real, real_labels, self.pairs, "pairs", t_size)).to(dev)
         self._pair_labels = np.arange(self.n)                  # every (fake, real) pair is a "class" of the kg_mmd call
@@ -325,6 +358,23 @@ class Evaluator:
             self.memorisation_per_class = self.classifier_per_class
         elif self.memorisation_per_class < 1:
             raise ValueError("Evaluator: memorisation='raw' needs memorisation_per_class >= 1, got %d" % self.memorisation_per_class)
+
+    def _check_kinematics_options(self, per_class, dataset, bones, mirror, still_eps):
+        """the skeleton tables (``metrics._kin_tables``); the limits that need the samples' shape follow in the set-up"""
+        self.kinematics_per_class = int(per_class)
+        self.kinematics_still_eps = float(still_eps)
+        self.kinematics_bones, self.kinematics_mirror = None, None
+        if self.kinematics_per_class < 0:
+            raise ValueError("Evaluator: kinematics_per_class=%d < 0" % self.kinematics_per_class)
+        if not self.kinematics_per_class:
+            return
+        if dataset is None and bones is None:
+            raise ValueError("Evaluator: kinematics_per_class=%d needs the skeleton: kinematics_dataset ('ntu' or 'h36m') or "
+                             "kinematics_bones" % self.kinematics_per_class)
+        if 2 * self.kinematics_per_class > nv.KIN_MAX_POINTS:
+            raise ValueError("Evaluator: kinematics_per_class=%d: real + generated = %d values per class, above the cap of %d" % (
+                self.kinematics_per_class, 2 * self.kinematics_per_class, nv.KIN_MAX_POINTS))
+        self.kinematics_bones, self.kinematics_mirror = metrics._kin_tables(dataset, bones, mirror, "Evaluator: kinematics_dataset")
 
     def _check_prdc_options(self, prdc_per_class, prdc_k):
         self.prdc_per_class, self.prdc_k = int(prdc_per_class), int(prdc_k)
@@ -653,6 +703,67 @@ class Evaluator:
                 words += [sc_["scores"][g, 0:1], sc_["scores"][g, 1:2]]
         return words
 
+    # ---- kinematic plausibility: W1 of six descriptors against the real set --------------------------------
+    def _kinematics_setup(self, real, real_labels, t_size, trunc, trunc_mode):
+        """the checks (``metrics._kin_check``); the real side, once: ``kinematics_per_class`` samples of every class, class by
+        class, and their descriptors (one kg_kin_desc launch; deterministic, so not part of the state) with their own means
+        and counts (``kinematics_real``); the static descriptor matrices and the workspace; per generator a Sampler, unless
+        a PRDC, Frechet, classifier or raw-memorisation round of the same count exists and is read instead"""
+        dev, K, P = self.device, self.n_classes, self.kinematics_per_class
+        bones, mirror, eps = self.kinematics_bones, self.kinematics_mirror, self.kinematics_still_eps
+        real_x = torch.as_tensor(self._select_real(real, real_labels, P, "classes", t_size)).to(dev)       # (K*P, C, t, V)
+        metrics._kin_check(real_x, "real", bones, mirror, eps, "Evaluator: kinematics")
+        if K * P >= 1 << 24:
+            raise ValueError("Evaluator: kinematics_per_class=%d: %d samples, kg_kin_desc takes fewer than 2^24" % (P, K * P))
+        _, C, T, V = real_x.shape
+        D = C * T * V
+        self._kin_shape = tuple(real_x.shape)
+        self.kin_samplers, self._kin_shared = {}, None
+        for kind, per, group in (("prdc", self.prdc_per_class, self.prdc_samplers),
+                                 ("frechet", self.frechet_per_class, self.frechet_samplers),
+                                 ("classifier", self.classifier_per_class, self.cls_samplers),
+                                 ("memorisation", self.memorisation_per_class if self.memorisation == "raw" else 0,
+                                  self.mem_samplers)):
+            if per == P and group:              # (a round that is itself shared has no Samplers: its owner came first)
+                self._kin_shared = kind
+                break
+        else:
+            self.kin_samplers = {k: Sampler(G, qtd=P, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False)
+                                 for k, G in self.gens.items()}
+        with torch.cuda.device(dev):
+            desc, degenerate = nv.kin_desc(nv.FrechetView(real_x, P * D, D, V, T * V), P, T, C, V, K, bones, mirror, eps)
+            self._kin_real_desc = desc
+            finite = torch.isfinite(desc).all(dim=2)                        # (K, P)
+            means = desc.double().mean(dim=1)                               # (K, 6)
+            self.kinematics_real = dict({q: means[:, i].mean() for i, q in enumerate(metrics.KIN_NAMES)}, class_means=means,
+                                        degenerate=degenerate, nonfinite=(~finite).sum(dim=1).to(torch.int32))
+            sets = min(len(self.gens), nv.KIN_MAX_SETS)
+            self._kin_desc = torch.zeros((sets, K, P, nv.KIN_DESC), dtype=torch.float32, device=dev)
+            nbytes = nv.kin_desc_sets_workspace_bytes(sets, P, T, C, V, K, bones, mirror, eps)
+            self._kin_ws = torch.zeros(nbytes // 4, dtype=torch.float32, device=dev)
+
+    def _kinematics_scores(self):
+        """the kinematic rounds of all generators (a PRDC, Frechet, classifier or raw-memorisation round of the same count when
+        one exists), then per group of up to KIN_MAX_SETS generators ONE kg_kin_desc_sets - the rounds read in place through
+        their shared strides: row j*K + c, so the class stride is a sample and the sample stride K samples - and ONE
+        kg_kin_scores against the cached real descriptors: the score words are one-element views of scores (nsets, 6), per
+        generator in the order of metrics.KIN_NAMES"""
+        K, P = self.n_classes, self.kinematics_per_class
+        shared = {"prdc": self.prdc_samplers, "frechet": self.frechet_samplers, "classifier": self.cls_samplers,
+                  "memorisation": self.mem_samplers}
+        rounds = [s._out for s in shared[self._kin_shared].values()] if self._kin_shared else self.kin_samplers.values()
+        outs, sn, sc = self._checked_rounds(rounds, self._kin_shape)
+        _, C, T, V = outs[0].shape
+        words = []
+        for q in range(0, len(outs), nv.KIN_MAX_SETS):
+            part = outs[q:q + nv.KIN_MAX_SETS]
+            desc, _ = nv.kin_desc_sets(
+                part, sn, K * sn, V, sc, P, T, C, V, K, self.kinematics_bones, self.kinematics_mirror, self.kinematics_still_eps,
+                out=self._kin_desc[:len(part)], ws=self._kin_ws)
+            res = nv.kin_scores(self._kin_real_desc, [desc[g] for g in range(len(part))])
+            words += [res["scores"][g, i:i + 1] for g in range(len(part)) for i in range(nv.KIN_DESC)]
+        return words
+
     # ---- the launch sequence -------------------------------------------------------------------------------------------
     def _round(self):
         """what a graph holds: per generator a Sampler round, the re-layout, kg_mmd per mode; then the record, then the
@@ -674,7 +785,12 @@ class Evaluator:
             scores += self._classifier_scores()
         if self.memorisation:
             scores += self._memorisation_scores()
-        if self._record2:
+        if self.kinematics_per_class:
+            scores += self._kinematics_scores()
+        if self._record3:
+            nv.eval_record3(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
+                            self.best_iter, self.flag, maximise=self.maximise)
+        elif self._record2:
             nv.eval_record2(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
                             self.best_iter, self.flag, maximise=self.maximise)
         else:
@@ -690,7 +806,7 @@ class Evaluator:
 
     def _all_samplers(self):
         return list(self.samplers.values()) + list(self.prdc_samplers.values()) + list(self.frechet_samplers.values()) \
-            + list(self.cls_samplers.values()) + list(self.mem_samplers.values())
+            + list(self.cls_samplers.values()) + list(self.mem_samplers.values()) + list(self.kin_samplers.values())
 
     def _capture(self):
         """Single-stream capture, no parallel branches.  The warm-up rounds in front of it are real evaluations:
@@ -777,6 +893,8 @@ class Evaluator:
                                 "multimodality_pairs": self.multimodality_pairs}
         if self.memorisation:                # (the training side is recomputed from the data: not part of the state)
             sd["memorisation"] = {"mode": self.memorisation, "per_class": self.memorisation_per_class}
+        if self.kinematics_per_class:        # (the real side's descriptors are recomputed from the data: not part of the state)
+            sd["kinematics"] = _kinematics_state(self)
         return sd
 
     def check_compatible(self, sd: dict) -> None:
@@ -800,6 +918,16 @@ class Evaluator:
         theirs = sd.get("memorisation")
         if (None if theirs is None else {"mode": str(dict(theirs)["mode"]), "per_class": int(dict(theirs)["per_class"])}) != mine:
             raise ValueError("Evaluator.load_state_dict: memorisation is %r in the state, %r here" % (theirs, mine))
+        # (an Evaluator-like object of before the kinematic columns has no such attribute: the option is off)
+        mine = _kinematics_state(self) if getattr(self, "kinematics_per_class", 0) else None
+        theirs = sd.get("kinematics")
+        if theirs is not None:
+            theirs = dict(theirs)
+            theirs = {"per_class": int(theirs["per_class"]), "still_eps": float(theirs["still_eps"]),
+                      "bones": [[int(v) for v in b] for b in theirs["bones"]],
+                      "mirror": [[int(v) for v in p] for p in theirs["mirror"]]}
+        if theirs != mine:
+            raise ValueError("Evaluator.load_state_dict: kinematics is %r in the state, %r here" % (theirs, mine))
         for k, mine in (("pairs", self.pairs), ("select", self.select), ("modes", list(self.modes)), ("names", list(self.names))):
             if (list(sd[k]) if isinstance(mine, list) else sd[k]) != mine:
                 raise ValueError("Evaluator.load_state_dict: %s is %r in the state, %r here" % (k, sd[k], mine))

@@ -99,7 +99,8 @@ class TrainLoop:
                  eval_frechet: int = 0, eval_frechet_modes=("pose", "motion"), eval_classifier=None,
                  eval_classifier_samples: int = 0, eval_classifier_batch: int = 512, eval_diversity_pairs: int = 200,
                  eval_multimodality_pairs: int = 20, eval_memorisation: Optional[str] = None,
-                 eval_memorisation_samples: int = 0, eval_memorisation_method: str = "exact"):
+                 eval_memorisation_samples: int = 0, eval_memorisation_method: str = "exact", *, eval_kinematics: int = 0,
+                 eval_kinematics_still_eps: float = 1e-3):
         self.G, self.D = G, D
         self.device = next(G.parameters()).device
         if self.device.type != "cuda":
@@ -167,6 +168,8 @@ class TrainLoop:
         # distance, diversity and multimodality on that many samples per class.  eval_memorisation ("features":
         # the classifier round's features; "raw": eval_memorisation_samples samples per class): and authenticity / label
         # agreement against the loop's own ResidentDataset, searched where it lies; a streamed dataset is refused.
+        # eval_kinematics (0: off): and the six kinematic W1 distances on that many samples per class, on the skeleton of the
+        # feeder's dataset.
         self.eval_interval = int(eval_interval) if eval_interval else None
         self.evaluator = None
         if self.eval_interval:
@@ -184,7 +187,10 @@ class TrainLoop:
                                        memorisation=eval_memorisation or None,
                                        memorisation_train=self.resident if eval_memorisation else None,
                                        memorisation_per_class=eval_memorisation_samples,
-                                       memorisation_method=eval_memorisation_method)
+                                       memorisation_method=eval_memorisation_method,
+                                       kinematics_per_class=eval_kinematics,
+                                       kinematics_dataset=getattr(feeder, "dataset", None) if eval_kinematics else None,
+                                       kinematics_still_eps=eval_kinematics_still_eps)
 
     # ---- schedule ------------------------------------------------------------------------------------------------
     @property

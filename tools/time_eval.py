@@ -42,7 +42,14 @@ round of its own) alternating in one process as under ``--frechet``; the same co
 ``metrics.memorisation_features`` / ``memorisation`` call per generator on rounds already drawn (eager: it reads the host; the
 leave-one-out distances given); then, each a graph of its own, kg_nn_sets over both generators against two kg_nn calls -
 "faster" only if the gap exceeds the larger spread - and kg_nn_scores alone.
-    python tools/time_eval.py [--rounds 3] [--prdc 100 | --frechet 100 | --classifier 100 | --memorisation features] [--log FILE]"""
+``--kinematics P`` (record: profiles/eval_kinematics_time.log): instead of the above, the cost of the six kinematic
+W1 columns per generator on P samples per class inside an evaluation, at the NTU and the H36M shapes, live + ema.  ONE
+evaluation replay three ways - with the columns (one kg_kin_desc_sets + one kg_kin_scores for both generators, the real
+descriptors cached), with the same columns composed from one ``metrics.kinematics_sets`` call per generator (a kg_kin_desc and a
+kg_kin_scores each), and without them - alternating in one process as under ``--frechet``; a difference is called real only
+when it exceeds three times the larger spread.
+    python tools/time_eval.py [--rounds 3] [--prdc 100 | --frechet 100 | --classifier 100 | --memorisation features |
+                               --kinematics 100] [--log FILE]"""
 import argparse
 import os
 import statistics
@@ -229,6 +236,72 @@ def frechet_part(args, say, dev):
         say("%s the two routes record the same bits: %s; last scores: %s" % (
             name, np.array_equal(ra["scores"].view(np.uint32), rb["scores"].view(np.uint32)),
             ", ".join("%s %.6g" % (n, v) for n, v in zip(ra["names"], ra["scores"][-1]))))
+        del ev, gens
+        torch.cuda.empty_cache()
+
+
+class ComposedKinematicsEvaluator(Evaluator):
+    """the kinematic columns as they would be without kg_kin_desc_sets: per generator one ``metrics.kinematics_sets`` call on its
+    round (one kg_kin_desc launch and one kg_kin_scores call each) against the cached real descriptors - the same bits, two
+    launches more per further generator"""
+
+    def _kinematics_scores(self):
+        K, P = self.n_classes, self.kinematics_per_class
+        labels = np.tile(np.arange(K), P)        # the Sampler's label vector: row j*K + c has class c (read in place)
+        words = []
+        for s in self.kin_samplers.values():
+            s._round()
+            res = metrics.kinematics_sets([s._out], self._kin_real_desc, labels, bones=self.kinematics_bones,
+                                          mirror=self.kinematics_mirror, still_eps=self.kinematics_still_eps)
+            words += [res["scores"][0, i:i + 1] for i in range(nv.KIN_DESC)]
+        return words
+
+
+def kinematics_part(args, say, dev):
+    """``--kinematics P``: see the module docstring"""
+    P = args.kinematics
+    for name, c in PRDC_SHAPES:
+        K = c["n_classes"]
+        gens = {}
+        for g, seed in (("live", 1234), ("ema", 4321)):      # two generators of different weights (no training needed here)
+            torch.manual_seed(seed)
+            gens[g] = Generator(c["latent"], c["channels"], K, c["t_size"], c["mlp"], dataset=c["dataset"]).to(dev)
+        rng = np.random.RandomState(0)
+        real = torch.as_tensor((rng.rand(K * P, c["channels"], c["t_size"], c["v"]) * 2 - 1).astype(np.float32))
+        labels = np.tile(np.arange(K), P)
+        say("%s shapes: %d classes x %d samples per class of %d frames, C %d, V %d, live + ema, six W1 columns per generator" % (
+            name, K, P, c["t_size"], c["channels"], c["v"]))
+        kw = dict(pairs=PAIRS, seed=0, kinematics_per_class=P, kinematics_dataset=c["dataset"])
+        ev = {"kg_kin_desc_sets, cached real side": Evaluator(gens, real, labels, **kw),
+              "metrics.kinematics_sets per generator": ComposedKinematicsEvaluator(gens, real, labels, **kw),
+              "without the kinematic columns": Evaluator(gens, real, labels, pairs=PAIRS, seed=0)}
+        for x in ev.values():
+            x.evaluate()                     # (captures)
+        torch.cuda.synchronize()
+        em = {k: [] for k in ev}
+        for r in range(args.rounds):
+            for k, x in ev.items():
+                ts = time_replays(x._graph, args.eval_replays)
+                x.n_evals += args.eval_replays + 1
+                for s in x._all_samplers():
+                    s.step_count += args.eval_replays + 1
+                em[k].append(statistics.median(ts))
+                say("%s evaluation replay, %-38s round %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
+                    name, k + ",", r, em[k][-1], args.eval_replays, min(ts), max(ts)))
+        m = {k: statistics.median(v) for k, v in em.items()}
+        sp = {k: max(v) - min(v) for k, v in em.items()}
+        a, b, off = list(ev)
+        gap, wide = m[b] - m[a], max(sp[a], sp[b])
+        verdict = "not separated (within three spreads)" if abs(gap) <= 3 * wide else (
+            "kg_kin_desc_sets is faster by more than three spreads" if gap > 0 else "kg_kin_desc_sets is slower by more than three spreads")
+        say("%s evaluation replay: %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f)" % (
+            name, a, m[a], sp[a], b, m[b], sp[b], off, m[off], sp[off]))
+        say("%s kinematic columns cost %+.4f ms through kg_kin_desc_sets, %+.4f ms composed; gap %+.4f ms against the larger spread "
+            "%.4f ms (three times: %.4f ms): %s" % (name, m[a] - m[off], m[b] - m[off], gap, wide, 3 * wide, verdict))
+        ra, rb = ev[a].records(), ev[b].records()
+        say("%s the two routes record the same bits: %s; last kinematic scores: %s" % (
+            name, np.array_equal(ra["scores"].view(np.uint32), rb["scores"].view(np.uint32)),
+            ", ".join("%s %.6g" % (n, v) for n, v in zip(ra["names"][-12:], ra["scores"][-1][-12:]))))
         del ev, gens
         torch.cuda.empty_cache()
 
@@ -477,6 +550,8 @@ def parse_args(argv=None):
     ap.add_argument("--memorisation-samples", type=int, default=100, help="samples per class of --memorisation")
     ap.add_argument("--memorisation_method", type=str, default="exact", choices=["exact", "gram"],
                     help="gram: time the memorisation columns through kg_nn_gram against the exact search (DESIGN.md 24)")
+    ap.add_argument("--kinematics", type=int, default=0,
+                    help="samples per class: time the kinematic columns of an evaluation instead (DESIGN.md 26)")
     ap.add_argument("--eval-replays", type=int, default=30,
                     help="replays of a whole evaluation / a Sampler round under --prdc and --frechet")
     ap.add_argument("--log", default=None, help="also write the lines to this file")
@@ -494,9 +569,11 @@ def main(argv=None):
         print(s, flush=True)
         lines.append(s)
 
-    if args.prdc or args.frechet or args.classifier or args.memorisation:
+    if args.prdc or args.frechet or args.classifier or args.memorisation or args.kinematics:
         say("device %s" % torch.cuda.get_device_name(0))
-        if args.memorisation:
+        if args.kinematics:
+            kinematics_part(args, say, dev)
+        elif args.memorisation:
             memorisation_part(args, say, dev)
         elif args.prdc:
             prdc_part(args, say, dev)

@@ -7,7 +7,11 @@ one call (torch.profiler) and the largest difference of the two sides' W1.  As c
 kg_kin_scores on their own, and the input bytes of kg_kin_desc over its time.
 Shapes: the NTU protocol (60 classes, 100 + 100 samples, T = 64, C 3, V 25), the H36M protocol (10 classes, 100 + 100, T = 64,
 C 2, V 16) and one unconditional set of 6000 + 6000 NTU samples (--big-calls calls).
-    python tools/time_kin.py [--calls 200] [--reps 3] [--big-calls 200] [--log profiles/kin_time.log]"""
+    python tools/time_kin.py [--calls 200] [--reps 3] [--big-calls 200] [--log profiles/kin_time.log]
+``--sets G`` (record: profiles/eval_kinematics_time.log): instead of the above, ONE kg_kin_desc_sets launch over
+G sets against G kg_kin_desc calls of the same build at the NTU and the H36M protocol shapes, alternating in the same way
+(outputs and workspaces allocated outside the timed calls on both sides, the bits compared once).
+    python tools/time_kin.py --sets 2 [--calls 200] [--reps 3] [--log FILE]"""
 import argparse
 import os
 import statistics
@@ -76,6 +80,52 @@ def stock_path(R, F, tabs):
     return stock_scores(stock_desc(R, *tabs), stock_desc(F, *tabs))
 
 
+def time_sets(args, dev, g):
+    """kg_kin_desc_sets over args.sets sets against that many kg_kin_desc calls"""
+    G = args.sets
+    say("kg_kin_desc_sets over %d sets (ONE launch) against %d kg_kin_desc calls; median of %d calls x %d repetitions" % (
+        G, G, args.calls, args.reps))
+    for name, graph, K, n, C, T, V in (("NTU protocol  60 x 100 x T 64, C 3, V 25", graph_ntu, 60, 100, 3, 64, 25),
+                                       ("H36M protocol 10 x 100 x T 64, C 2, V 16", Graph_h36m, 10, 100, 2, 64, 16)):
+        bones, mirror = graph.bones, graph.mirror_bones
+        xs = [make(K, n, C, T, V, dev, g, 1.0 / (1 + i)) for i in range(G)]
+        views = [view(x) for x in xs]
+        out = torch.zeros((G, K, n, 6), dtype=torch.float32, device=dev)
+        ref = torch.zeros((G, K, n, 6), dtype=torch.float32, device=dev)
+        ws = torch.zeros(_native.kin_desc_sets_workspace_bytes(G, n, T, C, V, K, bones, mirror) // 4, dtype=torch.float32, device=dev)
+
+        def one_launch():
+            return _native.kin_desc_sets(views, 0, 0, 0, 0, n, T, C, V, K, bones, mirror, STILL_EPS, out=out, ws=ws)
+
+        def per_set():
+            return [_native.kin_desc(views[i], n, T, C, V, K, bones, mirror, STILL_EPS, out=ref[i]) for i in range(G)]
+
+        sides = (("desc_sets ", one_launch), ("desc x %d  " % G, per_set))
+        meds = {s: [] for s, _ in sides}
+        for _ in range(args.reps):                      # alternating: sets, per set, sets, per set, ...
+            for s, fn in sides:
+                meds[s].append(median_ms(fn, args.calls))
+        deg = one_launch()[1]
+        degs = torch.stack([d for _, d in per_set()])
+        torch.cuda.synchronize()
+        same = torch.equal(out.view(torch.int32), ref.view(torch.int32)) and torch.equal(deg, degs)
+        say("%s  (N = %d)" % (name, args.calls))
+        res = {}
+        for s, fn in sides:
+            med, spread = statistics.median(meds[s]), max(meds[s]) - min(meds[s])
+            res[s] = (med, spread)
+            say("  %s %9.4f ms  spread %7.4f ms  medians %s  launches %3d" % (s, med, spread,
+                                                                            " ".join("%.4f" % v for v in meds[s]), launches(fn)))
+        (a, sa), (b, sb) = res[sides[0][0]], res[sides[1][0]]
+        gap, bar = b - a, max(sa, sb)
+        verdict = "faster by more than three spreads" if gap > 3 * bar else ("slower by more than three spreads" if -gap > 3 * bar
+                                                                            else "not separated (within three spreads)")
+        nbytes = 4.0 * G * K * n * C * T * V
+        say("  per-set calls - one launch = %+.4f ms against the larger spread %.4f ms (three times: %.4f ms): kg_kin_desc_sets is %s; "
+            "%.1f MB of input at %.3f TB/s; bits equal: %s" % (gap, bar, 3 * bar, verdict, nbytes / 1e6,
+                                                              nbytes / (a * 1e-3) / 1e12, same))
+
+
 def make(K, n, C, T, V, dev, g, scale):
     p0 = torch.randn((K, n, C, 1, V), device=dev, generator=g)
     own = torch.cumsum(0.02 * torch.randn((K, n, C, T, V), device=dev, generator=g), 3)
@@ -89,11 +139,14 @@ def main():
     ap.add_argument("--big-calls", type=int, default=200)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--log", type=str, default=None)
+    ap.add_argument("--sets", type=int, default=0, help="time kg_kin_desc_sets over this many sets against as many kg_kin_desc calls")
     args = ap.parse_args()
     if args.log:
         time_frechet._log = open(args.log, "w")
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
+    if args.sets:
+        return time_sets(args, dev, g)
     say("kg_kin_desc x 2 + kg_kin_scores against stock torch (index / diff / linalg.vector_norm / sort / cumsum, fp64); "
         "median of N calls x %d repetitions" % args.reps)
     for name, graph, K, n, C, T, V, calls in (("NTU protocol  60 x (100 + 100) x T 64, C 3, V 25", graph_ntu, 60, 100, 3, 64, 25, args.calls),

@@ -20,7 +20,10 @@ trained by tools/train_classifier.py on N samples per class - ``--eval_classifie
 ``--eval_memorisation features`` (the --eval_classifier round's features) or ``--eval_memorisation raw`` with
 ``--eval_memorisation_samples P`` (and ``--eval_memorisation_method gram`` for the matrix-core pre-filter) also scores authenticity and label agreement against the training set on the device: four
 more columns, ``--eval_select`` may name ``<live|ema>/label_agreement``; a dataset that is streamed - ``--max_resident_bytes``
-or half the free device memory is too small for it - is refused at start-up)."""
+or half the free device memory is too small for it - is refused at start-up; ``--eval_kinematics P`` also scores kinematic
+plausibility on P samples per class - the W1 distance of bone-length variation, asymmetry, speed, acceleration, jerk and
+stillness to the real samples', ``--eval_kinematics_still_eps`` the stillness threshold, DESIGN.md 26: twelve more columns,
+and ``--eval_select`` may name one, e.g. ``ema/jerk``)."""
 import argparse
 import os
 import sys
@@ -75,7 +78,8 @@ def parse_args(argv=None):
                         "with --eval_prdc also '<live|ema>/<precision|recall|density|coverage>' (larger is better); "
                         "with --eval_frechet also '<live|ema>/<pose_fd|motion_fd>' (smaller is better); "
                         "with --eval_classifier also '<live|ema>/accuracy' (larger is better) and '<live|ema>/feature_fd' "
-                        "(smaller is better)")
+                        "(smaller is better); "
+                        "with --eval_kinematics also '<live|ema>/<bone_cv|asymmetry|speed|accel|jerk|still>' (smaller is better)")
     p.add_argument("--eval_prdc", type=int, default=0,
                    help="samples per class on which an evaluation also scores precision / recall / density / coverage (0 = off)")
     p.add_argument("--eval_prdc_k", type=int, default=5, help="neighbours of --eval_prdc")
@@ -100,6 +104,11 @@ def parse_args(argv=None):
     p.add_argument("--eval_memorisation_method", type=str, default="exact", choices=["exact", "gram"],
                    help="gram: the memorisation searches through kg_nn_gram, the matrix-core pre-filter with exact re-score "
                         "(the same columns, DESIGN.md 24)")
+    p.add_argument("--eval_kinematics", type=int, default=0,
+                   help="samples per class on which an evaluation also scores kinematic plausibility: the W1 distance of six "
+                        "per-sample descriptors to the real samples' (0 = off; e.g. 100)")
+    p.add_argument("--eval_kinematics_still_eps", type=float, default=1e-3,
+                   help="a joint step shorter than this share of the sample's mean bone length counts as still")
     p.add_argument("--max_resident_bytes", type=int, default=None,
                    help="device memory the cropped dataset may take to stay resident (default: half of what is free); a larger "
                         "dataset is streamed")
@@ -168,6 +177,7 @@ def _make_loop(opt, G, D, feeder, eval_data, clf):
                      eval_diversity_pairs=opt.eval_diversity_pairs, eval_multimodality_pairs=opt.eval_multimodality_pairs,
                      eval_memorisation=opt.eval_memorisation, eval_memorisation_samples=opt.eval_memorisation_samples,
                      eval_memorisation_method=opt.eval_memorisation_method,
+                     eval_kinematics=opt.eval_kinematics, eval_kinematics_still_eps=opt.eval_kinematics_still_eps,
                      max_resident_bytes=opt.max_resident_bytes)
 
 
