@@ -524,30 +524,19 @@ EVAL_MAX_SCORES = 8
 COPY_IF_MAX_JOBS = 32
 
 
-class _EvalRecordArgs(C.Structure):
-    _fields_ = [("scores", c_f32p * EVAL_MAX_SCORES), ("nscores", C.c_int32), ("select", C.c_int32),
-                ("iter", C.c_void_p), ("count", C.c_void_p), ("ring_val", c_f32p), ("ring_iter", C.c_void_p),
-                ("ring_len", C.c_int64), ("best_val", c_f32p), ("best_iter", C.c_void_p), ("flag", C.c_void_p)]
+def _eval_record_struct(name: str, most: int, sense: bool):
+    """KgEvalRecordArgs / KgEvalRecord2Args / KgEvalRecord3Args: one field list, room for ``most`` scores, ``maximise`` last"""
+    fields = [("scores", c_f32p * most), ("nscores", C.c_int32), ("select", C.c_int32),
+              ("iter", C.c_void_p), ("count", C.c_void_p), ("ring_val", c_f32p), ("ring_iter", C.c_void_p),
+              ("ring_len", C.c_int64), ("best_val", c_f32p), ("best_iter", C.c_void_p), ("flag", C.c_void_p)]
+    return type(name, (C.Structure,), {"_fields_": fields + ([("maximise", C.c_int32)] if sense else [])})
 
 
 EVAL2_MAX_SCORES = 32
-
-
-class _EvalRecord2Args(C.Structure):
-    _fields_ = [("scores", c_f32p * EVAL2_MAX_SCORES), ("nscores", C.c_int32), ("select", C.c_int32),
-                ("iter", C.c_void_p), ("count", C.c_void_p), ("ring_val", c_f32p), ("ring_iter", C.c_void_p),
-                ("ring_len", C.c_int64), ("best_val", c_f32p), ("best_iter", C.c_void_p), ("flag", C.c_void_p),
-                ("maximise", C.c_int32)]
-
-
 EVAL3_MAX_SCORES = 64
-
-
-class _EvalRecord3Args(C.Structure):
-    _fields_ = [("scores", c_f32p * EVAL3_MAX_SCORES), ("nscores", C.c_int32), ("select", C.c_int32),
-                ("iter", C.c_void_p), ("count", C.c_void_p), ("ring_val", c_f32p), ("ring_iter", C.c_void_p),
-                ("ring_len", C.c_int64), ("best_val", c_f32p), ("best_iter", C.c_void_p), ("flag", C.c_void_p),
-                ("maximise", C.c_int32)]
+_EvalRecordArgs = _eval_record_struct("_EvalRecordArgs", EVAL_MAX_SCORES, False)
+_EvalRecord2Args = _eval_record_struct("_EvalRecord2Args", EVAL2_MAX_SCORES, True)
+_EvalRecord3Args = _eval_record_struct("_EvalRecord3Args", EVAL3_MAX_SCORES, True)
 
 
 class _CopyJob(C.Structure):
@@ -3423,9 +3412,10 @@ def trunc_lerp(x: torch.Tensor, t: torch.Tensor, truncation: float) -> torch.Ten
 
 # ---- scoring during training (kg_eval.hip; evaluate.Evaluator) --------------------------------------------------------------
 
-def _eval_record_args(struct, most: int, who: str, scores, select, iteration, count, ring_val, ring_iter, best_val, best_iter, flag):
-    """The tensor checks and the struct fill of ``eval_record`` / ``eval_record2``: an instance of ``struct`` (room for
-    ``most`` scores) with every field the two share; ``who`` is the entry point's name in the messages."""
+def _eval_record(struct, most: int, who: str, scores, select, iteration, count, ring_val, ring_iter, best_val, best_iter, flag,
+                 maximise=None):
+    """``eval_record`` / ``eval_record2`` / ``eval_record3``: the tensor checks, the fill of an instance of ``struct`` (room
+    for ``most`` scores; ``maximise``: None when it has no such field) and the launch; ``who`` is the entry point's name."""
     _need_cuda(iteration, count, ring_val, ring_iter, best_val, best_iter, flag, *scores)
     for t in scores:
         if t.dtype != torch.float32 or t.numel() != 1:
@@ -3449,7 +3439,9 @@ def _eval_record_args(struct, most: int, who: str, scores, select, iteration, co
     a.iter, a.count = _ptr(iteration), count.data_ptr()
     a.ring_val, a.ring_iter = ring_val.data_ptr(), ring_iter.data_ptr()
     a.best_val, a.best_iter, a.flag = best_val.data_ptr(), best_iter.data_ptr(), flag.data_ptr()
-    return a
+    if maximise is not None:
+        a.maximise = 1 if maximise else 0
+    _check(getattr(load_library(), who)(C.byref(a), _stream()), who)
 
 
 def eval_record(scores: Sequence[torch.Tensor], select: int, iteration: Optional[torch.Tensor], count: torch.Tensor,
@@ -3459,9 +3451,8 @@ def eval_record(scores: Sequence[torch.Tensor], select: int, iteration: Optional
     (len, nscores) fp32 and ``ring_iter`` (len, 2) int64 = [iteration, improved]; ``flag`` (int32) = scores[select] <
     best_val (strict), and then best_val / best_iter (int64) take the score and ``iteration[0]`` (int64; None: -1);
     ``count`` (int64) is advanced."""
-    a = _eval_record_args(_EvalRecordArgs, EVAL_MAX_SCORES, "kg_eval_record", scores, select, iteration, count, ring_val, ring_iter,
-                          best_val, best_iter, flag)
-    _check(load_library().kg_eval_record(C.byref(a), _stream()), "kg_eval_record")
+    _eval_record(_EvalRecordArgs, EVAL_MAX_SCORES, "kg_eval_record", scores, select, iteration, count, ring_val, ring_iter,
+                 best_val, best_iter, flag)
 
 
 def eval_record2(scores: Sequence[torch.Tensor], select: int, iteration: Optional[torch.Tensor], count: torch.Tensor,
@@ -3469,10 +3460,8 @@ def eval_record2(scores: Sequence[torch.Tensor], select: int, iteration: Optiona
                  flag: torch.Tensor, maximise: bool = False) -> None:
     """Enqueue kg_eval_record2: ``eval_record`` for up to EVAL2_MAX_SCORES scores and with a sense - ``maximise``: ``flag``
     = scores[select] > best_val (strict; the host starts best_val at -inf), else scores[select] < best_val."""
-    a = _eval_record_args(_EvalRecord2Args, EVAL2_MAX_SCORES, "kg_eval_record2", scores, select, iteration, count, ring_val,
-                          ring_iter, best_val, best_iter, flag)
-    a.maximise = 1 if maximise else 0
-    _check(load_library().kg_eval_record2(C.byref(a), _stream()), "kg_eval_record2")
+    _eval_record(_EvalRecord2Args, EVAL2_MAX_SCORES, "kg_eval_record2", scores, select, iteration, count, ring_val, ring_iter,
+                 best_val, best_iter, flag, bool(maximise))
 
 
 def eval_record3(scores: Sequence[torch.Tensor], select: int, iteration: Optional[torch.Tensor], count: torch.Tensor,
@@ -3480,10 +3469,8 @@ def eval_record3(scores: Sequence[torch.Tensor], select: int, iteration: Optiona
                  flag: torch.Tensor, maximise: bool = False) -> None:
     """Enqueue kg_eval_record3: ``eval_record2`` for up to EVAL3_MAX_SCORES scores (the same kernel template; with 32 scores or
     fewer it leaves the bits of ``eval_record2``)."""
-    a = _eval_record_args(_EvalRecord3Args, EVAL3_MAX_SCORES, "kg_eval_record3", scores, select, iteration, count, ring_val,
-                          ring_iter, best_val, best_iter, flag)
-    a.maximise = 1 if maximise else 0
-    _check(load_library().kg_eval_record3(C.byref(a), _stream()), "kg_eval_record3")
+    _eval_record(_EvalRecord3Args, EVAL3_MAX_SCORES, "kg_eval_record3", scores, select, iteration, count, ring_val, ring_iter,
+                 best_val, best_iter, flag, bool(maximise))
 
 
 def copy_if(flag: torch.Tensor, jobs: Sequence[Tuple[torch.Tensor, torch.Tensor]]) -> None:

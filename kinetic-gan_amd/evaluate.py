@@ -16,47 +16,51 @@ hipGraph on a single stream - that
   5. kg_copy_if: when it is, copies the selected generator - its flat parameters and every module buffer (BatchNorm
      running statistics and batch counters) - into a snapshot.
 
-With ``prdc_per_class > 0`` the same launch sequence also scores fidelity AND diversity: a second
-Sampler round of ``prdc_per_class`` samples per class from every generator - a round of its own, so that the MMD rounds
-and with them the MMD columns stay bit for bit what they are without it -, read in place through strides by ONE
-kg_prdc_sets call (three launches for all generators) against ``prdc_per_class`` real samples per class whose
-k-th-neighbour radii were computed once, at construction (kg_prdc_radii).  The record then holds, after the MMD scores,
-``"<g>/precision"``, ``"<g>/recall"``, ``"<g>/density"``, ``"<g>/coverage"`` per generator and goes through
-kg_eval_record2, which knows the sense of the deciding score: the four new names are better when larger.
+Five further score families add columns to the record, in this order (``FAMILIES`` is the one table that
+the names, the set-up, the launch sequence, the Sampler list, the state and its compatibility check are all driven by):
 
-With ``frechet_per_class > 0`` it also scores the Frechet pose and / or motion distance: a round of
-``frechet_per_class`` samples per class from every generator - the PRDC round itself when both options ask for the same
-count, else a round of its own -, read in place by ONE kg_frechet_sets call per mode (four launches for all generators)
-against the real side's cache, which kg_frechet_real computed once per mode at construction.  The record then ends with
-``"<g>/pose_fd"`` / ``"<g>/motion_fd"`` per generator (smaller is better) and goes through kg_eval_record2.
+  prdc          ``prdc_per_class > 0``: ``"<g>/precision"``, ``"<g>/recall"``, ``"<g>/density"``,
+                ``"<g>/coverage"`` (larger is better) - ONE kg_prdc_sets call (three launches for all generators) against the
+                real samples' k-th-neighbour radii (kg_prdc_radii);
+  frechet       ``frechet_per_class > 0``: ``"<g>/pose_fd"`` / ``"<g>/motion_fd"`` (smaller is better) - ONE
+                kg_frechet_sets call per mode (four launches for all generators) against the real side's cache
+                (kg_frechet_real);
+  classifier    ``classifier`` and ``classifier_per_class > 0``, the Action2Motion / ACTOR protocol in the
+                feature space of a trained ``classifier.Classifier``: the round goes through its trunk and head in chunks of
+                ``classifier_batch`` (plane slices read in place, features and predictions written into static matrices),
+                then ONE kg_frechet_sets call against the real features' cache and ONE kg_cls_scores call for all
+                generators: ``"<g>/accuracy"`` (larger is better), ``"<g>/feature_fd"`` (smaller is better),
+                ``"<g>/diversity"`` and ``"<g>/multimodality"`` (closer to the real set's value - ``classifier_real`` - is
+                better: recorded, never selected by);
+  memorisation  ``memorisation`` (``"features"`` or ``"raw"``), whether the generators replay the training set
+                ``memorisation_train``: every generator's query set - the classifier round's feature matrices in feature
+                space, a round of ``memorisation_per_class`` samples per class in raw space - goes through ONE kg_nn_sets
+                call (k = 1, two launches for all generators) against the training set and ONE kg_nn_scores launch:
+                ``"<g>/authenticity"`` (the share of samples that lie no closer to their nearest training sample than that
+                sample lies to another training sample: noise scores 1, a copier 0, the value to be near is
+                ``memorisation_real["authenticity"]`` - recorded, never selected by) and ``"<g>/label_agreement"`` (the
+                share whose nearest training sample carries the conditioning label; larger is better);
+  kinematics    ``kinematics_per_class > 0``, whether the samples are bodies at all: ONE kg_kin_desc_sets
+                launch over all generators' rounds and ONE kg_kin_scores call (two launches) measure, per descriptor, the
+                class-averaged Wasserstein-1 distance to the real samples' descriptors (``kinematics_real`` holds their
+                means): ``"<g>/bone_cv"``, ``"<g>/asymmetry"``, ``"<g>/speed"``, ``"<g>/accel"``, ``"<g>/jerk"``,
+                ``"<g>/still"`` (all smaller is better; a generator that emits non-finite values records NaN, which never
+                wins).
 
-With ``classifier`` and ``classifier_per_class > 0`` it also scores the Action2Motion / ACTOR protocol in
-the feature space of a trained ``classifier.Classifier``: a round of ``classifier_per_class`` samples per class from every
-generator - the PRDC or Frechet round when one has the same count, else a round of its own - goes through the
-classifier's trunk and head in chunks of ``classifier_batch`` (plane slices read in place, features and predictions
-written into static matrices), then ONE kg_frechet_sets call against the real features' cache and ONE kg_cls_scores call
-for all generators.  The record then ends with ``"<g>/accuracy"`` (larger is better), ``"<g>/feature_fd"`` (smaller is
-better), ``"<g>/diversity"`` and ``"<g>/multimodality"`` (closer to the real set's value - ``classifier_real`` - is
-better: recorded, never selected by) per generator.
+The rounds.  A family scores a Sampler round of its own count of samples per class from every generator, read in place
+through strides - never the MMD round, so that the MMD columns stay bit for bit what they are without it.  The sharing rule
+(``round_owners``): a family reads the round of the FIRST family, in the order above, that draws the same number of samples
+per class; only that family - the round's owner - has Samplers, and its round runs inside its own scores, before any reader's.
+Memorisation in feature space draws no round at all: it reads the classifier's feature matrices.
 
-With ``memorisation`` (``"features"`` or ``"raw"``) it also scores whether the generators replay the training
-set ``memorisation_train``: every generator's round - the classifier round's feature matrices in feature space, a round of
-``memorisation_per_class`` samples per class in raw space (a PRDC, Frechet or classifier round of that count when one
-exists) - is a query set of ONE kg_nn_sets call (k = 1, two launches for all generators) against the training set, whose
-features (feature space), leave-one-out distances and labels were computed once, at construction; ONE kg_nn_scores launch
-then writes the score words.  The record ends with ``"<g>/authenticity"`` (the share of samples that lie no closer to their
-nearest training sample than that sample lies to another training sample: noise scores 1, a copier 0, the value to be near
-is ``memorisation_real["authenticity"]`` - recorded, never selected by) and ``"<g>/label_agreement"`` (the share whose
-nearest training sample carries the conditioning label; larger is better) per generator.
+The real side.  A family is held against that many real samples per class, class by class on the device: selected and
+uploaded once per count (families of equal count alias one tensor; nothing writes to it), and everything a family derives
+from them - radii, Frechet caches, real features, leave-one-out distances, descriptors, the real side's own scores - is
+computed once, at construction, from the data.  It is deterministic, so none of it is part of the state.
 
-With ``kinematics_per_class > 0`` it also scores kinematic plausibility - whether the samples are bodies at
-all: every generator's round of ``kinematics_per_class`` samples per class (a PRDC, Frechet, classifier or raw-memorisation
-round of that count when one exists) is a set of ONE kg_kin_desc_sets launch, read in place through the rounds' shared
-strides, and ONE kg_kin_scores call (two launches) then measures, per descriptor, the class-averaged Wasserstein-1 distance
-to the real samples' descriptors, which were computed once, at construction (``kinematics_real`` holds their means).  The
-record then ends with ``"<g>/bone_cv"``, ``"<g>/asymmetry"``, ``"<g>/speed"``, ``"<g>/accel"``, ``"<g>/jerk"`` and
-``"<g>/still"`` per generator (all smaller is better; a generator that emits non-finite values records NaN, which never
-wins) and goes through kg_eval_record3, which has room for 64 scores.
+The record goes through the narrowest entry point that the families which are on allow: kg_eval_record (8 scores, smaller is
+better), kg_eval_record2 (32 scores and a sense: precision .. coverage, accuracy and label_agreement are better when larger)
+or, with the kinematic columns, kg_eval_record3 (64 scores).
 
 Nothing synchronises the host; everything is read through pointers when the launches run, so the captured evaluation
 follows the training replays in between.  ``records()``, ``best()`` and ``state_dict()`` read the device; the Evaluator
@@ -66,7 +70,7 @@ from __future__ import annotations
 
 import csv
 import warnings
-from typing import Dict, Optional, Sequence
+from typing import Callable, Dict, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -120,16 +124,10 @@ def score_names(generators: Sequence[str], modes: Sequence[str], prdc: bool = Fa
     with ``classifier`` - ``"<g>/<name>"`` generator by generator in the order of ``metrics.CLS_NAMES``, then - with
     ``memorisation`` - ``"<g>/<name>"`` generator by generator in the order of ``metrics.MEMORISATION_NAMES``, then - with
     ``kinematics`` - ``"<g>/<name>"`` generator by generator in the order of ``metrics.KIN_NAMES``"""
+    on = dict(prdc=prdc, frechet=frechet, classifier=classifier, memorisation=memorisation, kinematics=kinematics)
     names = ["%s/%s" % (g, m) for g in generators for m in modes]
-    if prdc:
-        names += ["%s/%s" % (g, q) for g in generators for q in metrics.PRDC_NAMES]
-    names += ["%s/%s_fd" % (g, f) for g in generators for f in frechet]
-    if classifier:
-        names += ["%s/%s" % (g, q) for g in generators for q in metrics.CLS_NAMES]
-    if memorisation:
-        names += ["%s/%s" % (g, q) for g in generators for q in metrics.MEMORISATION_NAMES]
-    if kinematics:
-        names += ["%s/%s" % (g, q) for g in generators for q in metrics.KIN_NAMES]
+    for f in FAMILIES:
+        names += ["%s/%s" % (g, q) for g in generators for q in f.columns(on[f.key])]
     return names
 
 
@@ -175,6 +173,65 @@ def _kinematics_state(ev) -> dict:
             "mirror": [[int(v) for v in p] for p in ev.kinematics_mirror]}
 
 
+class Family(NamedTuple):
+    """One score family of the record.  The functions take the Evaluator - or an Evaluator-like object of before the family
+    existed (``check_compatible``), which lacks its attributes: there the family is off."""
+    key: str              # its key in the state and in ``round_owners``; its methods are _<key>_setup and _<key>_scores
+    on: Callable          # (ev) -> what ``score_names`` takes for it: falsy when the family is off
+    columns: Callable     # (that value) -> its column names per generator
+    state: Callable       # (ev) -> what it contributes to the state: the options its columns depend on
+    count: Callable       # (ev) -> the samples per class of the round it draws (0: none)
+    samplers: str         # the attribute that holds its Samplers ({} unless it owns its round)
+    off: Callable         # () -> the public attributes it has when it is off
+    record: int           # the narrowest of RECORDS that takes its columns
+
+
+RECORDS = (("eval_record", "EVAL_MAX_SCORES"), ("eval_record2", "EVAL2_MAX_SCORES"), ("eval_record3", "EVAL3_MAX_SCORES"))
+FAMILIES = (
+    Family("prdc", lambda ev: ev.prdc_per_class, lambda on: metrics.PRDC_NAMES if on else (),
+           lambda ev: {"per_class": ev.prdc_per_class, "k": ev.prdc_k},
+           lambda ev: ev.prdc_per_class, "prdc_samplers", lambda: dict(prdc_real=None, prdc_radii=None), 1),
+    Family("frechet", lambda ev: ev.frechet_modes if ev.frechet_per_class else (), lambda modes: ["%s_fd" % f for f in modes],
+           lambda ev: {"per_class": ev.frechet_per_class, "modes": list(ev.frechet_modes)},
+           lambda ev: ev.frechet_per_class, "frechet_samplers", lambda: dict(frechet_real=None, frechet_cache={}), 1),
+    Family("classifier", lambda ev: getattr(ev, "classifier_per_class", 0), lambda on: metrics.CLS_NAMES if on else (),
+           lambda ev: {"per_class": ev.classifier_per_class, "diversity_pairs": ev.diversity_pairs,
+                       "multimodality_pairs": ev.multimodality_pairs},
+           lambda ev: ev.classifier_per_class, "cls_samplers", lambda: dict(classifier_real=None), 1),
+    Family("memorisation", lambda ev: getattr(ev, "memorisation", None), lambda on: metrics.MEMORISATION_NAMES if on else (),
+           lambda ev: {"mode": ev.memorisation, "per_class": ev.memorisation_per_class},
+           lambda ev: ev.memorisation_per_class if ev.memorisation == "raw" else 0,      # (feature space: the classifier's matrices)
+           "mem_samplers", lambda: dict(memorisation_real=None), 1),
+    Family("kinematics", lambda ev: getattr(ev, "kinematics_per_class", 0), lambda on: metrics.KIN_NAMES if on else (),
+           _kinematics_state, lambda ev: ev.kinematics_per_class, "kin_samplers", lambda: dict(kinematics_real=None), 2),
+)
+
+
+def round_owners(counts) -> dict:
+    """The sharing rule.  ``counts``: {family: samples per class of its round; 0: it draws none}, in the record's order.
+    Returns {family: the family whose round it reads, or None: it owns its Samplers (or draws no round)} - the owner is the
+    first family in the order with the same non-zero count, so an owner is never itself a reader."""
+    first, owners = {}, {}
+    for key, n in counts.items():
+        owner = first.setdefault(int(n), key) if n else key
+        owners[key] = None if owner == key else owner
+    return owners
+
+
+def plain_state(v):
+    """A state value as ``check_compatible`` compares it, whether it comes from ``state_dict()`` or back from a file: numpy and
+    Python integers as int, floats as float, tuples, lists and arrays as lists, dicts as dicts; str (and None) as they are"""
+    if isinstance(v, dict):
+        return {k: plain_state(x) for k, x in v.items()}
+    if isinstance(v, (tuple, list, np.ndarray)):
+        return [plain_state(x) for x in v]
+    if isinstance(v, (bool, np.bool_, int, np.integer)):
+        return int(v)
+    if isinstance(v, (float, np.floating)):
+        return float(v)
+    return v
+
+
 class Evaluator:
     """``generators``: {name: Generator} (one or more); the real side: a ``Feeder`` (``metrics.select_reference_samples``
     with ``per_class=pairs``, cropped to the generator's ``t_size``), or ``real`` (N, C, T, V) with class ids
@@ -192,19 +249,19 @@ class Evaluator:
     ``memorisation`` (None: off; ``"features"``: in the classifier's feature space, which needs ``classifier`` and
     ``classifier_per_class`` and scores that round; ``"raw"``: on ``memorisation_per_class`` samples per class): also score
     authenticity and label agreement against the training set ``memorisation_train`` - a ``train.ResidentDataset`` (raw space
-    searches it in place through its (scale, shift)) or (N, C, T, V) samples with ``memorisation_train_labels`` -, whose
-    leave-one-out distances (and features) are computed once here.  ``memorisation_real`` holds the two scores of the selected
+    searches it in place through its (scale, shift)) or (N, C, T, V) samples with ``memorisation_train_labels``.  ``memorisation_real`` holds the two scores of the selected
     real samples as queries: what a perfect generator scores - but only when ``real`` is held out from the training set
     (real samples that ARE training samples lie at distance 0 from themselves and score authenticity 0).  The Evaluator never
     writes to the training set.  ``memorisation_method`` (``"exact"``, ``"gram"``): with ``"gram"`` every search - the one-off
     leave-one-out pass included - runs through kg_nn_gram, the matrix-core pre-filter with exact re-score: the
-    same bits in every column; the training side's norms are computed once here, the six launches are part of the captured
-    evaluation, and ``memorisation_stats`` holds the (sets, 1, 2) certified / fallback row counts of the last call.
+    same bits in every column; the six launches are part of the captured evaluation, and ``memorisation_stats`` holds the (sets, 1, 2) certified / fallback row counts of the last call.
     ``kinematics_per_class`` (0: off): also score the six kinematic W1 distances of ``metrics.kinematics`` on that many fake
     and real samples per class, on the skeleton of ``kinematics_dataset`` (``"ntu"`` or ``"h36m"``) or the caller's
     ``kinematics_bones`` (B, 2) joint pairs and ``kinematics_mirror`` (M, 2) pairs of bone indices; ``kinematics_still_eps``
     is the threshold of the ``still`` descriptor.  ``kinematics_real`` then holds the real side's descriptor means (by
-    ``metrics.KIN_NAMES``), ``"class_means"`` (K, 6) and its ``"degenerate"`` / ``"nonfinite"`` sample counts."""
+    ``metrics.KIN_NAMES``), ``"class_means"`` (K, 6) and its ``"degenerate"`` / ``"nonfinite"`` sample counts.
+    Which family draws a round and which reads another's (``round_owner``; the ``*_samplers`` of a reader are empty), and that
+    the real side is derived once here and is no part of the state: the module docstring, stated there once."""
 
     def __init__(self, generators: Dict[str, torch.nn.Module], real, real_labels=None, pairs: int = 10,
                  modes: Sequence[str] = ("avg", "joint"), select: Optional[str] = None, seed: int = 0,
@@ -233,11 +290,10 @@ class Evaluator:
         if not self.modes:
             raise ValueError("Evaluator: at least one mode")
         self.gens = dict(generators)
-        self.names = score_names(list(self.gens), self.modes, bool(self.prdc_per_class), self.frechet_modes,
-                                 bool(self.classifier_per_class), bool(self.memorisation), kinematics=bool(self.kinematics_per_class))
-        self._record2 = bool(self.prdc_per_class or self.frechet_per_class or self.classifier_per_class or self.memorisation)
-        self._record3 = bool(self.kinematics_per_class)
-        most = nv.EVAL3_MAX_SCORES if self._record3 else (nv.EVAL2_MAX_SCORES if self._record2 else nv.EVAL_MAX_SCORES)
+        self.names = score_names(list(self.gens), self.modes, **{f.key: f.on(self) for f in FAMILIES})
+        # (the entry point by its name: looked up in _native at every call)
+        self._record, most = RECORDS[max([f.record for f in FAMILIES if f.on(self)], default=0)]
+        most = getattr(nv, most)
         if len(self.names) > most:
             raise ValueError("Evaluator: %d scores, at most %d fit one record" % (len(self.names), most))
         self.select = default_select(list(self.gens), self.modes) if select is None else str(select)
@@ -261,26 +317,30 @@ class Evaluator:
         if any(s.n_classes != self.n_classes for s in self.samplers.values()):
             raise ValueError("Evaluator: the generators differ in their number of classes")
         t_size = int(t_size) if t_size is not None else int(first.t_size)
-        if self.prdc_per_class:
-            self._prdc_setup(real, real_labels, t_size, trunc, trunc_mode)
-        else:
-            self.prdc_samplers, self.prdc_real, self.prdc_radii = {}, None, None
-        if self.frechet_per_class:
-            self._frechet_setup(real, real_labels, t_size, trunc, trunc_mode)
-        else:
-            self.frechet_samplers, self.frechet_real, self.frechet_cache = {}, None, {}
-        if self.classifier_per_class:
-            self._classifier_setup(real, real_labels, t_size, trunc, trunc_mode)
-        else:
-            self.cls_samplers, self.classifier_real = {}, None
-        if self.memorisation:
-            self._memorisation_setup(real, real_labels, t_size, trunc, trunc_mode, memorisation_train, memorisation_train_labels)
-        else:
-            self.mem_samplers, self.memorisation_real = {}, None
-        if self.kinematics_per_class:
-            self._kinematics_setup(real, real_labels, t_size, trunc, trunc_mode)
-        else:
-            self.kin_samplers, self.kinematics_real = {}, None
+        # the round pool: Samplers for the owners of a round only (round_owners); the MMD Samplers above stay outside it
+        counts = {f.key: f.count(self) for f in FAMILIES}
+        self.round_owner = round_owners(counts)
+        self._pool = {}
+        for f in FAMILIES:
+            owns = counts[f.key] and self.round_owner[f.key] is None
+            self._pool[f.key] = {k: Sampler(G, qtd=counts[f.key], seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False)
+                                 for k, G in self.gens.items()} if owns else {}
+            setattr(self, f.samplers, self._pool[f.key])
+        # the families' real side, once per count: (K*P, C, t, V) class by class on the device; nothing writes to it
+        self._real_sides = {}
+
+        def real_side(per_class):                # (called by the set-ups, after the checks that need no samples)
+            if per_class not in self._real_sides:
+                self._real_sides[per_class] = torch.as_tensor(self._select_real(real, real_labels, per_class, "classes", t_size)).to(dev)
+            return self._real_sides[per_class]
+
+        extra = {"memorisation": (memorisation_train, memorisation_train_labels)}
+        for f in FAMILIES:
+            if f.on(self):
+                getattr(self, "_%s_setup" % f.key)(real_side, *extra.get(f.key, ()))
+            else:
+                for k, v in f.off().items():
+                    setattr(self, k, v)
         # the real side, once: row j*K + c = the j-th selected real sample of class c (the Sampler's label order)
         self.real = torch.as_tensor(self._select_real(real, real_labels, self.pairs, "pairs", t_size)).to(dev)
         self._pair_labels = np.arange(self.n)                  # every (fake, real) pair is a "class" of the kg_mmd call
@@ -401,15 +461,18 @@ class Evaluator:
         rows = (pair_rows if order == "pairs" else class_rows)(lab, K, per_class)
         return np.ascontiguousarray(np.asarray(data, dtype=np.float32)[rows])
 
-    def _checked_rounds(self, samplers_or_outs, real_shape):
-        """One round of every Sampler given (a tensor given instead is a round that has been run already: the PRDC round the
-        Frechet scores share), each (P*K, C, T, V) with row j*K + c = sample j of class c and read in place - so it has to
-        have the real side's sample shape, be a plane, and all of them the same strides.  Returns (outs, sn, sc)."""
+    def _rounds(self, key):
+        """This evaluation's round of every generator for the family ``key``: run here when the family owns it, else the one
+        its owner ran earlier in this evaluation (``round_owners``).  Each is (P*K, C, T, V) with row j*K + c = sample j of
+        class c and read in place - so it has to have the real side's sample shape, be a plane, and all of them the same
+        strides.  Returns (outs, sn, sc)."""
+        owner = self.round_owner[key]
+        real_shape = self._real_sides[getattr(self, key + "_per_class")].shape
         outs = []
-        for out in samplers_or_outs:
-            if not torch.is_tensor(out):
-                out._round()
-                out = out._out
+        for s in self._pool[owner or key].values():
+            if owner is None:
+                s._round()
+            out = s._out
             if tuple(out.shape[1:]) != tuple(real_shape[1:]) or not nv.is_plane(out):
                 raise ValueError("Evaluator: generated samples %s against real samples %s" % (
                     tuple(out.shape[1:]), tuple(real_shape[1:])))
@@ -420,16 +483,12 @@ class Evaluator:
         return outs, sn, sc
 
     # ---- precision / recall / density / coverage -----------------------------------------------------------
-    def _prdc_setup(self, real, real_labels, t_size, trunc, trunc_mode):
-        """the real side, once: ``prdc_per_class`` samples of every class, class by class on the device, and their radii
-        (one kg_prdc_radii launch; deterministic, so not part of the state); per generator a second Sampler whose round
-        kg_prdc_sets reads in place"""
+    def _prdc_setup(self, real_side):
+        """the real samples' radii (one kg_prdc_radii launch) and the workspace"""
         dev, K, P = self.device, self.n_classes, self.prdc_per_class
-        self.prdc_real = torch.as_tensor(self._select_real(real, real_labels, P, "classes", t_size)).to(dev)    # (K*P, C, t, V)
+        self.prdc_real = real_side(P)
         self._prdc_D = int(np.prod(self.prdc_real.shape[1:]))
         self._prdc_rv = nv.PrdcView(self.prdc_real, P * self._prdc_D, self._prdc_D, 0)
-        self.prdc_samplers = {k: Sampler(G, qtd=P, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False)
-                              for k, G in self.gens.items()}
         with torch.cuda.device(dev):
             self.prdc_radii = nv.prdc_radii(self._prdc_rv, P, 1, self._prdc_D, K, self.prdc_k)
             sets = min(len(self.gens), nv.PRDC_MAX_SETS)
@@ -440,33 +499,27 @@ class Evaluator:
         """the PRDC rounds of all generators, then ONE kg_prdc_sets per PRDC_MAX_SETS generators: the (nsets, 4) class means,
         whose elements are the scores"""
         K, P = self.n_classes, self.prdc_per_class
-        outs, sn, sc = self._checked_rounds(self.prdc_samplers.values(), self.prdc_real.shape)
+        outs, sn, sc = self._rounds("prdc")
         _, C, T, V = outs[0].shape
         d_outer, d_inner, so = (1, C * T * V, 0) if C == 1 else (C, T * V, sc)
         rv = self._prdc_rv if d_outer == 1 else self._prdc_rv._replace(so=T * V)
         scores = []
-        for q in range(0, len(outs), nv.PRDC_MAX_SETS):
-            part = outs[q:q + nv.PRDC_MAX_SETS]
+        for part in nv._chunks(outs, nv.PRDC_MAX_SETS):
             res = nv.prdc_sets(rv, part, sn, K * sn, so, self.prdc_radii, P, P, d_outer, d_inner, K, self.prdc_k,
                                want_mean=True, ws=self._prdc_ws)
             scores += [res["mean"][g, i:i + 1] for g in range(len(part)) for i in range(4)]
         return scores
 
     # ---- Frechet pose / motion distance (DESIGN.md 19) --------------------------------------------------------------------
-    def _frechet_setup(self, real, real_labels, t_size, trunc, trunc_mode):
-        """the real side, once: ``frechet_per_class`` samples of every class, class by class on the device, and per mode
-        their cache (one kg_frechet_real call; deterministic, so not part of the state); per generator a Sampler of its
-        own whose round kg_frechet_sets reads in place - unless the PRDC round has the same count and is read instead"""
+    def _frechet_setup(self, real_side):
+        """the checks; per mode the real side's cache (one kg_frechet_real call) and the workspace"""
         dev, K, P = self.device, self.n_classes, self.frechet_per_class
-        self.frechet_real = torch.as_tensor(self._select_real(real, real_labels, P, "classes", t_size)).to(dev)  # (K*P, C, t, V)
+        self.frechet_real = real_side(P)
         _, C, T, V = self.frechet_real.shape
         if C * V > nv.FRECHET_MAX_DIM:
             raise ValueError("Evaluator: frechet needs d = C*V = %d <= %d" % (C * V, nv.FRECHET_MAX_DIM))
         if "motion" in self.frechet_modes and T < 2:
             raise ValueError("Evaluator: frechet mode 'motion' needs two frames, the samples have %d" % T)
-        self._frechet_shared = self.prdc_per_class == P
-        self.frechet_samplers = {} if self._frechet_shared else {
-            k: Sampler(G, qtd=P, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False) for k, G in self.gens.items()}
         D = C * T * V
         rv = nv.FrechetView(self.frechet_real, P * D, D, V, T * V if C > 1 else 0)
         with torch.cuda.device(dev):
@@ -476,19 +529,16 @@ class Evaluator:
             self._frechet_ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
 
     def _frechet_scores(self):
-        """the Frechet rounds of all generators (the PRDC rounds when they are shared), then per mode ONE kg_frechet_sets per
-        FRECHET_MAX_SETS generators: the mean32 words, which are the scores - generator by generator, mode by mode"""
+        """the Frechet rounds of all generators, then per mode ONE kg_frechet_sets per FRECHET_MAX_SETS generators: the mean32
+        words, which are the scores - generator by generator, mode by mode"""
         K, P = self.n_classes, self.frechet_per_class
-        # (shared: this evaluation's PRDC rounds, no third round)
-        rounds = [s._out for s in self.prdc_samplers.values()] if self._frechet_shared else self.frechet_samplers.values()
-        outs, sn, sc = self._checked_rounds(rounds, self.frechet_real.shape)
+        outs, sn, sc = self._rounds("frechet")
         _, C, T, V = outs[0].shape
         so = sc if C > 1 else 0
         per_mode = {}
         for f in self.frechet_modes:
             words = []
-            for q in range(0, len(outs), nv.FRECHET_MAX_SETS):
-                part = outs[q:q + nv.FRECHET_MAX_SETS]
+            for part in nv._chunks(outs, nv.FRECHET_MAX_SETS):
                 res = nv.frechet_sets(self.frechet_cache[f], part, sn, K * sn, V, so, P, T, f == "motion", C, V, K,
                                       ws=self._frechet_ws)
                 words += [res["mean32"][g:g + 1] for g in range(len(part))]
@@ -506,12 +556,10 @@ class Evaluator:
                 hi = min(x.shape[0], lo + self.classifier_batch)
                 nv.cls_head_fwd(clf._trunk(x[lo:hi]), *w, None, feat_out=feat[lo:hi], pred_out=pred[lo:hi])
 
-    def _classifier_setup(self, real, real_labels, t_size, trunc, trunc_mode):
-        """the checks; the real side, once: ``classifier_per_class`` samples of every class, class by class, their features
-        as ONE set through kg_frechet_real (the unconditional feature FD of ``metrics.classifier_scores``) and their own
-        accuracy / diversity / multimodality (``classifier_real``; deterministic, so not part of the state); the generators'
-        pair tables from the Sampler's label vector; per generator a Sampler - unless a PRDC or Frechet round of the same
-        count exists and is read instead - and static feature / prediction buffers"""
+    def _classifier_setup(self, real_side):
+        """the checks; the real samples' features as ONE set through kg_frechet_real (the unconditional feature FD of
+        ``metrics.classifier_scores``) and their own accuracy / diversity / multimodality (``classifier_real``); the
+        generators' pair tables from the Sampler's label vector and static feature / prediction buffers"""
         clf, dev, K, P = self.classifier, self.device, self.n_classes, self.classifier_per_class
         F = int(clf.feat_dim)
         if int(clf.n_classes) != K:
@@ -523,21 +571,12 @@ class Evaluator:
         if self.diversity_pairs > K * P or self.multimodality_pairs > P:
             raise ValueError("Evaluator: diversity_pairs=%d above K*P=%d or multimodality_pairs=%d above P=%d" % (
                 self.diversity_pairs, K * P, self.multimodality_pairs, P))
-        real_x = torch.as_tensor(self._select_real(real, real_labels, P, "classes", t_size)).to(dev)       # (K*P, C, t, V)
+        real_x = real_side(P)
         _, C, T, V = real_x.shape
         c_in = int(clf.st_gcn_networks[0].in_channels)
         if c_in != C or int(clf.t_size) != T:
             raise ValueError("Evaluator: the classifier takes (%d channels, %d frames), the samples have (%d, %d)" % (
                 c_in, int(clf.t_size), C, T))
-        self._cls_shape = tuple(real_x.shape)
-        if self.prdc_per_class == P:
-            self._cls_shared, self.cls_samplers = "prdc", {}
-        elif self.frechet_per_class == P:        # (not shared with PRDC, else the branch above: Samplers of its own)
-            self._cls_shared, self.cls_samplers = "frechet", {}
-        else:
-            self._cls_shared = None
-            self.cls_samplers = {k: Sampler(G, qtd=P, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False)
-                                 for k, G in self.gens.items()}
         n = K * P
         lab_gen = np.tile(np.arange(K), P)               # the Sampler's label vector: row j*K + c has class c
         lab_real = np.repeat(np.arange(K), P)
@@ -562,26 +601,19 @@ class Evaluator:
                                        device=dev)
 
     def _classifier_scores(self):
-        """the classifier rounds of all generators (a PRDC / Frechet round of the same count when one exists), their features;
-        then per group of generators ONE kg_frechet_sets and ONE kg_cls_scores: the score words are one-element views of
-        mean32 and scores - per generator in the order of metrics.CLS_NAMES"""
+        """the classifier rounds of all generators, their features; then per group of generators ONE kg_frechet_sets and ONE
+        kg_cls_scores: the score words are one-element views of mean32 and scores - per generator in the order of
+        metrics.CLS_NAMES"""
         K, P = self.n_classes, self.classifier_per_class
         n, F = K * P, int(self.classifier.feat_dim)
-        if self._cls_shared == "prdc":
-            rounds = [s._out for s in self.prdc_samplers.values()]
-        elif self._cls_shared == "frechet":
-            rounds = [s._out for s in self.frechet_samplers.values()]
-        else:
-            rounds = self.cls_samplers.values()
-        outs, _, _ = self._checked_rounds(rounds, self._cls_shape)
+        outs, _, _ = self._rounds("classifier")
         keys = list(self.gens)
         for k, out in zip(keys, outs):
             self._classifier_features(out, self._cls_feat[k], self._cls_pred[k])
-        most = min(nv.FRECHET_MAX_SETS, nv.CLS_MAX_SETS)
         words = []
-        for q in range(0, len(keys), most):
-            feats = [self._cls_feat[k] for k in keys[q:q + most]]
-            preds = [self._cls_pred[k] for k in keys[q:q + most]]
+        for part in nv._chunks(keys, min(nv.FRECHET_MAX_SETS, nv.CLS_MAX_SETS)):
+            feats = [self._cls_feat[k] for k in part]
+            preds = [self._cls_pred[k] for k in part]
             fd = nv.frechet_sets(self._cls_cache, feats, 0, F, 0, 0, n, 1, False, 1, F, 1, ws=self._cls_ws)
             sc = nv.cls_scores(feats, preds, self._cls_labels, *self._cls_tables, K)
             for g in range(len(feats)):
@@ -589,12 +621,11 @@ class Evaluator:
         return words
 
     # ---- authenticity / label agreement against the training set -------------------------------------------
-    def _memorisation_setup(self, real, real_labels, t_size, trunc, trunc_mode, train, train_labels):
-        """the checks; the training side, once: its int32 labels, in feature space its features (through the classifier in
-        chunks of ``classifier_batch``, a ResidentDataset normalised chunk by chunk with the arithmetic of its gather), the
-        train -> train leave-one-out distances (one kg_nn with exclude_self) and the real side's own two scores
-        (``memorisation_real``) - all deterministic, so not part of the state; the workspace; in raw space per generator a
-        Sampler, unless a PRDC, Frechet or classifier round of the same count exists and is read instead"""
+    def _memorisation_setup(self, real_side, train, train_labels):
+        """the checks; the training side: its int32 labels, in feature space its features (through the classifier in chunks of
+        ``classifier_batch``, a ResidentDataset normalised chunk by chunk with the arithmetic of its gather), the train -> train
+        leave-one-out distances (one kg_nn with exclude_self) and the real side's own two scores (``memorisation_real``); the
+        workspace"""
         who = "Evaluator"
         dev, K, P = self.device, self.n_classes, self.memorisation_per_class
         t, ta, own = metrics._nn_side(train, who, "memorisation_train")
@@ -612,7 +643,7 @@ class Evaluator:
         if K > nv.NN_SCORES_MAX_CLASSES:
             raise ValueError("Evaluator: %d classes, kg_nn_scores takes at most %d" % (K, nv.NN_SCORES_MAX_CLASSES))
         lab_t = metrics._label_ids(train_labels, N, "memorisation_train_labels", who)[0]
-        real_x = torch.as_tensor(self._select_real(real, real_labels, P, "classes", t_size)).to(dev)       # (K*P, C, t, V)
+        real_x = real_side(P)
         if tuple(t.shape[1:]) != tuple(real_x.shape[1:]):
             raise ValueError("Evaluator: the training samples are (channels, frames, joints) = %s, the generators' %s" % (
                 tuple(t.shape[1:]), tuple(real_x.shape[1:])))
@@ -621,11 +652,10 @@ class Evaluator:
         t = t.contiguous()                      # (a ResidentDataset's array is: nothing is copied)
         _, C, T, V = real_x.shape
         n = K * P
-        self._mem_shape, self._mem_train, self._mem_N = tuple(real_x.shape), t, N
+        self._mem_train, self._mem_N = t, N
         lab_real = np.repeat(np.arange(K), P)
         self._mem_qlab = torch.as_tensor(np.tile(np.arange(K), P).astype(np.int32)).to(dev)    # the Sampler's label vector
         self._mem_blab = torch.as_tensor(lab_t.astype(np.int32)).to(dev)
-        self.mem_samplers, self._mem_shared = {}, None
         with torch.cuda.device(dev):
             if self.memorisation == "features":
                 F = int(self.classifier.feat_dim)
@@ -642,15 +672,6 @@ class Evaluator:
                 real_q, train_q = self.classifier_real["features"], feat
             else:
                 D = C * T * V
-                for kind, per, group in (("prdc", self.prdc_per_class, self.prdc_samplers),
-                                         ("frechet", self.frechet_per_class, self.frechet_samplers),
-                                         ("classifier", self.classifier_per_class, self.cls_samplers)):
-                    if per == P and group:      # (a round that is itself shared has no Samplers: its owner came first)
-                        self._mem_shared = kind
-                        break
-                else:
-                    self.mem_samplers = {k: Sampler(G, qtd=P, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False)
-                                         for k, G in self.gens.items()}
                 self._mem_dims = (1, D) if C == 1 else (C, T * V)
                 self._mem_q = None              # (the rounds' strides, read when they exist)
                 self._mem_bv, self._mem_ba = nv.PrdcView(t, 0, D, 0 if C == 1 else T * V), ta
@@ -675,22 +696,18 @@ class Evaluator:
             self._mem_ws = torch.empty(max(1, nbytes // 4), dtype=torch.int32, device=dev)
 
     def _memorisation_scores(self):
-        """the query sets of all generators - the classifier round's feature matrices, or the raw rounds (a PRDC, Frechet or
-        classifier round of the same count when one exists) read in place -, then per group of generators ONE kg_nn_sets
-        (k = 1) and ONE kg_nn_scores: the score words are one-element views of scores, per generator in the order of
-        metrics.MEMORISATION_NAMES"""
+        """the query sets of all generators - the classifier round's feature matrices, or the raw rounds read in place -, then
+        per group of generators ONE kg_nn_sets (k = 1) and ONE kg_nn_scores: the score words are one-element views of scores,
+        per generator in the order of metrics.MEMORISATION_NAMES"""
         K, P, N = self.n_classes, self.memorisation_per_class, self._mem_N
         d_outer, d_inner = self._mem_dims
         if self.memorisation == "features":
             qs, (q_sc, q_sp, q_so) = [self._cls_feat[k] for k in self.gens], self._mem_q
         else:
-            shared = {"prdc": self.prdc_samplers, "frechet": self.frechet_samplers, "classifier": self.cls_samplers}
-            rounds = [s._out for s in shared[self._mem_shared].values()] if self._mem_shared else self.mem_samplers.values()
-            qs, sn, sc = self._checked_rounds(rounds, self._mem_shape)
+            qs, sn, sc = self._rounds("memorisation")
             q_sc, q_sp, q_so = 0, sn, (0 if d_outer == 1 else sc)
         words = []
-        for q in range(0, len(qs), nv.NN_MAX_SETS):
-            part = qs[q:q + nv.NN_MAX_SETS]
+        for part in nv._chunks(qs, nv.NN_MAX_SETS):
             if self._mem_gram:
                 idx, d2, self.memorisation_stats = nv.nn_gram(part, q_sc, q_sp, q_so, self._mem_bv, K * P, N, d_outer, d_inner, 1,
                                                               1, b_affine=self._mem_ba, base_norms=self._mem_norms,
@@ -704,32 +721,17 @@ class Evaluator:
         return words
 
     # ---- kinematic plausibility: W1 of six descriptors against the real set --------------------------------
-    def _kinematics_setup(self, real, real_labels, t_size, trunc, trunc_mode):
-        """the checks (``metrics._kin_check``); the real side, once: ``kinematics_per_class`` samples of every class, class by
-        class, and their descriptors (one kg_kin_desc launch; deterministic, so not part of the state) with their own means
-        and counts (``kinematics_real``); the static descriptor matrices and the workspace; per generator a Sampler, unless
-        a PRDC, Frechet, classifier or raw-memorisation round of the same count exists and is read instead"""
+    def _kinematics_setup(self, real_side):
+        """the checks (``metrics._kin_check``); the real samples' descriptors (one kg_kin_desc launch) with their own means and
+        counts (``kinematics_real``); the static descriptor matrices and the workspace"""
         dev, K, P = self.device, self.n_classes, self.kinematics_per_class
         bones, mirror, eps = self.kinematics_bones, self.kinematics_mirror, self.kinematics_still_eps
-        real_x = torch.as_tensor(self._select_real(real, real_labels, P, "classes", t_size)).to(dev)       # (K*P, C, t, V)
+        real_x = real_side(P)
         metrics._kin_check(real_x, "real", bones, mirror, eps, "Evaluator: kinematics")
         if K * P >= 1 << 24:
             raise ValueError("Evaluator: kinematics_per_class=%d: %d samples, kg_kin_desc takes fewer than 2^24" % (P, K * P))
         _, C, T, V = real_x.shape
         D = C * T * V
-        self._kin_shape = tuple(real_x.shape)
-        self.kin_samplers, self._kin_shared = {}, None
-        for kind, per, group in (("prdc", self.prdc_per_class, self.prdc_samplers),
-                                 ("frechet", self.frechet_per_class, self.frechet_samplers),
-                                 ("classifier", self.classifier_per_class, self.cls_samplers),
-                                 ("memorisation", self.memorisation_per_class if self.memorisation == "raw" else 0,
-                                  self.mem_samplers)):
-            if per == P and group:              # (a round that is itself shared has no Samplers: its owner came first)
-                self._kin_shared = kind
-                break
-        else:
-            self.kin_samplers = {k: Sampler(G, qtd=P, seed=self.seed, trunc=trunc, trunc_mode=trunc_mode, use_graph=False)
-                                 for k, G in self.gens.items()}
         with torch.cuda.device(dev):
             desc, degenerate = nv.kin_desc(nv.FrechetView(real_x, P * D, D, V, T * V), P, T, C, V, K, bones, mirror, eps)
             self._kin_real_desc = desc
@@ -743,20 +745,15 @@ class Evaluator:
             self._kin_ws = torch.zeros(nbytes // 4, dtype=torch.float32, device=dev)
 
     def _kinematics_scores(self):
-        """the kinematic rounds of all generators (a PRDC, Frechet, classifier or raw-memorisation round of the same count when
-        one exists), then per group of up to KIN_MAX_SETS generators ONE kg_kin_desc_sets - the rounds read in place through
-        their shared strides: row j*K + c, so the class stride is a sample and the sample stride K samples - and ONE
-        kg_kin_scores against the cached real descriptors: the score words are one-element views of scores (nsets, 6), per
-        generator in the order of metrics.KIN_NAMES"""
+        """the kinematic rounds of all generators, then per group of up to KIN_MAX_SETS generators ONE kg_kin_desc_sets - the
+        rounds read in place through their shared strides: row j*K + c, so the class stride is a sample and the sample stride
+        K samples - and ONE kg_kin_scores against the cached real descriptors: the score words are one-element views of
+        scores (nsets, 6), per generator in the order of metrics.KIN_NAMES"""
         K, P = self.n_classes, self.kinematics_per_class
-        shared = {"prdc": self.prdc_samplers, "frechet": self.frechet_samplers, "classifier": self.cls_samplers,
-                  "memorisation": self.mem_samplers}
-        rounds = [s._out for s in shared[self._kin_shared].values()] if self._kin_shared else self.kin_samplers.values()
-        outs, sn, sc = self._checked_rounds(rounds, self._kin_shape)
+        outs, sn, sc = self._rounds("kinematics")
         _, C, T, V = outs[0].shape
         words = []
-        for q in range(0, len(outs), nv.KIN_MAX_SETS):
-            part = outs[q:q + nv.KIN_MAX_SETS]
+        for part in nv._chunks(outs, nv.KIN_MAX_SETS):
             desc, _ = nv.kin_desc_sets(
                 part, sn, K * sn, V, sc, P, T, C, V, K, self.kinematics_bones, self.kinematics_mirror, self.kinematics_still_eps,
                 out=self._kin_desc[:len(part)], ws=self._kin_ws)
@@ -777,25 +774,12 @@ class Evaluator:
                 out = self._nchw[k]
             for mode in self.modes:
                 scores.append(metrics.calculate_mmd(out, self.real, self._pair_labels, mode).reshape(1))
-        if self.prdc_per_class:
-            scores += self._prdc_scores()
-        if self.frechet_per_class:
-            scores += self._frechet_scores()
-        if self.classifier_per_class:
-            scores += self._classifier_scores()
-        if self.memorisation:
-            scores += self._memorisation_scores()
-        if self.kinematics_per_class:
-            scores += self._kinematics_scores()
-        if self._record3:
-            nv.eval_record3(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
-                            self.best_iter, self.flag, maximise=self.maximise)
-        elif self._record2:
-            nv.eval_record2(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
-                            self.best_iter, self.flag, maximise=self.maximise)
-        else:
-            nv.eval_record(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
-                           self.best_iter, self.flag)
+        for f in FAMILIES:
+            if f.on(self):
+                scores += getattr(self, "_%s_scores" % f.key)()
+        sense = {} if self._record == "eval_record" else {"maximise": self.maximise}
+        getattr(nv, self._record)(scores, self._select, self.iteration, self.count, self.ring_val, self.ring_iter, self.best_val,
+                                  self.best_iter, self.flag, **sense)
         nv.copy_if(self.flag, self._jobs)
         self._scores = scores                # (under capture: the graph's own memory, kept alive with it)
 
@@ -805,8 +789,7 @@ class Evaluator:
         return ts + list(self.snap_buffers.values())
 
     def _all_samplers(self):
-        return list(self.samplers.values()) + list(self.prdc_samplers.values()) + list(self.frechet_samplers.values()) \
-            + list(self.cls_samplers.values()) + list(self.mem_samplers.values()) + list(self.kin_samplers.values())
+        return list(self.samplers.values()) + [s for group in self._pool.values() for s in group.values()]
 
     def _capture(self):
         """Single-stream capture, no parallel branches.  The warm-up rounds in front of it are real evaluations:
@@ -884,50 +867,17 @@ class Evaluator:
               "best_val": self.best_val.cpu(), "best_iter": self.best_iter.cpu(),
               "snapshot": {"flat": self.snap_flat.cpu(), "buffers": {k: b.cpu() for k, b in self.snap_buffers.items()}},
               "records": {k: rec[k] for k in ("iteration", "scores", "improved")}}
-        if self.prdc_per_class:              # (the real radii are recomputed from the data: not part of the state)
-            sd["prdc"] = {"per_class": self.prdc_per_class, "k": self.prdc_k}
-        if self.frechet_per_class:           # (the real side's cache is recomputed from the data: not part of the state)
-            sd["frechet"] = {"per_class": self.frechet_per_class, "modes": list(self.frechet_modes)}
-        if self.classifier_per_class:        # (the classifier's weights are the caller's, the real side is recomputed)
-            sd["classifier"] = {"per_class": self.classifier_per_class, "diversity_pairs": self.diversity_pairs,
-                                "multimodality_pairs": self.multimodality_pairs}
-        if self.memorisation:                # (the training side is recomputed from the data: not part of the state)
-            sd["memorisation"] = {"mode": self.memorisation, "per_class": self.memorisation_per_class}
-        if self.kinematics_per_class:        # (the real side's descriptors are recomputed from the data: not part of the state)
-            sd["kinematics"] = _kinematics_state(self)
+        for f in FAMILIES:                   # (the options only: the real side is recomputed from the data)
+            if f.on(self):
+                sd[f.key] = f.state(self)
         return sd
 
     def check_compatible(self, sd: dict) -> None:
-        mine = {"per_class": self.prdc_per_class, "k": self.prdc_k} if self.prdc_per_class else None
-        theirs = sd.get("prdc")
-        if (None if theirs is None else {k: int(v) for k, v in dict(theirs).items()}) != mine:
-            raise ValueError("Evaluator.load_state_dict: prdc is %r in the state, %r here" % (theirs, mine))
-        mine = {"per_class": self.frechet_per_class, "modes": list(self.frechet_modes)} if self.frechet_per_class else None
-        theirs = sd.get("frechet")
-        if (None if theirs is None else {"per_class": int(dict(theirs)["per_class"]), "modes": list(dict(theirs)["modes"])}) != mine:
-            raise ValueError("Evaluator.load_state_dict: frechet is %r in the state, %r here" % (theirs, mine))
-        # (an Evaluator-like object of before the classifier columns has none of these attributes: the option is off)
-        mine = None
-        if getattr(self, "classifier_per_class", 0):
-            mine = {"per_class": self.classifier_per_class, "diversity_pairs": self.diversity_pairs,
-                    "multimodality_pairs": self.multimodality_pairs}
-        theirs = sd.get("classifier")
-        if (None if theirs is None else {k: int(v) for k, v in dict(theirs).items()}) != mine:
-            raise ValueError("Evaluator.load_state_dict: classifier is %r in the state, %r here" % (theirs, mine))
-        mine = {"mode": self.memorisation, "per_class": self.memorisation_per_class} if getattr(self, "memorisation", None) else None
-        theirs = sd.get("memorisation")
-        if (None if theirs is None else {"mode": str(dict(theirs)["mode"]), "per_class": int(dict(theirs)["per_class"])}) != mine:
-            raise ValueError("Evaluator.load_state_dict: memorisation is %r in the state, %r here" % (theirs, mine))
-        # (an Evaluator-like object of before the kinematic columns has no such attribute: the option is off)
-        mine = _kinematics_state(self) if getattr(self, "kinematics_per_class", 0) else None
-        theirs = sd.get("kinematics")
-        if theirs is not None:
-            theirs = dict(theirs)
-            theirs = {"per_class": int(theirs["per_class"]), "still_eps": float(theirs["still_eps"]),
-                      "bones": [[int(v) for v in b] for b in theirs["bones"]],
-                      "mirror": [[int(v) for v in p] for p in theirs["mirror"]]}
-        if theirs != mine:
-            raise ValueError("Evaluator.load_state_dict: kinematics is %r in the state, %r here" % (theirs, mine))
+        # (called unbound on Evaluator-like objects of before a family existed: FAMILIES reads them with defaults)
+        for f in FAMILIES:
+            mine = plain_state(f.state(self)) if f.on(self) else None
+            if plain_state(sd.get(f.key)) != mine:
+                raise ValueError("Evaluator.load_state_dict: %s is %r in the state, %r here" % (f.key, sd.get(f.key), mine))
         for k, mine in (("pairs", self.pairs), ("select", self.select), ("modes", list(self.modes)), ("names", list(self.names))):
             if (list(sd[k]) if isinstance(mine, list) else sd[k]) != mine:
                 raise ValueError("Evaluator.load_state_dict: %s is %r in the state, %r here" % (k, sd[k], mine))

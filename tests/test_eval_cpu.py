@@ -88,6 +88,91 @@ def test_struct_sizes_match_header():
     assert _native.COPY_IF_MAX_JOBS >= 32
 
 
+FIELDS = ("scores", "nscores", "select", "iter", "count", "ring_val", "ring_iter", "ring_len", "best_val", "best_iter", "flag")
+
+
+@pytest.mark.parametrize("cls, size, offsets", [
+    ("_EvalRecordArgs", 136, (0, 64, 68, 72, 80, 88, 96, 104, 112, 120, 128)),
+    ("_EvalRecord2Args", 336, (0, 256, 260, 264, 272, 280, 288, 296, 304, 312, 320, 328)),
+    ("_EvalRecord3Args", 592, (0, 512, 516, 520, 528, 536, 544, 552, 560, 568, 576, 584))])
+def test_record_structs_keep_their_layout(cls, size, offsets):
+    """the three structs come from one field list: the sizes and offsets of the three hand-written classes before it"""
+    S = getattr(_native, cls)
+    names = FIELDS + (("maximise",) if len(offsets) == 12 else ())
+    assert issubclass(S, ctypes.Structure) and S.__name__ == cls and ctypes.sizeof(S) == size
+    assert tuple(n for n, _ in S._fields_) == names and tuple(getattr(S, n).offset for n in names) == offsets
+    types = dict(S._fields_)
+    assert ctypes.sizeof(types["scores"]) == offsets[1] and types["scores"]._type_ is ctypes.c_void_p
+    assert [types[n] for n in ("nscores", "select", "ring_len")] == [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
+    assert all(types[n] is ctypes.c_void_p for n in ("iter", "count", "ring_val", "ring_iter", "best_val", "best_iter", "flag"))
+    assert types.get("maximise", ctypes.c_int32) is ctypes.c_int32
+
+
+# ---- the sharing rule and the state normaliser ---------------------------------------------------------------------------
+
+ORDER = ("prdc", "frechet", "classifier", "memorisation", "kinematics")
+
+
+def _owners_by_the_four_chains(n):
+    """the rule as it was written before ``round_owners``, family by family (``group``: the family has Samplers of its own)"""
+    group = {"prdc": bool(n["prdc"])}
+    owner = {"prdc": None}
+    # frechet: a bool
+    shared = bool(n["frechet"]) and n["prdc"] == n["frechet"]
+    owner["frechet"] = "prdc" if shared else None
+    group["frechet"] = bool(n["frechet"]) and not shared
+    # classifier: if / elif over two names
+    owner["classifier"] = None
+    if n["classifier"]:
+        if n["prdc"] == n["classifier"]:
+            owner["classifier"] = "prdc"
+        elif n["frechet"] == n["classifier"]:
+            owner["classifier"] = "frechet"
+    group["classifier"] = bool(n["classifier"]) and owner["classifier"] is None
+    # memorisation, kinematics: for / else over the families before them
+    for key, before in (("memorisation", ORDER[:3]), ("kinematics", ORDER[:4])):
+        owner[key] = None
+        if n[key]:
+            for kind in before:
+                if n[kind] == n[key] and group[kind]:      # (a round that is itself shared has no Samplers: its owner came first)
+                    owner[key] = kind
+                    break
+        group[key] = bool(n[key]) and owner[key] is None
+    return owner, group
+
+
+def test_round_owners_is_the_rule_of_the_four_chains():
+    import itertools
+    cases = list(itertools.product((0, 3, 4), repeat=5))
+    assert len(cases) == 243
+    for case in cases:
+        n = dict(zip(ORDER, case))
+        got = evaluate.round_owners(n)
+        want, group = _owners_by_the_four_chains(n)
+        assert got == want and list(got) == list(ORDER), (n, got, want)
+        for key, owner in got.items():
+            if owner is not None:
+                assert got[owner] is None and n[owner] == n[key] != 0 and ORDER.index(owner) < ORDER.index(key), (n, got)
+            if n[key] == 0:
+                assert owner is None and key not in got.values(), (n, got)
+        assert {k for k in ORDER if n[k] and got[k] is None} == {k for k in ORDER if group[k]}      # who builds Samplers
+    assert [f.key for f in evaluate.FAMILIES] == list(ORDER)
+
+
+def test_plain_state_is_idempotent_and_keeps_what_differs():
+    plain = evaluate.plain_state
+    back = {"per_class": np.int64(8), "modes": ("pose", "motion"), "still_eps": np.float64(1e-3), "mode": "raw",
+            "bones": np.array([[0, 1], [1, 2]], dtype=np.int32), "mirror": [(0, 1)], "none": None}
+    once = plain(back)
+    assert once == {"per_class": 8, "modes": ["pose", "motion"], "still_eps": 1e-3, "mode": "raw", "bones": [[0, 1], [1, 2]],
+                    "mirror": [[0, 1]], "none": None}
+    assert plain(once) == once and plain(plain(np.int64(8))) == 8 and type(plain(np.int64(8))) is int
+    assert type(once["per_class"]) is int and type(once["still_eps"]) is float and type(once["bones"][0][0]) is int
+    assert plain({"per_class": np.int64(8), "modes": ("pose", "motion")}) == {"per_class": 8, "modes": ["pose", "motion"]}
+    assert plain({"still_eps": 2e-3}) != plain({"still_eps": 1e-3}) and plain({"mode": "raw"}) != plain({"mode": "features"})
+    assert plain(None) is None and plain("pose") == "pose"
+
+
 def _record_args(nscores=1, select=0, ring_len=4, null=None):
     a = _native._EvalRecordArgs()
     p = 0x1000

@@ -118,10 +118,10 @@ def test_columns_equal_the_composition(composed, kind):
 
 def test_round_sharing(composed):
     own, shared = composed["evs"]["own"], composed["evs"]["shared"]
-    assert list(own.kin_samplers) == ["a", "b"] and own._kin_shared is None and len(own._all_samplers()) == 4
+    assert list(own.kin_samplers) == ["a", "b"] and own.round_owner["kinematics"] is None and len(own._all_samplers()) == 4
     assert all(s.step_count == 3 for s in own._all_samplers())
     assert [int(s.step_dev.item()) for s in own._all_samplers()] == [3] * 4                 # the counters advance in lock-step
-    assert shared.kin_samplers == {} and shared._kin_shared == "prdc" and len(shared._all_samplers()) == 4
+    assert shared.kin_samplers == {} and shared.round_owner["kinematics"] == "prdc" and len(shared._all_samplers()) == 4
     assert len(composed["evs"]["shared/plain"]._all_samplers()) == 4                         # no Sampler was added
     # the same rounds either way (one seed, one counter): the same kinematic columns
     a, b = composed["recs"]["own"], composed["recs"]["shared"]
@@ -195,7 +195,7 @@ def test_everything_on_is_40_columns_through_record3(trained, composed, monkeypa
                  memorisation_train_labels=lab.numpy(), **KIN_KW)
     want = evaluate.score_names(("a", "b"), ("avg", "joint"), True, ("pose", "motion"), True, True, kinematics=True)
     assert ev.names == want and len(ev.names) == 40 and ev.names[-12:] == NEW and not ev.maximise
-    assert ev.kin_samplers == {} and ev._kin_shared == "prdc" and len(ev._all_samplers()) == 4
+    assert ev.kin_samplers == {} and ev.round_owner["kinematics"] == "prdc" and len(ev._all_samplers()) == 4
     assert ev.best() == {"value": float("inf"), "iteration": -1}
     col = ev.names.index("b/jerk")
     scales, weights = [1.0, 4.0, float("nan"), 0.25, 1.0, 16.0], []
@@ -221,6 +221,82 @@ def test_everything_on_is_40_columns_through_record3(trained, composed, monkeypa
     assert same_bits(ev.snap_flat, weights[first])
     E = ev.best_generator()
     assert same_bits(torch.cat([p.detach().reshape(-1) for p in E.parameters()]), weights[first])
+
+
+# prdc 3, frechet 3, classifier 4, kinematics 4, raw memorisation at 4 (a count others have) or 5 (a count nobody else has)
+MIXED = dict(prdc_per_class=3, prdc_k=2, frechet_per_class=3, classifier_per_class=4, classifier_batch=8, diversity_pairs=7,
+             multimodality_pairs=2, memorisation="raw", kinematics_per_class=4, kinematics_dataset="h36m", kinematics_still_eps=EPS)
+ALONE = {"prdc": ("prdc_per_class", "prdc_k"), "frechet": ("frechet_per_class",),
+         "classifier": ("classifier_per_class", "classifier_batch", "diversity_pairs", "multimodality_pairs"),
+         "memorisation": ("memorisation", "memorisation_per_class"),
+         "kinematics": ("kinematics_per_class", "kinematics_dataset", "kinematics_still_eps")}
+
+
+@pytest.fixture(scope="module")
+def alone(trained, composed):
+    """{(family, count): the family's columns of an Evaluator with that family alone, three evaluations}: computed once"""
+    train, lab = cls_def.synthetic_set(50, n_classes=K, per_class=8)
+    train, lab, cache = train.to(DEV), lab.numpy(), {}
+
+    def columns(family, kw):
+        key = (family, kw[family + "_per_class"])
+        if key not in cache:
+            extra = {"classifier": dict(classifier=trained),
+                     "memorisation": dict(memorisation_train=train, memorisation_train_labels=lab)}.get(family, {})
+            it = torch.full((1,), IT0, dtype=torch.int64, device=DEV)
+            ev = make_ev({"a": composed["Ga"], "b": composed["Gb"]}, it, **{k: kw[k] for k in ALONE[family]}, **extra)
+            assert list(ev.round_owner.values()) == [None] * 5 and len(ev._all_samplers()) == 4
+            for _ in range(3):
+                ev.evaluate()
+                it += 2
+            cache[key] = ev.records()["scores"][:, 4:]
+        return cache[key]
+    return dict(train=train, lab=lab, columns=columns)
+
+
+@pytest.mark.parametrize("mem", [4, 5])
+def test_every_family_on_with_mixed_counts(trained, composed, alone, mem):
+    """one table, one round pool, one real side per count: who owns which round, how many Samplers there are, which real-side
+    tensors are one, and every family's columns those of an Evaluator with that family alone (Samplers of one seed and count
+    draw the same rounds)"""
+    kw = dict(MIXED, memorisation_per_class=mem)
+    it = torch.full((1,), IT0, dtype=torch.int64, device=DEV)
+    ev = make_ev({"a": composed["Ga"], "b": composed["Gb"]}, it, classifier=trained, memorisation_train=alone["train"],
+                 memorisation_train_labels=alone["lab"], **kw)
+    owners = {"prdc": None, "frechet": "prdc", "classifier": None, "memorisation": "classifier" if mem == 4 else None,
+              "kinematics": "classifier"}
+    assert ev.round_owner == owners and list(ev.round_owner) == ["prdc", "frechet", "classifier", "memorisation", "kinematics"]
+    n_owners = sum(o is None for o in owners.values())
+    assert n_owners == (2 if mem == 4 else 3) and len(ev._all_samplers()) == 2 * (1 + n_owners)
+    assert len({id(s) for s in ev._all_samplers()}) == len(ev._all_samplers())
+    groups = dict(prdc=ev.prdc_samplers, frechet=ev.frechet_samplers, classifier=ev.cls_samplers, memorisation=ev.mem_samplers,
+                  kinematics=ev.kin_samplers)
+    for key, group in groups.items():
+        assert list(group) == (["a", "b"] if owners[key] is None else []), key
+        assert all(s.n == K * kw[key + "_per_class"] for s in group.values()), key
+    for _ in range(3):
+        ev.evaluate()
+        it += 2
+    assert all(s.step_count == 3 for s in ev._all_samplers())
+    assert [int(s.step_dev.item()) for s in ev._all_samplers()] == [3] * len(ev._all_samplers())      # in lock-step
+    # the real side: one tensor per count, which the families' attributes alias
+    sides = ev._real_sides
+    assert sorted(sides) == sorted({3, 4, mem}) and len({t.data_ptr() for t in sides.values()}) == len(sides)
+    assert ev.prdc_real.data_ptr() == ev.frechet_real.data_ptr() == sides[3].data_ptr() != sides[4].data_ptr()
+    x, y = real_set()
+    for per, t in sides.items():
+        assert same_bits(t, x[evaluate.class_rows(y, K, per)])
+    # every family's columns against that family alone
+    rec = ev.records()
+    assert rec["names"] == evaluate.score_names(("a", "b"), ("avg", "joint"), True, ("pose", "motion"), True, True, kinematics=True)
+    assert rec["scores"].shape == (3, 40) and ev._record == "eval_record3"
+    lo = 4
+    for f in evaluate.FAMILIES:
+        want = alone["columns"](f.key, kw)
+        got = rec["scores"][:, lo:lo + want.shape[1]]
+        assert want.shape[1] == 2 * len(f.columns(f.on(ev))) and same_bits(got, want), f.key
+        lo += want.shape[1]
+    assert lo == 40 and np.isfinite(rec["scores"]).all()
 
 
 def test_rejections(composed):
@@ -290,7 +366,7 @@ def test_train_loop_writes_the_columns(tmp_path):
     loop = TrainLoop(G, D, loop_feeder(tmp_path / "set"), 4, T, n_critic=2, seed=3, eval_pairs=2, ema_decay=0.9, eval_interval=2,
                      eval_kinematics=P, eval_kinematics_still_eps=EPS, eval_select="ema/jerk")
     ev = loop.evaluator
-    assert ev.names == LOOP_NAMES and not ev.maximise and ev.use_graph and ev._record3
+    assert ev.names == LOOP_NAMES and not ev.maximise and ev.use_graph and ev._record == "eval_record3"
     assert ev.kinematics_per_class == P and ev.kinematics_still_eps == EPS and len(ev.kinematics_bones) == V - 1
     for _ in range(4):
         loop.step()

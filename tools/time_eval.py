@@ -48,12 +48,18 @@ evaluation replay three ways - with the columns (one kg_kin_desc_sets + one kg_k
 descriptors cached), with the same columns composed from one ``metrics.kinematics_sets`` call per generator (a kg_kin_desc and a
 kg_kin_scores each), and without them - alternating in one process as under ``--frechet``; a difference is called real only
 when it exceeds three times the larger spread.
+``--all P`` (record: profiles/eval_refactor_time.log): instead of the above, ONE Evaluator with every family on
+and P samples per class everywhere (memorisation in ``--memorisation`` space, default raw), live + ema, at the NTU and the H36M
+shapes: how long its construction takes and what it leaves allocated on the device, then its evaluation replay, ``--rounds``
+rounds of ``--eval-replays`` replays with their spread, and a checksum of the recorded bits.
     python tools/time_eval.py [--rounds 3] [--prdc 100 | --frechet 100 | --classifier 100 | --memorisation features |
-                               --kinematics 100] [--log FILE]"""
+                               --kinematics 100 | --all 100] [--log FILE]"""
 import argparse
 import os
 import statistics
 import sys
+import time
+import zlib
 
 import numpy as np
 import torch
@@ -93,18 +99,76 @@ PRDC_SHAPES = (("NTU", dict(latent=512, channels=3, n_classes=60, t_size=64, mlp
                ("H36M", dict(latent=512, channels=2, n_classes=10, t_size=64, mlp=4, v=16, dataset="h36m")))
 
 
+def toy_setup(c, per_class, dev):
+    """(generators, real, labels): two generators of different weights (no training needed here) and a random real set of
+    ``per_class`` samples per class"""
+    K = c["n_classes"]
+    gens = {}
+    for g, seed in (("live", 1234), ("ema", 4321)):
+        torch.manual_seed(seed)
+        gens[g] = Generator(c["latent"], c["channels"], K, c["t_size"], c["mlp"], dataset=c["dataset"]).to(dev)
+    rng = np.random.RandomState(0)
+    real = torch.as_tensor((rng.rand(K * per_class, c["channels"], c["t_size"], c["v"]) * 2 - 1).astype(np.float32))
+    return gens, real, np.tile(np.arange(K), per_class)
+
+
+def time_alternating(graphs, rounds, replays, say, line=None, after=None, each=None):
+    """{label: the median ms of ``replays`` replays, per round}: the graphs alternate within every round.  ``line``: the log
+    line of one measurement (label, round, median, replays, min, max); ``after(label)``: called after a graph's replays;
+    ``each(round)``: called at the end of a round"""
+    meds = {k: [] for k in graphs}
+    for r in range(rounds):
+        for k, g in graphs.items():
+            ts = time_replays(g, replays)
+            if after:
+                after(k)
+            meds[k].append(statistics.median(ts))
+            if line:
+                say(line % (k + ",", r, meds[k][-1], replays, min(ts), max(ts)))
+        if each:
+            each(r)
+    return meds
+
+
+def time_evaluations(ev, rounds, replays, say, line=None, each=None):
+    """``time_alternating`` over the evaluation replays of {label: Evaluator}, captured here; the host mirrors of the counters
+    the replays advance are kept"""
+    for x in ev.values():
+        if x._graph is None:
+            x.evaluate()                 # (captures)
+    torch.cuda.synchronize()
+
+    def after(k):                        # (time_replays: one replay to warm up, then the timed ones)
+        ev[k].n_evals += replays + 1
+        for s in ev[k]._all_samplers():
+            s.step_count += replays + 1
+
+    return time_alternating({k: x._graph for k, x in ev.items()}, rounds, replays, say, line, after, each)
+
+
+def summary(meds):
+    """({label: median of its rounds}, {label: spread = max - min of its rounds})"""
+    return {k: statistics.median(v) for k, v in meds.items()}, {k: max(v) - min(v) for k, v in meds.items()}
+
+
+def verdict(gap, wide, what, times=1):
+    """``what`` is faster / slower only when the gap exceeds ``times`` x the larger spread"""
+    if abs(gap) <= times * wide:
+        return "not separated" + (" (within three spreads)" if times == 3 else "")
+    return "%s is %s" % (what, "faster" if gap > 0 else "slower") + (" by more than three spreads" if times == 3 else "")
+
+
+def same_records(a, b):
+    """whether two Evaluators recorded the same bits"""
+    return np.array_equal(a.records()["scores"].view(np.uint32), b.records()["scores"].view(np.uint32))
+
+
 def prdc_part(args, say, dev):
     """``--prdc N``: see the module docstring"""
     N, K5 = args.prdc, 5
     for name, c in PRDC_SHAPES:
         K = c["n_classes"]
-        gens = {}
-        for g, seed in (("live", 1234), ("ema", 4321)):      # two generators of different weights (no training needed here)
-            torch.manual_seed(seed)
-            gens[g] = Generator(c["latent"], c["channels"], K, c["t_size"], c["mlp"], dataset=c["dataset"]).to(dev)
-        rng = np.random.RandomState(0)
-        real = torch.as_tensor((rng.rand(K * N, c["channels"], c["t_size"], c["v"]) * 2 - 1).astype(np.float32))
-        labels = np.tile(np.arange(K), N)
+        gens, real, labels = toy_setup(c, N, dev)
         say("%s shapes: %d classes x %d samples per class, D = %d, live + ema, k = %d" % (
             name, K, N, c["channels"] * c["t_size"] * c["v"], K5))
         # b. the Sampler round of K x N samples alone, and what it holds
@@ -130,32 +194,14 @@ def prdc_part(args, say, dev):
         graphs = {"kg_prdc_sets, cached real radii": capture(lambda: nv.prdc_sets(
                       rv, list(outs.values()), sn, K * sn, sc, e.prdc_radii, N, N, C, T * V, K, K5, ws=e._prdc_ws)),
                   "kg_prdc per generator": capture(lambda: [nv.prdc(rv, v, N, N, C, T * V, K, K5, ws=ws1) for v in fv.values()])}
-        meds = {k: [] for k in graphs}
-        for r in range(args.reps):
-            for k, g in graphs.items():
-                ts = time_replays(g, args.replays)
-                meds[k].append(statistics.median(ts))
-                say("%s PRDC part, %-34s repetition %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
-                    name, k + ",", r, meds[k][-1], args.replays, min(ts), max(ts)))
-        m = {k: statistics.median(v) for k, v in meds.items()}
-        sp = {k: max(v) - min(v) for k, v in meds.items()}
+        m, sp = summary(time_alternating(graphs, args.reps, args.replays, say, name + " PRDC part, %-34s repetition %d: median "
+                                         "%.4f ms over %d replays (min %.4f, max %.4f)"))
         a, b = list(graphs)
         gap, wide = m[b] - m[a], max(sp.values())
-        verdict = "not separated" if abs(gap) <= wide else ("kg_prdc_sets is faster" if gap > 0 else "kg_prdc_sets is slower")
         say("%s PRDC part: %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f); gap %+.4f ms against the larger spread %.4f ms: %s" % (
-            name, a, m[a], sp[a], b, m[b], sp[b], gap, wide, verdict))
+            name, a, m[a], sp[a], b, m[b], sp[b], gap, wide, verdict(gap, wide, "kg_prdc_sets")))
         # b. the whole evaluation replay with and without PRDC
-        for x in ev.values():
-            x.evaluate()                     # (captures)
-        torch.cuda.synchronize()
-        em = {k: [] for k in ev}
-        for r in range(args.reps):
-            for k, x in ev.items():
-                ts = time_replays(x._graph, args.eval_replays)
-                x.n_evals += args.eval_replays + 1
-                for s in x._all_samplers():
-                    s.step_count += args.eval_replays + 1
-                em[k].append(statistics.median(ts))
+        em = time_evaluations(ev, args.reps, args.eval_replays, say)
         say("%s evaluation replay (%d pairs per class, avg and joint): without PRDC %.4f ms (spread %.4f), with PRDC %.4f ms "
             "(spread %.4f): %+.4f ms (median of %d repetitions of %d replays)" % (
                 name, PAIRS, statistics.median(em["off"]), max(em["off"]) - min(em["off"]), statistics.median(em["on"]),
@@ -198,43 +244,23 @@ def frechet_part(args, say, dev):
     N = args.frechet
     for name, c in PRDC_SHAPES:
         K = c["n_classes"]
-        gens = {}
-        for g, seed in (("live", 1234), ("ema", 4321)):      # two generators of different weights (no training needed here)
-            torch.manual_seed(seed)
-            gens[g] = Generator(c["latent"], c["channels"], K, c["t_size"], c["mlp"], dataset=c["dataset"]).to(dev)
-        rng = np.random.RandomState(0)
-        real = torch.as_tensor((rng.rand(K * N, c["channels"], c["t_size"], c["v"]) * 2 - 1).astype(np.float32))
-        labels = np.tile(np.arange(K), N)
+        gens, real, labels = toy_setup(c, N, dev)
         say("%s shapes: %d classes x %d samples per class of %d frames, d = %d, live + ema, pose and motion" % (
             name, K, N, c["t_size"], c["channels"] * c["v"]))
         ev = {"kg_frechet_sets, cached real side": Evaluator(gens, real, labels, pairs=PAIRS, seed=0, frechet_per_class=N),
               "kg_frechet per generator and mode": ComposedFrechetEvaluator(gens, real, labels, pairs=PAIRS, seed=0, frechet_per_class=N),
               "without Frechet": Evaluator(gens, real, labels, pairs=PAIRS, seed=0)}
-        for x in ev.values():
-            x.evaluate()                     # (captures)
-        torch.cuda.synchronize()
-        em = {k: [] for k in ev}
-        for r in range(args.rounds):
-            for k, x in ev.items():
-                ts = time_replays(x._graph, args.eval_replays)
-                x.n_evals += args.eval_replays + 1
-                for s in x._all_samplers():
-                    s.step_count += args.eval_replays + 1
-                em[k].append(statistics.median(ts))
-                say("%s evaluation replay, %-36s round %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
-                    name, k + ",", r, em[k][-1], args.eval_replays, min(ts), max(ts)))
-        m = {k: statistics.median(v) for k, v in em.items()}
-        sp = {k: max(v) - min(v) for k, v in em.items()}
+        m, sp = summary(time_evaluations(ev, args.rounds, args.eval_replays, say, name + " evaluation replay, %-36s round %d: "
+                                         "median %.4f ms over %d replays (min %.4f, max %.4f)"))
         a, b, off = list(ev)
         gap, wide = m[b] - m[a], max(sp[a], sp[b])
-        verdict = "not separated" if abs(gap) <= wide else ("kg_frechet_sets is faster" if gap > 0 else "kg_frechet_sets is slower")
         say("%s evaluation replay: %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f)" % (
             name, a, m[a], sp[a], b, m[b], sp[b], off, m[off], sp[off]))
         say("%s Frechet columns cost %+.4f ms through kg_frechet_sets, %+.4f ms composed; gap %+.4f ms against the larger spread "
-            "%.4f ms: %s" % (name, m[a] - m[off], m[b] - m[off], gap, wide, verdict))
-        ra, rb = ev[a].records(), ev[b].records()
+            "%.4f ms: %s" % (name, m[a] - m[off], m[b] - m[off], gap, wide, verdict(gap, wide, "kg_frechet_sets")))
+        ra = ev[a].records()
         say("%s the two routes record the same bits: %s; last scores: %s" % (
-            name, np.array_equal(ra["scores"].view(np.uint32), rb["scores"].view(np.uint32)),
+            name, same_records(ev[a], ev[b]),
             ", ".join("%s %.6g" % (n, v) for n, v in zip(ra["names"], ra["scores"][-1]))))
         del ev, gens
         torch.cuda.empty_cache()
@@ -262,45 +288,25 @@ def kinematics_part(args, say, dev):
     P = args.kinematics
     for name, c in PRDC_SHAPES:
         K = c["n_classes"]
-        gens = {}
-        for g, seed in (("live", 1234), ("ema", 4321)):      # two generators of different weights (no training needed here)
-            torch.manual_seed(seed)
-            gens[g] = Generator(c["latent"], c["channels"], K, c["t_size"], c["mlp"], dataset=c["dataset"]).to(dev)
-        rng = np.random.RandomState(0)
-        real = torch.as_tensor((rng.rand(K * P, c["channels"], c["t_size"], c["v"]) * 2 - 1).astype(np.float32))
-        labels = np.tile(np.arange(K), P)
+        gens, real, labels = toy_setup(c, P, dev)
         say("%s shapes: %d classes x %d samples per class of %d frames, C %d, V %d, live + ema, six W1 columns per generator" % (
             name, K, P, c["t_size"], c["channels"], c["v"]))
         kw = dict(pairs=PAIRS, seed=0, kinematics_per_class=P, kinematics_dataset=c["dataset"])
         ev = {"kg_kin_desc_sets, cached real side": Evaluator(gens, real, labels, **kw),
               "metrics.kinematics_sets per generator": ComposedKinematicsEvaluator(gens, real, labels, **kw),
               "without the kinematic columns": Evaluator(gens, real, labels, pairs=PAIRS, seed=0)}
-        for x in ev.values():
-            x.evaluate()                     # (captures)
-        torch.cuda.synchronize()
-        em = {k: [] for k in ev}
-        for r in range(args.rounds):
-            for k, x in ev.items():
-                ts = time_replays(x._graph, args.eval_replays)
-                x.n_evals += args.eval_replays + 1
-                for s in x._all_samplers():
-                    s.step_count += args.eval_replays + 1
-                em[k].append(statistics.median(ts))
-                say("%s evaluation replay, %-38s round %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
-                    name, k + ",", r, em[k][-1], args.eval_replays, min(ts), max(ts)))
-        m = {k: statistics.median(v) for k, v in em.items()}
-        sp = {k: max(v) - min(v) for k, v in em.items()}
+        m, sp = summary(time_evaluations(ev, args.rounds, args.eval_replays, say, name + " evaluation replay, %-38s round %d: "
+                                         "median %.4f ms over %d replays (min %.4f, max %.4f)"))
         a, b, off = list(ev)
         gap, wide = m[b] - m[a], max(sp[a], sp[b])
-        verdict = "not separated (within three spreads)" if abs(gap) <= 3 * wide else (
-            "kg_kin_desc_sets is faster by more than three spreads" if gap > 0 else "kg_kin_desc_sets is slower by more than three spreads")
         say("%s evaluation replay: %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f)" % (
             name, a, m[a], sp[a], b, m[b], sp[b], off, m[off], sp[off]))
         say("%s kinematic columns cost %+.4f ms through kg_kin_desc_sets, %+.4f ms composed; gap %+.4f ms against the larger spread "
-            "%.4f ms (three times: %.4f ms): %s" % (name, m[a] - m[off], m[b] - m[off], gap, wide, 3 * wide, verdict))
-        ra, rb = ev[a].records(), ev[b].records()
+            "%.4f ms (three times: %.4f ms): %s" % (name, m[a] - m[off], m[b] - m[off], gap, wide, 3 * wide,
+                                                    verdict(gap, wide, "kg_kin_desc_sets", times=3)))
+        ra = ev[a].records()
         say("%s the two routes record the same bits: %s; last kinematic scores: %s" % (
-            name, np.array_equal(ra["scores"].view(np.uint32), rb["scores"].view(np.uint32)),
+            name, same_records(ev[a], ev[b]),
             ", ".join("%s %.6g" % (n, v) for n, v in zip(ra["names"][-12:], ra["scores"][-1][-12:]))))
         del ev, gens
         torch.cuda.empty_cache()
@@ -308,7 +314,6 @@ def kinematics_part(args, say, dev):
 
 def time_calls(fn, n):
     """ms of each of n eager calls of fn, host synchronisations of its own included (wall clock around a device sync)"""
-    import time
     fn()
     torch.cuda.synchronize()
     ts = []
@@ -326,15 +331,9 @@ def classifier_part(args, say, dev):
     P = args.classifier
     for name, c in PRDC_SHAPES:
         K = c["n_classes"]
-        gens = {}
-        for g, seed in (("live", 1234), ("ema", 4321)):      # two generators of different weights (no training needed here)
-            torch.manual_seed(seed)
-            gens[g] = Generator(c["latent"], c["channels"], K, c["t_size"], c["mlp"], dataset=c["dataset"]).to(dev)
+        gens, real, labels = toy_setup(c, P, dev)
         torch.manual_seed(99)
         clf = Classifier(c["channels"], K, c["t_size"], dataset=c["dataset"]).to(dev)
-        rng = np.random.RandomState(0)
-        real = torch.as_tensor((rng.rand(K * P, c["channels"], c["t_size"], c["v"]) * 2 - 1).astype(np.float32))
-        labels = np.tile(np.arange(K), P)
         sd, sl = min(200, K * P), min(20, P)
         say("%s shapes: %d classes x %d samples per class of %d frames, feat_dim %d, %d diversity pairs, %d multimodality pairs "
             "per class, live + ema" % (name, K, P, c["t_size"], clf.feat_dim, sd, sl))
@@ -342,9 +341,6 @@ def classifier_part(args, say, dev):
                        multimodality_pairs=sl)
         off = Evaluator(gens, real, labels, pairs=PAIRS, seed=0)
         ev = {"with the classifier columns": on, "without them": off}
-        for x in ev.values():
-            x.evaluate()                     # (captures)
-        torch.cuda.synchronize()
         # the same columns from one metrics.classifier_scores call per generator, on rounds already drawn
         smp = {g: Sampler(G, qtd=P, seed=0) for g, G in gens.items()}
         outs = {g: s.next()[0] for g, s in smp.items()}
@@ -356,22 +352,17 @@ def classifier_part(args, say, dev):
                                               multimodality_pairs=sl) for o in outs.values()]
 
         t_round = statistics.median(time_replays(smp["live"]._graph, args.eval_replays))
-        em = {k: [] for k in list(ev) + ["composed"]}
-        for r in range(args.rounds):
-            for k, x in ev.items():
-                ts = time_replays(x._graph, args.eval_replays)
-                x.n_evals += args.eval_replays + 1
-                for s in x._all_samplers():
-                    s.step_count += args.eval_replays + 1
-                em[k].append(statistics.median(ts))
-                say("%s evaluation replay, %-30s round %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
-                    name, k + ",", r, em[k][-1], args.eval_replays, min(ts), max(ts)))
+        eager = []
+
+        def each(r):
             ts = time_calls(composed, max(3, args.eval_replays // 3))
-            em["composed"].append(statistics.median(ts))
+            eager.append(statistics.median(ts))
             say("%s metrics.classifier_scores per generator (2 calls, eager, real side recomputed), round %d: median %.4f ms over %d "
-                "calls (min %.4f, max %.4f)" % (name, r, em["composed"][-1], len(ts), min(ts), max(ts)))
-        m = {k: statistics.median(v) for k, v in em.items()}
-        sp = {k: max(v) - min(v) for k, v in em.items()}
+                "calls (min %.4f, max %.4f)" % (name, r, eager[-1], len(ts), min(ts), max(ts)))
+
+        em = time_evaluations(ev, args.rounds, args.eval_replays, say, name + " evaluation replay, %-30s round %d: median %.4f ms "
+                              "over %d replays (min %.4f, max %.4f)", each)
+        m, sp = summary(dict(em, composed=eager))
         a, b = list(ev)
         say("%s evaluation replay: %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f): the classifier columns cost %+.4f ms; "
             "two Sampler rounds of %d samples are %.4f ms of that" % (name, a, m[a], sp[a], b, m[b], sp[b], m[a] - m[b], K * P,
@@ -394,22 +385,20 @@ def classifier_part(args, say, dev):
 MEM_TRAIN = {"NTU": 40000, "H36M": 4000}       # synthetic training-set sizes (tools/time_nn.py)
 
 
+def toy_train(c, n, dev):
+    """(samples on the device, labels): a random training set of n samples"""
+    g = torch.Generator(device=dev).manual_seed(7)
+    return torch.rand((n, c["channels"], c["t_size"], c["v"]), device=dev, generator=g) * 2 - 1, np.arange(n) % c["n_classes"]
+
+
 def memorisation_part(args, say, dev):
     """``--memorisation {features,raw}``: see the module docstring"""
     from kinetic_gan_amd.classifier import Classifier
     mode, P = args.memorisation, args.memorisation_samples
     for name, c in PRDC_SHAPES:
         K, Nt = c["n_classes"], MEM_TRAIN[name]
-        gens = {}
-        for g, seed in (("live", 1234), ("ema", 4321)):      # two generators of different weights (no training needed here)
-            torch.manual_seed(seed)
-            gens[g] = Generator(c["latent"], c["channels"], K, c["t_size"], c["mlp"], dataset=c["dataset"]).to(dev)
-        rng = np.random.RandomState(0)
-        real = torch.as_tensor((rng.rand(K * P, c["channels"], c["t_size"], c["v"]) * 2 - 1).astype(np.float32))
-        labels = np.tile(np.arange(K), P)
-        g_ = torch.Generator(device=dev).manual_seed(7)
-        train = torch.rand((Nt, c["channels"], c["t_size"], c["v"]), device=dev, generator=g_) * 2 - 1
-        lab_t = np.arange(Nt) % K
+        gens, real, labels = toy_setup(c, P, dev)
+        train, lab_t = toy_train(c, Nt, dev)
         base = {}
         if mode == "features":
             torch.manual_seed(99)
@@ -430,19 +419,9 @@ def memorisation_part(args, say, dev):
             gram = Evaluator(gens, real, labels, pairs=PAIRS, seed=0, memorisation_train=train, memorisation_train_labels=lab_t,
                              memorisation_method="gram", **base, **mem)
             ev = {"with the memorisation columns": on, "with them through kg_nn_gram": gram, "without them": off}
-        for x in ev.values():
-            x.evaluate()                     # (captures)
-        torch.cuda.synchronize()
+        line = name + " evaluation replay, %-32s round %d: median %.4f ms over %d replays (min %.4f, max %.4f)"
         if args.memorisation_method == "gram":
-            em = {k: [] for k in ev}
-            for r in range(args.rounds):
-                for k, x in ev.items():
-                    ts = time_replays(x._graph, args.eval_replays)
-                    em[k].append(statistics.median(ts))
-                    say("%s evaluation replay, %-32s round %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
-                        name, k + ",", r, em[k][-1], args.eval_replays, min(ts), max(ts)))
-            m = {k: statistics.median(v) for k, v in em.items()}
-            sp = {k: max(v) - min(v) for k, v in em.items()}
+            m, sp = summary(time_evaluations(ev, args.rounds, args.eval_replays, say, line))
             a, b, c_ = list(ev)
             say("%s evaluation replay: exact %.4f ms (spread %.4f), kg_nn_gram %.4f ms (spread %.4f), without the columns %.4f ms "
                 "(spread %.4f): the columns cost %+.4f ms exact, %+.4f ms through the pre-filter" % (
@@ -468,22 +447,16 @@ def memorisation_part(args, say, dev):
             def composed():
                 return [metrics.memorisation(o, labels, train, lab_t, train_loo=on._mem_loo) for o in outs.values()]
 
-        em = {k: [] for k in list(ev) + ["composed"]}
-        for r in range(args.rounds):
-            for k, x in ev.items():
-                ts = time_replays(x._graph, args.eval_replays)
-                x.n_evals += args.eval_replays + 1
-                for s in x._all_samplers():
-                    s.step_count += args.eval_replays + 1
-                em[k].append(statistics.median(ts))
-                say("%s evaluation replay, %-32s round %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
-                    name, k + ",", r, em[k][-1], args.eval_replays, min(ts), max(ts)))
+        eager = []
+
+        def each(r):
             ts = time_calls(composed, max(3, args.eval_replays // 3))
-            em["composed"].append(statistics.median(ts))
+            eager.append(statistics.median(ts))
             say("%s metrics.memorisation%s per generator (2 calls, eager, train_loo given), round %d: median %.4f ms over %d calls "
-                "(min %.4f, max %.4f)" % (name, "_features" if mode == "features" else "", r, em["composed"][-1], len(ts), min(ts), max(ts)))
-        m = {k: statistics.median(v) for k, v in em.items()}
-        sp = {k: max(v) - min(v) for k, v in em.items()}
+                "(min %.4f, max %.4f)" % (name, "_features" if mode == "features" else "", r, eager[-1], len(ts), min(ts), max(ts)))
+
+        em = time_evaluations(ev, args.rounds, args.eval_replays, say, line, each)
+        m, sp = summary(dict(em, composed=eager))
         a, b = list(ev)
         say("%s evaluation replay: %s %.4f ms (spread %.4f), %s %.4f ms (spread %.4f): the memorisation columns cost %+.4f ms" % (
             name, a, m[a], sp[a], b, m[b], sp[b], m[a] - m[b]))
@@ -504,23 +477,15 @@ def memorisation_part(args, say, dev):
                   "kg_nn per generator": capture(lambda: [nv.nn(nv.PrdcView(q, q_sc, q_sp, q_so), bv, n, Nt, d_outer, d_inner, 1, 1,
                                                                 b_affine=ba, ws=ws1) for q in qs])}
         replays = args.replays if mode == "features" else args.eval_replays
-        meds = {k: [] for k in graphs}
-        for r in range(args.reps):
-            for k, g in graphs.items():
-                ts = time_replays(g, replays)
-                meds[k].append(statistics.median(ts))
-                say("%s search, %-30s repetition %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (
-                    name, k + ",", r, meds[k][-1], replays, min(ts), max(ts)))
-        gm = {k: statistics.median(v) for k, v in meds.items()}
-        gs = {k: max(v) - min(v) for k, v in meds.items()}
+        gm, gs = summary(time_alternating(graphs, args.reps, replays, say, name + " search, %-30s repetition %d: median %.4f ms "
+                                          "over %d replays (min %.4f, max %.4f)"))
         a, b = list(graphs)
         gap, wide = gm[b] - gm[a], max(gs.values())
-        verdict = "not separated" if abs(gap) <= wide else ("kg_nn_sets is faster" if gap > 0 else "kg_nn_sets is slower")
         split = lambda f, *x: f(*x) // (x[0] * 8) if f is nv.nn_workspace_bytes else f(*x) // (x[0] * x[1] * 8)      # noqa: E731
         say("%s search: %s %.4f ms (spread %.4f; %d chunks), %s %.4f ms (spread %.4f; %d chunks each); gap %+.4f ms against the larger "
             "spread %.4f ms: %s (two launches instead of four either way)" % (
                 name, a, gm[a], gs[a], split(nv.nn_sets_workspace_bytes, 2, n, Nt, d_outer, d_inner, 1, 1), b, gm[b], gs[b],
-                split(nv.nn_workspace_bytes, n, Nt, d_outer, d_inner, 1, 1), gap, wide, verdict))
+                split(nv.nn_workspace_bytes, n, Nt, d_outer, d_inner, 1, 1), gap, wide, verdict(gap, wide, "kg_nn_sets")))
         idx, d2 = nv.nn_sets(qs, q_sc, q_sp, q_so, bv, n, Nt, d_outer, d_inner, 1, 1, b_affine=ba, ws=on._mem_ws)
         g = capture(lambda: nv.nn_scores(idx, d2, on._mem_qlab, on._mem_blab, on._mem_loo, K))
         sm = [statistics.median(time_replays(g, args.replays)) for _ in range(args.reps)]
@@ -532,6 +497,47 @@ def memorisation_part(args, say, dev):
             float(on.memorisation_real["authenticity"]), float(on.memorisation_real["label_agreement"])))
         del ev, on, off, gens, smp, outs, graphs, g, composed, train, qs, bv, idx, d2, ws1
         torch.cuda.empty_cache()
+
+
+def all_part(args, say, dev):
+    """``--all P``: see the module docstring"""
+    from kinetic_gan_amd.classifier import Classifier
+    P, mode = args.all, args.memorisation or "raw"
+    for name, c in PRDC_SHAPES:
+        K, Nt = c["n_classes"], MEM_TRAIN[name]
+        gens, real, labels = toy_setup(c, P, dev)
+        train, lab_t = toy_train(c, Nt, dev)
+        torch.manual_seed(99)
+        clf = Classifier(c["channels"], K, c["t_size"], dataset=c["dataset"]).to(dev)
+        kw = dict(prdc_per_class=P, prdc_k=5, frechet_per_class=P, classifier=clf, classifier_per_class=P,
+                  diversity_pairs=min(200, K * P), multimodality_pairs=min(20, P), memorisation=mode, memorisation_train=train,
+                  memorisation_train_labels=lab_t, memorisation_per_class=P if mode == "raw" else 0, kinematics_per_class=P,
+                  kinematics_dataset=c["dataset"])
+        torch.cuda.synchronize()
+        m0, t0 = torch.cuda.memory_allocated(dev), time.perf_counter()
+        ev = Evaluator(gens, real, labels, pairs=PAIRS, seed=0, **kw)
+        torch.cuda.synchronize()
+        t1, m1 = time.perf_counter(), torch.cuda.memory_allocated(dev)
+        say("%s shapes: every family on, %d classes x %d samples per class everywhere, memorisation in %s space against %d training "
+            "samples, live + ema: %d columns, %d Samplers" % (name, K, P, mode, Nt, len(ev.names), len(ev._all_samplers())))
+        say("%s construction (real side a host tensor): %.1f ms; it leaves %.1f MB allocated on the device" % (
+            name, (t1 - t0) * 1e3, (m1 - m0) / 1e6))
+        em = time_evaluations({"every family on": ev}, args.rounds, args.eval_replays, say, name + " evaluation replay, %-18s round %d: "
+                              "median %.4f ms over %d replays (min %.4f, max %.4f)")
+        m, sp = summary(em)
+        rec = ev.records()
+        say("%s evaluation replay, every family on: %.4f ms (median of %d rounds), spread between rounds %.4f ms; crc32 of the %d "
+            "recorded rows: %08x" % (name, m["every family on"], args.rounds, sp["every family on"], len(rec["scores"]),
+                                     zlib.crc32(rec["scores"].tobytes())))
+        del ev, gens, train, clf
+        torch.cuda.empty_cache()
+
+
+def write_log(path, lines):
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
 
 
 def parse_args(argv=None):
@@ -552,6 +558,8 @@ def parse_args(argv=None):
                     help="gram: time the memorisation columns through kg_nn_gram against the exact search (DESIGN.md 24)")
     ap.add_argument("--kinematics", type=int, default=0,
                     help="samples per class: time the kinematic columns of an evaluation instead (DESIGN.md 26)")
+    ap.add_argument("--all", type=int, default=0,
+                    help="samples per class: construct and time ONE Evaluator with every family on instead (DESIGN.md 27)")
     ap.add_argument("--eval-replays", type=int, default=30,
                     help="replays of a whole evaluation / a Sampler round under --prdc and --frechet")
     ap.add_argument("--log", default=None, help="also write the lines to this file")
@@ -569,9 +577,11 @@ def main(argv=None):
         print(s, flush=True)
         lines.append(s)
 
-    if args.prdc or args.frechet or args.classifier or args.memorisation or args.kinematics:
+    if args.all or args.prdc or args.frechet or args.classifier or args.memorisation or args.kinematics:
         say("device %s" % torch.cuda.get_device_name(0))
-        if args.kinematics:
+        if args.all:
+            all_part(args, say, dev)
+        elif args.kinematics:
             kinematics_part(args, say, dev)
         elif args.memorisation:
             memorisation_part(args, say, dev)
@@ -581,11 +591,7 @@ def main(argv=None):
             classifier_part(args, say, dev)
         else:
             frechet_part(args, say, dev)
-        if args.log:
-            os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
-            with open(args.log, "w") as fh:
-                fh.write("\n".join(lines) + "\n")
-        return
+        return write_log(args.log, lines)
     feeder = SyntheticFeeder(64 * BATCH + 17, CFG["channels"], CFG["t_size"], CFG["v"], CFG["n_classes"])
     data = ResidentDataset(feeder, CFG["t_size"], dev)
     say("device %s; NTU-60 shapes, %d samples per iteration, a generator step in every iteration, %d resident samples; "
@@ -608,14 +614,8 @@ def main(argv=None):
         say("%d evaluation replays done; %d copy jobs, snapshot of %d parameters" % (args.only_eval, len(ev._jobs), ev.snap_flat.numel()))
         return
     # 1. the evaluation replay alone, and its parts
-    meds = []
-    for r in range(args.reps):
-        ts = time_replays(ev._graph, args.replays)
-        ev.n_evals += args.replays + 1       # (host mirrors of the counters the replays advanced)
-        for s in ev.samplers.values():
-            s.step_count += args.replays + 1
-        meds.append(statistics.median(ts))
-        say("evaluation replay, repetition %d: median %.4f ms over %d replays (min %.4f, max %.4f)" % (r, meds[-1], args.replays, min(ts), max(ts)))
+    meds = time_evaluations({"evaluation replay": ev}, args.reps, args.replays, say,
+                            "%s repetition %d: median %.4f ms over %d replays (min %.4f, max %.4f)")["evaluation replay"]
     say("evaluation replay: %.4f ms (median of %d repetitions), spread between repetitions %.4f ms" % (
         statistics.median(meds), args.reps, max(meds) - min(meds)))
     smp = Sampler(loops["on"].G, qtd=PAIRS, seed=0)
@@ -659,10 +659,7 @@ def main(argv=None):
     b = ev.best()
     say("generator weights of the two loops after %d iterations equal: %s; %d evaluations recorded, best %s %.6f at iteration %d" % (
         loops["on"].step_count, same, len(rec["iteration"]), ev.select, b["value"], b["iteration"]))
-    if args.log:
-        os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
-        with open(args.log, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    write_log(args.log, lines)
 
 
 if __name__ == "__main__":
