@@ -240,6 +240,33 @@ int     kg_agg_outer_sum_many(const KgOuterSumJobs* jobs, void* stream);
 /* several kg_agg_outer problems (every job with its own ws / ws_bytes / out; defer_sum ignored) in one launch for the
  * matrix-core form plus one launch for all slab sums: the adjacency gradients of a whole backward pass            */
 int     kg_agg_outer_many(const KgAggArgs* jobs, int32_t njobs, void* stream);
+/* tests / tuning (additive, ABI v9): the kernel form, the template instantiation and the launch geometry kg_agg_expand /
+ * kg_agg_reduce / kg_agg_outer take for these arguments under the current KG_AGG_* switches - from the same host
+ * planning functions as the launch itself.  Only dimensions, strides and the null-ness of res / mask are read: no pointer is
+ * dereferenced, nothing is launched.  Fields that do not belong to the reported form are 0.                          */
+#define KG_AGG_OP_EXPAND 0
+#define KG_AGG_OP_REDUCE 1
+#define KG_AGG_OP_OUTER 2
+#define KG_AGG_FORM_FRAME 0          /* one thread per frame: kg_agg_{expand,reduce}_kernel<K, WP>                     */
+#define KG_AGG_FORM_STREAM 1         /* kg_agg_{expand,reduce}_stream_kernel<K, VM>                                    */
+#define KG_AGG_FORM_MFMA 2           /* kg_agg_mfma_kernel<KI, KO, KS, RES, MSK>                                       */
+#define KG_AGG_FORM_OUTER_ELEM 3     /* kg_agg_outer_kernel<K>                                                         */
+#define KG_AGG_FORM_OUTER_MFMA 4     /* kg_agg_outer_mfma_kernel<K, TV, TW>                                            */
+typedef struct KgAggPlanInfo {
+    int32_t form, K;
+    int32_t WP;                              /* frame form: W padded to 4 / 8 / 16 / 28                                */
+    int32_t VM, FO;                          /* stream form: V padded to 4 / 8 / 16 / 25, output frames per workgroup  */
+    int32_t KI, KO, KS, RES, MSK;            /* mfma form: the instantiation ...                                       */
+    int32_t SUB, tiles_per_c, ntiles;        /* ... sub-tiles per tile, tiles per channel, tiles of the launch         */
+    int32_t TV, TW;                          /* outer mfma form: 16-wide tiles over V / W                              */
+    int32_t P, F, chunks, units, slabs;      /* outer: frame blocks per MFMA tile (mfma form), frames per unit, units per
+                                                channel, units of the launch, partial slabs (= workgroups)             */
+    int32_t grid_x, grid_y, lds_bytes;       /* every form; lds_bytes = dynamic LDS of the launch                      */
+} KgAggPlanInfo;
+int     kg_agg_plan_info(const KgAggArgs* a, int32_t op, KgAggPlanInfo* info);
+/* launch[i] = index of the shared kg_agg_outer_many launch job i rides in, or -1 when it is launched on its own;
+ * slabs[i] = partial slabs (workgroups) the launch's budget (KG_AGG_OUTER_BUDGET) gives it.  The walk of kg_agg_outer_many. */
+int     kg_agg_outer_many_plan(const KgAggArgs* jobs, int32_t njobs, int32_t* launch, int32_t* slabs);
 
 /* ---- fused aggregation + gcn contraction of a discriminator block ("disc block forward", first half) -----------
  *   out[m, (n,t,w)] = sum_k sum_c W(k,m,c) * ( sum_v x[c, (n,t,v)] * A[k,v,w] )  + add[m, (n, t*a_tstride, w)]
@@ -264,6 +291,18 @@ typedef struct KgAggConvArgs {
 
 int kg_aggconv_supported(const KgAggConvArgs* a);
 int kg_aggconv(const KgAggConvArgs* a, void* stream);
+/* tests / tuning (additive, ABI v9): the form kg_aggconv (label_J = 0) or kg_aggconv_label (label_J = J of its label bias, > 0)
+ * takes for these arguments under the current KG_AGGCONV_* switches, from the launchers' own planning function; no pointer
+ * is dereferenced (null-ness of add / xa is read), nothing is launched.
+ * tiny = 1: kg_aggconv_tiny_kernel<MT, RG, LB>;  tiny = 0: kg_aggconv_kernel<BM, XE, KS, XA, ADD, 1, 4, 1>, tapmask / spanp
+ * as the kernel receives them.  Fields of the other form are 0.                                                       */
+typedef struct KgAggConvPlanInfo {
+    int32_t tiny;
+    int32_t MT, RG, LB;
+    int32_t BM, KS, XE, XA, ADD, tapmask, spanp;
+    int32_t grid_x, grid_y, lds_bytes;
+} KgAggConvPlanInfo;
+int kg_aggconv_plan_info(const KgAggConvArgs* a, int32_t label_J, KgAggConvPlanInfo* info);
 
 /* ---- generator st_gcn block on the coarse grid ("fused G-block", generator.py:168-182) -------------------------------
  * The block's 1x1 convs commute with upsample_s (x U, generator.py:185-200) and the nearest frame repeat

@@ -119,6 +119,29 @@ class _AggArgs(C.Structure):
                 ("mask", c_f32p), ("m_sN", C.c_int64), ("m_sC", C.c_int64), ("slope", C.c_float)]
 
 
+AGG_OP_EXPAND, AGG_OP_REDUCE, AGG_OP_OUTER = 0, 1, 2
+# kernel forms of the aggregation family, as kg_agg_plan_info names them
+AGG_FORM_FRAME, AGG_FORM_STREAM, AGG_FORM_MFMA, AGG_FORM_OUTER_ELEM, AGG_FORM_OUTER_MFMA = 0, 1, 2, 3, 4
+AGG_FORM_NAMES = {AGG_FORM_FRAME: "frame", AGG_FORM_STREAM: "stream", AGG_FORM_MFMA: "mfma",
+                  AGG_FORM_OUTER_ELEM: "outer-elementwise", AGG_FORM_OUTER_MFMA: "outer-mfma"}
+
+
+class _AggPlanInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "form", "K", "WP", "VM", "FO", "KI", "KO", "KS", "RES", "MSK", "SUB", "tiles_per_c", "ntiles", "TV", "TW",
+        "P", "F", "chunks", "units", "slabs", "grid_x", "grid_y", "lds_bytes")]
+
+
+class _AggConvPlanInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "tiny", "MT", "RG", "LB", "BM", "KS", "XE", "XA", "ADD", "tapmask", "spanp", "grid_x", "grid_y", "lds_bytes")]
+
+
+def plan_dict(p) -> dict:
+    """a plan report (_AggPlanInfo / _AggConvPlanInfo) as a plain dict"""
+    return {n: getattr(p, n) for n, _ in p._fields_}
+
+
 class _OuterSumJob(C.Structure):
     _fields_ = [("ws", c_f32p), ("out", c_f32p), ("nout", C.c_int32), ("slabs", C.c_int32)]
 
@@ -597,6 +620,9 @@ EXPORTS = {
     "kg_wgrad_many_plan": (C.c_int, [C.POINTER(_WgradArgs), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kg_aggconv_supported": (C.c_int, [C.POINTER(_AggConvArgs)]),
     "kg_aggconv": (C.c_int, [C.POINTER(_AggConvArgs), C.c_void_p]),
+    "kg_aggconv_plan_info": (C.c_int, [C.POINTER(_AggConvArgs), C.c_int32, C.POINTER(_AggConvPlanInfo)]),
+    "kg_agg_plan_info": (C.c_int, [C.POINTER(_AggArgs), C.c_int32, C.POINTER(_AggPlanInfo)]),
+    "kg_agg_outer_many_plan": (C.c_int, [C.POINTER(_AggArgs), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kg_agg_expand": (C.c_int, [C.POINTER(_AggArgs), C.c_void_p]),
     "kg_agg_reduce": (C.c_int, [C.POINTER(_AggArgs), C.c_void_p]),
     "kg_agg_outer_workspace_bytes": (C.c_int64, [C.POINTER(_AggArgs)]),
@@ -1146,6 +1172,23 @@ def wgrad_reduce_many(jobs: list):
     jobs.clear()
 
 
+last_agg_plan = None      # set to a list: agg_expand() / agg_reduce() / agg_outer() append the plan (a dict, "op" added) of every
+#                           launch, agg_outer_finish() one dict(op="outer_many", launch=[..], slabs=[..]) per call
+last_aggconv_plan = None  # set to a list: aggconv() / aggconv_label() append the plan (a dict) of every launch
+
+
+def _record_agg_plan(lib, a, op):
+    p = _AggPlanInfo()
+    _check(lib.kg_agg_plan_info(C.byref(a), op, C.byref(p)), "kg_agg_plan_info")
+    last_agg_plan.append(dict(plan_dict(p), op=("expand", "reduce", "outer")[op]))
+
+
+def _record_aggconv_plan(lib, a, label_J):
+    p = _AggConvPlanInfo()
+    _check(lib.kg_aggconv_plan_info(C.byref(a), label_J, C.byref(p)), "kg_aggconv_plan_info")
+    last_aggconv_plan.append(plan_dict(p))
+
+
 def _agg_args(N, Cc, K, V, W, T, rep, A):
     a = _AggArgs()
     a.N, a.C, a.K, a.V, a.W, a.T, a.rep = N, Cc, K, V, W, T, rep
@@ -1175,6 +1218,8 @@ def agg_expand(x: torch.Tensor, A: torch.Tensor, rep: int = 1) -> torch.Tensor:
     _bind(a, "x", "x", x)
     out = _bind(a, "out", "o", new_plane(n, k * c, t * rep, w, x.device))
     _count("kg_agg", 2.0 * k * v * w * c * n * t * rep)
+    if last_agg_plan is not None:        # tests / tuning: record which kernel form and instantiation runs
+        _record_agg_plan(lib, a, AGG_OP_EXPAND)
     _check(lib.kg_agg_expand(C.byref(a), _stream()), "kg_agg_expand")
     return out
 
@@ -1196,6 +1241,8 @@ def aggconv(x: torch.Tensor, A: torch.Tensor, nbr: torch.Tensor, pcount, w: torc
     lib = load_library()
     a, out, xa, flops, _keep = _aggconv_args(x, A, nbr, pcount, w, wv, M, add, add_tstride, want_xa)
     _count("kg_aggconv", flops)
+    if last_aggconv_plan is not None:    # tests / tuning: record which kernel form and instantiation runs
+        _record_aggconv_plan(lib, a, 0)
     _check(lib.kg_aggconv(C.byref(a), _stream()), "kg_aggconv")
     return out, xa
 
@@ -1249,6 +1296,8 @@ def aggconv_label(x: torch.Tensor, A: torch.Tensor, nbr: torch.Tensor, pcount, w
     lb.labels, lb.emb = labels.data_ptr(), emb.data_ptr()
     lb.w, lb.w_sK, lb.w_sC = wg.data_ptr(), M * cin, cin
     _count("kg_aggconv", flops)
+    if last_aggconv_plan is not None:
+        _record_aggconv_plan(lib, a, J)
     _check(lib.kg_aggconv_label(C.byref(a), C.byref(lb), _stream()), "kg_aggconv_label")
     return out, xa
 
@@ -1282,6 +1331,8 @@ def agg_reduce(y: torch.Tensor, A: torch.Tensor, fold: int = 1, res: Optional[to
         _bind(a, "mask", "m", mask)
     a.slope = slope
     _count("kg_agg", 2.0 * k * v * w * c * n * tin)
+    if last_agg_plan is not None:
+        _record_agg_plan(lib, a, AGG_OP_REDUCE)
     _check(lib.kg_agg_reduce(C.byref(a), _stream()), "kg_agg_reduce")
     return out
 
@@ -1313,6 +1364,8 @@ def agg_outer(x: torch.Tensor, y: torch.Tensor, K: int, rep: int = 1, out: Optio
         # nothing is launched now: the record keeps the operands and the scratch alive until agg_outer_finish
         defer.append(dict(args=a, keep=(x, y, ws, out)))
         return out
+    if last_agg_plan is not None:
+        _record_agg_plan(lib, a, AGG_OP_OUTER)
     _check(lib.kg_agg_outer(C.byref(a), _stream()), "kg_agg_outer")
     return out
 
@@ -1326,6 +1379,10 @@ def agg_outer_finish(jobs: list):
         arr = (_AggArgs * len(jobs))()
         for i, j in enumerate(jobs):
             C.memmove(C.byref(arr[i]), C.byref(j["args"]), C.sizeof(_AggArgs))
+        if last_agg_plan is not None:    # tests / tuning: the shared launch and the slabs of every job
+            la, ns = (C.c_int32 * len(jobs))(), (C.c_int32 * len(jobs))()
+            _check(lib.kg_agg_outer_many_plan(arr, len(jobs), la, ns), "kg_agg_outer_many_plan")
+            last_agg_plan.append(dict(op="outer_many", launch=list(la), slabs=list(ns)))
         _check(lib.kg_agg_outer_many(arr, len(jobs), _stream()), "kg_agg_outer_many")
     jobs.clear()
 

@@ -787,13 +787,19 @@ __global__ __launch_bounds__(256) void kg_agg_outer_sum_many_kernel(const KgOute
     if (e < j.nout && threadIdx.x < 64) j.out[e] = s;
 }
 
-int validate(const KgAggArgs* a, const char* who) {
+// dimensions only: what the launch plans read (kg_agg_plan_info checks no more than this)
+int validate_dims(const KgAggArgs* a, const char* who) {
     KG_REQUIRE(a != nullptr, "%s: null args", who);
     KG_REQUIRE(a->N > 0 && a->C > 0 && a->T > 0 && a->rep >= 1, "%s: bad dims", who);
     KG_REQUIRE(a->C <= 65535, "%s: C=%d too large", who, a->C);
     KG_REQUIRE(a->K == 1 || a->K == 3, "%s: K=%d (1 or 3)", who, a->K);
     KG_REQUIRE(a->V >= 1 && a->V <= 25 && a->W >= 1 && a->W <= 25, "%s: V=%d W=%d (1..25)", who, a->V, a->W);
     KG_REQUIRE((long)a->N * a->T * a->rep < (1L << 30), "%s: too many frames", who);
+    return 0;
+}
+
+int validate(const KgAggArgs* a, const char* who) {
+    if (int rc = validate_dims(a, who)) return rc;
     KG_REQUIRE(a->a && a->x && a->out, "%s: null pointer", who);
     return 0;
 }
@@ -806,9 +812,12 @@ int outer_slabs(const KgAggArgs* a, int* nunits, int* row_tiles) {
 }
 
 // W padded to a multiple of 4: 4, 8, 16 or 28
+int agg_wp(int W) { return W <= 4 ? 4 : (W <= 8 ? 8 : (W <= 16 ? 16 : 28)); }
+
+// pl: the launch's plan (KgAggPlanInfo, form KG_AGG_FORM_FRAME)
 #define KG_AGG_DISPATCH(KERNEL, grid)                                                                  \
     do {                                                                                               \
-        const int wp = a->W <= 4 ? 4 : (a->W <= 8 ? 8 : (a->W <= 16 ? 16 : 28));                       \
+        const int wp = pl.WP;                                                                          \
         if (a->K == 3) {                                                                               \
             if (wp == 4) hipLaunchKernelGGL((KERNEL<3, 4>), grid, dim3(NT), 0, s, *a, ep);                 \
             else if (wp == 8) hipLaunchKernelGGL((KERNEL<3, 8>), grid, dim3(NT), 0, s, *a, ep);            \
@@ -824,6 +833,12 @@ int outer_slabs(const KgAggArgs* a, int* nunits, int* row_tiles) {
 
 }  // namespace
 
+// ---- launch plans ---------------------------------------------------------------------------------------------------------
+// Which kernel form and instantiation a launch takes, and its geometry, is decided ONCE, by plan_expand / plan_reduce /
+// plan_outer / outer_many_walk below; the launchers and the reports (kg_agg_plan_info, kg_agg_outer_many_plan) both run
+// them, so a report cannot drift from the launch.  A plan reads dimensions, strides, the null-ness of optional pointers and
+// the cached environment; it dereferences nothing.
+
 // frames per workgroup of the stream kernels: ~8 passes of the NT / W frame slots, a multiple of `mult`, inside the
 // LDS budget (per_frame floats per output frame)
 static int stream_frames(int W, int mult, int per_frame, int lds_floats) {
@@ -835,12 +850,15 @@ static int stream_frames(int W, int mult, int per_frame, int lds_floats) {
     return fo < mult ? mult : fo;
 }
 
+// V padded to the register file of an instantiation: 4, 8, 16 or 25
+static int agg_vm(int V) { return V <= 4 ? 4 : (V <= 8 ? 8 : (V <= 16 ? 16 : 25)); }
+
 #define KG_AGG_STREAM_GO(KERNEL, K_)                                                                       \
     do {                                                                                                   \
-        if (a->V <= 4)       hipLaunchKernelGGL((KERNEL<K_, 4>), grid, dim3(NT), lds, s, *a, fo, ep);         \
-        else if (a->V <= 8)  hipLaunchKernelGGL((KERNEL<K_, 8>), grid, dim3(NT), lds, s, *a, fo, ep);         \
-        else if (a->V <= 16) hipLaunchKernelGGL((KERNEL<K_, 16>), grid, dim3(NT), lds, s, *a, fo, ep);        \
-        else                 hipLaunchKernelGGL((KERNEL<K_, 25>), grid, dim3(NT), lds, s, *a, fo, ep);        \
+        if (pl.VM == 4)       hipLaunchKernelGGL((KERNEL<K_, 4>), grid, dim3(NT), lds, s, *a, fo, ep);        \
+        else if (pl.VM == 8)  hipLaunchKernelGGL((KERNEL<K_, 8>), grid, dim3(NT), lds, s, *a, fo, ep);        \
+        else if (pl.VM == 16) hipLaunchKernelGGL((KERNEL<K_, 16>), grid, dim3(NT), lds, s, *a, fo, ep);       \
+        else                  hipLaunchKernelGGL((KERNEL<K_, 25>), grid, dim3(NT), lds, s, *a, fo, ep);       \
     } while (0)
 
 // KG_AGG_STREAM: "0" frame-per-thread kernels only, "1" stream kernels wherever the layout allows (tests),
@@ -856,9 +874,15 @@ static bool agg_mfma_wanted(bool heuristic) {
     return v < 0 ? heuristic : v == 1;
 }
 
+static void plan_clear(const KgAggArgs* a, KgAggPlanInfo* p) {
+    *p = KgAggPlanInfo{};
+    p->K = a->K;
+    p->grid_y = 1;
+}
+
 // expand (KI = 1, KO = 3) / reduce (KI = 3, KO = 1) on the matrix cores; returns false when the launch is not eligible
 template <int KI, int KO>
-static bool agg_mfma_launch(const KgAggArgs* a, hipStream_t s, int* rc, const AggEpi& ep) {
+static bool plan_mfma(const KgAggArgs* a, KgAggPlanInfo* p) {
     const long nrows = (long)a->N * a->T;
     const int lc = KI * a->V;
     if (a->K != 3 || a->rep != 1 || a->V > 25 || a->W > 25) return false;
@@ -884,22 +908,39 @@ static bool agg_mfma_launch(const KgAggArgs* a, hipStream_t s, int* rc, const Ag
     const int ks = (lc + 1) / 2;
     int cap = (KI == 3 && ks <= 8) ? 768 : 512;
     if (const int e = kg_env().agg_mfma_grid) cap = e > 0 ? e : cap;      // tuning hook
-    const int grid = (int)(ntiles < cap ? ntiles : cap);
-    const size_t lds = (size_t)sub * per128;
-    const bool hr = KO == 1 && a->res != nullptr, hm = KO == 1 && a->mask != nullptr;
+    plan_clear(a, p);
+    p->form = KG_AGG_FORM_MFMA;
+    p->KI = KI;
+    p->KO = KO;
+    if (KI == 3) p->KS = ks <= 8 ? 8 : (ks <= 17 ? 17 : 38);
+    else         p->KS = ks <= 3 ? 3 : (ks <= 6 ? 6 : 13);
+    p->RES = KO == 1 && a->res != nullptr;
+    p->MSK = KO == 1 && a->mask != nullptr;
+    p->SUB = sub;
+    p->tiles_per_c = tiles_per_c;
+    p->ntiles = (int)ntiles;
+    p->grid_x = (int)(ntiles < cap ? ntiles : cap);
+    p->lds_bytes = sub * per128;
+    return true;
+}
+
+template <int KI, int KO>
+static int agg_mfma_launch(const KgAggArgs* a, hipStream_t s, const KgAggPlanInfo& pl, const AggEpi& ep) {
+    const int grid = pl.grid_x, ntiles = pl.ntiles, tiles_per_c = pl.tiles_per_c, sub = pl.SUB;
+    const size_t lds = (size_t)pl.lds_bytes;
+    const bool hr = pl.RES != 0, hm = pl.MSK != 0;
 #define KG_AGM_GO(KS_) do { \
-        if (KO == 1 && hr && hm) hipLaunchKernelGGL((kg_agg_mfma_kernel<KI, KO, KS_, KO == 1, KO == 1>), dim3(grid), dim3(NT), lds, s, *a, (int)ntiles, tiles_per_c, sub, ep); \
-        else if (KO == 1 && hr)  hipLaunchKernelGGL((kg_agg_mfma_kernel<KI, KO, KS_, KO == 1, false>), dim3(grid), dim3(NT), lds, s, *a, (int)ntiles, tiles_per_c, sub, ep); \
-        else if (KO == 1 && hm)  hipLaunchKernelGGL((kg_agg_mfma_kernel<KI, KO, KS_, false, KO == 1>), dim3(grid), dim3(NT), lds, s, *a, (int)ntiles, tiles_per_c, sub, ep); \
-        else                     hipLaunchKernelGGL((kg_agg_mfma_kernel<KI, KO, KS_, false, false>), dim3(grid), dim3(NT), lds, s, *a, (int)ntiles, tiles_per_c, sub, ep); } while (0)
+        if (KO == 1 && hr && hm) hipLaunchKernelGGL((kg_agg_mfma_kernel<KI, KO, KS_, KO == 1, KO == 1>), dim3(grid), dim3(NT), lds, s, *a, ntiles, tiles_per_c, sub, ep); \
+        else if (KO == 1 && hr)  hipLaunchKernelGGL((kg_agg_mfma_kernel<KI, KO, KS_, KO == 1, false>), dim3(grid), dim3(NT), lds, s, *a, ntiles, tiles_per_c, sub, ep); \
+        else if (KO == 1 && hm)  hipLaunchKernelGGL((kg_agg_mfma_kernel<KI, KO, KS_, false, KO == 1>), dim3(grid), dim3(NT), lds, s, *a, ntiles, tiles_per_c, sub, ep); \
+        else                     hipLaunchKernelGGL((kg_agg_mfma_kernel<KI, KO, KS_, false, false>), dim3(grid), dim3(NT), lds, s, *a, ntiles, tiles_per_c, sub, ep); } while (0)
     if (KI == 3) {
-        if (ks <= 8) KG_AGM_GO(8); else if (ks <= 17) KG_AGM_GO(17); else KG_AGM_GO(38);
+        if (pl.KS == 8) KG_AGM_GO(8); else if (pl.KS == 17) KG_AGM_GO(17); else KG_AGM_GO(38);
     } else {
-        if (ks <= 3) KG_AGM_GO(3); else if (ks <= 6) KG_AGM_GO(6); else KG_AGM_GO(13);
+        if (pl.KS == 3) KG_AGM_GO(3); else if (pl.KS == 6) KG_AGM_GO(6); else KG_AGM_GO(13);
     }
 #undef KG_AGM_GO
-    *rc = kg_launch_status(KI == 3 ? "kg_agg_reduce (mfma)" : "kg_agg_expand (mfma)");
-    return true;
+    return kg_launch_status(KI == 3 ? "kg_agg_reduce (mfma)" : "kg_agg_expand (mfma)");
 }
 
 static AggEpi agg_epi(const KgAggArgs* a) {
@@ -918,49 +959,60 @@ static AggEpi agg_epi(const KgAggArgs* a) {
     return ep;
 }
 
-extern "C" int kg_agg_expand(const KgAggArgs* a, void* stream) {
-    if (int rc = validate(a, "kg_agg_expand")) return rc;
+// what kg_agg_expand / kg_agg_reduce require beyond the dimensions (no pointer is read)
+static int expand_check(const KgAggArgs* a) {
     KG_REQUIRE(a->res == nullptr && a->mask == nullptr, "kg_agg_expand: the res / mask epilogue belongs to kg_agg_reduce");
-    const AggEpi ep = agg_epi(a);
+    return 0;
+}
+
+static int reduce_check(const KgAggArgs* a) {
+    KG_REQUIRE((a->res == nullptr && a->mask == nullptr) || a->rep == 1, "kg_agg_reduce: res / mask epilogue with fold=%d", a->rep);
+    KG_REQUIRE(a->res == nullptr || (a->r_T > 0 && a->r_V > 0 && a->r_tstride >= 1 && (a->r_inv != nullptr || a->r_V == a->W)),
+               "kg_agg_reduce: bad residual geometry (r_T=%d r_V=%d r_tstride=%d)", a->r_T, a->r_V, a->r_tstride);
+    return 0;
+}
+
+static void plan_frame(const KgAggArgs* a, long nrows, KgAggPlanInfo* p) {
+    plan_clear(a, p);
+    p->form = KG_AGG_FORM_FRAME;
+    p->WP = agg_wp(a->W);
+    p->grid_x = kg_cdiv(nrows, NT);
+    p->grid_y = a->C;
+}
+
+static void plan_stream(const KgAggArgs* a, long nrows, int fo, size_t lds, KgAggPlanInfo* p) {
+    plan_clear(a, p);
+    p->form = KG_AGG_FORM_STREAM;
+    p->VM = agg_vm(a->V);
+    p->FO = fo;
+    p->grid_x = kg_cdiv(nrows, fo);
+    p->grid_y = a->C;
+    p->lds_bytes = (int)lds;
+}
+
+static void plan_expand(const KgAggArgs* a, KgAggPlanInfo* p) {
     const long nrows = (long)a->N * a->T * a->rep;
-    hipStream_t s = (hipStream_t)stream;
     // measured (profiles/r01_v12_time_agg.log): the matrix-core kernel wins for wide frames (V*W >= 200: 1.7x at
     // V=25/W=11, 3-5x at V=W=25); at V=W=11 the stream kernel below is still ahead for expand
     // (3-channel planes of 64 samples - the generator's last block, D0's input gradient: 12 k frames - take it too:
     // 30.4 -> 9.5 us, tools/time_agg_c3.py; one thread per frame puts 48 workgroups on the chip there)
-    if (agg_mfma_wanted(a->V * a->W >= 200 && nrows * a->C >= (1L << 13))) {
-        int rc = 0;
-        if (agg_mfma_launch<1, 3>(a, s, &rc, ep)) return rc;
-    }
+    if (agg_mfma_wanted(a->V * a->W >= 200 && nrows * a->C >= (1L << 13)) && plan_mfma<1, 3>(a, p)) return;
     const bool streams = a->N == 1 || (a->x_sN == (long)a->T * a->V && a->o_sN == (long)a->T * a->rep * a->W);
     // measured (profiles/r01_v9_time_agg.log): the stream kernel wins 1.1-2.2x when a frame has >= 4 output columns
     // and the launch is big enough to fill the chip; tiny launches / W < 4 stay with one thread per frame
     if (streams && a->rep <= 64 && agg_stream_wanted(a->W >= 4 && nrows * a->C >= (1L << 17))) {
         const int fo = stream_frames(a->W, 4 * a->rep, a->V, 8192 * a->rep - 2 * a->V * a->rep);
         const size_t lds = (size_t)((fo / a->rep + 2) * a->V + 4) * sizeof(float);
-        dim3 grid(kg_cdiv(nrows, fo), a->C);
-        if (a->K == 3) KG_AGG_STREAM_GO(kg_agg_expand_stream_kernel, 3);
-        else           KG_AGG_STREAM_GO(kg_agg_expand_stream_kernel, 1);
-        return kg_launch_status("kg_agg_expand (stream)");
+        return plan_stream(a, nrows, fo, lds, p);
     }
-    dim3 grid(kg_cdiv(nrows, NT), a->C);
-    KG_AGG_DISPATCH(kg_agg_expand_kernel, grid);
-    return kg_launch_status("kg_agg_expand");
+    plan_frame(a, nrows, p);
 }
 
-extern "C" int kg_agg_reduce(const KgAggArgs* a, void* stream) {
-    if (int rc = validate(a, "kg_agg_reduce")) return rc;
-    KG_REQUIRE((a->res == nullptr && a->mask == nullptr) || a->rep == 1, "kg_agg_reduce: res / mask epilogue with fold=%d", a->rep);
-    KG_REQUIRE(a->res == nullptr || (a->r_T > 0 && a->r_V > 0 && a->r_tstride >= 1 && (a->r_inv != nullptr || a->r_V == a->W)),
-               "kg_agg_reduce: bad residual geometry (r_T=%d r_V=%d r_tstride=%d)", a->r_T, a->r_V, a->r_tstride);
-    const AggEpi ep = agg_epi(a);
+static void plan_reduce(const KgAggArgs* a, KgAggPlanInfo* p) {
     const long nrows = (long)a->N * a->T;
-    hipStream_t s = (hipStream_t)stream;
     // reduce contracts K*V values per output: the matrix cores win from V*W >= 50 on (profiles/r01_v12_time_agg.log)
-    if (agg_mfma_wanted(a->V * a->W >= 50 && nrows * a->C >= (1L << 13))) {        // (21.6 -> 11.2 us at 3 x 4096 frames)
-        int rc = 0;
-        if (agg_mfma_launch<3, 1>(a, s, &rc, ep)) return rc;
-    }
+    // (21.6 -> 11.2 us at 3 x 4096 frames)
+    if (agg_mfma_wanted(a->V * a->W >= 50 && nrows * a->C >= (1L << 13)) && plan_mfma<3, 1>(a, p)) return;
     const bool streams = a->N == 1 || (a->x_sN == (long)a->T * a->rep * a->V && a->o_sN == (long)a->T * a->W);
     const int per_frame = a->K * a->rep * a->V;
     // the stream reduce pays one LDS read per FMA and only wins when the output frame is much wider than the input
@@ -968,12 +1020,47 @@ extern "C" int kg_agg_reduce(const KgAggArgs* a, void* stream) {
     if (streams && 4 * per_frame <= 12288 && agg_stream_wanted(a->W >= 2 * a->V && nrows * a->C >= (1L << 17))) {
         const int fo = stream_frames(a->W, 4, per_frame, 12288);
         const size_t lds = (size_t)(fo * per_frame + 4) * sizeof(float);
-        dim3 grid(kg_cdiv(nrows, fo), a->C);
+        return plan_stream(a, nrows, fo, lds, p);
+    }
+    plan_frame(a, nrows, p);
+}
+
+extern "C" int kg_agg_expand(const KgAggArgs* a, void* stream) {
+    if (int rc = validate(a, "kg_agg_expand")) return rc;
+    if (int rc = expand_check(a)) return rc;
+    const AggEpi ep = agg_epi(a);
+    hipStream_t s = (hipStream_t)stream;
+    KgAggPlanInfo pl;
+    plan_expand(a, &pl);
+    if (pl.form == KG_AGG_FORM_MFMA) return agg_mfma_launch<1, 3>(a, s, pl, ep);
+    dim3 grid(pl.grid_x, pl.grid_y);
+    if (pl.form == KG_AGG_FORM_STREAM) {
+        const int fo = pl.FO;
+        const size_t lds = (size_t)pl.lds_bytes;
+        if (a->K == 3) KG_AGG_STREAM_GO(kg_agg_expand_stream_kernel, 3);
+        else           KG_AGG_STREAM_GO(kg_agg_expand_stream_kernel, 1);
+        return kg_launch_status("kg_agg_expand (stream)");
+    }
+    KG_AGG_DISPATCH(kg_agg_expand_kernel, grid);
+    return kg_launch_status("kg_agg_expand");
+}
+
+extern "C" int kg_agg_reduce(const KgAggArgs* a, void* stream) {
+    if (int rc = validate(a, "kg_agg_reduce")) return rc;
+    if (int rc = reduce_check(a)) return rc;
+    const AggEpi ep = agg_epi(a);
+    hipStream_t s = (hipStream_t)stream;
+    KgAggPlanInfo pl;
+    plan_reduce(a, &pl);
+    if (pl.form == KG_AGG_FORM_MFMA) return agg_mfma_launch<3, 1>(a, s, pl, ep);
+    dim3 grid(pl.grid_x, pl.grid_y);
+    if (pl.form == KG_AGG_FORM_STREAM) {
+        const int fo = pl.FO;
+        const size_t lds = (size_t)pl.lds_bytes;
         if (a->K == 3) KG_AGG_STREAM_GO(kg_agg_reduce_stream_kernel, 3);
         else           KG_AGG_STREAM_GO(kg_agg_reduce_stream_kernel, 1);
         return kg_launch_status("kg_agg_reduce (stream)");
     }
-    dim3 grid(kg_cdiv(nrows, NT), a->C);
     KG_AGG_DISPATCH(kg_agg_reduce_kernel, grid);
     return kg_launch_status("kg_agg_reduce");
 }
@@ -1015,15 +1102,33 @@ extern "C" int64_t kg_agg_outer_workspace_bytes(const KgAggArgs* a) {
     return (int64_t)512 * a->K * a->V * a->W * (int64_t)sizeof(float);      // at most 512 slabs on either path
 }
 
-static int outer_slab_count(const KgAggArgs* a) {
+// the plan of one kg_agg_outer problem (dimensions already checked): the matrix-core form for stream-contiguous launches,
+// else the element-wise kernel; slabs = workgroups = partial slabs written
+static void plan_outer(const KgAggArgs* a, KgAggPlanInfo* p) {
+    plan_clear(a, p);
     int nunits, row_tiles;
-    int slabs = outer_slabs(a, &nunits, &row_tiles);
-    if (outer_streams(a) && kg_env().agg_outer_mfma != 0) {
+    const int slabs = outer_slabs(a, &nunits, &row_tiles);
+    if (outer_streams(a) && kg_env().agg_outer_mfma != 0) {    // KG_AGG_OUTER_MFMA=0: element-wise kernel only (tests)
         const OuterGeom gm = outer_geom(a);
-        const long units = (long)a->C * kg_cdiv((long)a->N * a->T, gm.F);
-        slabs = (int)(units < 512 ? units : 512);
+        const int chunks = kg_cdiv((long)a->N * a->T, gm.F);
+        const long units = (long)a->C * chunks;
+        p->form = KG_AGG_FORM_OUTER_MFMA;
+        p->TV = a->V > 16 ? 2 : 1;
+        p->TW = a->W > 16 ? 2 : 1;
+        p->P = gm.P;
+        p->F = gm.F;
+        p->chunks = chunks;
+        p->units = (int)units;
+        p->slabs = (int)(units < 512 ? units : 512);
+        p->lds_bytes = (int)outer_mfma_lds(a, gm);
+    } else {
+        p->form = KG_AGG_FORM_OUTER_ELEM;
+        p->F = OUT_R;
+        p->chunks = row_tiles;
+        p->units = nunits;
+        p->slabs = slabs;
     }
-    return slabs;
+    p->grid_x = p->slabs;
 }
 
 extern "C" int kg_agg_outer_slabs(const KgAggArgs* a) {
@@ -1032,7 +1137,9 @@ extern "C" int kg_agg_outer_slabs(const KgAggArgs* a) {
         kg_set_error("kg_agg_outer_slabs: bad arguments");
         return -1;
     }
-    return outer_slab_count(a);
+    KgAggPlanInfo pl;
+    plan_outer(a, &pl);
+    return pl.slabs;
 }
 
 extern "C" int kg_agg_outer_sum_many(const KgOuterSumJobs* jobs, void* stream) {
@@ -1047,27 +1154,31 @@ extern "C" int kg_agg_outer_sum_many(const KgOuterSumJobs* jobs, void* stream) {
     return kg_launch_status("kg_agg_outer_sum_many");
 }
 
-extern "C" int kg_agg_outer(const KgAggArgs* a, void* stream) {
+static int outer_dims(const KgAggArgs* a) {
     KG_REQUIRE(a != nullptr, "kg_agg_outer: null args");
     KG_REQUIRE(a->N > 0 && a->C > 0 && a->T > 0 && a->rep >= 1, "kg_agg_outer: bad dims");
     KG_REQUIRE(a->K == 1 || a->K == 3, "kg_agg_outer: K=%d", a->K);
     KG_REQUIRE(a->V >= 1 && a->V <= 25 && a->W >= 1 && a->W <= 25, "kg_agg_outer: V=%d W=%d", a->V, a->W);
+    return 0;
+}
+
+extern "C" int kg_agg_outer(const KgAggArgs* a, void* stream) {
+    if (int rc = outer_dims(a)) return rc;
     KG_REQUIRE(a->x && a->y && a->out && a->ws, "kg_agg_outer: null pointer");
-    int nunits, row_tiles;
-    int slabs = outer_slabs(a, &nunits, &row_tiles);
     const int nout = a->K * a->V * a->W;
     KG_REQUIRE(a->ws_bytes >= (int64_t)512 * nout * 4, "kg_agg_outer: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    if (outer_streams(a) && kg_env().agg_outer_mfma != 0) {    // KG_AGG_OUTER_MFMA=0: element-wise kernel only (tests)
-        const OuterGeom gm = outer_geom(a);
-        const int chunks = kg_cdiv((long)a->N * a->T, gm.F);
-        const long units = (long)a->C * chunks;
-        slabs = (int)(units < 512 ? units : 512);
-        const size_t lds = outer_mfma_lds(a, gm);
+    KgAggPlanInfo pl;
+    plan_outer(a, &pl);
+    const int slabs = pl.slabs;
+    if (pl.form == KG_AGG_FORM_OUTER_MFMA) {
+        const OuterGeom gm = {pl.P, pl.F};
+        const int chunks = pl.chunks, units = pl.units;
+        const size_t lds = (size_t)pl.lds_bytes;
         KG_REQUIRE(lds <= 65536, "kg_agg_outer: LDS budget exceeded (%ld bytes)", (long)lds);
-        const int tv = a->V > 16 ? 2 : 1, tw = a->W > 16 ? 2 : 1;
+        const int tv = pl.TV, tw = pl.TW;
 #define KG_OUTER_GO(K_, TV_, TW_) \
-    hipLaunchKernelGGL((kg_agg_outer_mfma_kernel<K_, TV_, TW_>), dim3(slabs), dim3(NT), lds, s, *a, (int)units, chunks, gm)
+    hipLaunchKernelGGL((kg_agg_outer_mfma_kernel<K_, TV_, TW_>), dim3(slabs), dim3(NT), lds, s, *a, units, chunks, gm)
         if (a->K == 3) {
             if (tv == 1) { if (tw == 1) KG_OUTER_GO(3, 1, 1); else KG_OUTER_GO(3, 1, 2); }
             else         { if (tw == 1) KG_OUTER_GO(3, 2, 1); else KG_OUTER_GO(3, 2, 2); }
@@ -1081,6 +1192,7 @@ extern "C" int kg_agg_outer(const KgAggArgs* a, void* stream) {
         hipLaunchKernelGGL(kg_agg_outer_sum, dim3(kg_cdiv(nout, 64)), dim3(256), 0, s, a->ws, a->out, nout, slabs);
         return kg_launch_status("kg_agg_outer_sum");
     }
+    const int nunits = pl.units, row_tiles = pl.chunks;
     if (a->K == 3) hipLaunchKernelGGL(kg_agg_outer_kernel<3>, dim3(slabs), dim3(NT), 0, s, *a, nunits, row_tiles);
     else           hipLaunchKernelGGL(kg_agg_outer_kernel<1>, dim3(slabs), dim3(NT), 0, s, *a, nunits, row_tiles);
     if (int rc = kg_launch_status("kg_agg_outer")) return rc;
@@ -1089,37 +1201,24 @@ extern "C" int kg_agg_outer(const KgAggArgs* a, void* stream) {
     return kg_launch_status("kg_agg_outer_sum");
 }
 
-// Several adjacency gradients at once: the jobs that take the matrix-core kernel share ONE launch, the others are
-// launched one by one, and all slab sums finish in one kg_agg_outer_sum_many launch per 16 jobs.  Every job brings its
-// own workspace (kg_agg_outer_workspace_bytes) and destination.
-extern "C" int kg_agg_outer_many(const KgAggArgs* jobs, int32_t njobs, void* stream) {
-    KG_REQUIRE(jobs != nullptr && njobs >= 1, "kg_agg_outer_many: no jobs");
-    hipStream_t s = (hipStream_t)stream;
-    OuterMany m;
-    m.njobs = 0;
-    int wgs = 0;
-    size_t lds = 0;
+// The walk of a kg_agg_outer_many call, shared by the launcher and kg_agg_outer_many_plan: the jobs in order, each
+// with its plan, the slabs the budget gives it and the index of the shared launch it rides in (-1: launched on its
+// own); `flush` is called where a shared launch is complete (OUTER_MANY_MAX jobs, or a slab-sum launch needs its slabs),
+// `sums` where KG_OUTER_SUM_MAX_JOBS jobs wait for their slab sums, and at the end.  ptrs: also require the operands.
+template <class Job, class Flush, class Sums>
+static int outer_many_walk(const KgAggArgs* jobs, int32_t njobs, bool ptrs, Job&& job, Flush&& flush_cb, Sums&& sums_cb) {
+    int in_launch = 0, in_sums = 0, launch = 0;
     auto flush = [&]() -> int {
-        if (m.njobs == 0) return 0;
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)kg_agg_outer_many_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(kg_agg_outer_many_kernel, dim3(wgs), dim3(NT), lds, s, m);
-        m.njobs = 0;
-        wgs = 0;
-        lds = 0;
-        return kg_launch_status("kg_agg_outer_many");
+        if (in_launch == 0) return 0;
+        in_launch = 0;
+        ++launch;
+        return flush_cb();
     };
-    KgOuterSumJobs sums;
-    sums.njobs = 0;
     auto flush_sums = [&]() -> int {
-        if (sums.njobs == 0) return 0;
+        if (in_sums == 0) return 0;
         if (int rc = flush()) return rc;                       // the slabs of these jobs must have been enqueued
-        const int rc = kg_agg_outer_sum_many(&sums, stream);
-        sums.njobs = 0;
-        return rc;
+        in_sums = 0;
+        return sums_cb();
     };
     // ONE budget of workgroups for the whole launch - two per CU, what is resident at once (60 KB of LDS each) - dealt to
     // the jobs in proportion to their units.  With up to 512 workgroups per JOB (rounds 1-2) the six-block launch of the
@@ -1139,41 +1238,117 @@ extern "C" int kg_agg_outer_many(const KgAggArgs* jobs, int32_t njobs, void* str
         KG_REQUIRE(a->N > 0 && a->C > 0 && a->T > 0 && a->rep >= 1, "kg_agg_outer_many: job %d bad dims", i);
         KG_REQUIRE(a->K == 1 || a->K == 3, "kg_agg_outer_many: job %d K=%d", i, a->K);
         KG_REQUIRE(a->V >= 1 && a->V <= 25 && a->W >= 1 && a->W <= 25, "kg_agg_outer_many: job %d V=%d W=%d", i, a->V, a->W);
-        KG_REQUIRE(a->x && a->y && a->out && a->ws, "kg_agg_outer_many: job %d null pointer", i);
-        const int nout = a->K * a->V * a->W;
-        KG_REQUIRE(a->ws_bytes >= (int64_t)512 * nout * 4, "kg_agg_outer_many: job %d workspace too small", i);
-        for (int k = 0; k < i; ++k) KG_REQUIRE(jobs[k].out != a->out, "kg_agg_outer_many: jobs %d and %d share a destination", k, i);
-        int slabs;
-        if (outer_streams(a) && kg_env().agg_outer_mfma != 0) {
-            const OuterGeom gm = outer_geom(a);
-            const int chunks = kg_cdiv((long)a->N * a->T, gm.F);
-            const long units = (long)a->C * chunks;
-            slabs = (int)(units < 512 ? units : 512);
+        if (ptrs) {
+            KG_REQUIRE(a->x && a->y && a->out && a->ws, "kg_agg_outer_many: job %d null pointer", i);
+            const int nout = a->K * a->V * a->W;
+            KG_REQUIRE(a->ws_bytes >= (int64_t)512 * nout * 4, "kg_agg_outer_many: job %d workspace too small", i);
+            for (int k = 0; k < i; ++k) KG_REQUIRE(jobs[k].out != a->out, "kg_agg_outer_many: jobs %d and %d share a destination", k, i);
+        }
+        KgAggPlanInfo pl;
+        plan_outer(a, &pl);
+        int slabs = pl.slabs;
+        if (pl.form == KG_AGG_FORM_OUTER_MFMA) {
             if (budget > 0 && total_units > 0.0) {
-                const long want = (long)(budget * ((double)units / total_units) + 0.5);
+                const long want = (long)(budget * ((double)pl.units / total_units) + 0.5);
                 slabs = (int)(want < 1 ? 1 : (want < slabs ? want : slabs));
             }
-            const size_t l = outer_mfma_lds(a, gm);
-            KG_REQUIRE(l <= 65536, "kg_agg_outer_many: LDS budget exceeded (%ld bytes)", (long)l);
-            OuterManyJob& j = m.job[m.njobs++];
-            j.a = *a;
-            j.nunits = (int)units; j.chunks = chunks; j.gm = gm;
-            j.wg_begin = wgs; j.nwg = slabs;
-            j.variant = (a->K == 3 ? 4 : 0) + (a->V > 16 ? 2 : 0) + (a->W > 16 ? 1 : 0);
-            wgs += slabs;
-            if (l > lds) lds = l;
-            if (m.njobs == OUTER_MANY_MAX)
+            KG_REQUIRE(pl.lds_bytes <= 65536, "kg_agg_outer_many: LDS budget exceeded (%ld bytes)", (long)pl.lds_bytes);
+            if (int rc = job(i, launch, slabs, pl)) return rc;
+            if (++in_launch == OUTER_MANY_MAX)
                 if (int rc = flush()) return rc;
         } else {
-            KgAggArgs one = *a;
-            one.defer_sum = 1;
-            slabs = outer_slab_count(a);
-            if (int rc = kg_agg_outer(&one, stream)) return rc;
+            if (int rc = job(i, -1, slabs, pl)) return rc;
         }
-        KgOuterSumJob& r = sums.job[sums.njobs++];
-        r.ws = a->ws; r.out = a->out; r.nout = nout; r.slabs = slabs;
-        if (sums.njobs == KG_OUTER_SUM_MAX_JOBS)
+        if (++in_sums == KG_OUTER_SUM_MAX_JOBS)
             if (int rc = flush_sums()) return rc;
     }
     return flush_sums();
+}
+
+// Several adjacency gradients at once: the jobs that take the matrix-core kernel share ONE launch, the others are
+// launched one by one, and all slab sums finish in one kg_agg_outer_sum_many launch per 16 jobs.  Every job brings its
+// own workspace (kg_agg_outer_workspace_bytes) and destination.
+extern "C" int kg_agg_outer_many(const KgAggArgs* jobs, int32_t njobs, void* stream) {
+    KG_REQUIRE(jobs != nullptr && njobs >= 1, "kg_agg_outer_many: no jobs");
+    hipStream_t s = (hipStream_t)stream;
+    OuterMany m;
+    m.njobs = 0;
+    int wgs = 0;
+    size_t lds = 0;
+    KgOuterSumJobs sums;
+    sums.njobs = 0;
+    return outer_many_walk(
+        jobs, njobs, true,
+        [&](int i, int launch, int slabs, const KgAggPlanInfo& pl) -> int {
+            const KgAggArgs* a = &jobs[i];
+            if (launch >= 0) {
+                OuterManyJob& j = m.job[m.njobs++];
+                j.a = *a;
+                j.nunits = pl.units; j.chunks = pl.chunks; j.gm = OuterGeom{pl.P, pl.F};
+                j.wg_begin = wgs; j.nwg = slabs;
+                j.variant = (a->K == 3 ? 4 : 0) + (pl.TV == 2 ? 2 : 0) + (pl.TW == 2 ? 1 : 0);
+                wgs += slabs;
+                if ((size_t)pl.lds_bytes > lds) lds = (size_t)pl.lds_bytes;
+            } else {
+                KgAggArgs one = *a;
+                one.defer_sum = 1;
+                if (int rc = kg_agg_outer(&one, stream)) return rc;
+            }
+            KgOuterSumJob& r = sums.job[sums.njobs++];
+            r.ws = a->ws; r.out = a->out; r.nout = a->K * a->V * a->W; r.slabs = slabs;
+            return 0;
+        },
+        [&]() -> int {
+            static bool attr_set = false;
+            if (!attr_set) {
+                (void)hipFuncSetAttribute((const void*)kg_agg_outer_many_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+                attr_set = true;
+            }
+            hipLaunchKernelGGL(kg_agg_outer_many_kernel, dim3(wgs), dim3(NT), lds, s, m);
+            m.njobs = 0;
+            wgs = 0;
+            lds = 0;
+            return kg_launch_status("kg_agg_outer_many");
+        },
+        [&]() -> int {
+            const int rc = kg_agg_outer_sum_many(&sums, stream);
+            sums.njobs = 0;
+            return rc;
+        });
+}
+
+// ---- plan reports (tests / tuning): nothing is launched, no pointer is read ----------------------------------------------------
+extern "C" int kg_agg_plan_info(const KgAggArgs* a, int32_t op, KgAggPlanInfo* info) {
+    KG_REQUIRE(a != nullptr && info != nullptr, "kg_agg_plan_info: null argument");
+    KG_REQUIRE(op == KG_AGG_OP_EXPAND || op == KG_AGG_OP_REDUCE || op == KG_AGG_OP_OUTER, "kg_agg_plan_info: op=%d", op);
+    KgAggPlanInfo pl;
+    if (op == KG_AGG_OP_OUTER) {
+        if (int rc = outer_dims(a)) return rc;
+        plan_outer(a, &pl);
+        KG_REQUIRE(pl.form != KG_AGG_FORM_OUTER_MFMA || pl.lds_bytes <= 65536, "kg_agg_outer: LDS budget exceeded (%ld bytes)",
+                   (long)pl.lds_bytes);
+    } else if (op == KG_AGG_OP_EXPAND) {
+        if (int rc = validate_dims(a, "kg_agg_expand")) return rc;
+        if (int rc = expand_check(a)) return rc;
+        plan_expand(a, &pl);
+    } else {
+        if (int rc = validate_dims(a, "kg_agg_reduce")) return rc;
+        if (int rc = reduce_check(a)) return rc;
+        plan_reduce(a, &pl);
+    }
+    *info = pl;
+    return 0;
+}
+
+extern "C" int kg_agg_outer_many_plan(const KgAggArgs* jobs, int32_t njobs, int32_t* launch, int32_t* slabs) {
+    KG_REQUIRE(jobs != nullptr && njobs >= 1, "kg_agg_outer_many_plan: no jobs");
+    KG_REQUIRE(launch != nullptr && slabs != nullptr, "kg_agg_outer_many_plan: null output");
+    return outer_many_walk(
+        jobs, njobs, false,
+        [&](int i, int l, int n, const KgAggPlanInfo&) -> int {
+            launch[i] = l;
+            slabs[i] = n;
+            return 0;
+        },
+        []() -> int { return 0; }, []() -> int { return 0; });
 }

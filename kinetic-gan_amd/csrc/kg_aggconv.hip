@@ -497,25 +497,85 @@ void launch_tiny_rg(int rg, dim3 grid, size_t lds, hipStream_t s, const KgAggCon
     else              hipLaunchKernelGGL((kg_aggconv_tiny_kernel<MT, 1, LB>), grid, dim3(AT_NT), lds, s, *a, l, pl);
 }
 
+
+// floats of one staged source row: the frames a 128-column tile can touch
+int span_of(const KgAggConvArgs* a) { return ((BN - 1) / a->W + 2) * a->V; }
+
+// ---- launch plans: the form, instantiation and geometry of a launch are decided here, once, for the launchers and for
+// kg_aggconv_plan_info alike (dimensions, null-ness of add / xa and the cached environment; nothing is dereferenced)
+
 // RG: threads per column.  More of them shorten every thread's row loop but repeat the per-workgroup staging: four
 // where 256-column workgroups would leave most CUs with fewer than two (64 samples: 192 of them), else one (measured
 // on MI355X at the bench shapes, profiles/d0_fused_probe.log: 64 samples 7.6 / 8.0 / 8.7 us bias-free and 15.0 / 15.1 /
 // 16.5 us with the label bias for RG = 4 / 2 / 1; 192 samples 12.8 / 14.6 / 17.1 and 22.1 / 28.6 / 34.3 us for RG = 1 / 2 / 4)
-template <bool LB>
-int launch_tiny(const KgAggConvArgs* a, const KgLabelBiasArgs* lb, hipStream_t s) {
+// label_J: 0, or the embedding width of the label form (LB)
+int plan_tiny(const KgAggConvArgs* a, int label_J, KgAggConvPlanInfo* p) {
     const int tw = a->T * a->W;
     int rg = (long)a->N * kg_cdiv(tw, AT_NT) < 512 ? 4 : 1;
     if (kg_env().aggconv_tiny_rg == 1 || kg_env().aggconv_tiny_rg == 2 || kg_env().aggconv_tiny_rg == 4) rg = kg_env().aggconv_tiny_rg;
     const int cps = kg_cdiv(tw, AT_NT / rg);
     KG_REQUIRE((long)a->N * cps < (1L << 31), "kg_aggconv (tiny): too many workgroups");
+    const bool LB = label_J > 0;
+    *p = KgAggConvPlanInfo{};
+    p->tiny = 1;
+    p->MT = a->M <= 32 ? 32 : 64;
+    p->RG = rg;
+    p->LB = LB;
+    p->grid_x = a->N * cps;
+    p->grid_y = 1;
+    p->lds_bytes = (int)((size_t)(((a->K * a->V * a->W + 3) & ~3) + (LB ? a->K * a->M * label_J + label_J : 0)) * sizeof(float));
+    return 0;
+}
+
+int plan_tile(const KgAggConvArgs* a, KgAggConvPlanInfo* p) {
+    const int span = span_of(a);
+    KG_REQUIRE(span <= 384, "kg_aggconv: source span %d floats per tile > 384 (use kg_agg_expand + kg_conv)", span);
+    *p = KgAggConvPlanInfo{};
+    p->spanp = (span + 3) / 4 * 4;
+    p->tapmask = 0;
+    for (int k = 0; k < a->K; ++k)
+        if (a->pcount[k] > 0) p->tapmask |= 1 << k;
+    p->XA = a->xa != nullptr;
+    const bool wide = p->spanp > 192;
+    // tuning hook (tools/time_aggconv.py): KG_AGGCONV_PLAN = "<BM><KS>", e.g. "642"
+    const int envplan = kg_env().aggconv_plan;
+    // 64-row tiles (every source row staged and aggregated once per 64 output channels) where they still leave every
+    // CU two or more workgroups; measured on MI355X (profiles/r02_time_aggconv.log)
+    const long ctiles = kg_cdiv((long)a->N * a->T * a->W, BN);
+    int bm = (a->M >= 64 && a->M <= 128 && ctiles * kg_cdiv(a->M, 64) >= 600) ? 64 : 32, ks = 1;
+    // the critic's 3n launches (D2 / D3 at 192 samples, tools/time_aggconv.py KG_AGGCONV_SWEEP=1): eight waves that
+    // split the channel slices in two share one staged source span per 64 rows - 10-12 % faster than the above
+    if (a->M >= 128 && ctiles * kg_cdiv(a->M, 64) >= 900) { bm = 64; ks = 2; }
+    if (envplan > 0) {
+        bm = envplan / 10;
+        ks = envplan % 10;
+    }
+    // (any other number is the 32-row tile / the four-wave form)
+    p->BM = bm == 64 ? 64 : 32;
+    p->KS = ks == 2 ? 2 : 1;
+    p->XE = wide ? 6 : 3;
+    p->ADD = a->add || a->M % p->BM != 0;
+    p->grid_x = (int)ctiles;
+    p->grid_y = kg_cdiv(a->M, p->BM);
+    size_t lds = (size_t)(2 * DK * p->spanp + 2 * 3 * DK * (p->BM + 1)) * sizeof(float);
+    if (p->KS == 2 && lds < (size_t)NW * (p->BM / 32) * 16 * 64 * sizeof(float)) lds = (size_t)NW * (p->BM / 32) * 16 * 64 * sizeof(float);
+    p->lds_bytes = (int)lds;
+    return 0;
+}
+
+template <bool LB>
+int launch_tiny(const KgAggConvArgs* a, const KgLabelBiasArgs* lb, hipStream_t s) {
+    KgAggConvPlanInfo p;
+    if (int rc = plan_tiny(a, LB ? lb->J : 0, &p)) return rc;
+    const int rg = p.RG;
     AtPlan pl;
-    pl.fc = FastDiv::make((unsigned)cps);
+    pl.fc = FastDiv::make((unsigned)(p.grid_x / a->N));
     pl.fw = FastDiv::make((unsigned)a->W);
     pl.fm = FastDiv::make((unsigned)a->M);
-    const size_t lds = (size_t)(((a->K * a->V * a->W + 3) & ~3) + (LB ? a->K * a->M * lb->J + lb->J : 0)) * sizeof(float);
+    const size_t lds = (size_t)p.lds_bytes;
     KgLabelBiasArgs none = {};
     const KgLabelBiasArgs& l = LB ? *lb : none;
-    const dim3 grid((unsigned)(a->N * cps));
+    const dim3 grid((unsigned)p.grid_x);
     static unsigned long long attr_mask = 0;
     if (LB && kg_first_on_device(attr_mask)) {
         KG_SET_DYN_LDS((kg_aggconv_tiny_kernel<32, 1, LB>), 80 * 1024);
@@ -525,17 +585,17 @@ int launch_tiny(const KgAggConvArgs* a, const KgLabelBiasArgs* lb, hipStream_t s
         KG_SET_DYN_LDS((kg_aggconv_tiny_kernel<64, 2, LB>), 80 * 1024);
         KG_SET_DYN_LDS((kg_aggconv_tiny_kernel<64, 4, LB>), 80 * 1024);
     }
-    if (a->M <= 32) launch_tiny_rg<32, LB>(rg, grid, lds, s, a, l, pl);
+    if (p.MT == 32) launch_tiny_rg<32, LB>(rg, grid, lds, s, a, l, pl);
     else            launch_tiny_rg<64, LB>(rg, grid, lds, s, a, l, pl);
     return kg_launch_status(LB ? "kg_aggconv_label" : "kg_aggconv (tiny)");
 }
 
-int validate(const KgAggConvArgs* a) {
+int validate(const KgAggConvArgs* a, bool ptrs = true) {
     KG_REQUIRE(a != nullptr, "kg_aggconv: null args");
     KG_REQUIRE(a->N > 0 && a->Cin > 0 && a->M > 0 && a->T > 0 && a->V > 0 && a->W > 0, "kg_aggconv: bad dims");
     KG_REQUIRE(a->K >= 1 && a->K <= 3, "kg_aggconv: K=%d (1..3)", a->K);
     KG_REQUIRE((long)a->N * a->T * a->W < (1L << 31) && (long)a->N * a->T < (1L << 30), "kg_aggconv: too many columns");
-    KG_REQUIRE(a->x && a->a && a->nbr && a->w && a->out, "kg_aggconv: null pointer");
+    KG_REQUIRE(!ptrs || (a->x && a->a && a->nbr && a->w && a->out), "kg_aggconv: null pointer");
     for (int k = 0; k < 3; ++k)
         KG_REQUIRE(a->pcount[k] >= 0 && a->pcount[k] <= PMAX, "kg_aggconv: pcount[%d]=%d", k, a->pcount[k]);
     KG_REQUIRE(a->pcount[0] <= 1 && a->pcount[2] <= 1,
@@ -548,15 +608,14 @@ int validate(const KgAggConvArgs* a) {
     return 0;
 }
 
-// floats of one staged source row: the frames a 128-column tile can touch
-int span_of(const KgAggConvArgs* a) { return ((BN - 1) / a->W + 2) * a->V; }
-
 template <int BM, int XE, int KS, bool XA>
-int launch_xa(const KgAggConvArgs* a, const AcPlan& pl, hipStream_t s) {
-    const int ncols = a->N * a->T * a->W;
-    dim3 grid(kg_cdiv(ncols, BN), kg_cdiv(a->M, BM));
-    size_t lds = (size_t)(2 * DK * pl.spanp + 2 * 3 * DK * (BM + 1)) * sizeof(float);
-    if (KS == 2 && lds < (size_t)NW * (BM / 32) * 16 * 64 * sizeof(float)) lds = (size_t)NW * (BM / 32) * 16 * 64 * sizeof(float);
+int launch_xa(const KgAggConvArgs* a, const KgAggConvPlanInfo& p, hipStream_t s) {
+    AcPlan pl;
+    pl.spanp = p.spanp;
+    pl.tapmask = p.tapmask;
+    pl.xa_store = p.XA;
+    dim3 grid(p.grid_x, p.grid_y);
+    const size_t lds = (size_t)p.lds_bytes;
     auto kern0 = kg_aggconv_kernel<BM, XE, KS, XA, false, 1, 4, 1>;
     auto kern1 = kg_aggconv_kernel<BM, XE, KS, XA, true, 1, 4, 1>;
     static unsigned long long attr_mask = 0;
@@ -564,14 +623,24 @@ int launch_xa(const KgAggConvArgs* a, const AcPlan& pl, hipStream_t s) {
         KG_SET_DYN_LDS(kern0, 96 * 1024);
         KG_SET_DYN_LDS(kern1, 96 * 1024);
     }
-    if (a->add || a->M % BM != 0) hipLaunchKernelGGL(kern1, grid, dim3(64 * NW * KS), lds, s, *a, pl);
-    else                          hipLaunchKernelGGL(kern0, grid, dim3(64 * NW * KS), lds, s, *a, pl);
+    if (p.ADD) hipLaunchKernelGGL(kern1, grid, dim3(64 * NW * KS), lds, s, *a, pl);
+    else       hipLaunchKernelGGL(kern0, grid, dim3(64 * NW * KS), lds, s, *a, pl);
     return kg_launch_status("kg_aggconv");
 }
 
 template <int BM, int XE, int KS>
-int launch(const KgAggConvArgs* a, const AcPlan& pl, hipStream_t s) {
-    return pl.xa_store ? launch_xa<BM, XE, KS, true>(a, pl, s) : launch_xa<BM, XE, KS, false>(a, pl, s);
+int launch(const KgAggConvArgs* a, const KgAggConvPlanInfo& p, hipStream_t s) {
+    return p.XA ? launch_xa<BM, XE, KS, true>(a, p, s) : launch_xa<BM, XE, KS, false>(a, p, s);
+}
+
+// what kg_aggconv_label requires of the launch geometry (label_J: the embedding width)
+int label_check(const KgAggConvArgs* a, int label_J) {
+    KG_REQUIRE(a->add == nullptr, "kg_aggconv_label: the label bias takes the place of `add`");
+    KG_REQUIRE(tiny_geometry(a), "kg_aggconv_label: K=%d Cin=%d M=%d V=%d W=%d is not the tiny-channel geometry",
+               a->K, a->Cin, a->M, a->V, a->W);
+    KG_REQUIRE(label_J > 0 && label_J <= AT_MAXJ && a->K * a->M * label_J <= AT_MAXWC,
+               "kg_aggconv_label: J=%d exceeds the kernel's LDS tables", label_J);
+    return 0;
 }
 
 }  // namespace
@@ -586,47 +655,42 @@ extern "C" int kg_aggconv(const KgAggConvArgs* a, void* stream) {
     if (int rc = validate(a)) return rc;
     KG_REQUIRE(a->xa == nullptr || (a->xa_sC > 0), "kg_aggconv: xa strides");
     if (tiny_form(a)) return launch_tiny<false>(a, nullptr, (hipStream_t)stream);
-    const int span = span_of(a);
-    KG_REQUIRE(span <= 384, "kg_aggconv: source span %d floats per tile > 384 (use kg_agg_expand + kg_conv)", span);
-    KG_REQUIRE(a->xa == nullptr || (a->xa_sC > 0), "kg_aggconv: xa strides");
-    AcPlan pl;
-    pl.spanp = (span + 3) / 4 * 4;
-    pl.tapmask = 0;
-    for (int k = 0; k < a->K; ++k)
-        if (a->pcount[k] > 0) pl.tapmask |= 1 << k;
-    pl.xa_store = a->xa != nullptr;
+    KgAggConvPlanInfo p;
+    if (int rc = plan_tile(a, &p)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const bool wide = pl.spanp > 192;
-    // tuning hook (tools/time_aggconv.py): KG_AGGCONV_PLAN = "<BM><KS>", e.g. "642"
-    const int envplan = kg_env().aggconv_plan;
-    // 64-row tiles (every source row staged and aggregated once per 64 output channels) where they still leave every
-    // CU two or more workgroups; measured on MI355X (profiles/r02_time_aggconv.log)
-    const long ctiles = kg_cdiv((long)a->N * a->T * a->W, BN);
-    int bm = (a->M >= 64 && a->M <= 128 && ctiles * kg_cdiv(a->M, 64) >= 600) ? 64 : 32, ks = 1;
-    // the critic's 3n launches (D2 / D3 at 192 samples, tools/time_aggconv.py KG_AGGCONV_SWEEP=1): eight waves that
-    // split the channel slices in two share one staged source span per 64 rows - 10-12 % faster than the above
-    if (a->M >= 128 && ctiles * kg_cdiv(a->M, 64) >= 900) { bm = 64; ks = 2; }
-    if (envplan > 0) {
-        bm = envplan / 10;
-        ks = envplan % 10;
-    }
-    if (bm == 64 && ks == 2) return wide ? launch<64, 6, 2>(a, pl, s) : launch<64, 3, 2>(a, pl, s);
-    if (bm == 64)            return wide ? launch<64, 6, 1>(a, pl, s) : launch<64, 3, 1>(a, pl, s);
-    if (ks == 2)             return wide ? launch<32, 6, 2>(a, pl, s) : launch<32, 3, 2>(a, pl, s);
-    return wide ? launch<32, 6, 1>(a, pl, s) : launch<32, 3, 1>(a, pl, s);
+    const bool wide = p.XE == 6;
+    if (p.BM == 64 && p.KS == 2) return wide ? launch<64, 6, 2>(a, p, s) : launch<64, 3, 2>(a, p, s);
+    if (p.BM == 64)              return wide ? launch<64, 6, 1>(a, p, s) : launch<64, 3, 1>(a, p, s);
+    if (p.KS == 2)               return wide ? launch<32, 6, 2>(a, p, s) : launch<32, 3, 2>(a, p, s);
+    return wide ? launch<32, 6, 1>(a, p, s) : launch<32, 3, 1>(a, p, s);
 }
 
 extern "C" int kg_aggconv_label(const KgAggConvArgs* a, const KgLabelBiasArgs* lb, void* stream) {
     if (int rc = validate(a)) return rc;
     KG_REQUIRE(a->xa == nullptr || (a->xa_sC > 0), "kg_aggconv_label: xa strides");
-    KG_REQUIRE(a->add == nullptr, "kg_aggconv_label: the label bias takes the place of `add`");
-    KG_REQUIRE(tiny_geometry(a), "kg_aggconv_label: K=%d Cin=%d M=%d V=%d W=%d is not the tiny-channel geometry",
-               a->K, a->Cin, a->M, a->V, a->W);
     KG_REQUIRE(lb != nullptr && lb->labels && lb->emb && lb->w, "kg_aggconv_label: null label-bias args");
+    if (int rc = label_check(a, lb->J)) return rc;
     KG_REQUIRE(lb->N == a->N && lb->K == a->K && lb->C == a->M && lb->V == a->V && lb->W == a->W,
                "kg_aggconv_label: label bias (N=%d K=%d C=%d V=%d W=%d) does not match the launch", lb->N, lb->K, lb->C,
                lb->V, lb->W);
-    KG_REQUIRE(lb->L > 0 && lb->J > 0 && lb->J <= AT_MAXJ && a->K * a->M * lb->J <= AT_MAXWC,
-               "kg_aggconv_label: L=%d J=%d exceed the kernel's LDS tables", lb->L, lb->J);
+    KG_REQUIRE(lb->L > 0, "kg_aggconv_label: L=%d", lb->L);
     return launch_tiny<true>(a, lb, (hipStream_t)stream);
+}
+
+// tests / tuning: the plan of kg_aggconv (label_J = 0) / kg_aggconv_label (label_J > 0); nothing is launched
+extern "C" int kg_aggconv_plan_info(const KgAggConvArgs* a, int32_t label_J, KgAggConvPlanInfo* info) {
+    KG_REQUIRE(a != nullptr && info != nullptr, "kg_aggconv_plan_info: null argument");
+    KG_REQUIRE(label_J >= 0, "kg_aggconv_plan_info: label_J=%d", label_J);
+    if (int rc = validate(a, false)) return rc;
+    KgAggConvPlanInfo p;
+    if (label_J > 0) {
+        if (int rc = label_check(a, label_J)) return rc;
+        if (int rc = plan_tiny(a, label_J, &p)) return rc;
+    } else if (tiny_form(a)) {
+        if (int rc = plan_tiny(a, 0, &p)) return rc;
+    } else {
+        if (int rc = plan_tile(a, &p)) return rc;
+    }
+    *info = p;
+    return 0;
 }

@@ -112,8 +112,16 @@ int main(void) {
     ac.x_sN = 704; ac.x_sC = 64 * 704; ac.w_sT = 64 * 32; ac.w_sO = 32; ac.w_sI = 1; ac.o_sN = 704; ac.o_sC = 64 * 704;
     ac.pcount[0] = 1; ac.pcount[1] = 4; ac.pcount[2] = 1;
     CHECK(kg_aggconv_supported(&ac) == 1);
+    KgAggConvPlanInfo acp;
+    CHECK(kg_aggconv_plan_info(&ac, 0, &acp) == 0 && acp.tiny == 0 && acp.BM == 32 && acp.KS == 1 && acp.XE == 3 && acp.tapmask == 7);
+    CHECK(kg_aggconv_plan_info(&ac, 0, 0) < 0 && kg_aggconv_plan_info(0, 0, &acp) < 0);
+    CHECK(kg_aggconv_plan_info(&ac, 20, &acp) < 0 && strstr(kg_last_error(), "tiny-channel") != 0);
+    ac.Cin = 3; ac.M = 32;
+    CHECK(kg_aggconv_plan_info(&ac, 20, &acp) == 0 && acp.tiny == 1 && acp.LB == 1 && acp.MT == 32);
+    ac.Cin = 32; ac.M = 64;
     ac.V = 25; ac.W = 1;
     CHECK(kg_aggconv_supported(&ac) == 0);
+    CHECK(kg_aggconv_plan_info(&ac, 0, &acp) < 0 && strstr(kg_last_error(), "span") != 0);
     ac.pcount[0] = 3;
     CHECK(kg_aggconv(&ac, 0) < 0);
     /* aggregation / reductions: scratch sizing and rejection of broken arguments */
@@ -122,6 +130,21 @@ int main(void) {
     ag.N = 64; ag.C = 32; ag.K = 3; ag.V = 11; ag.W = 11; ag.T = 64; ag.rep = 1;
     ag.x = ag.y = (const float*)0x1000; ag.x_sN = 704; ag.x_sC = 64 * 704; ag.y_sN = 704; ag.y_sC = 64 * 704;
     CHECK(kg_agg_outer_workspace_bytes(&ag) > 0);
+    /* plan reports: the launchers' planning functions on geometry alone (no operand is needed, nothing is launched) */
+    KgAggPlanInfo agp;
+    ag.o_sN = 704; ag.o_sC = 64 * 704;
+    for (int op = KG_AGG_OP_EXPAND; op <= KG_AGG_OP_OUTER; ++op) CHECK(kg_agg_plan_info(&ag, op, &agp) == 0 && agp.grid_x >= 1);
+    CHECK(agp.form == KG_AGG_FORM_OUTER_MFMA && agp.slabs == agp.grid_x && agp.slabs == kg_agg_outer_slabs(&ag));
+    CHECK(kg_agg_plan_info(&ag, 3, &agp) < 0 && kg_agg_plan_info(&ag, 0, 0) < 0 && kg_agg_plan_info(0, 0, &agp) < 0);
+    {
+        KgAggArgs many[19];
+        int32_t la[19], ns[19];
+        for (int i = 0; i < 19; ++i) { many[i] = ag; many[i].rep = i == 0 ? 2 : 1; many[i].y_sN = 704 * many[i].rep; many[i].y_sC = 64 * many[i].y_sN; }
+        CHECK(kg_agg_outer_many_plan(many, 19, la, ns) == 0 && la[0] == -1 && la[1] == 0 && la[8] == 0 && la[9] == 1 && la[15] == 1 && la[16] == 2);
+        CHECK(kg_agg_outer_many_plan(many, 0, la, ns) < 0 && kg_agg_outer_many_plan(many, 19, 0, ns) < 0);
+        many[7].V = 26;
+        CHECK(kg_agg_outer_many_plan(many, 19, la, ns) < 0 && strstr(kg_last_error(), "job 7") != 0);
+    }
     ag.K = 0;
     CHECK(kg_agg_expand(&ag, 0) < 0);
     KgRowsumArgs rs;

@@ -183,6 +183,83 @@ def test_wgrad_plan_reports_validate_without_gpu(lib):
     assert _native.last_wgrad_plan is None          # the hook is off unless a test switches it on
 
 
+def test_agg_plan_reports_validate_without_gpu(lib):
+    """kg_agg_plan_info / kg_agg_outer_many_plan / kg_aggconv_plan_info (additive, ABI v9): null arguments and a bad `op` are
+    rejected by name, bad geometry fails with the launcher's own message and leaves the output untouched, good geometry is
+    planned on the host - no operand pointer is needed, nothing is launched - and agrees with kg_agg_outer_slabs /
+    kg_aggconv_supported."""
+    p = _native._AggPlanInfo()
+    p.form = -7
+    a = _native._AggArgs()
+    assert lib.kg_agg_plan_info(None, 0, ctypes.byref(p)) < 0 and b"kg_agg_plan_info: null" in lib.kg_last_error()
+    assert lib.kg_agg_plan_info(ctypes.byref(a), 0, None) < 0 and b"kg_agg_plan_info: null" in lib.kg_last_error()
+    assert lib.kg_agg_plan_info(ctypes.byref(a), 3, ctypes.byref(p)) < 0 and b"kg_agg_plan_info: op=3" in lib.kg_last_error()
+    for op, who in ((_native.AGG_OP_EXPAND, b"kg_agg_expand: bad dims"), (_native.AGG_OP_REDUCE, b"kg_agg_reduce: bad dims"),
+                    (_native.AGG_OP_OUTER, b"kg_agg_outer: bad dims")):
+        assert lib.kg_agg_plan_info(ctypes.byref(a), op, ctypes.byref(p)) < 0 and who in lib.kg_last_error()
+    assert p.form == -7
+    a.N, a.C, a.K, a.V, a.W, a.T, a.rep = 64, 32, 3, 25, 11, 64, 1            # all pointers null: geometry only
+    a.x_sN, a.x_sC, a.y_sN, a.y_sC, a.o_sN, a.o_sC = 64 * 25, 64 * 64 * 25, 64 * 11, 64 * 64 * 11, 64 * 11, 64 * 64 * 11
+    assert lib.kg_agg_plan_info(ctypes.byref(a), _native.AGG_OP_EXPAND, ctypes.byref(p)) == 0
+    assert p.form == _native.AGG_FORM_MFMA and (p.KI, p.KO, p.KS, p.RES, p.MSK) == (1, 3, 13, 0, 0) and p.ntiles == p.tiles_per_c * 32
+    assert lib.kg_agg_plan_info(ctypes.byref(a), _native.AGG_OP_OUTER, ctypes.byref(p)) == 0
+    assert p.form == _native.AGG_FORM_OUTER_MFMA and (p.K, p.TV, p.TW) == (3, 2, 1) and p.slabs == lib.kg_agg_outer_slabs(ctypes.byref(a)) == p.grid_x
+    a.mask = 0x1000                                                           # (never read)
+    assert lib.kg_agg_plan_info(ctypes.byref(a), _native.AGG_OP_EXPAND, ctypes.byref(p)) < 0 and b"kg_agg_reduce" in lib.kg_last_error()
+    a.V, a.W, a.o_sN, a.o_sC = 11, 25, 64 * 25, 64 * 64 * 25
+    a.x_sN, a.x_sC = 64 * 11, 64 * 64 * 11
+    assert lib.kg_agg_plan_info(ctypes.byref(a), _native.AGG_OP_REDUCE, ctypes.byref(p)) == 0
+    assert p.form == _native.AGG_FORM_MFMA and (p.KI, p.KO, p.KS, p.RES, p.MSK) == (3, 1, 17, 0, 1)
+    a.rep = 2
+    assert lib.kg_agg_plan_info(ctypes.byref(a), _native.AGG_OP_REDUCE, ctypes.byref(p)) < 0 and b"fold" in lib.kg_last_error()
+    a.mask = None
+    assert lib.kg_agg_plan_info(ctypes.byref(a), _native.AGG_OP_REDUCE, ctypes.byref(p)) == 0 and p.form != _native.AGG_FORM_MFMA
+    # kg_agg_outer_many_plan
+    arr = (_native._AggArgs * 3)()
+    la, ns = (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)()
+    assert lib.kg_agg_outer_many_plan(None, 1, la, ns) < 0 and b"kg_agg_outer_many_plan: no jobs" in lib.kg_last_error()
+    assert lib.kg_agg_outer_many_plan(arr, 0, la, ns) < 0 and b"kg_agg_outer_many_plan: no jobs" in lib.kg_last_error()
+    assert lib.kg_agg_outer_many_plan(arr, 3, None, ns) < 0 and b"kg_agg_outer_many_plan: null output" in lib.kg_last_error()
+    assert lib.kg_agg_outer_many_plan(arr, 3, la, None) < 0 and b"kg_agg_outer_many_plan: null output" in lib.kg_last_error()
+    assert lib.kg_agg_outer_many_plan(arr, 3, la, ns) < 0 and b"kg_agg_outer_many: job 0 bad dims" in lib.kg_last_error()   # empty structs
+    for i in range(3):
+        j = arr[i]
+        j.N, j.C, j.K, j.V, j.W, j.T, j.rep = 8, 4 + i, 3, 11, 5, 16, 2 if i == 1 else 1
+        j.x_sN, j.x_sC, j.y_sN, j.y_sC = 16 * 11, 8 * 16 * 11, 16 * j.rep * 5, 8 * 16 * j.rep * 5
+    assert lib.kg_agg_outer_many_plan(arr, 3, la, ns) == 0 and list(la) == [0, -1, 0]
+    assert list(ns) == [lib.kg_agg_outer_slabs(ctypes.byref(arr[i])) for i in range(3)]
+    arr[2].K = 2
+    assert lib.kg_agg_outer_many_plan(arr, 3, la, ns) < 0 and b"job 2 K=2" in lib.kg_last_error()
+    # kg_aggconv_plan_info
+    q = _native._AggConvPlanInfo()
+    q.tiny = -7
+    c = _native._AggConvArgs()
+    assert lib.kg_aggconv_plan_info(None, 0, ctypes.byref(q)) < 0 and b"kg_aggconv_plan_info: null" in lib.kg_last_error()
+    assert lib.kg_aggconv_plan_info(ctypes.byref(c), 0, None) < 0 and b"kg_aggconv_plan_info: null" in lib.kg_last_error()
+    assert lib.kg_aggconv_plan_info(ctypes.byref(c), -1, ctypes.byref(q)) < 0 and b"label_J=-1" in lib.kg_last_error()
+    assert lib.kg_aggconv_plan_info(ctypes.byref(c), 0, ctypes.byref(q)) < 0 and b"kg_aggconv: bad dims" in lib.kg_last_error()
+    assert q.tiny == -7
+    c.N, c.Cin, c.M, c.T, c.V, c.W, c.K = 192, 64, 128, 64, 11, 5, 3          # the critic's D2 launch at 192 samples
+    c.x_sN, c.x_sC, c.w_sT, c.w_sO, c.w_sI, c.o_sN, c.o_sC = 64 * 11, 192 * 64 * 11, 128 * 64, 64, 1, 64 * 5, 192 * 64 * 5
+    c.pcount[0], c.pcount[1], c.pcount[2] = 1, 4, 1
+    assert lib.kg_aggconv_plan_info(ctypes.byref(c), 0, ctypes.byref(q)) == 0
+    assert (q.tiny, q.BM, q.KS, q.XE, q.XA, q.ADD, q.tapmask) == (0, 64, 2, 6, 0, 0, 7) and q.spanp == (127 // 5 + 2) * 11 + 3 & ~3
+    assert (q.grid_x, q.grid_y) == (192 * 64 * 5 // 128, 2)
+    c.xa, c.add = 0x1000, 0x1000                                              # (never read)
+    assert lib.kg_aggconv_plan_info(ctypes.byref(c), 0, ctypes.byref(q)) == 0 and (q.XA, q.ADD) == (1, 1)
+    assert lib.kg_aggconv_plan_info(ctypes.byref(c), 20, ctypes.byref(q)) < 0 and b"takes the place of `add`" in lib.kg_last_error()
+    c.add = None
+    assert lib.kg_aggconv_plan_info(ctypes.byref(c), 20, ctypes.byref(q)) < 0 and b"tiny-channel geometry" in lib.kg_last_error()
+    c.Cin, c.M = 3, 32
+    assert lib.kg_aggconv_plan_info(ctypes.byref(c), 20, ctypes.byref(q)) == 0 and (q.tiny, q.MT, q.RG, q.LB) == (1, 32, 4, 1)     # 192 x 2 workgroups of 256 columns < 512: four threads per column
+    assert q.lds_bytes == 4 * ((3 * 11 * 5 + 3 & ~3) + 3 * 32 * 20 + 20)
+    assert lib.kg_aggconv_plan_info(ctypes.byref(c), 0, ctypes.byref(q)) == 0 and (q.tiny, q.LB) == (1, 0)
+    c.V, c.W = 25, 1                                                          # 129 frames x 25 floats per staged row
+    c.Cin = 8
+    assert lib.kg_aggconv_plan_info(ctypes.byref(c), 0, ctypes.byref(q)) < 0 and b"source span" in lib.kg_last_error()
+    assert _native.last_agg_plan is None and _native.last_aggconv_plan is None       # the hooks are off unless a test switches them on
+
+
 def test_mapping_network_entry_points_validate_without_gpu(lib):
     """kg_linear_fwd / kg_linear_bwd / kg_embed_bwd (ABI v6): argument checking happens before any launch."""
     a = _native._LinearArgs()

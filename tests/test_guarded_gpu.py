@@ -27,6 +27,7 @@ from kinetic_gan_amd.wgan_gp import Trainer
 from oracle import prim_ref
 from oracle.fill import rand_inputs, rand_noise
 from tests import guard
+from tests import test_agg_forms_gpu as ta
 from tests import test_d0_fused_gpu as td
 from tests import test_ema_gpu as te
 from tests import test_kernels_gpu as tk
@@ -250,6 +251,8 @@ KERNEL_CASES = {
     "agg V = 1": _k(tk.test_agg_family, 2, 512, 8, 1, 1, 3, 1, expect=["agg_expand", "agg_reduce", "agg_outer"]),
     "agg rep 3": _k(tk.test_agg_family, 2, 40, 6, 7, 16, 1, 3, expect=["agg_expand", "agg_reduce", "agg_outer"]),
     "agg_reduce residual + mask epilogue": _k(tk.test_agg_reduce_residual_and_mask_epilogue, 5, 64, 32, 5, 11, 2, True, 3, "auto", expect=["agg_reduce"]),
+    "agg_reduce on the matrix cores, ragged last tile, residual + mask epilogue": _k(ta.test_agg_case, "mfma reduce SUB3 V5 485 frames", expect=["agg_reduce"]),
+    "aggconv forced 64-row tile with two k-groups (642)": _k(ta.test_aggconv_case, "tile 642 XE6 XA1 ADD1", expect=["aggconv"]),
     "agg_outer deferred sums": _k(tk.test_agg_outer_deferred_sums_one_launch, expect=["agg_outer", "agg_outer_finish"]),
     "gen_expand / fold / adj_finish, 3 channels": _k(tk.test_gen_expand_fold_adjfinish, *tk.GEN_CASES[0], expect=["gen_expand", "gen_fold", "gen_adj_finish"]),
     "gen_expand / fold / adj_finish, single vertex": _k(tk.test_gen_expand_fold_adjfinish, *tk.GEN_CASES[4], expect=["gen_expand", "gen_fold", "gen_adj_finish"]),

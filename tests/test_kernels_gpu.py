@@ -431,16 +431,23 @@ def test_agg_family(N, C, T, V, W, K, rep, monkeypatch):
     y2c = layouts(y2r)[1][1]
     monkeypatch.setenv("KG_AGG_MFMA", "0")
     for mode in ("0", "1", "mfma"):
+        # the form that must run: the forced one wherever the launch is eligible (matrix cores: K = 3 and rep = 1; these
+        # channel-major operands take the stream kernels at every size), else one thread per frame
+        want = nv.AGG_FORM_STREAM if mode == "1" else nv.AGG_FORM_MFMA if mode == "mfma" and K == 3 and rep == 1 else nv.AGG_FORM_FRAME
         if mode == "mfma":
             monkeypatch.delenv("KG_AGG_STREAM")
             monkeypatch.setenv("KG_AGG_MFMA", "1")
             mode = "0"
         monkeypatch.setenv("KG_AGG_STREAM", mode)
+        plan = []
+        monkeypatch.setattr(nv, "last_agg_plan", plan)
         close(nv.agg_expand(xl.to(d), A.to(d), rep), pr.agg_expand(x, A, rep))
         close(nv.agg_reduce(y2c.to(d), A.to(d), rep), pr.agg_reduce(y2r, A, rep))
         At = A.transpose(1, 2).contiguous().to(d)
         close(nv.agg_expand(xl.to(d), At.transpose(1, 2), rep), pr.agg_expand(x, A, rep))
         close(nv.agg_reduce(y2c.to(d), At.transpose(1, 2), rep), pr.agg_reduce(y2r, A, rep))
+        monkeypatch.setattr(nv, "last_agg_plan", None)
+        assert [p["form"] for p in plan] == [want] * 4, (mode, want, plan)
     monkeypatch.delenv("KG_AGG_STREAM")
     monkeypatch.delenv("KG_AGG_MFMA")
     # reduce: y2 has V on its vertex axis
@@ -1295,10 +1302,17 @@ def test_agg_reduce_residual_and_mask_epilogue(N, C, T, V, W, s, drop, K, form, 
     mask = layouts(rnd(N, C, T, W, seed=3))[1][1]
     invd = None if inv is None else inv.to(d)
     ref = pr.agg_reduce(y, A, 1, res=res, res_tstride=s, res_inv=inv, mask=mask)
+    plan = []
+    monkeypatch.setattr(nv, "last_agg_plan", plan)
     close(nv.agg_reduce(y.to(d), A.to(d), 1, res=res.to(d), res_tstride=s, res_inv=invd, mask=mask.to(d)), ref)
     close(nv.agg_reduce(y.to(d), A.to(d), 1, mask=mask.to(d), slope=0.1), pr.agg_reduce(y, A, 1, mask=mask, slope=0.1))
     close(nv.agg_reduce(y.to(d), A.to(d), 1, res=res.to(d), res_tstride=s, res_inv=invd), pr.agg_reduce(y, A, 1, res=res, res_tstride=s, res_inv=inv))
     close(nv.agg_reduce(y.to(d), A.to(d), 1), pr.agg_reduce(y, A, 1))
+    monkeypatch.setattr(nv, "last_agg_plan", None)
+    if form != "auto":       # the forced form ran wherever the launch is eligible (matrix cores: K = 3; the stream kernels take all of these)
+        want = {"frame": nv.AGG_FORM_FRAME, "stream": nv.AGG_FORM_STREAM, "mfma": nv.AGG_FORM_MFMA if K == 3 else nv.AGG_FORM_FRAME}[form]
+        assert [p["form"] for p in plan] == [want] * 4 and [(p["RES"], p["MSK"]) for p in plan] == (
+            [(1, 1), (0, 1), (1, 0), (0, 0)] if want == nv.AGG_FORM_MFMA else [(0, 0)] * 4), (form, plan)
 
 
 @pytest.mark.parametrize("N,C,T,V,bn_t,res,act", [(64, 3, 64, 25, False, "identity", "tanh"), (64, 32, 16, 11, False, "bn", "lrelu"),
