@@ -123,6 +123,36 @@ int     kg_conv(const KgConvArgs* a, void* stream);
  * arguments.  Replaces nothing in the reference (a layout transform of discriminator.py:99-105,115-120's weights).       */
 int64_t kg_conv_pack_bytes(const KgConvArgs* a);
 int     kg_conv_pack(const KgConvArgs* a, void* wpack, int64_t wpack_bytes, void* stream);
+/* tests / tuning (additive, ABI v9): the kernel family, the template instantiation and the launch geometry kg_conv /
+ * kg_conv_many take for these arguments under the current KG_CONV_* switches - from the same host functions as the launch
+ * itself.  Only dimensions, strides, the null-ness of add / mask / sync / vmap / wpack and the 16-byte alignment of x / wpack
+ * are read: no pointer is dereferenced, nothing is launched.  Fields that do not belong to the reported family are 0.    */
+#define KG_CONV_FAMILY_DIRECT 0      /* kg_conv_kernel<BM, NW, KF, KW, FAST, PLAIN, INK>                               */
+#define KG_CONV_FAMILY_TINY 1        /* kg_conv_tiny_kernel<MT>                                                        */
+#define KG_CONV_FAMILY_BS 2          /* kg_conv_bs_kernel<TM, RWV, CWV>: bf16-split, column (or 4-byte window) staging */
+#define KG_CONV_FAMILY_BSW 3         /* kg_conv_bsw_kernel<TM, RWV, CWV, PLAIN>: bf16-split, every group a 16-byte window */
+#define KG_CONV_FAMILY_MANY 4        /* kg_conv_many_kernel<BM, KF, PLAIN> (KgConvManyForm)                            */
+#define KG_CONV_FAMILY_RING 5        /* the LDS-ring form (not in the default build): only `tile` is reported          */
+typedef struct KgConvFormInfo {
+    int32_t family, tile;                    /* tile: the code of kg_conv_plan_info                                   */
+    int32_t BM, NW, KW, KF, FAST, PLAIN, INK;/* direct: the instantiation (KW 4 = K32x32); bs / bsw: BM (rows), PLAIN (bsw) */
+    int32_t TM, RWV, CWV;                    /* bs / bsw: the tile variant                                            */
+    int32_t MT;                              /* tiny: 4 / 16 rows                                                     */
+    int32_t nsplit, per;                     /* workgroups along K, K-slices per split                                */
+    int32_t epilogue;                        /* 1: the kg_conv_splitk_epilogue launch follows (K-split, not INK)      */
+    int32_t pack, wpack;                     /* bs / bsw: the weight-pack launch precedes; the caller's wpack is used  */
+    int32_t win[2];                          /* bs / bsw: group staged as a window (0 no, 1 4-byte, 2 16-byte loads)   */
+    int32_t xcd;                             /* 1: XCD-aware 1-D tile order (column tiles padded to a multiple of 8)   */
+    int32_t grid_x, grid_y, grid_z;
+} KgConvFormInfo;
+int     kg_conv_form_info(const KgConvArgs* a, KgConvFormInfo* info);
+typedef struct KgConvManyForm {
+    int32_t tile;                            /* the shared launch's plan tile (0 / 1 / 2), or -1: one kg_conv per job  */
+    int32_t BM, KF, PLAIN;                   /* kg_conv_many_kernel<BM, KF, PLAIN> (every job: NW 4, KW 1, FAST 2)     */
+    int32_t njobs, total_wg;                 /* grid of the shared launch                                             */
+    int32_t xcd[4], wg_begin[4], nwg[4];     /* per job: tile order, first workgroup, workgroups that do work          */
+} KgConvManyForm;
+int     kg_conv_many_form(const KgConvArgs* jobs, int32_t njobs, KgConvManyForm* form);
 
 /* ---- weight gradient of the tap GEMM -----------------------------------------------------------
  *   dW(d, m, c) = sum_j  G[m, j] * X[c (+ d*Cin if CHANBLOCK), src(j, d)]      (src as `forward`)

@@ -137,9 +137,26 @@ class _AggConvPlanInfo(C.Structure):
         "tiny", "MT", "RG", "LB", "BM", "KS", "XE", "XA", "ADD", "tapmask", "spanp", "grid_x", "grid_y", "lds_bytes")]
 
 
+# kernel families of kg_conv / kg_conv_many, as kg_conv_form_info names them
+CONV_FAMILY_DIRECT, CONV_FAMILY_TINY, CONV_FAMILY_BS, CONV_FAMILY_BSW, CONV_FAMILY_MANY, CONV_FAMILY_RING = 0, 1, 2, 3, 4, 5
+CONV_FAMILY_NAMES = {CONV_FAMILY_DIRECT: "direct", CONV_FAMILY_TINY: "tiny", CONV_FAMILY_BS: "bs", CONV_FAMILY_BSW: "bsw",
+                     CONV_FAMILY_MANY: "many", CONV_FAMILY_RING: "ring"}
+
+
+class _ConvFormInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "family", "tile", "BM", "NW", "KW", "KF", "FAST", "PLAIN", "INK", "TM", "RWV", "CWV", "MT", "nsplit", "per",
+        "epilogue", "pack", "wpack")] + [("win", C.c_int32 * 2)] + [(n, C.c_int32) for n in ("xcd", "grid_x", "grid_y", "grid_z")]
+
+
+class _ConvManyForm(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tile", "BM", "KF", "PLAIN", "njobs", "total_wg")] + [
+        ("xcd", C.c_int32 * 4), ("wg_begin", C.c_int32 * 4), ("nwg", C.c_int32 * 4)]
+
+
 def plan_dict(p) -> dict:
     """a plan report (_AggPlanInfo / _AggConvPlanInfo) as a plain dict"""
-    return {n: getattr(p, n) for n, _ in p._fields_}
+    return {n: (getattr(p, n) if isinstance(getattr(p, n), int) else list(getattr(p, n))) for n, _ in p._fields_}
 
 
 class _OuterSumJob(C.Structure):
@@ -606,6 +623,8 @@ EXPORTS = {
     "kg_peak_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "kg_conv_workspace_bytes": (C.c_int64, [C.POINTER(_ConvArgs)]),
     "kg_conv_plan_info": (C.c_int, [C.POINTER(_ConvArgs), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "kg_conv_form_info": (C.c_int, [C.POINTER(_ConvArgs), C.POINTER(_ConvFormInfo)]),
+    "kg_conv_many_form": (C.c_int, [C.POINTER(_ConvArgs), C.c_int32, C.POINTER(_ConvManyForm)]),
     "kg_conv": (C.c_int, [C.POINTER(_ConvArgs), C.c_void_p]),
     "kg_conv_pack_bytes": (C.c_int64, [C.POINTER(_ConvArgs)]),
     "kg_conv_pack": (C.c_int, [C.POINTER(_ConvArgs), C.c_void_p, C.c_int64, C.c_void_p]),
@@ -936,6 +955,28 @@ class Group(NamedTuple):
 
 
 last_conv_plan = None     # set to a list to have conv() report (tile, nsplit) of its last launch
+last_conv_form = None     # set to a list: conv() / conv_many() append the form (a dict: family name, instantiation, geometry) of
+                          # every launch, in call order - kg_conv_form_info / kg_conv_many_form on the arguments of the launch
+
+
+def conv_form_dict(a) -> dict:
+    """kg_conv_form_info of a filled KgConvArgs as a dict, `family` by name"""
+    f = _ConvFormInfo()
+    _check(load_library().kg_conv_form_info(C.byref(a), C.byref(f)), "kg_conv_form_info")
+    d = plan_dict(f)
+    d["family"] = CONV_FAMILY_NAMES[f.family]
+    return d
+
+
+def conv_many_form_dict(arr, n: int) -> dict:
+    """kg_conv_many_form of n KgConvArgs as a dict (family "many"; tile -1: one kg_conv launch per job)"""
+    f = _ConvManyForm()
+    _check(load_library().kg_conv_many_form(arr, n, C.byref(f)), "kg_conv_many_form")
+    d = plan_dict(f)
+    for k in ("xcd", "wg_begin", "nwg"):
+        d[k] = d[k][:n]
+    d["family"] = "many"
+    return d
 
 # Executed-work accounting (bench.py: SURVEY 8d "if the build prunes ... it must also report executed FLOPs"): set
 # to a dict and every launch adds the flops it really performs (2 per multiply-add, per kernel family).
@@ -1037,6 +1078,8 @@ def conv(groups: Sequence[Group], N: int, M: int, T_out: int, V_out: int,
     # (scratch only for a K-split launch, which completes its tiles itself through the ticket counters: no epilogue launch;
     #  ws and keep are held until the launch below is enqueued)
     ws = _workspace("kg_conv_workspace_bytes", a, groups[0].x.device, tickets="sync", lazy=True)
+    if last_conv_form is not None:       # (after the workspace: the ticket counters decide the completion form)
+        last_conv_form.append(conv_form_dict(a))
     _check(lib.kg_conv(C.byref(a), _stream()), "kg_conv")
     return out
 
@@ -1064,6 +1107,11 @@ def conv_many(jobs: Sequence[dict]) -> list:
             t = C.c_int32()
             lib.kg_conv_many_plan(arr, len(chunk), C.byref(t))
             last_conv_plan[:] = [t.value, 1]
+        if last_conv_form is not None:       # the shared launch, or (tile -1) the single launches that replace it
+            mf = conv_many_form_dict(arr, len(chunk))
+            last_conv_form.append(mf)
+            if mf["tile"] < 0:
+                last_conv_form.extend(conv_form_dict(arr[i]) for i in range(len(chunk)))
         _check(lib.kg_conv_many(arr, len(chunk), _stream()), "kg_conv_many")
     return outs
 

@@ -1499,10 +1499,30 @@ bool tiny_eligible(const KgConvArgs* a) {
     return terms <= TINY_MAXK && terms * (a->M <= 4 ? 4 : 16) <= 192;
 }
 
-int launch_tiny(const KgConvArgs* a, hipStream_t s) {
+// ---- launch forms.  Which instantiation a launch takes and its geometry are decided by form_tiny / form_direct / form_bs /
+// many_walk below; the launchers and the reports (kg_conv_form_info, kg_conv_many_form) both run them.  They read
+// dimensions, strides, the null-ness of add / mask / sync / vmap / wpack and the 16-byte alignment of x / wpack - no operand.
+void form_clear(KgConvFormInfo* f) {
+    *f = KgConvFormInfo{};
+    f->nsplit = 1;
+}
+
+void form_tiny(const KgConvArgs* a, KgConvFormInfo* f) {
+    form_clear(f);
     const int ncols = a->N * a->T_out * a->V_out;
-    if (a->M <= 4) hipLaunchKernelGGL(kg_conv_tiny_kernel<4>, dim3(kg_cdiv(ncols, 256)), dim3(256), 0, s, *a);
-    else           hipLaunchKernelGGL(kg_conv_tiny_kernel<16>, dim3(kg_cdiv(ncols, 256)), dim3(256), 0, s, *a);
+    f->family = KG_CONV_FAMILY_TINY;
+    f->tile = 11;
+    f->MT = a->M <= 4 ? 4 : 16;
+    f->per = 0;
+    for (int i = 0; i < a->ngroups; ++i) f->per += slices_of(a->g[i]);
+    f->grid_x = kg_cdiv(ncols, 256); f->grid_y = 1; f->grid_z = 1;
+}
+
+int launch_tiny(const KgConvArgs* a, hipStream_t s) {
+    KgConvFormInfo f;
+    form_tiny(a, &f);
+    if (f.MT == 4) hipLaunchKernelGGL(kg_conv_tiny_kernel<4>, dim3(f.grid_x), dim3(256), 0, s, *a);
+    else           hipLaunchKernelGGL(kg_conv_tiny_kernel<16>, dim3(f.grid_x), dim3(256), 0, s, *a);
     return kg_launch_status("kg_conv (tiny)");
 }
 
@@ -1743,21 +1763,39 @@ Plan make_plan(const KgConvArgs* a) {
     return p;
 }
 
-int launch_bs(const KgConvArgs* a, const Plan& p, hipStream_t s) {
+void form_bs(const KgConvArgs* a, const Plan& p, KgConvFormInfo* f) {
+    form_clear(f);
     const int ncols = a->N * a->T_out * a->V_out;
     const int ct = kg_cdiv(ncols, bs_bn(p.bs)), rt = kg_cdiv(a->M, bs_bm(p.bs));
-    dim3 grid(p.bsp.xcd ? (ct + 7) / 8 * 8 * rt : ct, p.bsp.xcd ? 1 : rt, 1);
-    const bool packed = bs_packed(a, p.bsp);
+    f->tile = 40 + p.bs;
+    f->TM = BS_TILES[p.bs].tm; f->RWV = BS_TILES[p.bs].rwv; f->CWV = BS_TILES[p.bs].cwv;
+    f->BM = bs_bm(p.bs);
+    f->nsplit = p.sp.nsplit; f->per = p.sp.per;
+    f->xcd = p.bsp.xcd;
+    f->grid_x = p.bsp.xcd ? (ct + 7) / 8 * 8 * rt : ct; f->grid_y = p.bsp.xcd ? 1 : rt; f->grid_z = 1;
+    f->wpack = bs_packed(a, p.bsp) ? 1 : 0;
+    f->pack = f->wpack ? 0 : 1;
+    // every group a 16-byte window (the D0 / D1 tails): the hand-scheduled instantiation
+    bool allwin = kg_env().conv_bs_asm != 0;
+    for (int i = 0; i < a->ngroups; ++i) { allwin = allwin && p.bsp.win[i] == 2; f->win[i] = p.bsp.win[i]; }
+    f->family = allwin ? KG_CONV_FAMILY_BSW : KG_CONV_FAMILY_BS;
+    // (the lean epilogue, see store_tile)
+    f->PLAIN = (allwin && a->add == nullptr && a->mask == nullptr && a->M % bs_bm(p.bs) == 0) ? 1 : 0;
+}
+
+int launch_bs(const KgConvArgs* a, const Plan& p, hipStream_t s) {
+    KgConvFormInfo f;
+    form_bs(a, p, &f);
+    dim3 grid(f.grid_x, f.grid_y, 1);
+    const bool packed = f.wpack != 0;
     kg_u32x4* const P = reinterpret_cast<kg_u32x4*>(packed ? const_cast<void*>(a->wpack) : (void*)a->ws);        // (16-byte aligned: checked by kg_conv)
-    if (!packed) {
+    if (f.pack) {
         hipLaunchKernelGGL(kg_conv_bs_pack_kernel, dim3(kg_cdiv((long)p.bsp.nsteps * p.bsp.mpad * 4, 256)), dim3(256), 0, s, *a, p.bsp, P);
         if (int rc = kg_launch_status("kg_conv (bf16-split, weight pack)")) return rc;
     }
-    // every group a 16-byte window (the D0 / D1 tails): the hand-scheduled instantiation
-    bool allwin = kg_env().conv_bs_asm != 0;
-    for (int i = 0; i < a->ngroups; ++i) allwin = allwin && p.bsp.win[i] == 2;
+    const bool allwin = f.family == KG_CONV_FAMILY_BSW;
     if (allwin) {
-        const bool plain = a->add == nullptr && a->mask == nullptr && a->M % bs_bm(p.bs) == 0;       // (the lean epilogue, see store_tile)
+        const bool plain = f.PLAIN != 0;
         static unsigned long long attr_mask = 0;
         if (kg_first_on_device(attr_mask)) {
 #define KG_BSW_ATTR(TM_, RWV_, CWV_, BM_) do { \
@@ -1781,31 +1819,49 @@ int launch_bs(const KgConvArgs* a, const Plan& p, hipStream_t s) {
     return kg_launch_status("kg_conv (bf16-split)");
 }
 
-template <int BM, int NW, int KW = 1>
-int launch(const KgConvArgs* a, const Plan& p, hipStream_t s) {
+void form_direct(const KgConvArgs* a, const Plan& p, KgConvFormInfo* f) {
+    form_clear(f);
+    const int BM = tile_bm(p.tile), KW = tile_kw(p.tile) ? 4 : 1, NW = tile_kw(p.tile) ? 4 : tile_bn(p.tile) / 32;
     const int ncols = a->N * a->T_out * a->V_out;
+    f->family = KG_CONV_FAMILY_DIRECT;
+    f->tile = (int32_t)p.tile;
+    f->BM = BM; f->NW = NW; f->KW = KW;
+    f->nsplit = p.sp.nsplit; f->per = p.sp.per;
+    f->xcd = p.sp.xcd;
     // 1-D tile grid, column tiles padded to a multiple of 8 (kg_tile_of_block)
     const int ct = kg_cdiv(ncols, 32 * NW / KW), rt = kg_cdiv(a->M, BM);
-    dim3 grid(p.sp.xcd ? (ct + 7) / 8 * 8 * rt : ct, p.sp.xcd ? 1 : rt, p.sp.nsplit);
+    f->grid_x = p.sp.xcd ? (ct + 7) / 8 * 8 * rt : ct; f->grid_y = p.sp.xcd ? 1 : rt; f->grid_z = p.sp.nsplit;
     // a K-split launch completes its tiles itself when the caller handed over zeroed ticket counters for them (finish_split);
     // KG_CONV_INKERNEL=0 or no counters: the separate epilogue launch
-    Split sp = p.sp;
     const int ink_max = kg_env().conv_inkernel_max > 0 ? kg_env().conv_inkernel_max : 4;
-    sp.inkernel = (BM <= 64 && sp.nsplit > 1 && sp.nsplit <= ink_max && kg_env().conv_inkernel != 0 && a->sync != nullptr &&
-                   (long)ct * rt <= a->sync_len) ? 1 : 0;
+    f->INK = (BM <= 64 && p.sp.nsplit > 1 && p.sp.nsplit <= ink_max && kg_env().conv_inkernel != 0 && a->sync != nullptr &&
+              (long)ct * rt <= a->sync_len) ? 1 : 0;
+    f->epilogue = (p.sp.nsplit > 1 && !f->INK) ? 1 : 0;
     // full K-slices everywhere (32-bit-load kernels: slices of 32 channels): the FAST instantiation
     bool fast = kg_env().conv_fast != 0;
     for (int i = 0; i < a->ngroups; ++i) fast = fast && (a->g[i].Cin % 32 == 0);
-    const bool kf = a->g[0].w_sI <= a->g[0].w_sO;
+    f->FAST = !fast ? 0 : a->ngroups == 1 ? 1 : 2;
+    f->KF = a->g[0].w_sI <= a->g[0].w_sO ? 1 : 0;
     // (the lean epilogue for the full-slice instantiations of launches without add / mask; K-split partial tiles never reach it)
-    const bool plain = a->add == nullptr && a->mask == nullptr && a->M % BM == 0 && kg_env().conv_plain_epi != 0;
+    f->PLAIN = (fast && a->add == nullptr && a->mask == nullptr && a->M % BM == 0 && kg_env().conv_plain_epi != 0) ? 1 : 0;
+}
+
+template <int BM, int NW, int KW = 1>
+int launch(const KgConvArgs* a, const Plan& p, hipStream_t s) {
+    KgConvFormInfo f;
+    form_direct(a, p, &f);
+    const int ncols = a->N * a->T_out * a->V_out;
+    dim3 grid(f.grid_x, f.grid_y, f.grid_z);
+    Split sp = p.sp;
+    sp.inkernel = f.INK;
+    const bool kf = f.KF != 0, plain = f.PLAIN != 0;
 #define KG_CONV_GO3(KF_, FAST_, PLAIN_, INK_) hipLaunchKernelGGL((kg_conv_kernel<BM, NW, KF_, KW, FAST_, PLAIN_, INK_>), grid, dim3(64 * NW), 0, s, *a, sp)
 #define KG_CONV_GO2(KF_, FAST_, PLAIN_) do { if constexpr (BM <= 64) { if (sp.inkernel) KG_CONV_GO3(KF_, FAST_, PLAIN_, true); else KG_CONV_GO3(KF_, FAST_, PLAIN_, false); } \
                                              else KG_CONV_GO3(KF_, FAST_, PLAIN_, false); } while (0)
 #define KG_CONV_GO(KF_, FAST_) do { if (plain) KG_CONV_GO2(KF_, FAST_, true); else KG_CONV_GO2(KF_, FAST_, false); } while (0)
-    if (fast && a->ngroups == 1) {
+    if (f.FAST == 1) {
         if (kf) KG_CONV_GO(true, 1); else KG_CONV_GO(false, 1);
-    } else if (fast) {
+    } else if (f.FAST == 2) {
         if (kf) KG_CONV_GO(true, 2); else KG_CONV_GO(false, 2);
     } else {
         if (kf) KG_CONV_GO2(true, 0, false); else KG_CONV_GO2(false, 0, false);
@@ -1814,7 +1870,7 @@ int launch(const KgConvArgs* a, const Plan& p, hipStream_t s) {
 #undef KG_CONV_GO2
 #undef KG_CONV_GO
     if (int rc = kg_launch_status("kg_conv")) return rc;
-    if (p.sp.nsplit > 1 && !sp.inkernel) {
+    if (f.epilogue) {
         dim3 g2(kg_cdiv(ncols, 256), a->M);
         hipLaunchKernelGGL(kg_conv_splitk_epilogue, g2, dim3(256), 0, s, *a, p.sp.nsplit);
         return kg_launch_status("kg_conv_splitk_epilogue");
@@ -1883,6 +1939,27 @@ extern "C" int kg_conv_plan_info(const KgConvArgs* a, int32_t* tile, int32_t* ns
     Plan p = make_plan(a);
     *tile = p.bs >= 0 ? 40 + p.bs : p.ring >= 0 ? 20 + p.ring : (int32_t)p.tile;      // 20..: ring tiles, 40..: bf16-split tiles
     *nsplit = p.sp.nsplit;
+    return 0;
+}
+
+extern "C" int kg_conv_form_info(const KgConvArgs* a, KgConvFormInfo* info) {
+    if (int rc = validate(a)) return rc;
+    KG_REQUIRE(info != nullptr, "kg_conv_form_info: null output");
+    if (tiny_eligible(a)) {
+        form_tiny(a, info);
+        return 0;
+    }
+    const Plan p = make_plan(a);
+    if (p.ring >= 0) {
+        form_clear(info);
+        info->family = KG_CONV_FAMILY_RING;
+        info->tile = 20 + p.ring;
+        info->per = p.sp.per;
+    } else if (p.bs >= 0) {
+        form_bs(a, p, info);
+    } else {
+        form_direct(a, p, info);
+    }
     return 0;
 }
 
@@ -1955,6 +2032,55 @@ static int many_tile(const KgConvArgs* jobs, int njobs) {
     return tile;
 }
 
+// The walk of a shared kg_conv_many launch with plan tile `mt` (many_tile), for the launcher and kg_conv_many_form: every job's
+// first workgroup, workgroups and tile order, and the instantiation.  m may be null (the report).
+static void many_walk(const KgConvArgs* jobs, int njobs, int mt, ConvMany* m, KgConvManyForm* f) {
+    const Tile tile = (Tile)mt;
+    *f = KgConvManyForm{};
+    f->tile = mt;
+    f->njobs = njobs;
+    f->BM = tile_bm(tile);
+    f->KF = jobs[0].g[0].w_sI <= jobs[0].g[0].w_sO ? 1 : 0;
+    if (m) m->njobs = njobs;
+    int total = 0;
+    for (int i = 0; i < njobs; ++i) {
+        const KgConvArgs* a = &jobs[i];
+        const int ncols = a->N * a->T_out * a->V_out;
+        ConvManyJob local;
+        ConvManyJob& j = m ? m->job[i] : local;
+        if (m) j.a = *a;
+        j.sp.nsplit = 1;
+        j.sp.inkernel = 0;                // (not read by kg_conv_many_kernel; defined, so that the kernel arguments hold no stack garbage)
+        j.sp.per = slices_of(a->g[0]) + (a->ngroups > 1 ? slices_of(a->g[1]) : 0);
+        j.wg_begin = total;               // (a multiple of 8: the XCD of a workgroup is its index in the launch & 7)
+        j.ctiles = kg_cdiv(ncols, 128);
+        const int rtl = kg_cdiv(a->M, tile_bm(tile));
+        j.sp.xcd = kg_xcd_grouped(j.ctiles, rtl, kg_env().conv_xcd_min > 0 ? kg_env().conv_xcd_min : KG_XCD_MIN_TILES) ? 1 : 0;
+        j.nwg = j.ctiles * rtl;
+        total += j.sp.xcd ? (j.ctiles + 7) / 8 * 8 * rtl : (j.nwg + 7) / 8 * 8;
+        f->xcd[i] = j.sp.xcd; f->wg_begin[i] = j.wg_begin; f->nwg[i] = j.nwg;
+    }
+    f->total_wg = total;
+    bool plain = kg_env().conv_plain_epi != 0;
+    for (int i = 0; i < njobs; ++i) plain = plain && jobs[i].add == nullptr && jobs[i].mask == nullptr && jobs[i].M % tile_bm(tile) == 0;
+    f->PLAIN = plain ? 1 : 0;
+}
+
+extern "C" int kg_conv_many_form(const KgConvArgs* jobs, int32_t njobs, KgConvManyForm* form) {
+    KG_REQUIRE(jobs != nullptr && njobs >= 1 && form != nullptr, "kg_conv_many_form: bad arguments");
+    for (int i = 0; i < njobs; ++i)
+        if (int rc = validate(&jobs[i])) return rc;
+    const int mt = many_tile(jobs, njobs);
+    if (mt < 0) {                 // one kg_conv launch per job (kg_conv_form_info says which)
+        *form = KgConvManyForm{};
+        form->tile = -1;
+        form->njobs = njobs;
+        return 0;
+    }
+    many_walk(jobs, njobs, mt, nullptr, form);
+    return 0;
+}
+
 extern "C" int kg_conv_many_plan(const KgConvArgs* jobs, int32_t njobs, int32_t* tile) {
     KG_REQUIRE(jobs != nullptr && njobs >= 1 && tile != nullptr, "kg_conv_many_plan: bad arguments");
     for (int i = 0; i < njobs; ++i)
@@ -1979,27 +2105,12 @@ extern "C" int kg_conv_many(const KgConvArgs* jobs, int32_t njobs, void* stream)
             if (int rc = kg_conv(&jobs[i], stream)) return rc;
         return 0;
     }
-    const Tile tile = (Tile)mt;
-    const bool kf = jobs[0].g[0].w_sI <= jobs[0].g[0].w_sO;
     ConvMany m;
-    m.njobs = njobs;
-    int total = 0;
-    for (int i = 0; i < njobs; ++i) {
-        const KgConvArgs* a = &jobs[i];
-        const int ncols = a->N * a->T_out * a->V_out;
-        ConvManyJob& j = m.job[i];
-        j.a = *a;
-        j.sp.nsplit = 1;
-        j.sp.per = slices_of(a->g[0]) + (a->ngroups > 1 ? slices_of(a->g[1]) : 0);
-        j.wg_begin = total;               // (a multiple of 8: the XCD of a workgroup is its index in the launch & 7)
-        j.ctiles = kg_cdiv(ncols, 128);
-        const int rtl = kg_cdiv(a->M, tile_bm(tile));
-        j.sp.xcd = kg_xcd_grouped(j.ctiles, rtl, kg_env().conv_xcd_min > 0 ? kg_env().conv_xcd_min : KG_XCD_MIN_TILES) ? 1 : 0;
-        j.nwg = j.ctiles * rtl;
-        total += j.sp.xcd ? (j.ctiles + 7) / 8 * 8 * rtl : (j.nwg + 7) / 8 * 8;
-    }
-    bool plain = kg_env().conv_plain_epi != 0;
-    for (int i = 0; i < njobs; ++i) plain = plain && jobs[i].add == nullptr && jobs[i].mask == nullptr && jobs[i].M % tile_bm(tile) == 0;
+    KgConvManyForm f;
+    many_walk(jobs, njobs, mt, &m, &f);
+    const Tile tile = (Tile)mt;
+    const bool kf = f.KF != 0, plain = f.PLAIN != 0;
+    const int total = f.total_wg;
 #define KG_MANY_GO(BM_) do { if (kf && plain)  hipLaunchKernelGGL((kg_conv_many_kernel<BM_, true, true>), dim3(total), dim3(256), 0, s, m); \
                              else if (kf)      hipLaunchKernelGGL((kg_conv_many_kernel<BM_, true, false>), dim3(total), dim3(256), 0, s, m); \
                              else if (plain)   hipLaunchKernelGGL((kg_conv_many_kernel<BM_, false, true>), dim3(total), dim3(256), 0, s, m); \

@@ -52,6 +52,9 @@ int main(void) {
         int32_t tile = -1, ns = -1;
         CHECK(kg_conv_plan_info(&a, &tile, &ns) == 0 && tile >= 0 && ns >= 1);
         CHECK(kg_conv_workspace_bytes(&a) >= 0);
+        KgConvFormInfo cf;
+        CHECK(kg_conv_form_info(&a, &cf) == 0 && cf.tile == tile && cf.nsplit == ns && cf.grid_x >= 1 && cf.grid_y >= 1 && cf.grid_z >= 1);
+        CHECK(cf.family == KG_CONV_FAMILY_TINY || (cf.family == KG_CONV_FAMILY_DIRECT && cf.BM >= 32 && cf.epilogue == (ns > 1)));
         if (ns > 1) CHECK(kg_conv_workspace_bytes(&a) == (int64_t)ns * a.M * a.N * a.T_out * a.V_out * 4);
     }
     KgConvArgs bad = conv_args(4, 8, 8, 8, 5, 3, 1);
@@ -60,6 +63,13 @@ int main(void) {
     bad = conv_args(4, 8, 8, 8, 5, 2, 1);
     CHECK(kg_conv(&bad, 0) < 0 && strstr(kg_last_error(), "taps") != 0);
     CHECK(kg_conv(0, 0) < 0);
+    {
+        KgConvFormInfo cf;
+        CHECK(kg_conv_form_info(&bad, &cf) < 0 && strstr(kg_last_error(), "taps") != 0);
+        CHECK(kg_conv_form_info(0, &cf) < 0);
+        bad = conv_args(4, 8, 8, 8, 5, 3, 1);
+        CHECK(kg_conv_form_info(&bad, 0) < 0 && kg_conv_form_info(&bad, &cf) == 0);
+    }
     /* conv_many: the shared-launch decision (host only) - two full-slice problems share a launch, a ragged one does not */
     {
         KgConvArgs mj[3] = {conv_args(64, 64, 64, 64, 11, 3, 1), conv_args(64, 64, 32, 64, 11, 1, 1), conv_args(64, 40, 32, 64, 11, 1, 1)};
@@ -69,6 +79,11 @@ int main(void) {
         CHECK(kg_conv_many_plan(mj, 1, &mt) == 0 && mt == -1);
         CHECK(kg_conv_many_plan(0, 2, &mt) < 0);
         CHECK(kg_conv_many(mj, 0, 0) < 0);
+        KgConvManyForm mf;
+        CHECK(kg_conv_many_form(mj, 2, &mf) == 0 && mf.tile >= 0 && mf.tile <= 2 && mf.njobs == 2 && mf.wg_begin[0] == 0 &&
+              mf.wg_begin[1] % 8 == 0 && mf.total_wg >= mf.wg_begin[1] + mf.nwg[1]);
+        CHECK(kg_conv_many_form(mj, 3, &mf) == 0 && mf.tile == -1);
+        CHECK(kg_conv_many_form(0, 2, &mf) < 0 && kg_conv_many_form(mj, 2, 0) < 0 && kg_conv_many_form(mj, 0, &mf) < 0);
     }
     /* wgrad: single layer, several layers, duplicate destinations */
     KgWgradArgs jobs[12];

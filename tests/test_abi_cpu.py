@@ -51,12 +51,12 @@ def test_struct_sizes_match_header():
     C program against the header)."""
     mirrors = abi_layout.mirrors()
     assert sorted(mirrors) == abi_layout.header_structs()
-    assert len(mirrors) >= 42
+    assert len(mirrors) >= 44
     checked = 0
     for cname in sorted(mirrors):
         abi_layout.assert_mirror(cname)
         checked += len(abi_layout.header_layout(cname))
-    assert checked >= 802       # sizeof of 42 structs + offsetof of their 760 fields
+    assert checked >= 836       # sizeof of 44 structs + offsetof of their 792 fields
 
 
 def test_constants_match_header():
@@ -258,6 +258,37 @@ def test_agg_plan_reports_validate_without_gpu(lib):
     c.Cin = 8
     assert lib.kg_aggconv_plan_info(ctypes.byref(c), 0, ctypes.byref(q)) < 0 and b"source span" in lib.kg_last_error()
     assert _native.last_agg_plan is None and _native.last_aggconv_plan is None       # the hooks are off unless a test switches them on
+
+
+def test_conv_form_reports_validate_without_gpu(lib):
+    """kg_conv_form_info / kg_conv_many_form (additive, ABI v9): null arguments are rejected, the argument checks are those of
+    the launch, nothing is launched and no operand is read (every pointer here is a made-up address)"""
+    f, mf = _native._ConvFormInfo(), _native._ConvManyForm()
+    a = _native._ConvArgs()
+    assert lib.kg_conv_form_info(None, ctypes.byref(f)) < 0 and b"kg_conv: null args" in lib.kg_last_error()
+    assert lib.kg_conv_form_info(ctypes.byref(a), ctypes.byref(f)) < 0 and b"kg_conv: bad dims" in lib.kg_last_error()
+    a.N, a.M, a.T_out, a.V_out, a.ngroups = 2, 33, 9, 9, 1
+    g = a.g[0]
+    g.x, g.w, g.x_sN, g.x_sC, g.Cin, g.T_in, g.V_in = 0x1000, 0x1000, 81, 162, 64, 9, 9
+    g.w_sT, g.w_sO, g.w_sI, g.w_MB, g.taps, g.t_stride = 33 * 64, 64, 1, 1 << 30, 3, 1
+    assert lib.kg_conv_form_info(ctypes.byref(a), None) < 0 and b"kg_conv_form_info: null output" in lib.kg_last_error()
+    assert lib.kg_conv_form_info(ctypes.byref(a), ctypes.byref(f)) == 0
+    assert (f.family, f.tile, f.BM, f.NW, f.KW, f.KF, f.FAST, f.PLAIN, f.INK, f.nsplit, f.epilogue) == (
+        _native.CONV_FAMILY_DIRECT, 2, 32, 4, 1, 1, 1, 0, 0, 1, 0) and (f.grid_x, f.grid_y, f.grid_z) == (2, 2, 1)
+    g.taps = 2
+    assert lib.kg_conv_form_info(ctypes.byref(a), ctypes.byref(f)) < 0 and b"taps=2" in lib.kg_last_error()
+    g.taps = 3
+    arr = (_native._ConvArgs * 2)(a, a)
+    assert lib.kg_conv_many_form(None, 2, ctypes.byref(mf)) < 0 and b"kg_conv_many_form: bad arguments" in lib.kg_last_error()
+    assert lib.kg_conv_many_form(arr, 0, ctypes.byref(mf)) < 0 and lib.kg_conv_many_form(arr, 2, None) < 0
+    assert lib.kg_conv_many_form(arr, 2, ctypes.byref(mf)) == 0
+    assert (mf.tile, mf.BM, mf.KF, mf.PLAIN, mf.njobs, mf.total_wg) == (2, 32, 1, 0, 2, 16) and list(mf.wg_begin)[:2] == [0, 8]
+    assert lib.kg_conv_many_form(arr, 1, ctypes.byref(mf)) == 0 and mf.tile == -1          # one job: a plain kg_conv launch
+    arr[1].g[0].Cin = 40
+    assert lib.kg_conv_many_form(arr, 2, ctypes.byref(mf)) == 0 and mf.tile == -1          # partial K-slices: one launch per job
+    arr[1].ngroups = 3
+    assert lib.kg_conv_many_form(arr, 2, ctypes.byref(mf)) < 0 and b"ngroups=3" in lib.kg_last_error()
+    assert _native.last_conv_form is None                                                  # the hook is off unless a test switches it on
 
 
 def test_mapping_network_entry_points_validate_without_gpu(lib):

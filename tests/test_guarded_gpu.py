@@ -28,6 +28,7 @@ from oracle import prim_ref
 from oracle.fill import rand_inputs, rand_noise
 from tests import guard
 from tests import test_agg_forms_gpu as ta
+from tests import test_conv_forms_gpu as tf
 from tests import test_d0_fused_gpu as td
 from tests import test_ema_gpu as te
 from tests import test_kernels_gpu as tk
@@ -227,6 +228,8 @@ KERNEL_CASES = {
     "conv wave K-split transposed, V = 1": _k(tk.test_conv_wave_ksplit_tile, 96, 80, 8, 1, 5, True, expect=["conv"]),
     "conv parity launches (o_tstride)": _k(tk.test_transposed_stride2_tcn_as_two_parity_launches, 2, 96, 8, 1, expect=["conv"]),
     "conv_many": _k(tk.test_conv_many_equals_single_launches, 64, 2, 6, kernel_path="default", expect=["conv_many"]),
+    "conv V_out 70 through a vertex map (map entries loaded per column)": _k(tf.test_edge, "V_out 70 vmap forward", expect=["conv"]),
+    "conv_many, an XCD-grouped job between two plain ones": _k(tf.test_many, "many three jobs one XCD", expect=["conv_many"]),
     "conv chanblock / blocked transpose, N = 1": _k(tk.test_conv_chanblock_and_blocked_transpose, 1, 7, 33, 5, 3, expect=["conv"]),
     "wgrad ragged": _k(tk.test_wgrad, 3, 70, 65, 10, 7, 3, TAP_TIME, 2, expect=["wgrad"]),
     "wgrad one element": _k(tk.test_wgrad, 1, 1, 1, 1, 1, 3, TAP_TIME, 1, expect=["wgrad"]),
@@ -364,6 +367,7 @@ INPUT_SIDE = {
     "conv bf16-split form, 16-byte window loads": _k(tk.test_conv_two_groups_tail_default_plan, kernel_path="bs0", env={"KG_CONV_BS": "1", "KG_CONV_BS_TILE": "0"}),
     "conv K-split, residual + mask": _k(tk.test_ksplit_completion_forms_are_deterministic, fast="1", tile=4, split=3),
     "conv wave K-split": _k(tk.test_conv_wave_ksplit_tile, 33, 70, 6, 5, 3, False),
+    "conv V_out 70 through a vertex map": _k(tf.test_edge, "V_out 70 vmap transposed"),
     "aggconv ragged": _k(tk.test_aggconv_fused_gcn, "ntu", 3, False, 9, 40, 33, 8, 0),
     "aggconv block 0": _k(tk.test_aggconv_fused_gcn, "ntu", 0, True, 3, 3, 32, 64, 60),
     "wgrad ragged": _k(tk.test_wgrad, 3, 70, 65, 10, 7, 3, TAP_TIME, 2),

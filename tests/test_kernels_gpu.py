@@ -160,6 +160,19 @@ def plane(t, d):
     return out
 
 
+CONV_TILES = {0: (128, 4, 1), 1: (64, 4, 1), 2: (32, 4, 1), 3: (64, 2, 1), 4: (32, 2, 1), 9: (32, 4, 4)}      # plan tile -> BM, NW, KW
+
+
+def assert_forced_form(f, tile, **fields):
+    """f, the form record of a launch under KG_CONV_PLAN (_native.last_conv_form): the direct kernel's instantiation of that tile
+    ran, with the given template arguments, and a K-split was completed one way or the other"""
+    BM, NW, KW = CONV_TILES[tile]
+    want = dict(family="direct", tile=tile, BM=BM, NW=NW, KW=KW, **fields)
+    bad = {k: (v, f[k]) for k, v in want.items() if f[k] != v}
+    assert not bad, "(expected, reported) form differs at %s: %r" % (bad, f)
+    assert f["INK"] + f["epilogue"] == int(f["nsplit"] > 1) and (f["INK"] == 0 or BM <= 64), f
+
+
 PLANE_CASES = [
     # N, Cin, M, T, V, taps, mode, transposed
     (64, 32, 64, 64, 11, 3, TAP_TIME, False), (64, 64, 64, 64, 11, 3, TAP_TIME, True),
@@ -193,6 +206,7 @@ def test_conv_forced_tiles_on_plane_tensors(N, Cin, M, T, V, taps, mode, transpo
     bias = rnd(mo, seed=5).to(d)
     addt = plane(rnd(N, mo, T, V, seed=6).to(d), d)
     nv.last_conv_plan = []
+    nv.last_conv_form = []
     try:
         for plan in ("", "0,1", "1,1", "3,1", "4,2", "2,3", "9,1"):
             if plan:
@@ -200,9 +214,14 @@ def test_conv_forced_tiles_on_plane_tensors(N, Cin, M, T, V, taps, mode, transpo
             out = nv.conv([g], N, mo, T, V, bias0=bias, add=addt, act=nv.ACT_LRELU)
             if plan:
                 assert nv.last_conv_plan[0] == int(plan.split(",")[0]), (plan, nv.last_conv_plan)
+                # the forced instantiation ran: the tile, full / partial K-slices, the weight orientation, the general epilogue
+                assert_forced_form(nv.last_conv_form[-1], int(plan.split(",")[0]), nsplit=nv.last_conv_plan[1],
+                                   FAST=int(g.Cin % 32 == 0 and os.environ.get("KG_CONV_FAST") != "0"), KF=int(not transposed), PLAIN=0)
             close(out, pr.conv([g], N, mo, T, V, bias0=bias, add=addt, act=nv.ACT_LRELU))
+        assert len(nv.last_conv_form) == 7
     finally:
         nv.last_conv_plan = None
+        nv.last_conv_form = None
 
 
 def test_packed_weights_cached_across_launches():
@@ -220,25 +239,32 @@ def test_packed_weights_cached_across_launches():
     pack = nv.conv_pack(groups(1), 1, M, T, V)
     assert pack is not None and pack.numel() * 4 == 7 * 12 * 128 * 16         # steps x (3 terms x 4 octets) x rows padded to 128
     nv.last_conv_plan = []
+    nv.last_conv_form = []
     try:
         for n in (2, 5, 64):
             gs = groups(n, seed=n)
             out = nv.conv(gs, n, M, T, V, wpack=pack, **kw)
             assert nv.last_conv_plan[0] in (40, 41, 42), nv.last_conv_plan
+            f = nv.last_conv_form[-1]       # the tile kernel alone, on the caller's buffer: no weight-pack launch
+            assert f["family"] in ("bs", "bsw") and (f["wpack"], f["pack"], f["tile"]) == (1, 0, nv.last_conv_plan[0]), f
             close(out, pr.conv(gs, n, M, T, V, **kw))
         # a transposed launch cannot take the form: the buffer is ignored, the direct kernel runs
         gy = plane(rnd(2, M, T, V, seed=9).to(d), d)
         gt = [Group(gy, wt, WView(1, 3, M * 3), M, 3, TAP_TIME, 1, True, None)]
         out = nv.conv(gt, 2, M, T, V, wpack=pack)
         assert nv.last_conv_plan[0] < 20, nv.last_conv_plan
+        f = nv.last_conv_form[-1]
+        assert (f["family"], f["wpack"], f["pack"], f["KF"]) == ("direct", 0, 0, 0), f
         close(out, pr.conv(gt, 2, M, T, V))
         # new weights, same buffer
         wt.mul_(-0.5); wr.add_(0.25)
         assert nv.conv_pack(groups(1), 1, M, T, V, out=pack) is pack
         gs = groups(3, seed=7)
         close(nv.conv(gs, 3, M, T, V, wpack=pack, **kw), pr.conv(gs, 3, M, T, V, **kw))
+        assert nv.last_conv_form[-1]["wpack"] == 1 and len(nv.last_conv_form) == 5
     finally:
         nv.last_conv_plan = None
+        nv.last_conv_form = None
 
 
 def test_conv_two_groups_tail_default_plan(monkeypatch, kernel_path):
@@ -745,20 +771,25 @@ def test_ksplit_completion_forms_are_deterministic(monkeypatch, fast, tile, spli
     monkeypatch.setenv("KG_CONV_PLAN", "%d,%d" % (tile, split))
     monkeypatch.setenv("KG_CONV_INKERNEL_MAX", "8")
     nv.last_conv_plan = []
+    nv.last_conv_form = []
     try:
         got = {}
         for form in ("1", "0"):
             monkeypatch.setenv("KG_CONV_INKERNEL", form)
             outs = [nv.conv([g], N, M, T // 2, V, **kw) for _ in range(3)]
             assert nv.last_conv_plan == [tile, split], nv.last_conv_plan       # the launch really is K-split
+            for f in nv.last_conv_form[-3:]:                                  # and completed in the form this round forces
+                assert_forced_form(f, tile, nsplit=split, FAST=int(fast), KF=1, PLAIN=0, INK=int(form), epilogue=1 - int(form))
             for o in outs:
                 close(o, ref)
                 assert torch.equal(o, outs[0])
             got[form] = outs[0]
         close(got["1"], got["0"], 2e-6)
         assert not (nv._sync_buffer(d) != 0).any()          # every ticket counter is back at zero
+        assert len(nv.last_conv_form) == 6
     finally:
         nv.last_conv_plan = None
+        nv.last_conv_form = None
 
 
 @pytest.mark.parametrize("N,C,T,V", [(64, 3, 64, 25), (5, 2, 32, 16), (3, 7, 9, 5)])
@@ -980,18 +1011,25 @@ def test_conv_wave_ksplit_tile(M, Cin, T, V, N, transposed, monkeypatch):
     ref = pr.conv([g0, g1], N, M, T, V, **kw)
     outs = {}
     nv.last_conv_plan = []
+    nv.last_conv_form = []
     try:
         for plan in ("2,1", "9,1", "9,2"):
             monkeypatch.setenv("KG_CONV_PLAN", plan)
             outs[plan] = nv.conv([g0, g1], N, M, T, V, **kw)
             assert nv.last_conv_plan[0] == int(plan.split(",")[0]), (plan, nv.last_conv_plan)
+            # the general two-group instantiation (24 residual channels: partial K-slices), split across workgroups when asked
+            assert_forced_form(nv.last_conv_form[-1], int(plan.split(",")[0]), nsplit=int(plan.split(",")[1]), FAST=0, PLAIN=0,
+                               KF=int(not transposed), INK=int(plan == "9,2"))
             close(outs[plan], ref, 2e-5)
         # every other frame of a twice-as-long destination, starting at frame 1
         big = nv.new_plane(N, M, 2 * T, V, d).zero_()
         nv.conv([g0, g1], N, M, T, V, out=big, out_t0=1, out_tstride=2, **kw)
         assert torch.equal(big[:, :, 1::2], outs["9,2"]) and float(big[:, :, 0::2].abs().max()) == 0.0
+        assert_forced_form(nv.last_conv_form[-1], 9, nsplit=2, INK=1)
+        assert len(nv.last_conv_form) == 4
     finally:
         nv.last_conv_plan = None
+        nv.last_conv_form = None
 
 
 def test_bn_bwd_many_equals_single_launches():
@@ -1377,12 +1415,21 @@ def test_conv_many_equals_single_launches(M, stride, N, monkeypatch, kernel_path
 
     js, gz = jobs()
     nv.last_conv_plan = []
+    nv.last_conv_form = []
     try:
         outs = nv.conv_many(js)
         if not kernel_path.startswith(("ring", "bs")):      # (the shared launch does not use the ring / bf16-split forms: either way is right there)
             assert (nv.last_conv_plan[0] >= 0) == (kernel_path == "default"), nv.last_conv_plan     # really ONE launch
+        f = nv.last_conv_form[0]
+        assert f["family"] == "many" and f["tile"] == nv.last_conv_plan[0] and f["njobs"] == len(js), f
+        if f["tile"] >= 0:      # the shared kernel's instantiation: transposed weights, whole row tiles without add / mask
+            assert (f["BM"], f["KF"], f["PLAIN"]) == ({0: 128, 1: 64, 2: 32}[f["tile"]], 0, int(Cr % f["BM"] == 0 and M % f["BM"] == 0)), f
+            assert len(nv.last_conv_form) == 1 and f["wg_begin"][0] == 0 and all(b % 8 == 0 for b in f["wg_begin"]), f
+        else:                   # one recorded single launch per job behind the call's record
+            assert [g["family"] != "many" for g in nv.last_conv_form[1:]] == [True] * len(js), nv.last_conv_form
     finally:
         nv.last_conv_plan = None
+        nv.last_conv_form = None
     js1, gz1 = jobs()
     singles = [nv.conv(**j) for j in js1]
     close(gz, gz1, 5e-6)            # (bit-identical unless a single launch takes the wave-level K-split tile: other summation order)
