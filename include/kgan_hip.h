@@ -1535,6 +1535,78 @@ int64_t kg_kin_desc_sets_workspace_bytes(const KgKinDescSetsArgs* a);   /* < 0 f
 int64_t kg_kin_desc_sets_lds_bytes(const KgKinDescSetsArgs* a);         /* < 0 for invalid arguments                   */
 int     kg_kin_desc_sets(const KgKinDescSetsArgs* a, void* stream);
 
+/* ---- projection into W: per-sample objective and per-sample optimiser step (additive, ABI v9; DESIGN.md 29, csrc/kg_proj.hip)
+ * The tail of one iteration of project.Projector behind the generator's forward and backward pass: two launches.
+ *
+ * kg_proj_loss: ONE launch, a workgroup per sample.  x (n, C, T, V) generated, y the target, both through sample / channel /
+ * frame strides (elements) of their own with the joints contiguous; y is read as  y' = fp32(fp32(y * scale) + shift)  (two
+ * separately rounded fp32 operations: what two stock launches compute), so a row of a resident dataset or a crop in T is read
+ * in place.  m: weights >= 0, (T, V) per sample at sample stride sm (sm = 0: one mask for all samples); NULL: all ones.
+ * bones: HOST (B, 2) joints, 0 <= B <= KG_KIN_MAX_BONES, copied into the launch.  With
+ *     d = fp32(x - y')                                               one fp32 subtraction
+ *     Wp = C sum_{t,v} m[t,v]                                        L_pos  = sum_{c,t,v} m d^2 / Wp
+ *     mv[t,v] = m[t,v] m[t+1,v],  Wv = C sum_{t<T-1,v} mv            L_vel  = sum mv (d[c,t+1,v] - d[c,t,v])^2 / Wv
+ *     mb[t,b] = m[t,a_b] m[t,c_b], Wb = sum mb,
+ *     s_x = sum_c (x[c,t,a_b] - x[c,t,c_b])^2, s_y likewise on y'    L_bone = sum mb (s_x - s_y)^2 / Wb
+ *     L = (lambda_pos L_pos + lambda_vel L_vel) + lambda_bone L_bone
+ * everything after d in fp64 (the bone differences are exact there), every output word rounded once:
+ *     loss (n, 4) = [L, L_pos, L_vel, L_bone],   gx (n, C, T, V) contiguous = dL_i / dx_i  (d counts as x - y').
+ * A term whose lambda is 0 or whose W is 0 (T < 2 for the velocity term, B == 0 for the bone term) is off: its loss word is 0
+ * and it adds nothing to L or gx.  An entry whose weight is not > 0 is selected away, never multiplied: a NaN in a masked-out
+ * target entry changes no output bit.  The frames are staged in LDS in chunks of KG_PROJ_CHUNK_FRAMES with one halo frame on
+ * each side, so T has no cap.  Each thread adds its terms in frame order, then a shuffle tree and the four waves in order: the
+ * shape of every sum depends on (C, T, V, B) alone.  No atomics, no host synchronisation, capturable; two calls, same bits.
+ * Rejected (< 0, kg_last_error() names the field) before any GPU call: null x / y / loss / gx (null bones with B > 0); n, C, T
+ * or V < 1; C > KG_PROJ_MAX_CHANNELS; V > KG_PROJ_MAX_JOINTS; B outside [0, KG_KIN_MAX_BONES]; a bone joint outside [0, V); a
+ * negative stride; a lambda that is negative or not finite; scale or shift not finite.
+ *
+ * kg_proj_step: ONE launch, a workgroup per sample i.  w, am, av (n, D) fp32 the latents and their Adam moments, gw (n, D)
+ * the gradient of L_i, wmean (K, D), labels (n) int64, loss (n, 4) of kg_proj_loss, *step the 1-based number of THIS step in
+ * device memory (as kg_adam_step: the launch does not advance it).  With s = *step, fp64 inside, every output rounded once:
+ *     prior_i = mean_d (w - wmean[label_i])^2,   obj_i = fp32(L_i + lambda_w prior_i)      (lambda_w == 0: obj_i = L_i)
+ *     hist[(s - 1) n + i] = obj_i                                   (hist (S, n) may be NULL; 1 <= s <= S, else no write)
+ *     frozen_i = obj_i not finite, or a gw[i, :] not finite, or label_i outside [0, K):
+ *                w, am, av, best_* of the sample keep their bits and nonfinite[i] += 1
+ *     else: if obj_i < best_obj[i]: best_obj[i] = obj_i, best_loss[i, :] = loss[i, :], best_w[i, :] = w[i, :] (before the update)
+ *           g = gw + 2 lambda_w (w - wmean[label_i]) / D
+ *           lr_s = lr min(1, s / ramp_up) (s > S - ramp_down ? (1 + cos(pi (s - (S - ramp_down)) / ramp_down)) / 2 : 1)
+ *                  (ramp_up / ramp_down == 0: that factor is 1)
+ *           am = b1 am + (1 - b1) g,  av = b2 av + (1 - b2) g^2,  w -= lr_s (am / (1 - b1^s)) / (sqrt(av / (1 - b2^s)) + eps)
+ * No atomics, no host synchronisation, capturable.
+ * Rejected (< 0, kg_last_error() names the field) before any GPU call: null w / am / av / gw / wmean / labels / loss / step /
+ * best_obj / best_loss / best_w / nonfinite; n, D or K < 1; lambda_w negative or not finite; lr negative or not finite; b1 or b2
+ * outside [0, 1); eps negative or not finite; S < 1; ramp_up or ramp_down outside [0, S].
+ * Call site: project.Projector._iteration.                                                                                   */
+#define KG_PROJ_MAX_CHANNELS 3
+#define KG_PROJ_MAX_JOINTS 32
+#define KG_PROJ_CHUNK_FRAMES 32
+typedef struct KgProjLossArgs {
+    const float* x;  int64_t x_sn, x_sc, x_st;  /* generated: sample, channel, frame strides (elements)                        */
+    const float* y;  int64_t y_sn, y_sc, y_st;  /* target, read as y * scale + shift                                           */
+    float scale, shift;
+    const float* m;  int64_t sm;                /* weights (T, V) per sample, sample stride sm (0: shared); NULL: all ones      */
+    int32_t n, C, T, V, B;
+    const int32_t* bones;                       /* HOST: (B, 2) joints; may be NULL when B == 0                                */
+    double lambda_pos, lambda_vel, lambda_bone;
+    float* loss;                                /* out: (n, 4)                                                                 */
+    float* gx;                                  /* out: (n, C, T, V) contiguous                                                */
+} KgProjLossArgs;
+typedef struct KgProjStepArgs {
+    float* w;  float* am;  float* av;           /* in / out: (n, D)                                                            */
+    const float* gw;                            /* (n, D)                                                                      */
+    const float* wmean;                         /* (K, D)                                                                      */
+    const int64_t* labels;                      /* (n)                                                                         */
+    const float* loss;                          /* (n, 4)                                                                      */
+    const int32_t* step;                        /* device: the 1-based number of this step                                     */
+    float* best_obj;  float* best_loss;  float* best_w;     /* in / out: (n), (n, 4), (n, D)                                   */
+    float* hist;                                /* out: (S, n); may be NULL                                                    */
+    int32_t* nonfinite;                         /* in / out: (n)                                                               */
+    int32_t n, D, K, S, ramp_up, ramp_down;
+    double lambda_w, lr, b1, b2, eps;
+} KgProjStepArgs;
+int     kg_proj_loss(const KgProjLossArgs* a, void* stream);
+int     kg_proj_step(const KgProjStepArgs* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

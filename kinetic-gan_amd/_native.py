@@ -516,6 +516,29 @@ class _KinScoresArgs(C.Structure):
                 ("mean_real", C.c_void_p), ("mean_fake", C.c_void_p), ("w1", C.c_void_p), ("w1_mean", C.c_void_p),
                 ("scores", c_f32p), ("nonfinite", C.c_void_p)]
 
+PROJ_MAX_CHANNELS, PROJ_MAX_JOINTS, PROJ_CHUNK_FRAMES = 3, 32, 32
+
+
+class _ProjLossArgs(C.Structure):
+    _fields_ = [("x", c_f32p), ("x_sn", C.c_int64), ("x_sc", C.c_int64), ("x_st", C.c_int64),
+                ("y", c_f32p), ("y_sn", C.c_int64), ("y_sc", C.c_int64), ("y_st", C.c_int64),
+                ("scale", C.c_float), ("shift", C.c_float),
+                ("m", c_f32p), ("sm", C.c_int64),
+                ("n", C.c_int32), ("C", C.c_int32), ("T", C.c_int32), ("V", C.c_int32), ("B", C.c_int32),
+                ("bones", C.c_void_p),
+                ("lambda_pos", C.c_double), ("lambda_vel", C.c_double), ("lambda_bone", C.c_double),
+                ("loss", c_f32p), ("gx", c_f32p)]
+
+
+class _ProjStepArgs(C.Structure):
+    _fields_ = [("w", c_f32p), ("am", c_f32p), ("av", c_f32p), ("gw", c_f32p), ("wmean", c_f32p),
+                ("labels", C.c_void_p), ("loss", c_f32p), ("step", C.c_void_p),
+                ("best_obj", c_f32p), ("best_loss", c_f32p), ("best_w", c_f32p), ("hist", c_f32p), ("nonfinite", C.c_void_p),
+                ("n", C.c_int32), ("D", C.c_int32), ("K", C.c_int32), ("S", C.c_int32),
+                ("ramp_up", C.c_int32), ("ramp_down", C.c_int32),
+                ("lambda_w", C.c_double), ("lr", C.c_double), ("b1", C.c_double), ("b2", C.c_double), ("eps", C.c_double)]
+
+
 STEP_MAX_PLANES = 8
 STREAM_Z, STREAM_ALPHA, STREAM_NOISE_D, STREAM_NOISE_G = 0, 1, 2, 3
 
@@ -746,6 +769,8 @@ EXPORTS = {
     "kg_kin_desc_sets": (C.c_int, [C.POINTER(_KinDescSetsArgs), C.c_void_p]),
     "kg_kin_scores_lds_bytes": (C.c_int64, [C.POINTER(_KinScoresArgs)]),
     "kg_kin_scores": (C.c_int, [C.POINTER(_KinScoresArgs), C.c_void_p]),
+    "kg_proj_loss": (C.c_int, [C.POINTER(_ProjLossArgs), C.c_void_p]),
+    "kg_proj_step": (C.c_int, [C.POINTER(_ProjStepArgs), C.c_void_p]),
 }
 
 _lib = None
@@ -3302,6 +3327,98 @@ def kin_scores(real_desc: torch.Tensor, fake_descs: Sequence[torch.Tensor]) -> d
     _count(who, 0.0)
     _check(load_library().kg_kin_scores(C.byref(a), _stream()), who)
     return out
+
+
+# ---- projection into W: per-sample objective and optimiser step (kg_proj.hip) ---------------------------------
+
+def _proj_loss_shape(n: int, Cc: int, T: int, V: int, bones, lambdas, scale: float = 1.0, shift: float = 0.0):
+    """a ``_ProjLossArgs`` with everything but the device pointers and strides, and the host table it points to (hold it until
+    the call)"""
+    a = _ProjLossArgs()
+    a.n, a.C, a.T, a.V = int(n), int(Cc), int(T), int(V)
+    a.B, tb = _kin_table(bones, "bones")
+    a.bones = C.cast(tb, C.c_void_p) if tb is not None else None
+    a.lambda_pos, a.lambda_vel, a.lambda_bone = (float(v) for v in lambdas)
+    a.scale, a.shift = float(scale), float(shift)
+    return a, tb
+
+
+def _proj_view(who: str, name: str, t: torch.Tensor, shape):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} must be an fp32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    if t.shape[3] > 1 and t.stride(3) != 1:
+        raise ValueError(f"{who}: the joints of {name} must be contiguous")
+    return t.data_ptr(), t.stride(0), t.stride(1), t.stride(2)
+
+
+def proj_loss(x: torch.Tensor, y: torch.Tensor, bones, lambdas, mask: Optional[torch.Tensor] = None, scale: float = 1.0,
+              shift: float = 0.0, loss: Optional[torch.Tensor] = None, gx: Optional[torch.Tensor] = None):
+    """Enqueue kg_proj_loss (ONE launch, a workgroup per sample) on the current stream; no host synchronisation.  ``x``, ``y``
+    (n, C, T, V) fp32 through strides of their own (joints contiguous), ``y`` read as ``y * scale + shift``; ``mask`` None,
+    (T, V) for all samples or (n, T, V), contiguous fp32 weights >= 0; ``bones`` a host sequence of joint pairs (may be
+    empty); ``lambdas`` = (pos, vel, bone).  Returns (loss (n, 4) fp32 = [L, L_pos, L_vel, L_bone], gx (n, C, T, V) contiguous
+    fp32) - ``loss`` / ``gx`` if given."""
+    who = "kg_proj_loss"
+    if x.dim() != 4:
+        raise ValueError(f"{who}: x must be (n, C, T, V)")
+    n, Cc, T, V = x.shape
+    a, keep = _proj_loss_shape(n, Cc, T, V, bones, lambdas, scale, shift)
+    a.x, a.x_sn, a.x_sc, a.x_st = _proj_view(who, "x", x, x.shape)
+    a.y, a.y_sn, a.y_sc, a.y_st = _proj_view(who, "y", y, x.shape)
+    if mask is not None:
+        if mask.dtype != torch.float32 or not mask.is_contiguous() or tuple(mask.shape) not in ((T, V), (n, T, V)):
+            raise ValueError(f"{who}: mask must be a contiguous fp32 tensor of shape (T, V) or (n, T, V), got {tuple(mask.shape)}")
+        a.m, a.sm = mask.data_ptr(), (T * V if mask.dim() == 3 else 0)
+    _need_cuda(x, y, mask, loss, gx)
+    dev = x.device
+    if loss is None:
+        loss = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    else:
+        _dest(loss, n * 4, f"{who}: loss must be a contiguous fp32 tensor of n * 4 elements")
+    if gx is None:
+        gx = torch.empty((n, Cc, T, V), dtype=torch.float32, device=dev)
+    else:
+        _dest(gx, n * Cc * T * V, f"{who}: gx must be a contiguous fp32 tensor of n * C * T * V elements")
+    a.loss, a.gx = loss.data_ptr(), gx.data_ptr()
+    _count(who, 0.0)
+    _check(load_library().kg_proj_loss(C.byref(a), _stream()), who)
+    return loss, gx
+
+
+def _proj_step_shape(n: int, D: int, K: int, S: int, lr: float, b1: float, b2: float, eps: float, lambda_w: float,
+                     ramp_up: int, ramp_down: int) -> _ProjStepArgs:
+    a = _ProjStepArgs()
+    a.n, a.D, a.K, a.S, a.ramp_up, a.ramp_down = int(n), int(D), int(K), int(S), int(ramp_up), int(ramp_down)
+    a.lambda_w, a.lr, a.b1, a.b2, a.eps = float(lambda_w), float(lr), float(b1), float(b2), float(eps)
+    return a
+
+
+def proj_step(w, am, av, gw, wmean, labels, loss, step_t, best_obj, best_loss, best_w, nonfinite, hist, S: int, lr: float,
+              b1: float, b2: float, eps: float, lambda_w: float = 0.0, ramp_up: int = 0, ramp_down: int = 0) -> None:
+    """Enqueue kg_proj_step (ONE launch, a workgroup per sample) on the current stream: the prior, the schedule, one Adam step
+    on the latents ``w`` (n, D) with moments ``am``, ``av`` and the best-so-far record ``best_obj`` (n), ``best_loss`` (n, 4),
+    ``best_w`` (n, D); ``hist`` (S, n) or None; ``nonfinite`` (n) int32 counts the steps a sample was frozen.  ``step_t`` holds
+    the 1-based number of THIS step (int32, device); the launch does not advance it.  All tensors contiguous."""
+    who = "kg_proj_step"
+    n, D = w.shape
+    K = wmean.shape[0]
+    a = _proj_step_shape(n, D, K, S, lr, b1, b2, eps, lambda_w, ramp_up, ramp_down)
+    f32 = [("w", w, n * D), ("am", am, n * D), ("av", av, n * D), ("gw", gw, n * D), ("wmean", wmean, K * D), ("loss", loss, n * 4),
+           ("best_obj", best_obj, n), ("best_loss", best_loss, n * 4), ("best_w", best_w, n * D)]
+    if hist is not None:
+        f32.append(("hist", hist, int(S) * n))
+    for name, t, cnt in f32:
+        _dest(t, cnt, f"{who}: {name} must be a contiguous fp32 tensor of {cnt} elements")
+    for name, t, cnt, dt in (("labels", labels, n, torch.int64), ("step", step_t, 1, torch.int32), ("nonfinite", nonfinite, n, torch.int32)):
+        if t.dtype != dt or t.numel() != cnt or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of {cnt} elements")
+    _need_cuda(w, am, av, gw, wmean, labels, loss, step_t, best_obj, best_loss, best_w, nonfinite, hist)
+    a.w, a.am, a.av, a.gw, a.wmean = w.data_ptr(), am.data_ptr(), av.data_ptr(), gw.data_ptr(), wmean.data_ptr()
+    a.labels, a.loss, a.step = labels.data_ptr(), loss.data_ptr(), step_t.data_ptr()
+    a.best_obj, a.best_loss, a.best_w = best_obj.data_ptr(), best_loss.data_ptr(), best_w.data_ptr()
+    a.hist, a.nonfinite = _ptr(hist), nonfinite.data_ptr()
+    _count(who, 0.0)
+    _check(load_library().kg_proj_step(C.byref(a), _stream()), who)
 
 
 # ---- inputs of a training iteration (kg_input.hip) ------------------------------------------------------------------------

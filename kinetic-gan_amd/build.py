@@ -9,7 +9,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libkgan_hip.so")
-SOURCES = ["kg_conv.hip", "kg_wgrad.hip", "kg_agg.hip", "kg_aggconv.hip", "kg_gen.hip", "kg_genblock.hip", "kg_disc.hip", "kg_map.hip", "kg_comm.hip", "kg_misc.hip", "kg_mmd.hip", "kg_input.hip", "kg_sample.hip", "kg_eval.hip", "kg_prdc.hip", "kg_frechet.hip", "kg_cls.hip", "kg_nn.hip", "kg_nn_gram.hip", "kg_kin.hip"]
+SOURCES = ["kg_conv.hip", "kg_wgrad.hip", "kg_agg.hip", "kg_aggconv.hip", "kg_gen.hip", "kg_genblock.hip", "kg_disc.hip", "kg_map.hip", "kg_comm.hip", "kg_misc.hip", "kg_mmd.hip", "kg_input.hip", "kg_sample.hip", "kg_eval.hip", "kg_prdc.hip", "kg_frechet.hip", "kg_cls.hip", "kg_nn.hip", "kg_nn_gram.hip", "kg_kin.hip", "kg_proj.hip"]
 
 
 def _stale() -> bool:

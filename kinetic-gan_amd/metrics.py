@@ -1027,3 +1027,46 @@ def select_reference_samples(feeder, classes: Optional[Sequence[int]] = None, t_
     raw[order] = block
     labels = np.repeat(np.arange(classes.size), per_class)
     return raw, labels, index
+
+
+# ---- reconstruction error: projection of real motions into W (project.Projector, kg_proj.hip) -----------------------
+
+RECON_NAMES = ("recon_pos", "recon_vel", "recon_bone")
+
+
+def reconstruction(G, real, labels_real=None, dataset: str = "ntu", per_class: Optional[int] = None, scale: float = 1.0,
+                   shift: float = 0.0, mask=None, **projector_kw) -> dict:
+    """How well the generator can represent given motions: the first ``per_class`` real samples of every class (``frechet``'s
+    conventions: one-hot rows or class ids, default all, ragged classes raise) are projected into W in batches of the
+    Projector's ``n`` (``projector_kw``: the arguments of ``project.Projector``; default n = min(samples, 64)) and scored by the
+    terms of their best objective.  Smaller is better; on held-out data this is a per-sample recall without a k-NN radius or a
+    feature extractor, on training data it complements ``memorisation``.  Leaves on the device: ``values`` (K, 3) the class
+    means of the best L_pos, L_vel, L_bone (``RECON_NAMES``), ``mean`` (3,) their mean over classes, ``per_sample`` (K, P, 4) =
+    [L, L_pos, L_vel, L_bone], ``best_w`` (K, P, D), ``recon`` (K, P, C, T, V) and ``nonfinite`` (K, P) int32.  ``scale`` /
+    ``shift`` / ``mask``: as in ``Projector.project``, shared by all samples (mask (T, V))."""
+    from .project import Projector
+    who = "reconstruction"
+    real = _as_f32(real)
+    if real.dim() != 4:
+        raise ValueError("%s: real samples are (N, C, T, V), got %s" % (who, tuple(real.shape)))
+    lab, K = _label_ids(labels_real, real.shape[0], "labels_real", who)
+    idx = _class_rows(lab, K, per_class, "real", who)
+    P = idx.shape[1]
+    flat, classes = idx.reshape(-1), np.repeat(np.arange(K), P)
+    n = int(projector_kw.pop("n", min(flat.size, 64)))
+    proj = Projector(G, n, dataset=dataset, **projector_kw)
+    dev = proj.device
+    real = real.to(dev)
+    rows = []
+    for b in range(0, flat.size, n):
+        cnt = min(n, flat.size - b)
+        pad = np.zeros(n - cnt, dtype=np.int64)                          # a short last batch is filled up with its first sample
+        sel = np.concatenate([flat[b:b + cnt], flat[b:b + 1][pad]])
+        lb = np.concatenate([classes[b:b + cnt], classes[b:b + 1][pad]])
+        out = proj.project(real.index_select(0, torch.as_tensor(sel, device=dev)), lb, mask=mask, scale=scale, shift=shift)
+        rows.append({k: out[k][:cnt] for k in ("best_loss", "best_w", "recon", "nonfinite")})
+    cat = {k: torch.cat([r[k] for r in rows], 0) for k in rows[0]}
+    per_sample = cat["best_loss"].reshape(K, P, 4)
+    values = per_sample[:, :, 1:].mean(1)
+    return dict(values=values, mean=values.mean(0), per_sample=per_sample, best_w=cat["best_w"].reshape(K, P, -1),
+                recon=cat["recon"].reshape((K, P) + tuple(cat["recon"].shape[1:])), nonfinite=cat["nonfinite"].reshape(K, P))
