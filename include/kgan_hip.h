@@ -483,6 +483,29 @@ int     kg_genblock_fwd(const KgGenBlockArgs* a, void* stream);
 int64_t kg_genblock_bwd_lds_bytes(const KgGenBlockBwdArgs* a);
 int64_t kg_genblock_bwd_workspace_bytes(const KgGenBlockBwdArgs* a);
 int     kg_genblock_bwd(const KgGenBlockBwdArgs* a, void* stream);
+/* tests / tuning (additive, ABI v9): the kernel instantiation, the path of the two channel contractions and the launch
+ * geometry kg_genblock_fwd / _bwd / _infer take for a block under the current KG_GB_RT switch - from the same host functions
+ * as the launchers.  Only dimensions and flags are read: nothing is dereferenced, nothing is launched.
+ *   geometry   index into the compile-time geometries (GB_GEOMETRIES of csrc/kg_genblock.hip), -1: the run-time form
+ *   mfma0/1    1: the head contraction (yc forward, gx backward) / the tcn contraction runs on the matrix cores - for a
+ *              compile-time geometry the path the kernel itself resolves from its constants
+ *   mv0/1      the row bucket (4 / 16 / 32) of the VALU path, 0 on the matrix-core path
+ *   lds_bytes  dynamic LDS of the launch, -1 where the launcher (or its eligibility query) refuses the block
+ *   grid_x     workgroups (one per sample)                                                                            */
+#define KG_GB_DIR_FWD 0
+#define KG_GB_DIR_BWD 1
+#define KG_GB_DIR_INFER 2
+typedef struct KgGenBlockFormQuery {
+    int32_t N, groups;                      /* groups: forward only (1 elsewhere)                                        */
+    int32_t Cin, C, K, Kp, Tc, Vc, T, V, rep, res_kind, bn_t;
+    int32_t dir;                            /* KG_GB_DIR_*                                                               */
+    int32_t prev;                           /* backward: the previous block's tail statistics ride along (px given)      */
+    int32_t wg_aligned, wr_aligned, wt_aligned;     /* 16-byte alignment of the weight pointers (forward, inference)     */
+} KgGenBlockFormQuery;
+typedef struct KgGenBlockForm {
+    int32_t geometry, mfma0, mfma1, mv0, mv1, lds_bytes, grid_x;
+} KgGenBlockForm;
+int     kg_genblock_form(const KgGenBlockFormQuery* q, KgGenBlockForm* form);
 
 /* ---- per-channel reductions over (n, t, v) ---------------------------------------------------------
  *   out[0*C + c] = sum x ;  out[1*C + c] = sum x*(y - shift[c])   (y == NULL: sum (x - shift[c])^2)

@@ -348,6 +348,18 @@ class _GenBlockBwdArgs(C.Structure):
                 ("ws", c_f32p), ("ws_bytes", C.c_int64), ("counters", C.c_void_p), ("counters_len", C.c_int32)]
 
 
+GB_DIR_FWD, GB_DIR_BWD, GB_DIR_INFER = 0, 1, 2       # KgGenBlockFormQuery.dir
+
+
+class _GenBlockFormQuery(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "N", "groups", "Cin", "C", "K", "Kp", "Tc", "Vc", "T", "V", "rep", "res_kind", "bn_t", "dir", "prev",
+        "wg_aligned", "wr_aligned", "wt_aligned")]
+
+
+class _GenBlockForm(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("geometry", "mfma0", "mfma1", "mv0", "mv1", "lds_bytes", "grid_x")]
+
 
 MMD_MAX_BW = 16
 
@@ -685,6 +697,7 @@ EXPORTS = {
     "kg_genblock_bwd_lds_bytes": (C.c_int64, [C.POINTER(_GenBlockBwdArgs)]),
     "kg_genblock_bwd_workspace_bytes": (C.c_int64, [C.POINTER(_GenBlockBwdArgs)]),
     "kg_genblock_bwd": (C.c_int, [C.POINTER(_GenBlockBwdArgs), C.c_void_p]),
+    "kg_genblock_form": (C.c_int, [C.POINTER(_GenBlockFormQuery), C.POINTER(_GenBlockForm)]),
     "kg_head_fwd": (C.c_int, [C.POINTER(_HeadArgs), C.c_void_p]),
     "kg_head_bwd": (C.c_int, [C.POINTER(_HeadArgs), C.c_void_p]),
     "kg_head_wgrad": (C.c_int, [C.POINTER(_HeadArgs), C.c_void_p]),
@@ -1710,6 +1723,35 @@ def genblock_supported(d: GenBlockDims, n: int, wg, wr, wt, backward: bool = Fal
     return lib.kg_genblock_lds_bytes(C.byref(a)) >= 0
 
 
+last_genblock_form = None  # set to a list: genblock_fwd / genblock_bwd / genblock_infer append the form (genblock_form: a dict)
+                           # of every launch, in call order - as last_conv_form
+
+
+def genblock_form(d: GenBlockDims, n: int, direction: str = "fwd", *, groups: int = 1, prev: bool = False,
+                  wg_aligned: bool = True, wr_aligned: bool = True, wt_aligned: bool = True) -> dict:
+    """kg_genblock_form: the instantiation (``geometry``: index into the compile-time geometries, -1 = the run-time form),
+    the path of the two contractions (mfma0 / mfma1, VALU row buckets mv0 / mv1), the dynamic LDS (-1: refused) and the grid
+    of a ``direction`` ("fwd" / "bwd" / "infer") launch under the current KG_GB_RT switch.  Host code only: no GPU."""
+    q = _GenBlockFormQuery()
+    q.N, q.groups = n, groups
+    q.Cin, q.C, q.K, q.Kp, q.Tc, q.Vc, q.T, q.V, q.rep = d.Cin, d.C, d.K, d.Kp, d.Tc, d.Vc, d.T, d.V, d.rep
+    q.res_kind, q.bn_t = d.res_kind, int(d.bn_t)
+    q.dir = {"fwd": GB_DIR_FWD, "bwd": GB_DIR_BWD, "infer": GB_DIR_INFER}[direction]
+    q.prev, q.wg_aligned, q.wr_aligned, q.wt_aligned = int(prev), int(wg_aligned), int(wr_aligned), int(wt_aligned)
+    f = _GenBlockForm()
+    _check(load_library().kg_genblock_form(C.byref(q), C.byref(f)), "kg_genblock_form")
+    out = {k: getattr(f, k) for k, *_ in _GenBlockForm._fields_}
+    out["dir"] = direction
+    return out
+
+
+def _gb_record_form(d: GenBlockDims, n: int, direction: str, a, groups: int = 1, prev: bool = False):
+    if last_genblock_form is not None:
+        al = lambda p: p is None or p % 16 == 0
+        last_genblock_form.append(genblock_form(d, n, direction, groups=groups, prev=prev, wg_aligned=al(a.wg), wr_aligned=al(a.wr),
+                                                wt_aligned=al(a.wt)))
+
+
 def _gb_bn(layer: _GenBnLayer, bn: dict, c: int, groups: int, device):
     vecs = [_vec(bn.get(k), c, "genblock_fwd") for k in ("gamma", "beta", "running_mean", "running_var")]
     nbt = bn.get("num_batches_tracked")
@@ -1793,6 +1835,7 @@ def genblock_fwd(d: GenBlockDims, *, x=None, pend=None, wg, wr=None, br=None, wt
         ws = _workspace("kg_genblock_workspace_bytes", a, dev, tickets="counters")
     _count("kg_genblock", 2.0 * n * (Mh * d.Cin * d.Tc * d.Vc + 3 * d.C * d.C * d.T * d.V) +
            2.0 * n * (d.Kp + (1 if d.res_kind else 0)) * d.Vc * d.V * d.C * d.Tc)
+    _gb_record_form(d, n, "fwd", a, groups=groups)
     _check(lib.kg_genblock_fwd(C.byref(a), _stream()), "kg_genblock_fwd")
     return dict(x=x, yc=yc, z=z, r=r, u=u, ct=ct, cr=cr, out=out)
 
@@ -1869,6 +1912,7 @@ def genblock_bwd(d: GenBlockDims, *, g, out, u=None, r=None, coef, wg, wr=None, 
         ws = _workspace("kg_genblock_bwd_workspace_bytes", a, dev, tickets="counters")
     _count("kg_genblock", 2.0 * n * (Mh * d.Cin * d.Tc * d.Vc + 3 * d.C * d.C * d.T * d.V) +
            2.0 * n * (d.Kp + (1 if d.res_kind else 0)) * d.Vc * d.V * d.C * d.T)
+    _gb_record_form(d, n, "bwd", a, prev=prev is not None)
     _check(lib.kg_genblock_bwd(C.byref(a), _stream()), "kg_genblock_bwd")
     if dr is None and d.res_kind != 0:
         dr = du
@@ -3590,6 +3634,7 @@ def genblock_infer(d: GenBlockDims, *, x, wg, wr=None, br=None, wt, bt=None, B, 
     Mh = d.Kp * d.C + (d.C if d.res_kind == 2 else 0)
     _count("kg_genblock", 2.0 * n * (Mh * d.Cin * d.Tc * d.Vc + 3 * d.C * d.C * d.T * d.V) +
            2.0 * n * (d.Kp + (1 if d.res_kind else 0)) * d.Vc * d.V * d.C * d.Tc)
+    _gb_record_form(d, n, "infer", a)
     _check(lib.kg_genblock_infer(C.byref(a), _stream()), "kg_genblock_infer")
     return out
 

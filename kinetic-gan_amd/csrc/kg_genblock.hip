@@ -1095,6 +1095,36 @@ bool geo_matches(const Dims& d, int bn_t) {
            d.res_kind == G::RES && (bn_t != 0) == (G::BNT != 0);
 }
 
+// Limits of the single-pass row -> thread maps (gb_row_threads: one row per thread at most, no loop over rows) and of the merge
+// area, as the launchers and kg_genblock_form apply them.
+// forward: the per-sample BatchNorm partials reduce (branch, channel) rows - at most NT of them
+bool fwd_stat_rows_fit(const Dims& d, int bn_t) { return ((bn_t ? 1 : 0) + (d.res_kind == 2 ? 1 : 0)) * (long)d.C <= NT; }
+// forward: the last arriver's (mean, var) of every (branch, batch, channel) live in the weight staging area
+bool fwd_merge_fits(int groups, int C) { return 4L * groups * C <= GB_VALU_MAXMK; }
+// backward with the previous block's tail statistics: one row per input channel, at most NT of them
+bool bwd_prev_rows_fit(const Dims& d) { return d.Cin <= NT; }
+bool bwd_prev_cols_fit(const Dims& d) { return d.Tc * d.Vc <= 512; }
+
+// the contraction paths a compile-time geometry resolves from its constants (the kernels' own `mfma0` / `mfma1`)
+template <typename G>
+void geo_paths(bool bwd, bool* m0, bool* m1) {
+    constexpr int Nc = G::Tc * G::Vc, Nf = G::T * G::V, Mh = G::Kp * G::C + (G::RES == 2 ? G::C : 0);
+    *m0 = bwd ? gb_use_mfma(G::Cin, Mh, Nc, true) : gb_use_mfma(Mh, G::Cin, Nc, false);
+    *m1 = gb_use_mfma(G::C, 3 * G::C, Nf, bwd);
+}
+// the launchers' GB_TRY chain as a number: the index into GB_GEOMETRIES of the instantiation that serves the block (its
+// paths in m0 / m1), -1: GbRt.  Inference does not match on the BatchNorm flag.
+int geo_index(const Dims& d, int bn_t, bool infer, bool bwd, bool* m0, bool* m1) {
+    int idx = 0;
+#define GB_IDX(...) do { using G_ = GbGeo<__VA_ARGS__>; \
+        if (geo_matches<G_>(d, infer ? G_::BNT : bn_t)) { geo_paths<G_>(bwd, m0, m1); return idx; } \
+        ++idx; } while (0)
+    GB_GEOMETRIES(GB_IDX);
+#undef GB_IDX
+    return -1;
+}
+int valu_bucket(bool mfma, int M) { return mfma ? 0 : (M <= 4 ? 4 : M <= 16 ? 16 : 32); }
+
 }  // namespace
 
 extern "C" int64_t kg_genblock_lds_bytes(const KgGenBlockArgs* a) {
@@ -1103,6 +1133,7 @@ extern "C" int64_t kg_genblock_lds_bytes(const KgGenBlockArgs* a) {
     GbLayout L;
     const long b = make_layout(dims_of(a), false, L);
     if (b < 0) return -1;
+    if (!fwd_stat_rows_fit(dims_of(a), a->bn_t)) return -1;
     // 16-byte row loads of the matrix-core contractions
     if (L.mfma0 && !(aligned16(a->wg) && (a->res_kind != 2 || aligned16(a->wr)))) return -1;
     if (L.mfma1 && !aligned16(a->wt)) return -1;
@@ -1119,7 +1150,7 @@ extern "C" int kg_genblock_fwd(const KgGenBlockArgs* a, void* stream) {
     KG_REQUIRE(a != nullptr, "kg_genblock_fwd: null args");
     if (int rc = check_dims(dims_of(a), "kg_genblock_fwd")) return rc;
     KG_REQUIRE(a->groups >= 1 && a->N % a->groups == 0, "kg_genblock_fwd: N=%d is not a multiple of groups=%d", a->N, a->groups);
-    KG_REQUIRE(4L * a->groups * a->C <= GB_VALU_MAXMK, "kg_genblock_fwd: groups=%d x C=%d statistics do not fit the merge area", a->groups, a->C);
+    KG_REQUIRE(fwd_merge_fits(a->groups, a->C), "kg_genblock_fwd: groups=%d x C=%d statistics do not fit the merge area", a->groups, a->C);
     const int64_t lds = kg_genblock_lds_bytes(a);
     KG_REQUIRE(lds >= 0, "kg_genblock_fwd: the block does not fit the fused form (kg_genblock_lds_bytes)");
     KG_REQUIRE(a->wg && a->wt && a->b, "kg_genblock_fwd: null weight / adjacency pointer");
@@ -1183,7 +1214,8 @@ extern "C" int kg_genblock_bwd(const KgGenBlockBwdArgs* a, void* stream) {
     KG_REQUIRE(a->du.p && a->gyc.p && a->zf.p && a->gx.p, "kg_genblock_bwd: null output tensor");
     KG_REQUIRE(a->res_kind != 2 || a->dr.p, "kg_genblock_bwd: conv residual without dr");
     if (a->px.p) {
-        KG_REQUIRE(a->Tc * a->Vc <= 512, "kg_genblock_bwd: previous block's statistics need Tc * Vc <= 512 (got %d)", a->Tc * a->Vc);
+        KG_REQUIRE(bwd_prev_cols_fit(dims_of(a)), "kg_genblock_bwd: previous block's statistics need Tc * Vc <= 512 (got %d)", a->Tc * a->Vc);
+        KG_REQUIRE(bwd_prev_rows_fit(dims_of(a)), "kg_genblock_bwd: previous block's statistics need Cin <= %d (got %d)", NT, a->Cin);
         KG_REQUIRE(a->pcoef, "kg_genblock_bwd: previous block's statistics without pcoef");
         KG_REQUIRE(a->pu.p == nullptr || (a->pmean_t && a->prstd_t), "kg_genblock_bwd: previous BatchNorm (tcn) needs its statistics");
         KG_REQUIRE(a->pmean_r == nullptr || (a->pr.p && a->prstd_r), "kg_genblock_bwd: previous BatchNorm (residual) needs r and its statistics");
@@ -1257,6 +1289,36 @@ extern "C" int kg_genblock_infer(const KgGenBlockInferArgs* a, void* stream) {
 #undef GB_TRY
     hipLaunchKernelGGL(kg_genblock_infer_kernel<GbRt>, dim3(a->N), dim3(NT), (size_t)lds, (hipStream_t)stream, *a, L);
     return kg_launch_status("kg_genblock_infer");
+}
+
+extern "C" int kg_genblock_form(const KgGenBlockFormQuery* q, KgGenBlockForm* form) {
+    KG_REQUIRE(q != nullptr, "kg_genblock_form: null query");
+    KG_REQUIRE(form != nullptr, "kg_genblock_form: null output");
+    KG_REQUIRE(q->dir == KG_GB_DIR_FWD || q->dir == KG_GB_DIR_BWD || q->dir == KG_GB_DIR_INFER, "kg_genblock_form: dir=%d", q->dir);
+    const Dims d{q->N, q->Cin, q->C, q->K, q->Kp, q->Tc, q->Vc, q->T, q->V, q->rep, q->res_kind};
+    if (int rc = check_dims(d, "kg_genblock_form")) return rc;
+    const bool bwd = q->dir == KG_GB_DIR_BWD, infer = q->dir == KG_GB_DIR_INFER;
+    *form = KgGenBlockForm{};
+    form->geometry = -1;
+    form->grid_x = q->N;
+    GbLayout L;
+    long b = make_layout(d, bwd, L);
+    bool m0 = L.mfma0 != 0, m1 = L.mfma1 != 0;
+    if (b >= 0) {
+        if (!bwd) {                         // the rules of kg_genblock_lds_bytes / kg_genblock_infer_lds_bytes / kg_genblock_fwd
+            if (m0 && !(q->wg_aligned && (q->res_kind != 2 || q->wr_aligned))) b = -1;
+            if (m1 && !q->wt_aligned) b = -1;
+            if (infer && (q->T <= 1 || q->Tc * q->Vc < GB_INFER_MIN_COLS)) b = -1;
+            if (!infer && !(q->groups >= 1 && q->N % q->groups == 0 && fwd_stat_rows_fit(d, q->bn_t) && fwd_merge_fits(q->groups, q->C))) b = -1;
+        } else if (q->prev && !(bwd_prev_cols_fit(d) && bwd_prev_rows_fit(d))) b = -1;       // kg_genblock_bwd
+    }
+    form->lds_bytes = (int32_t)b;
+    if (b < 0) return 0;
+    if (!kg_env().gb_rt) form->geometry = geo_index(d, q->bn_t, infer, bwd, &m0, &m1);
+    form->mfma0 = m0; form->mfma1 = m1;
+    form->mv0 = valu_bucket(m0, bwd ? q->Cin : L.Mh);
+    form->mv1 = valu_bucket(m1, q->C);
+    return 0;
 }
 
 #ifdef KG_GB_STAMP

@@ -465,8 +465,12 @@ def gen_tail_bwd(g, out, act, u=None, bn_t=None, r=None, bn_r=None, noise=None, 
 
 # ---- fused generator block (kg_genblock_fwd / kg_genblock_bwd): the staged entry points composed -------------------------
 
-def _gb_lds_bytes(d, backward):
-    """the eligibility rule of kg_genblock.hip (make_layout): per-sample working set <= 150 KB of LDS, contraction shapes"""
+def _gb_lds_bytes(d, backward, stats=True):
+    """the eligibility rule of kg_genblock.hip (make_layout): per-sample working set <= 150 KB of LDS, contraction shapes;
+    ``stats`` (the training forward; False: inference, which takes no statistics): at most 512 (branch, channel) rows of
+    BatchNorm partials - the kernel reduces one row per thread group in a single pass"""
+    if not backward and stats and ((1 if d.bn_t else 0) + (1 if d.res_kind == 2 else 0)) * d.C > 512:
+        return -1
     def path(M, K, N, at):
         if (at or K % 16 == 0) and (M >= 17 or N >= 64):
             return True, True

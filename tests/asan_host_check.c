@@ -190,6 +190,17 @@ int main(void) {
     CHECK(kg_genblock_bwd(&gbb, 0) < 0);
     gbb.Tc = 128; gbb.T = 256;
     CHECK(kg_genblock_bwd_lds_bytes(&gbb) == -1);                /* t_size = 256: the sample does not fit LDS */
+    /* the form report: host code only */
+    KgGenBlockFormQuery fq;
+    KgGenBlockForm ff;
+    memset(&fq, 0, sizeof fq);
+    fq.N = 4; fq.groups = 2; fq.Cin = 64; fq.C = 32; fq.K = 3; fq.Kp = 3; fq.Tc = 8; fq.Vc = 5; fq.T = 16; fq.V = 11; fq.rep = 2;
+    fq.res_kind = 2; fq.wg_aligned = fq.wr_aligned = fq.wt_aligned = 1;
+    for (fq.dir = KG_GB_DIR_FWD; fq.dir <= KG_GB_DIR_INFER; ++fq.dir)
+        CHECK(kg_genblock_form(&fq, &ff) == 0 && ff.geometry == 1 && ff.mfma0 == 1 && ff.mfma1 == 1 && ff.lds_bytes > 0 && ff.grid_x == 4);
+    fq.dir = KG_GB_DIR_FWD; fq.C = 272; fq.bn_t = 1; fq.Tc = fq.T = 1; fq.Vc = fq.V = 1; fq.rep = 1; fq.Cin = 16;
+    CHECK(kg_genblock_form(&fq, &ff) == 0 && ff.lds_bytes == -1);    /* 544 rows of BatchNorm partials: refused */
+    CHECK(kg_genblock_form(&fq, 0) < 0 && kg_genblock_form(0, &ff) < 0);
     printf("asan host check ok\n");
     return 0;
 }

@@ -55,7 +55,7 @@ def bn_eval_coef(jobs):
 
 
 def genblock_infer_supported(d, n, wg, wr, wt):
-    return d.T > 1 and d.Tc * d.Vc >= 16 and prim_ref._gb_lds_bytes(d, False) >= 0
+    return d.T > 1 and d.Tc * d.Vc >= 16 and prim_ref._gb_lds_bytes(d, False, stats=False) >= 0
 
 
 def genblock_infer(d, *, x, wg, wr=None, br=None, wt, bt=None, B, U=None, ct=None, cr=None, noise=None, nw=None, slope=0.2,
